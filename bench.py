@@ -12,6 +12,11 @@ followed by the greedy decoder head, i.e. what PagedAttentionInferenceModel::for
 iteration with n_new_items = 0 (reference src/inference_model.cpp:52-82).  Every rank owns an
 independent shard of the batch rows (weak scaling); the only cross-GPU traffic is the all-gather of
 the generated token ids.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps (one timed region), writes the last step's outputs if
+--dump-outputs DIR is given, and prints the line.  --full adds everything else the line can carry: repeated regions,
+the roofline pass, the other form of the step, the other configurations, the engine workload, the CPU baseline and,
+with N > 1 ranks, the collective report.
 """
 import argparse
 import ctypes
@@ -548,6 +553,11 @@ def main():
                     help="KV page / weight element type (accumulation, q, scores and outputs are always fp32); "
                          "auto = what BASELINE.json names for the workload: bf16 for c4, fp32 for c2/c3; fp8 = the opt-in "
                          "extension (OCP e4m3 pages, bf16 weights; lean composition only) -- never the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated timed regions, roofline, the other form of the step, the "
+                         "`configs` block, the CPU baseline and (N > 1) the collective report; off = the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="step mode: write what the timed path computed in its last step to DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-configs", action="store_true",
@@ -573,8 +583,9 @@ def main():
                          "host thread each) so one engine's host bookkeeping overlaps the other's kernels")
     ap.add_argument("--engine-repeats", type=int, default=5,
                     help="engine mode: runs of the workload (a fresh engine each, same items); the median run is reported")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="step mode: timed regions of exactly --steps steps each (same state); the median region is `value`")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="step mode: timed regions of exactly --steps steps each (same state); the median region is `value` "
+                         "(default: 1, 5 with --full)")
     ap.add_argument("--engine-shape", action="store_true",
                     help="engine mode: run the --workload shape (e.g. c4) instead of the reference's profiling shape e1")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsing "
@@ -589,6 +600,10 @@ def main():
     args = ap.parse_args()
     if args.dtype == "auto":
         args.dtype = "bf16" if args.workload == "c4" else "f32"
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.dump_outputs and args.mode != "step":
+        raise SystemExit("--dump-outputs writes the outputs of the step mode")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher (nothing has touched the GPU yet)
@@ -714,6 +729,46 @@ def region_stats(regions, steps):
     ms = sorted(r / steps * 1e3 for r in regions)
     return {"regions": len(ms), "median_ms_per_step": ms[len(ms) // 2] if len(ms) % 2 else 0.5 * (ms[len(ms) // 2 - 1] + ms[len(ms) // 2]),
             "min_ms_per_step": ms[0], "max_ms_per_step": ms[-1], "all_ms_per_step": [r / steps * 1e3 for r in regions]}
+
+
+DUMP_SAMPLE_ROWS = 256        # rows whose newly written cache slots --dump-outputs writes (a fixed, seeded sample)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(wl, out_dir, materialising):
+    """--dump-outputs: what the timed path computed in its last step, as its caller receives it -- q, attention_result,
+    the token ids and the advanced lengths of every row; the probabilities and logits where the materialising form
+    writes them; and the cache slots the step wrote (K and V of the latest token at length-2, x of the generated token
+    at length-1) for a fixed, seeded sample of rows.  float32 (float64 for integers), this rank's rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    L = wl.lengths.cpu().numpy().astype(np.int64)
+    rows = np.sort(np.random.default_rng(0xD0).choice(wl.B, min(wl.B, DUMP_SAMPLE_ROWS), replace=False))
+    r = torch.from_numpy(rows).to(wl.dev)
+    s_kv = torch.from_numpy(L[rows] - 2).to(wl.dev)
+    s_x = torch.from_numpy(L[rows] - 1).to(wl.dev)
+    if wl.layout == "paged":
+        pv = wl.pool.view(-1, PAGE, 3, wl.D)                        # [page, slot, x | K | V, D]
+        ids = torch.from_numpy(wl.page_ids).to(wl.dev)
+        k, v = (pv[ids[r, s_kv // PAGE], s_kv % PAGE, seg] for seg in (1, 2))
+        x = pv[ids[r, s_x // PAGE], s_x % PAGE, 0]
+    else:
+        k, v, x = wl.kt_cache[r, :, s_kv], wl.v_cache[r, s_kv, :], wl.inp_embedding[r, s_x, :]
+
+    def f32(t):
+        t = t.cpu()
+        return (t.view(torch.float8_e4m3fn) if t.dtype == torch.uint8 else t).float().numpy()   # fp8: OCP e4m3 codes
+
+    arrays = {"q_output": f32(wl.q_output), "attention_result": f32(wl.attention_result),
+              "tokens": wl.decoder_result.view(-1).cpu().numpy().astype(np.float64), "lengths": L.astype(np.float64),
+              "sample_rows": rows.astype(np.float64), "sample_new_kv": np.stack([f32(k), f32(v)], axis=1),
+              "sample_new_x": f32(x)}
+    if materialising:
+        arrays["probabilities"] = f32(wl.qkt_output)
+        arrays["emb_score"] = f32(wl.emb_score)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def median_region(regions):
@@ -860,6 +915,8 @@ def run_step_bench(args, rank, world, dev, dist):
     regions = tmax.tolist()
     elapsed = median_region(regions)
     total_tokens = float(tokens.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(wl, args.dump_outputs, materialising=not lean)
     form = ("lean composition: what the layers run -- no scores / probabilities / emb_score materialised, chunks merged "
             "inside the scan launch" if lean else
             "materialising composition: the reference's launch sequence, qkt_output probabilities and emb_score written")
@@ -891,10 +948,12 @@ def run_step_bench(args, rank, world, dev, dist):
             "parallelism": f"row-sharded replicas x{world}, all-gather of token ids",
         },
     }
-    if world > 1:
+    if world > 1 and args.full:
         coll = collective_report(wl, step, args, world, dist, gather, dev, out["ms_per_step"])
         if rank == 0:
             out["collective"] = coll
+    if not args.full:
+        return out
     if rank == 0 and not args.no_roofline:
         lengths_now = wl.lengths.cpu().numpy()
         reps = max(10, args.steps)

@@ -46,7 +46,7 @@ def test_plain_gpus_1_needs_no_launcher():
 @pytest.mark.gpu
 def test_two_ranks_share_the_gpu_over_gloo():
     out = _run(["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--workload", "c3",
-                "--no-cpu-baseline", "--no-roofline"], timeout=600)
+                "--full", "--no-cpu-baseline", "--no-roofline"], timeout=600)
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["value"] > 0
     assert out["config"]["rows_per_gpu"] == 256 and out["scaling"] == "weak"
     # the N > 1 line proves what the collective saw

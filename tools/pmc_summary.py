@@ -1,8 +1,8 @@
 """Summarise rocprofv3 --pmc passes into profiles/pmc_<workload>.json (per-kernel HBM traffic per launch).
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py ...
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py ...
-    python tools/pmc_summary.py c4 gpurun_out/pmc_fetch gpurun_out/pmc_write [bench line of the counter run]
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d OUT/pmc_fetch -- python3 bench.py --full ...
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d OUT/pmc_write -- python3 bench.py --full ...
+    python tools/pmc_summary.py c4 OUT/pmc_fetch OUT/pmc_write [bench line of the counter run]
 
 With the counter run's own bench line (its lengths differ from a default run's: fewer steps), the summary also records the
 ALGORITHMIC bytes per launch of the dominant kernel in that run, so that traffic / algorithmic compares like with like.

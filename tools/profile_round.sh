@@ -21,18 +21,18 @@ run_pmc() {    # name, counter, bench args...
     rocprofv3 --kernel-trace --pmc "$counter" --output-format csv -d "$OUT/pmc_${counter}_$name" -- python3 "$B" "$@" > "$OUT/pmc_${counter}_$name.json" 2> "$OUT/pmc_${counter}_$name.err" || echo "pmc $counter $name failed"
     echo "pmc $counter $name done"
 }
-run_stats c4_bf16 --no-configs --no-cpu-baseline
-run_stats c4_f32 --dtype f32 --no-configs --no-cpu-baseline
-run_stats c4_fp8 --dtype fp8 --no-configs --no-cpu-baseline
-run_stats c3 --workload c3 --no-configs --no-cpu-baseline
-run_stats c2 --workload c2 --no-configs --no-cpu-baseline
+run_stats c4_bf16 --full --no-configs --no-cpu-baseline
+run_stats c4_f32 --full --dtype f32 --no-configs --no-cpu-baseline
+run_stats c4_fp8 --full --dtype fp8 --no-configs --no-cpu-baseline
+run_stats c3 --full --workload c3 --no-configs --no-cpu-baseline
+run_stats c2 --full --workload c2 --no-configs --no-cpu-baseline
 run_stats engine_e1 --mode engine
 run_stats engine_e1_sequential_lean --mode engine --sequential-loop
 run_stats engine_e1_sequential_reference --mode engine --sequential-loop --reference-launch-sequence
 for cfg in "c4_bf16" "c4_f32 --dtype f32" "c4_fp8 --dtype fp8" "c3 --workload c3" "c2 --workload c2"; do
     set -- $cfg
     name=$1; shift
-    run_pmc $name FETCH_SIZE "$@" --steps 10 --warmup 2 --repeats 1 --no-configs --no-cpu-baseline
-    run_pmc $name WRITE_SIZE "$@" --steps 10 --warmup 2 --repeats 1 --no-configs --no-cpu-baseline
+    run_pmc $name FETCH_SIZE "$@" --full --steps 10 --warmup 2 --repeats 1 --no-configs --no-cpu-baseline
+    run_pmc $name WRITE_SIZE "$@" --full --steps 10 --warmup 2 --repeats 1 --no-configs --no-cpu-baseline
 done
 echo all done
