@@ -73,6 +73,16 @@ int mli_engine_set_pipelined(mli_engine* engine, int enabled);
 /* Queue one item (ItemStorage::add_new_item). */
 int mli_engine_add_item(mli_engine* engine, int id, const int* tokens, int n_tokens);
 
+/* EXTENSION: queue an item that is decoded by sampling (temperature > 0) or greedily (temperature == 0): the contract of
+ * mli_sample_tokens (mli_kernels.h), drawn at each new token's position with this item's seed, so an item's tokens do
+ * not depend on its slot, the batch, the loop, n_forward_rounds, preemption or step graphs.  -1 with a message for
+ * temperature < 0 or not finite, top_k < 0, top_p outside (0, 1], an id already queued by this entry point, or an
+ * engine created with reference_length_reset_quirk.  The engine chooses its head once, at the first step or run:
+ * sampled if a queued item has temperature > 0 (plain mli_engine_add_item items then decode with temperature 0),
+ * otherwise the greedy head, after which an item with temperature > 0 is refused. */
+int mli_engine_add_item_sampled(mli_engine* engine, int id, const int* tokens, int n_tokens, float temperature,
+                                int top_k, float top_p, unsigned long long seed);
+
 /* Run to completion (the reference's start_*_engine). */
 int mli_engine_run(mli_engine* engine, mli_engine_stats* stats);
 

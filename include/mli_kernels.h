@@ -286,6 +286,42 @@ int mli_paged_decoder_fused(const float* batch_result, const float* emb_table, c
                             int n_decoder_results, int i_decoder, int elem_bf16,
                             void* scratch, size_t scratch_bytes, void* stream);
 
+/* EXTENSION: sampled decoder head.  Per batch row b the parameters are device arrays [n_batch]
+ * (structure of arrays): temperature T (f32), top_k K (i32), top_p P (f32), seed (i64, read as a 64-bit pattern).
+ * The token is drawn at position L = lengths[b]:
+ *   - T == 0: the greedy token, bit-identical to mli_[paged_]decoder_fused on the same logits (K and P ignored);
+ *   - otherwise, over the finite logits x: keep x >= the K-th largest (K == 0: all), then x >= t_p, the largest kept
+ *     value whose softmax(x / T) mass over the kept values >= it is at least P (P == 1: all); the token is the argmax of
+ *     x / T + g over that set (ties: lower index), g = -log(-log(u)), u = ((w >> 9) + 0.5f) * 2^-23 (exact, in (0, 1)),
+ *     w = Philox4x32-10(counter (v >> 2, L, 0, 0), key (seed low word, seed high word))[v & 3].
+ *   - no finite logit: the greedy head's token for that case (-1); empty rows (L == 0) as in the greedy heads.
+ * The draw depends on (logits, T, K, P, seed, L) only and is run-to-run deterministic.
+ * Out-of-domain device values never fault: T < 0 or NaN decodes greedily, K < 0 acts as 0, P > 1 or NaN acts as 1,
+ * P <= 0 keeps only the largest value (ties included).
+ *
+ * mli_sample_scratch_bytes: device scratch mli_sample_tokens needs (0: none; scratch may then be NULL).
+ * mli_sample_tokens: token pick only, logits [n_batch, n_vocab] -> tokens [n_batch]; lengths are read, never written.
+ * mli_decoder_sampled / mli_paged_decoder_sampled: the plain logits GEMM into the front of `scratch`
+ *   (mli_decoder_sampled_scratch_bytes: the fp32 logits [n_batch, n_vocab] and the pick's own scratch), the pick, then
+ *   what mli_[paged_]decoder_fused does with the token: decoder_result, lengths, next input embedding (contiguous or
+ *   paged fp32 / bf16 / fp8, `elem`). */
+size_t mli_sample_scratch_bytes(int n_batch, int n_vocab);
+int mli_sample_tokens(const float* logits, const float* temperature, const int* top_k, const float* top_p,
+                      const int64_t* seed, const int* lengths, int* tokens, int n_batch, int n_vocab,
+                      void* scratch, size_t scratch_bytes, void* stream);
+size_t mli_decoder_sampled_scratch_bytes(int n_batch, int n_vocab);
+int mli_decoder_sampled(const float* batch_result, const float* emb_table, const float* wpe_table,
+                        float* inp_embedding, int* lengths, int* decoder_result,
+                        int n_batch, int n_vocab, int n_sequence, int emb_dim,
+                        const float* temperature, const int* top_k, const float* top_p, const int64_t* seed,
+                        void* scratch, size_t scratch_bytes, void* stream);
+int mli_paged_decoder_sampled(const float* batch_result, const float* emb_table, const float* wpe_table,
+                              void* const* page_table, int* lengths, int* decoder_result,
+                              int n_batch, int n_vocab, int n_sequence, int emb_dim,
+                              int n_decoder_results, int i_decoder, int elem,
+                              const float* temperature, const int* top_k, const float* top_p, const int64_t* seed,
+                              void* scratch, size_t scratch_bytes, void* stream);
+
 /* PREFILL of the newly inserted rows in ONE launch: the encoder as the fill GEMM's prologue.  The A
  * tile rows are computed on the fly as emb_table[inp[b, s]] + wpe[s] -- nothing is read back from the input-embedding
  * segment -- multiplied by [Wk | Wv], and the workgroups of the first column tile also write those rows to segment 0

@@ -70,6 +70,11 @@ SIGNATURES = {
     "mli_decoder_scratch_bytes": [_I, _I],
     "mli_decoder_fused": [_P] * 6 + [_I] * 4 + [_P, _Z, _P],
     "mli_paged_decoder_fused": [_P] * 6 + [_I] * 7 + [_P, _Z, _P],
+    "mli_sample_scratch_bytes": [_I, _I],
+    "mli_sample_tokens": [_P] * 7 + [_I] * 2 + [_P, _Z, _P],
+    "mli_decoder_sampled_scratch_bytes": [_I, _I],
+    "mli_decoder_sampled": [_P] * 6 + [_I] * 4 + [_P] * 4 + [_P, _Z, _P],
+    "mli_paged_decoder_sampled": [_P] * 6 + [_I] * 7 + [_P] * 4 + [_P, _Z, _P],
     "mli_paged_prefill": [_P] * 8 + [_I] * 5 + [_P],
     "mli_prefill": [_P] * 10 + [_I] * 5 + [_P],
     "mli_paged_decode_step": [_P] * 10 + [_I] * 7 + [_P, _Z, _P, _Z, _P],
@@ -107,6 +112,7 @@ ENGINE_SIGNATURES = {
     "mli_engine_create": [ctypes.POINTER(EngineConfig), _P, _P, _P, _P, _P, _PP],
     "mli_engine_destroy": [_P],
     "mli_engine_add_item": [_P, _I, _P, _I],
+    "mli_engine_add_item_sampled": [_P, _I, _P, _I, ctypes.c_float, _I, ctypes.c_float, ctypes.c_ulonglong],
     "mli_engine_use_private_stream": [_P],
     "mli_engine_set_pipelined": [_P, _I],
     "mli_engine_run": [_P, ctypes.POINTER(EngineStats)],
@@ -139,7 +145,8 @@ class ShardStats(ctypes.Structure):
 
 
 _RESTYPES = {"mli_shard_last_error": ctypes.c_char_p, "mli_shard_group_destroy": None, "mli_shard_group_engine": _P,
-             "mli_attention_workspace_bytes": _Z, "mli_decoder_scratch_bytes": _Z, "mli_engine_last_error": ctypes.c_char_p,
+             "mli_attention_workspace_bytes": _Z, "mli_decoder_scratch_bytes": _Z,
+             "mli_sample_scratch_bytes": _Z, "mli_decoder_sampled_scratch_bytes": _Z, "mli_engine_last_error": ctypes.c_char_p,
              "mli_engine_destroy": None, "mli_engine_set_lean_layers": None,
              "mli_engine_set_step_graphs": None}
 

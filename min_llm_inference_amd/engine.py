@@ -4,6 +4,7 @@ Mirrors how the reference's drivers use the engine (tests/paged_for_profile.cpp:
 and the model, then run start_*_engine to completion.  Nothing is computed in Python.
 """
 import ctypes
+import math
 
 import numpy as np
 
@@ -16,6 +17,23 @@ PAGED_FP8 = 4  # extension, opt-in: fp8 (OCP e4m3) pages, bf16 weights
 def _fp(a):
     a = np.ascontiguousarray(a, dtype=np.float32)
     return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
+    """Checked (temperature, top_k, top_p, seed) for mli_engine_add_item_sampled, or None when every argument is at its
+    default (greedy: the plain entry point).  Raises ValueError where the library would refuse the item."""
+    if (temperature, top_k, top_p, seed) == (0.0, 0, 1.0, 0):
+        return None
+    temperature, top_p = float(temperature), float(top_p)
+    if not math.isfinite(temperature) or temperature < 0:
+        raise ValueError(f"temperature must be finite and >= 0, got {temperature}")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0, got {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must lie in (0, 1], got {top_p}")
+    if int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be an integer in [0, 2**64), got {seed}")
+    return temperature, int(top_k), top_p, int(seed)
 
 
 class Engine:
@@ -44,9 +62,16 @@ class Engine:
     def set_pipelined(self, enabled=True):
         self._check(self._lib.mli_engine_set_pipelined(self._h, int(enabled)))
 
-    def add_item(self, item_id, tokens):
+    def add_item(self, item_id, tokens, temperature=0.0, top_k=0, top_p=1.0, seed=0):
+        """Queue an item.  With every sampling argument at its default it is decoded greedily by the plain entry point;
+        otherwise by mli_engine_add_item_sampled (temperature 0 is still greedy)."""
+        params = sampling_params(temperature, top_k, top_p, seed)
         t = np.ascontiguousarray(tokens, dtype=np.int32)
-        self._check(self._lib.mli_engine_add_item(self._h, int(item_id), t.ctypes.data_as(ctypes.c_void_p), len(t)))
+        if params is None:
+            self._check(self._lib.mli_engine_add_item(self._h, int(item_id), t.ctypes.data_as(ctypes.c_void_p), len(t)))
+        else:
+            self._check(self._lib.mli_engine_add_item_sampled(self._h, int(item_id), t.ctypes.data_as(ctypes.c_void_p),
+                                                              len(t), *params))
 
     def run(self):
         st = EngineStats()

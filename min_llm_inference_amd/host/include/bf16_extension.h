@@ -61,6 +61,8 @@ public:
     void forward(const TensorInt& inp, TensorInt& lengths, const TensorInt& new_item_indices,
                  TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
+    // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling)
+    void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }
 
 private:
     PagedAttentionBf16Layer attention_layer_;
@@ -68,6 +70,7 @@ private:
     TensorFloat attention_result_;
     TensorFloat emb_score_;
     int n_forward_rounds_;
+    const SlotSampling* sampling_ = nullptr;
 };
 
 void start_paged_attention_bf16_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table,

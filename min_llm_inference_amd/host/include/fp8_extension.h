@@ -7,6 +7,8 @@
 // elem = MLI_ELEM_FP8): there is no scores-materialising form to fall back to.
 #pragma once
 
+#include <memory>
+
 #include "bf16_extension.h"
 
 // floats to ask MemoryBlockManager for so that one block holds 16 x 3 x emb_dim fp8 elements
@@ -36,13 +38,18 @@ public:
     void forward(const TensorInt& inp, TensorInt& lengths, const TensorInt& new_item_indices,
                  TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
+    // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling); allocates the
+    // logits buffer the sampled head needs
+    void set_sampling(const SlotSampling* sampling);
 
 private:
     PagedAttentionFp8Layer attention_layer_;
-    size_t n_batch_, n_sequence_, emb_dim_;
+    size_t n_batch_, n_sequence_, emb_dim_, n_vocab_;
     TensorFloat attention_result_;
     TensorFloat decoder_scratch_;
     int n_forward_rounds_;
+    const SlotSampling* sampling_ = nullptr;
+    std::unique_ptr<TensorFloat> emb_score_;  // [n_batch, n_vocab], allocated when sampling is set
 };
 
 void start_paged_attention_fp8_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table,

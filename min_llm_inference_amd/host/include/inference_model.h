@@ -14,6 +14,8 @@ public:
     void forward(const TensorInt& inp, TensorInt& lengths, const TensorInt& new_item_indices,
                  TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
                  const TensorFloat& pos_emb_table);
+    // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling)
+    void set_sampling(const SlotSampling* sampling) { decoder_layer_.set_sampling(sampling); }
 
 private:
     SelfAttentionLayer attention_layer_;
@@ -33,6 +35,7 @@ public:
     void forward(const TensorInt& inp, TensorInt& lengths, const TensorInt& new_item_indices,
                  TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
+    void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
 
 private:
     PagedAttentionLayer paged_attention_layer_;
@@ -52,6 +55,7 @@ public:
     void forward(const TensorInt& inp, TensorInt& lengths, const TensorInt& new_item_indices,
                  TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table, GemmHandle handle);
+    void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
 
 private:
     PagedAttentionCublasLayer paged_attention_layer_;

@@ -3,6 +3,8 @@
 // position lengths[b].
 #pragma once
 
+#include <cstdint>
+
 #include "kernels/paged_attention.h"
 #include "tensor.hpp"
 
@@ -25,6 +27,23 @@ void launch_paged_attention_decoder_fused(const TensorFloat& batch_result, const
                                           TensorFloat& emb_score, const TensorFloat& wpe_table,
                                           TensorFloatPoint& page_table, TensorInt& lengths, TensorInt& decoder_result,
                                           int i_decoder);
+
+// EXTENSION: the sampled decoder head (mli_decoder_sampled / mli_paged_decoder_sampled).  Per-slot device
+// arrays [n_batch] of the draw's parameters; a slot with temperature 0 decodes greedily.  emb_score receives the logits.
+struct SlotSampling {
+    const float* temperature;
+    const int* top_k;
+    const float* top_p;
+    const int64_t* seed;
+};
+void launch_decoder_sampled(const TensorFloat& batch_result, const TensorFloat& emb_table, TensorFloat& emb_score,
+                            const TensorFloat& wpe_table, TensorFloat& inp_embedding, TensorInt& lengths,
+                            TensorInt& decoder_result, const SlotSampling& sampling);
+// elem = MLI_ELEM_* of the pages
+void launch_paged_attention_decoder_sampled(const TensorFloat& batch_result, const TensorFloat& emb_table,
+                                            TensorFloat& emb_score, const TensorFloat& wpe_table,
+                                            TensorFloatPoint& page_table, TensorInt& lengths, TensorInt& decoder_result,
+                                            int i_decoder, int elem, const SlotSampling& sampling);
 
 void launch_paged_attention_cublas_decoder_multi_rounds(const TensorFloat& batch_result,
                                                         const TensorFloat& emb_table, TensorFloat& emb_score,

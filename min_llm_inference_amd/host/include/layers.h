@@ -7,6 +7,8 @@
 #include "tensor.hpp"
 #include "utils.h"
 
+struct SlotSampling;  // kernels/decoder.h
+
 class SelfAttentionLayer : public NonCopyableNonClonable {
 public:
     SelfAttentionLayer(TensorFloat&& wk, TensorFloat&& wq, TensorFloat&& wv, size_t n_batch, size_t input_dim,
@@ -81,8 +83,12 @@ public:
     void forward(const TensorFloat& batch_result, const TensorFloat& emb_table, const TensorFloat& wpe_table,
                  TensorFloat& inp_embedding, TensorInt& lengths, TensorInt& decoder_result);
 
+    // EXTENSION: from now on forward() runs the sampled head with these per-slot parameters (nullptr: the greedy head)
+    void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }
+
 private:
     TensorFloat emb_score_;  // [n_batch, n_vocab]
+    const SlotSampling* sampling_ = nullptr;
 };
 
 class PagedDecoderLayer : public NonCopyableNonClonable {
@@ -91,8 +97,11 @@ public:
     void forward(const TensorFloat& batch_result, const TensorFloat& emb_table, const TensorFloat& wpe_table,
                  TensorFloatPoint& page_table, TensorInt& lengths, TensorInt& decoder_result, int i_decoder_round);
 
+    void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }  // EXTENSION, as DecoderLayer's
+
 private:
     TensorFloat emb_score_;
+    const SlotSampling* sampling_ = nullptr;
 };
 
 class PagedCublasDecoderLayer : public NonCopyableNonClonable {
@@ -102,6 +111,9 @@ public:
                  TensorFloatPoint& page_table, TensorInt& lengths, TensorInt& decoder_result, int i_decoder_round,
                  GemmHandle& handle);
 
+    void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }  // EXTENSION, as DecoderLayer's
+
 private:
     TensorFloat emb_score_;
+    const SlotSampling* sampling_ = nullptr;
 };

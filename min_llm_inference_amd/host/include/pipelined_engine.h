@@ -27,11 +27,16 @@
 // (inp, lengths, new_item_indices, decoder_result, n_new_items): one forward of any paged model
 using PagedForward = std::function<void(const TensorInt&, TensorInt&, const TensorInt&, TensorInt&, int)>;
 
+// called with the slots admitted for the next forward, after their lengths are queued and before that forward: the place
+// for further per-slot, stream-ordered device updates (the engine's sampling parameters)
+using PagedAdmitHook = std::function<void(const std::vector<int>& slots)>;
+
 // Returns the number of forward launches.
 long long run_paged_engine_pipelined(ItemStorage& item_storage, ProcessingStorage& processing_storage,
                                      MemoryBlockManager& memory_block_manager,
                                      PagedAttentionsManager& paged_attention_manager, size_t n_batch_size,
-                                     size_t n_sequence, const PagedForward& forward, int n_forward_rounds = 1);
+                                     size_t n_sequence, const PagedForward& forward, int n_forward_rounds = 1,
+                                     const PagedAdmitHook& on_admit = {});
 
 void start_paged_attention_inference_engine_pipelined(const TensorFloat& emb_table, const TensorFloat& pos_table,
                                                       ItemStorage& item_storage, ProcessingStorage& processing_storage,

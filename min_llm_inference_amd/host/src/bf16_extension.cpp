@@ -3,6 +3,7 @@
 #include <cstring>
 #include <utility>
 
+#include "kernels/decoder.h"
 #include "mli_kernels.h"
 #include "runtime.h"
 #include "utils.h"
@@ -123,7 +124,10 @@ void PagedAttentionBf16InferenceModel::forward(const TensorInt& inp, TensorInt& 
                                                        (int)n_batch_, (int)n_sequence_, (int)emb_dim_, fresh);
             attention_layer_.forward(page_table, lengths, new_item_indices, attention_result_, fresh);
         }
-        if (mli::runtime::lean_layers()) {
+        if (sampling_) {
+            launch_paged_attention_decoder_sampled(attention_result_, emb_table, emb_score_, pos_emb_table, page_table,
+                                                   lengths, decoder_result, round, MLI_ELEM_BF16, *sampling_);
+        } else if (mli::runtime::lean_layers()) {
             HIP_CHECK(mli_paged_decoder_fused(attention_result_.data(), emb_table.data(), pos_emb_table.data(),
                                               reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
                                               decoder_result.data(), (int)n_batch_, (int)emb_table.shape()[0],

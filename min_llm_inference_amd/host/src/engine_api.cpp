@@ -2,6 +2,7 @@
 // host in another language -- or bench.py -- can step them and interleave the multi-GPU token gather.
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -9,6 +10,7 @@
 #include <memory>
 #include <numeric>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "bf16_extension.h"
@@ -16,6 +18,7 @@
 #include "fp8_extension.h"
 #include "inference_model.h"
 #include "inferencer.h"
+#include "kernels/decoder.h"
 #include "mli_engine.h"
 #include "pipelined_engine.h"
 #include "runtime.h"
@@ -70,6 +73,96 @@ struct mli_engine {
     void* stream = nullptr;     // private compute stream (mli_engine_use_private_stream), else the thread's
     bool lean_layers = g_default_lean_layers.load();   // this engine's composition and replay switches (runtime.h)
     bool step_graphs = g_default_step_graphs.load();
+
+    // EXTENSION: sampled decoding (mli_engine_add_item_sampled).  The parameters live here, keyed by item
+    // id, so a preempted item keeps its stream; the decoder head reads them from per-slot device arrays, filled when an
+    // item takes a slot.  The head is chosen once, at the first step or run: sampled if a queued item has T > 0.
+    struct Sampling {
+        float temperature = 0.f;
+        int top_k = 0;
+        float top_p = 1.f;
+        unsigned long long seed = 0;
+    };
+    struct SlotArrays {  // [n_batch] each
+        TensorFloat temperature, top_p;
+        TensorInt top_k;
+        Tensor<int64_t> seed;
+        SlotArrays(size_t B, DeviceType d)
+            : temperature({B}, d, TensorDataType::SYNC_ALLOCATE), top_p({B}, d, TensorDataType::SYNC_ALLOCATE),
+              top_k({B}, d, TensorDataType::SYNC_ALLOCATE), seed({B}, d, TensorDataType::SYNC_ALLOCATE) {}
+    };
+    std::unordered_map<int, Sampling> sampling;
+    int head = -1;  // -1 = not chosen yet, 0 = greedy (the existing heads), 1 = sampled
+    std::unique_ptr<SlotArrays> slots_device, slots_host;
+    SlotSampling slot_sampling{};
+
+    Sampling sampling_of(int id) const {
+        auto it = sampling.find(id);
+        return it == sampling.end() ? Sampling{} : it->second;
+    }
+
+    void choose_head() {
+        if (head >= 0) return;
+        head = 0;
+        for (const auto& kv : sampling)
+            if (kv.second.temperature > 0.f) head = 1;
+        if (!head) return;
+        const size_t B = cfg.n_batch;
+        slots_device = std::make_unique<SlotArrays>(B, DeviceType::DEVICE);
+        slots_host = std::make_unique<SlotArrays>(B, DeviceType::HOST);
+        for (size_t b = 0; b < B; ++b) set_slot_host((int)b, Sampling{});
+        upload_slots();
+        slot_sampling = {slots_device->temperature.data(), slots_device->top_k.data(), slots_device->top_p.data(),
+                         slots_device->seed.data()};
+        if (naive_model) naive_model->set_sampling(&slot_sampling);
+        if (paged_model) paged_model->set_sampling(&slot_sampling);
+        if (gemm_model) gemm_model->set_sampling(&slot_sampling);
+        if (bf16_model) bf16_model->set_sampling(&slot_sampling);
+        if (fp8_model) fp8_model->set_sampling(&slot_sampling);
+    }
+
+    void set_slot_host(int b, const Sampling& s) {
+        slots_host->temperature.data()[b] = s.temperature;
+        slots_host->top_k.data()[b] = s.top_k;
+        slots_host->top_p.data()[b] = s.top_p;
+        slots_host->seed.data()[b] = (int64_t)s.seed;
+    }
+
+    void upload_slots() {
+        slots_device->temperature.copy_from(slots_host->temperature);
+        slots_device->top_k.copy_from(slots_host->top_k);
+        slots_device->top_p.copy_from(slots_host->top_p);
+        slots_device->seed.copy_from(slots_host->seed);
+    }
+
+    // sequential loop: after the whole-tensor insert, every slot's parameters in the same stream-ordered way
+    void refresh_slots_sequential() {
+        if (head != 1) return;
+        for (int b = 0; b < cfg.n_batch; ++b)
+            set_slot_host(b, processing_storage.batch_id_processing(b) ? sampling_of(processing_storage.get_token(b).first)
+                                                                       : Sampling{});
+        upload_slots();
+    }
+
+    // pipelined loop: the admitted slots only, by scatter (the other slots' items are in flight)
+    void scatter_admitted(const std::vector<int>& slots) {
+        if (head != 1 || slots.empty()) return;
+        std::vector<long long> idx(slots.begin(), slots.end());
+        std::vector<float> t, p;
+        std::vector<int> k;
+        std::vector<int64_t> s;
+        for (int b : slots) {
+            const Sampling v = sampling_of(processing_storage.get_token(b).first);
+            t.push_back(v.temperature);
+            k.push_back(v.top_k);
+            p.push_back(v.top_p);
+            s.push_back((int64_t)v.seed);
+        }
+        slots_device->temperature.scatter_from_host(idx.data(), t.data(), idx.size());
+        slots_device->top_k.scatter_from_host(idx.data(), k.data(), idx.size());
+        slots_device->top_p.scatter_from_host(idx.data(), p.data(), idx.size());
+        slots_device->seed.scatter_from_host(idx.data(), s.data(), idx.size());
+    }
 
     ~mli_engine() {
         if (stream) {
@@ -182,7 +275,9 @@ struct mli_engine {
         get_global_throughput_counter().start_record();
         std::vector<int> all(cfg.n_batch);
         std::iota(all.begin(), all.end(), 0);
+        choose_head();
         insert(all);
+        refresh_slots_sequential();
         started = true;
     }
 
@@ -194,6 +289,7 @@ struct mli_engine {
             throw std::runtime_error("the pipelined loop serves the paged kinds with n_forward_rounds <= PAGE_BLOCK_SIZE / 2");
         pages->set_length_reset_quirk(cfg.reference_length_reset_quirk != 0);
         get_global_throughput_counter().reset();
+        choose_head();
         started = true;
         iterations = run_paged_engine_pipelined(
             item_storage, processing_storage, *pool, *pages, cfg.n_batch, cfg.n_sequence,
@@ -210,7 +306,7 @@ struct mli_engine {
                 else
                     gemm_model->forward(inp, lengths, new_idx, result, n_new, emb_table, pos_table,
                                         pages->get_page_table_device(), handle);
-            }, cfg.n_forward_rounds);
+            }, cfg.n_forward_rounds, [&](const std::vector<int>& slots) { scatter_admitted(slots); });
     }
 
     double t_forward = 0, t_result = 0, t_pages = 0, t_insert = 0;  // host seconds per phase (MLI_ENGINE_TIMING=1)
@@ -246,6 +342,7 @@ struct mli_engine {
                                                      cfg.n_forward_rounds);
         const double t3 = now();
         insert(free_slots);
+        refresh_slots_sequential();
         if (paged() && processing_storage.size() == 0 && item_storage.new_count() > 0)
             throw std::runtime_error("paged engine: the page pool is too small for the next queued item");
         const double t4 = now();
@@ -323,6 +420,31 @@ void mli_engine_destroy(mli_engine* e) {
 int mli_engine_add_item(mli_engine* e, int id, const int* tokens, int n_tokens) {
     if (!e || !tokens || n_tokens <= 0 || n_tokens + 1 > e->cfg.n_sequence) { g_last_error = "bad item"; return -1; }
     MLI_GUARD(e->item_storage.add_new_item(std::make_pair(id, std::vector<int>(tokens, tokens + n_tokens))))
+}
+
+int mli_engine_add_item_sampled(mli_engine* e, int id, const int* tokens, int n_tokens, float temperature, int top_k,
+                                float top_p, unsigned long long seed) {
+    if (!e || !tokens || n_tokens <= 0 || n_tokens + 1 > e->cfg.n_sequence) { g_last_error = "bad item"; return -1; }
+    MLI_GUARD({
+        if (!(temperature >= 0.f) || !std::isfinite(temperature))
+            throw std::invalid_argument("sampled item: temperature must be finite and >= 0");
+        if (top_k < 0) throw std::invalid_argument("sampled item: top_k must be >= 0");
+        if (!(top_p > 0.f && top_p <= 1.f)) throw std::invalid_argument("sampled item: top_p must lie in (0, 1]");
+        if (e->cfg.reference_length_reset_quirk)
+            throw std::invalid_argument("sampled items and the reference's length-reset quirk exclude each other (its "
+                                        "length resets replay positions)");
+        if (e->sampling.count(id)) throw std::invalid_argument("sampled item: duplicate id " + std::to_string(id));
+        if (e->head == 0 && temperature > 0.f)
+            throw std::runtime_error("this engine chose the greedy head at its first step: a sampled item (temperature "
+                                     "> 0) must be queued before the first step or run");
+        e->item_storage.add_new_item(std::make_pair(id, std::vector<int>(tokens, tokens + n_tokens)));
+        mli_engine::Sampling params;
+        params.temperature = temperature;
+        params.top_k = top_k;
+        params.top_p = top_p;
+        params.seed = seed;
+        e->sampling[id] = params;
+    })
 }
 
 int mli_engine_use_private_stream(mli_engine* e) {

@@ -2,6 +2,7 @@
 
 #include <utility>
 
+#include "kernels/decoder.h"
 #include "mli_kernels.h"
 #include "runtime.h"
 #include "utils.h"
@@ -35,7 +36,7 @@ PagedAttentionFp8InferenceModel::PagedAttentionFp8InferenceModel(PagedAttentionF
                                                                  size_t n_sequence, size_t emb_dim, size_t n_vocab,
                                                                  int n_forward_rounds)
     : attention_layer_(std::move(attention_layer)), n_batch_(n_batch), n_sequence_(n_sequence), emb_dim_(emb_dim),
-      attention_result_(std::vector<size_t>{n_batch, emb_dim}, DeviceType::DEVICE),
+      n_vocab_(n_vocab), attention_result_(std::vector<size_t>{n_batch, emb_dim}, DeviceType::DEVICE),
       decoder_scratch_(std::vector<size_t>{(mli_decoder_scratch_bytes((int)n_batch, (int)n_vocab) + 3) / 4}, DeviceType::DEVICE),
       n_forward_rounds_(n_forward_rounds) {}
 
@@ -46,6 +47,11 @@ void PagedAttentionFp8InferenceModel::forward(const TensorInt& inp, TensorInt& l
         const int fresh = round == 0 ? n_new_items : 0;  // later rounds only decode
         attention_layer_.prefill(emb_table, pos_emb_table, inp, page_table, lengths, new_item_indices, fresh);
         attention_layer_.forward(page_table, lengths, new_item_indices, attention_result_, 0);
+        if (sampling_) {
+            launch_paged_attention_decoder_sampled(attention_result_, emb_table, *emb_score_, pos_emb_table, page_table,
+                                                   lengths, decoder_result, round, MLI_ELEM_FP8, *sampling_);
+            continue;
+        }
         HIP_CHECK(mli_paged_decoder_fused(attention_result_.data(), emb_table.data(), pos_emb_table.data(),
                                           reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
                                           decoder_result.data(), (int)n_batch_, (int)emb_table.shape()[0],
@@ -53,4 +59,10 @@ void PagedAttentionFp8InferenceModel::forward(const TensorInt& inp, TensorInt& l
                                           decoder_scratch_.data(), decoder_scratch_.get_total_size() * sizeof(float),
                                           mli::runtime::compute_stream()));
     }
+}
+
+void PagedAttentionFp8InferenceModel::set_sampling(const SlotSampling* sampling) {
+    if (sampling && !emb_score_)
+        emb_score_ = std::make_unique<TensorFloat>(std::vector<size_t>{n_batch_, n_vocab_}, DeviceType::DEVICE);
+    sampling_ = sampling;
 }

@@ -6,6 +6,7 @@
 #include "kernels/encoder.h"
 #include "kernels/paged_attention.h"
 #include "kernels/self_attention_inference_optimized.h"
+#include "mli_kernels.h"
 #include "runtime.h"
 
 namespace {
@@ -111,7 +112,10 @@ DecoderLayer::DecoderLayer(size_t n_batch, size_t n_vocab) : emb_score_(device_t
 void DecoderLayer::forward(const TensorFloat& batch_result, const TensorFloat& emb_table,
                            const TensorFloat& wpe_table, TensorFloat& inp_embedding, TensorInt& lengths,
                            TensorInt& decoder_result) {
-    if (mli::runtime::lean_layers())
+    if (sampling_)
+        launch_decoder_sampled(batch_result, emb_table, emb_score_, wpe_table, inp_embedding, lengths, decoder_result,
+                               *sampling_);
+    else if (mli::runtime::lean_layers())
         launch_decoder_fused(batch_result, emb_table, emb_score_, wpe_table, inp_embedding, lengths, decoder_result);
     else
         launch_decoder(batch_result, emb_table, emb_score_, wpe_table, inp_embedding, lengths, decoder_result);
@@ -123,7 +127,10 @@ PagedDecoderLayer::PagedDecoderLayer(size_t n_batch, size_t n_vocab)
 void PagedDecoderLayer::forward(const TensorFloat& batch_result, const TensorFloat& emb_table,
                                 const TensorFloat& wpe_table, TensorFloatPoint& page_table, TensorInt& lengths,
                                 TensorInt& decoder_result, int i_decoder_round) {
-    if (mli::runtime::lean_layers())
+    if (sampling_)
+        launch_paged_attention_decoder_sampled(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
+                                               decoder_result, i_decoder_round, MLI_ELEM_F32, *sampling_);
+    else if (mli::runtime::lean_layers())
         launch_paged_attention_decoder_fused(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
                                              decoder_result, i_decoder_round);
     else
@@ -138,7 +145,10 @@ void PagedCublasDecoderLayer::forward(const TensorFloat& batch_result, const Ten
                                       const TensorFloat& wpe_table, TensorFloatPoint& page_table,
                                       TensorInt& lengths, TensorInt& decoder_result, int i_decoder_round,
                                       GemmHandle& handle) {
-    if (mli::runtime::lean_layers())
+    if (sampling_)
+        launch_paged_attention_decoder_sampled(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
+                                               decoder_result, i_decoder_round, MLI_ELEM_F32, *sampling_);
+    else if (mli::runtime::lean_layers())
         launch_paged_attention_decoder_fused(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
                                              decoder_result, i_decoder_round);
     else

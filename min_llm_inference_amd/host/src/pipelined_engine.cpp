@@ -28,7 +28,8 @@ struct MarkerHandle {
 
 long long run_paged_engine_pipelined(ItemStorage& item_storage, ProcessingStorage& processing_storage,
                                      MemoryBlockManager& pool, PagedAttentionsManager& pages, size_t n_batch_size,
-                                     size_t n_sequence, const PagedForward& forward, int n_forward_rounds) {
+                                     size_t n_sequence, const PagedForward& forward, int n_forward_rounds,
+                                     const PagedAdmitHook& on_admit) {
     // Every in-flight row has up to R tokens in flight and is about to produce R more, so the page bookkeeping is asked
     // for tokens + 2 R positions; its rule "a row needs at most one more page per pass" holds while 2 R <= PAGE_BLOCK_SIZE.
     const int R = n_forward_rounds;
@@ -94,6 +95,7 @@ long long run_paged_engine_pipelined(ItemStorage& item_storage, ProcessingStorag
                                              static_cast<size_t>(hi - lo) * S + lengths_host.data()[hi]);
         }
         lengths_device.scatter_from_host(idx.data(), val.data(), idx.size());
+        if (on_admit) on_admit(adm.slots);
         new_idx_device.copy_range_from_async(staging, 0, adm.slots.size());
         pages.maybe_flush_changes();
         return static_cast<int>(adm.slots.size());

@@ -337,6 +337,59 @@ def paged_decoder_fused(batch_result, emb_table, wpe_table, page_table, lengths,
                                                   _stream()), "mli_paged_decoder_fused")
 
 
+def _sampling_args(temperature, top_k, top_p, seed):
+    """The four per-row parameter arrays of the sampled heads (device tensors: f32, i32, f32, i64)."""
+    for t, dt, name in ((temperature, torch.float32, "temperature"), (top_k, torch.int32, "top_k"),
+                        (top_p, torch.float32, "top_p"), (seed, torch.int64, "seed")):
+        if t.dtype != dt:
+            raise MliError(f"{name} must be {dt}, got {t.dtype}")
+    return _p(temperature), _p(top_k), _p(top_p), _p(seed)
+
+
+def sample_tokens(logits, temperature, top_k, top_p, seed, lengths, tokens=None):
+    """EXTENSION: seeded temperature / top-k / top-p draw per row of logits [B, V] at position lengths[b]
+    (mli_sample_tokens).  Returns tokens [B] int32."""
+    B, V = logits.shape
+    if tokens is None:
+        tokens = torch.empty(B, dtype=torch.int32, device=logits.device)
+    lib = load_library()
+    need = int(lib.mli_sample_scratch_bytes(B, V))
+    sc = torch.empty(max(need, 16), dtype=torch.uint8, device=logits.device) if need else None
+    _check(lib.mli_sample_tokens(_p(logits), *_sampling_args(temperature, top_k, top_p, seed), _p(lengths), _p(tokens),
+                                 B, V, _p(sc), need, _stream()), "mli_sample_tokens")
+    return tokens
+
+
+def _sampled_scratch(n_batch, n_vocab, device):
+    need = int(load_library().mli_decoder_sampled_scratch_bytes(n_batch, n_vocab))
+    return torch.empty(max(need, 16), dtype=torch.uint8, device=device), need
+
+
+def decoder_sampled(batch_result, emb_table, wpe_table, inp_embedding, lengths, decoder_result, temperature, top_k,
+                    top_p, seed):
+    """EXTENSION: decoder_fused with the sampled head (mli_decoder_sampled): logits GEMM, draw, length update, next
+    embedding."""
+    B, D = batch_result.shape
+    sc, need = _sampled_scratch(B, emb_table.shape[0], batch_result.device)
+    _check(load_library().mli_decoder_sampled(_p(batch_result), _p(emb_table), _p(wpe_table), _p(inp_embedding),
+                                              _p(lengths), _p(decoder_result), B, emb_table.shape[0],
+                                              wpe_table.shape[0], D, *_sampling_args(temperature, top_k, top_p, seed),
+                                              _p(sc), need, _stream()), "mli_decoder_sampled")
+
+
+def paged_decoder_sampled(batch_result, emb_table, wpe_table, page_table, lengths, decoder_result, i_decoder, elem,
+                          temperature, top_k, top_p, seed):
+    """EXTENSION: paged_decoder_fused with the sampled head (mli_paged_decoder_sampled)."""
+    B, D = batch_result.shape
+    n_res = decoder_result.shape[1] if decoder_result.dim() == 2 else 1
+    sc, need = _sampled_scratch(B, emb_table.shape[0], batch_result.device)
+    _check(load_library().mli_paged_decoder_sampled(_p(batch_result), _p(emb_table), _p(wpe_table), _p(page_table),
+                                                    _p(lengths), _p(decoder_result), B, emb_table.shape[0],
+                                                    wpe_table.shape[0], D, n_res, i_decoder, int(elem),
+                                                    *_sampling_args(temperature, top_k, top_p, seed), _p(sc), need,
+                                                    _stream()), "mli_paged_decoder_sampled")
+
+
 def stream_wait_stream(waiter, signaller):
     """torch streams: `waiter` waits for everything queued on `signaller` so far (mli_stream_wait_stream)."""
     _check(load_library().mli_stream_wait_stream(ctypes.c_void_p(waiter.cuda_stream), ctypes.c_void_p(signaller.cuda_stream)),
