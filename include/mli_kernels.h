@@ -400,14 +400,6 @@ int mli_f32_to_fp8(const float* src, uint8_t* dst, size_t n, void* stream);
  *   "nt_loads"         non-temporal hint on the K/V stream: 2 (default) = where the rows' K/V (n_batch * n_sequence *
  *                      emb_dim * 2 elements) exceeds 768 MiB, i.e. nothing of it survives in the 256 MiB Infinity Cache
  *                      until the next step; 1 = always, 0 = never (plain loads)
- *   "qkt_token_batch"  4 | 8 (default) | 16: K rows a wave keeps in flight per load batch
- *   "flash_decode"     1 (default) = the paged compositions run the single-pass fused scan (each page visited
- *                      once for K and V, online softmax) when emb_dim fits (fp32 <= 2048, bf16 <= 4096);
- *                      0 = separate q.K^T / softmax / softmax.V passes
- *   "scan_partial_last" 1 (default) = the single-pass scan runs full chunks first and every row's remainder behind
- *                      them, cut into pieces of "scan_tail_tokens" tokens (what is still running when the queue runs
- *                      dry is short), 0 = plain chunk order
- *   "scan_tail_tokens" 0 (default) = the remainder stays one piece, else a power of two in [64, chunk]: piece size
  *   "scan_stream"      (lean mode) 1 (default) = batches that fill the chip (n_batch * n_sequence >= 2^21, n_batch <= 2048,
  *                      n_sequence >= 256) are scanned in EQUAL PAGE SHARES: the pages of all rows form one sequence
  *                      that 2 x CUs workgroups split evenly, each streaming its share across row boundaries and merging
@@ -420,8 +412,6 @@ int mli_f32_to_fp8(const float* src, uint8_t* dst, size_t n, void* stream);
  *                      many pages (default 64, 16..256) to the workgroups that finish their share first
  *   "scan_merge"       (lean mode) 1 (default) = the workgroup that completes a row merges its chunks inside the scan
  *                      launch, 0 = a separate combine launch; bit-identical results
- *   "scan_dynamic_items" 1 = the single-pass scan hands its (row, chunk) items out through a ticket counter (balances
- *                      the XCDs on ragged lengths; the counter reset costs what it gains), 0 (default) = by grid position
  *   "fused_softmax"    (separate-pass form only) 1 = the compositions fold the masked softmax into the qkt / softmax.V kernels, 0 = three
  *                      launches as the reference (qkt, softmax_in_place_with_lengths, softmax_v), -1 (default) =
  *                      fuse when n_batch * n_sequence <= 2^20 (launch-bound steps)
@@ -430,9 +420,6 @@ int mli_f32_to_fp8(const float* src, uint8_t* dst, size_t n, void* stream);
  *   "latest_compact"   1 (default) = the decode projection multiplies a device-built list of the non-empty batch rows where
  *                      the reduction is >= 1024 long (building the list costs every workgroup ~2 us), 2 = wherever
  *                      possible, 0 = all rows (empty ones as zeros); identical results
- *   "gemm_deep_k"      1 (default) = the bf16 GEMM stages 128 k per tile for latency-bound shapes, 0 = 32 everywhere
- *   "naive_scan_fused" 1 (default) = mli_self_attention_lean runs the single-launch contiguous scan, 0 = it returns
- *                      MLI_ERR_BAD_ARG (callers fall back to mli_inference_self_attention)
  *   "scan_row_order"   1 (default) = single-pass scans with one workgroup per row (short sequences) and more than 512 rows
  *                      hand the rows out longest first, 0 = in grid order (identical results)
  *   "gemm_split"       1 (default) = the fp32 GEMM with 64-row tiles (prefill, logits, projections of batches that do not

@@ -92,39 +92,22 @@ __device__ __forceinline__ int longest_first_row(const int* __restrict__ lengths
     return found_row;
 }
 
-template <class E, int NJ, bool NT, int TBR, int MINW, int WAVES, bool DS = false, bool SCORES = true, int RPI = 1>
-__global__ __launch_bounds__(WAVES * kWave, MINW) void fused_decode_scan_kernel(
+template <class E, int NJ, bool NT, int TBR, bool DS, bool SCORES, int RPI>
+__global__ __launch_bounds__(kFuThreads, 2) void fused_decode_scan_kernel(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ qkt, float* __restrict__ out, float2* ml, float* partial,
-    int S, int D, int ct, int ml_per_row, int nchunk_max, int direct, unsigned* __restrict__ ticket, int tail,
-    int slots, unsigned* arrivals) {
+    int S, int D, int ct, int ml_per_row, int nchunk_max, int direct, unsigned* arrivals) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    // Which (row, chunk) this workgroup takes.  Static: its grid position.  With a ticket counter: the next item in
-    // the same order (rows fast, then chunks), whichever workgroup asks first.  Workgroups are dealt to the 8 XCDs
-    // round-robin by grid position, so the static form gives every XCD a fixed eighth of the rows -- with ragged
-    // lengths the XCDs' totals differ by +-10 % and the slowest one sets the kernel time (tools/scan_trace.py: last
-    // workgroup of an XCD at 615..701 us); tickets let the XCDs that run ahead take more items.
-    // Workgroups are dealt to the 8 XCDs round-robin by linear grid position, i.e. by blockIdx.x % 8 (n_batch is a
-    // multiple of 8 in every configuration that fills the chip).  Rotating the row index by the chunk index spreads
-    // the chunks of one row over the XCDs, so every XCD streams a mix of all rows instead of a fixed eighth of them
-    // whose total length differs from the others' by +-10 % (tools/scan_trace.py: XCDs done at 615 .. 701 us).
-    int c = blockIdx.y;
+    // Which (row, chunk) this workgroup takes follows from its grid position.  Workgroups are dealt to the 8 XCDs
+    // round-robin by linear grid position, i.e. by blockIdx.x % 8 (n_batch is a multiple of 8 in every configuration
+    // that fills the chip).  Rotating the row index by the chunk index spreads the chunks of one row over the XCDs, so
+    // every XCD streams a mix of all rows instead of a fixed eighth of them whose total length differs from the
+    // others' by +-10 % (tools/scan_trace.py: XCDs done at 615 .. 701 us).
+    const int c = blockIdx.y;
     int b = (int)((blockIdx.x + (unsigned)c) % gridDim.x);
-    if constexpr (WAVES * kWave == kFuThreads) {
-        if (direct == 2) b = longest_first_row(lengths, (int)gridDim.x, S, (int)blockIdx.x);
-    }
-    if (ticket != nullptr) {
-        __shared__ unsigned item_sh;
-        if (threadIdx.x == 0) item_sh = atomicAdd(ticket, 1u);
-        __syncthreads();
-        const unsigned item = item_sh;
-        if (item >= gridDim.x * gridDim.y) return;  // cannot happen with a zeroed counter; never index out of range
-        b = (int)(item % gridDim.x);
-        c = (int)(item / gridDim.x);
-    }
-    fused_scan_item<E, NJ, NT, TBR, WAVES, DS, SCORES, RPI>(q, page_table, lengths, qkt, out, ml, partial, S, D, ct, ml_per_row,
-                                                             nchunk_max, direct, tail, slots, arrivals, b, c, c == 0,
-                                                             (int)gridDim.x, smem_raw);
+    if (direct == 2) b = longest_first_row(lengths, (int)gridDim.x, S, (int)blockIdx.x);
+    fused_scan_item<E, NJ, NT, TBR, DS, SCORES, RPI>(q, page_table, lengths, qkt, out, ml, partial, S, D, ct, ml_per_row,
+                                                     nchunk_max, direct, arrivals, b, c, c == 0, (int)gridDim.x, smem_raw);
 }
 
 // grid = (B, kCombineParts).  Every part merges the row's chunk statistics (cheap, identical result), part 0 also
@@ -133,11 +116,11 @@ constexpr int kCombineParts = 4;
 
 __global__ __launch_bounds__(kFuThreads) void fused_decode_combine_kernel(
     const float2* __restrict__ ml, const float* __restrict__ partial, const int* __restrict__ lengths,
-    float* __restrict__ qkt, float* __restrict__ out, int S, int D, int ct, int ml_per_row, int slots, int tail) {
+    float* __restrict__ qkt, float* __restrict__ out, int S, int D, int ct, int ml_per_row, int nchunk) {
     const int b = blockIdx.x;
     const int part = blockIdx.y;
     const int L = min(lengths[b], S);
-    const int nc = row_items(L, ct, tail);
+    const int nc = (L + ct - 1) / ct;
     float* qkt_row = qkt + (int64_t)b * S;
     const int per = ((S + kCombineParts - 1) / kCombineParts + 3) & ~3;
     const int i0 = part * per, i1 = min(S, i0 + per);
@@ -153,7 +136,7 @@ __global__ __launch_bounds__(kFuThreads) void fused_decode_combine_kernel(
     for (int i = 0; i < nc; ++i) l = fmaf(row[i].y, expf(row[i].x - m), l);
     const float inv_l = 1.f / l;
     if (part == 0) {
-        const float* pr = partial + (int64_t)b * slots * D;
+        const float* pr = partial + (int64_t)b * nchunk * D;
         for (int d = threadIdx.x; d < D; d += kFuThreads) {
             float r = 0.f;
             for (int i = 0; i < nc; ++i) r = fmaf(pr[(int64_t)i * D + d], expf(row[i].x - m), r);
@@ -164,30 +147,12 @@ __global__ __launch_bounds__(kFuThreads) void fused_decode_combine_kernel(
     for (int i = i0 + threadIdx.x; i < i1; i += kFuThreads) qkt_row[i] = i < L ? expf(qkt_row[i] - m) * inv_l : 0.f;
 }
 
-static thread_local int g_flash = 1;
-static thread_local int g_flash_variant = 0;  // register-budget variants of the scan kernel (tuning)
-// mli_tune "scan_partial_last": 1 (default) = full chunks first, every row's remainder behind them in pieces of
-// "scan_tail_tokens" tokens; 0 = plain chunk order
-static thread_local int g_partial_last = 1;
-void set_partial_last(int v) { g_partial_last = v != 0; }
-// mli_tune "scan_tail_tokens": 0 (default) = the whole remainder as one piece, else a power of two in [64, chunk].
-// Measured at config 4 (bf16, 512-token chunks, lean form): one piece 658.7 us, 256-token pieces 661.9, 128: 668.7,
-// 64: 688.0 -- every item costs about 2.5 us of a workgroup slot (prologue chain lengths -> page pointers -> first K
-// rows, epilogue merge and publication), more than the shorter end of the launch gives back.
-static thread_local int g_tail_tokens = 0;
-void set_tail_tokens(int v) { g_tail_tokens = v; }
-// mli_tune "scan_dynamic_items": ticketed (row, chunk) assignment.  Off by default: it shortens the kernel by 0.6-1.5 %
-// (4-10 us at config 4), and the hipMemsetAsync that zeroes the counter before every launch costs the stream ~8 us.
-static thread_local int g_dynamic_items = 0;
-void set_dynamic_items(int v) { g_dynamic_items = v != 0; }
-// mli_tune "scan_merge" (lean mode only): 1 (default) = the workgroup that completes a row merges its chunks inside
-// the scan launch, 0 = the separate combine launch (bit-identical results)
 static thread_local int g_row_order = 1;  // mli_tune "scan_row_order": 0 = one-workgroup-per-row grids take the rows in grid order
 void set_row_order(int v) { g_row_order = v != 0; }
+// mli_tune "scan_merge" (lean mode only): 1 (default) = the workgroup that completes a row merges its chunks inside
+// the scan launch, 0 = the separate combine launch (bit-identical results)
 static thread_local int g_scan_merge = 1;
 void set_scan_merge(int v) { g_scan_merge = v != 0; }
-void set_flash_decode(int v) { g_flash = v != 0; }
-void set_flash_variant(int v) { g_flash_variant = v; }
 
 // Tokens per workgroup of the single-pass scan: the largest power of two <= 512 that still cuts the batch into
 // >= 2048 (row, chunk) slots, i.e. with ragged lengths about two rounds of real items for the 512 workgroups the chip
@@ -195,7 +160,7 @@ void set_flash_variant(int v) { g_flash_variant = v; }
 // scan launch: 46.9 us against 49.6 at 256 and 54.3 at 512, where 384 items of very unequal size cannot even fill the
 // 512 slots once; lean form 52.5 / 53.1 / 56.2).
 static int fused_chunk_tokens(int B, int S) {
-    if (tuned_chunk_tokens() != 0) return sv_chunk_tokens_for(B, S);  // forced (mli_tune / MLI_CHUNK_TOKENS)
+    if (tuned_chunk_tokens() != 0) return sv_chunk_tokens_for(B, S);  // forced (mli_tune)
     int ct = 512;
     while (ct > 64 && (int64_t)B * ceil_div_i(S, ct) < 2048) ct >>= 1;
     return ct;
@@ -210,7 +175,7 @@ static int launch_fused_decode(const float* q, const void* const* page_table, co
                                float* out, int B, int S, int D, void* ws, size_t ws_bytes, hipStream_t st,
                                int phases = 3) {
     const bool lean = (phases & 4) != 0;
-    if (lean && g_scan_merge && g_flash) {
+    if (lean && g_scan_merge) {
         // chip-filling batches: equal page shares instead of (row, chunk) workgroups (attention_stream.hip); one launch
         // does the whole job, so the "combine only" phase has nothing left to do
         const int r = (phases & 1) ? launch_stream_decode<E>(q, page_table, lengths, out, B, S, D, ws, ws_bytes, st)
@@ -219,22 +184,19 @@ static int launch_fused_decode(const float* q, const void* const* page_table, co
     }
     const int Du = D / E::EPL;
     const int nj = ceil_div_i(Du, kWave);
-    if (!g_flash || nj > 8 || D % E::EPL != 0 || S % kPage != 0) return 0;
+    if (nj > 8 || D % E::EPL != 0 || S % kPage != 0) return 0;
     constexpr bool kFp8 = std::is_same<E, ElemFP8>::value;
     if (kFp8 && (!lean || nj > 2)) return 0;   // the fp8 extension: lean form, rows of up to two lane loads (emb_dim <= 2048)
     // fp8 rows narrower than one load instruction: 2 or 4 token slots per instruction (scan_common.hpp)
     const int rpi = kFp8 ? (Du <= 16 ? 4 : Du <= 32 ? 2 : 1) : 1;
     const bool dsplit = nj > 2;  // wide rows: the four waves split the row instead of the pages
     const int nj_ds = ceil_div_i(Du, kWave * kFuWaves);  // 1 or 2
-    // variant 3: single-wave workgroups of 128 tokens -- every wave is its own scheduling unit, no LDS merge,
-    // no barrier; the hardware dispatcher does the load balancing
-    const bool solo = g_flash_variant == 3 && S > 128 && !dsplit && !(phases & 4);
     // short sequences with a full batch: one workgroup per row (no partials, no combine launch) beats two 64-token
     // chunks (README workload, S = 128: 200 vs 209 us)
-    const int ct = solo ? 128 : (S <= 128 && B >= 256 && tuned_chunk_tokens() == 0) ? 128 : fused_chunk_tokens(B, S);
+    const int ct = (S <= 128 && B >= 256 && tuned_chunk_tokens() == 0) ? 128 : fused_chunk_tokens(B, S);
     const int nchunk = ceil_div_i(S, ct);
     // one workgroup per row: hand the rows out longest first where the batch has more rows than the chip has workgroup slots
-    const bool ordered = g_row_order && nchunk == 1 && !solo && B > 512 && B <= kMaxOrderedRows && S / kPage <= kMaxOrderedPages;
+    const bool ordered = g_row_order && nchunk == 1 && B > 512 && B <= kMaxOrderedRows && S / kPage <= kMaxOrderedPages;
     const int direct = nchunk == 1 ? (ordered ? 2 : 1) : 0;
     const size_t stats_bytes = stats_region_bytes_for(B, S);
     float2* ml = nullptr;
@@ -248,92 +210,47 @@ static int launch_fused_decode(const float* q, const void* const* page_table, co
     // lean mode: arrival counters (one per row, zero between launches) in front of the workspace body
     unsigned* arrivals = nullptr;
     if (lean && !direct && g_scan_merge && B <= kMaxArrivalRows) arrivals = ws_arrivals(ws);  // ws != nullptr: checked above
-    // ticket counter for the dynamic (row, chunk) assignment: in the part of the workspace the partial sums of this
-    // chunk size leave unused, zeroed on the stream before every launch
-    unsigned* ticket = nullptr;
-    if (!direct && g_dynamic_items && (phases & 1) && (int64_t)B * nchunk >= 1024) {
-        const size_t off = (stats_bytes + (size_t)B * nchunk * D * sizeof(float) + 255) & ~(size_t)255;
-        if (off + sizeof(unsigned) <= ws_bytes) {
-            ticket = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + off);
-            if (hipMemsetAsync(ticket, 0, sizeof(unsigned), st) != hipSuccess) ticket = nullptr;
-        }
-    }
-    const int waves = solo ? 1 : kFuWaves;
     // page pointers of the chunk | reduction buffer (also holds the row's chunk statistics during the in-kernel merge)
-    const size_t red_bytes = (dsplit ? (size_t)2 * kFuWaves * 16 : (size_t)waves * nj * (kWave / rpi) * E::EPL) * sizeof(float);
+    const size_t red_bytes = (dsplit ? (size_t)2 * kFuWaves * 16 : (size_t)kFuWaves * nj * (kWave / rpi) * E::EPL) * sizeof(float);
     const size_t stat_bytes_row = (size_t)ml_per_row * 8;  // upper bound of the triples a row can have
     const size_t smem = (size_t)(ct / kPage) * 8 + (red_bytes > stat_bytes_row ? red_bytes : stat_bytes_row);
-    dim3 grid(B, nchunk);
-    // tail > 0: full chunks first, the remainders behind them in pieces of `tail` tokens (slots = triples per row)
-    int tail = 0, slots = nchunk;
-    if (!direct && ticket == nullptr && g_partial_last) {
-        tail = g_tail_tokens ? g_tail_tokens : ct;
-        if (tail > ct || tail < 64 || (tail & (tail - 1))) tail = ct;
-        // a row with a remainder has at most nchunk - 1 full chunks: nchunk + pieces - 1 triples per row at most (the
-        // workspace is sized for 64-token chunks: room for every layout with no more items per row than that)
-        if (nchunk + ct / tail - 1 > ml_per_row) tail = ct;
-        slots = nchunk + ct / tail - 1;
-        grid = dim3(B, nchunk + ct / tail);
-        if ((size_t)B * slots * D * sizeof(float) + stats_bytes > ws_bytes) return 0;
-    }
+    // several chunks per row: grid rows 0 .. nchunk-1 run the full chunks, grid row nchunk every row's remainder as one
+    // item (fused_scan_item)
+    const dim3 grid(B, direct ? 1 : nchunk + 1);
     const bool nt = nt_loads_for(B, S, D, E::kBytes);
-#define MLI_FU_LAUNCH(NJ, NT, TBR, MINW, WAVES, ...)                                                              \
-    hipLaunchKernelGGL((fused_decode_scan_kernel<E, NJ, NT, TBR, MINW, WAVES, ##__VA_ARGS__>), grid,               \
-                       dim3(WAVES * kWave), smem, st, q, page_table, lengths, qkt, out, ml, partial, S, D, ct,     \
-                       ml_per_row, nchunk, direct, ticket, tail, slots, arrivals)
+    // TBR = rows per load batch: TBR * RPI = 8 token slots for rows of one lane load, 4 for rows of two
+#define MLI_FU_LAUNCH(NJ, DS, SCORES, RPI)                                                                                \
+    do {                                                                                                                 \
+        if (nt)                                                                                                          \
+            hipLaunchKernelGGL((fused_decode_scan_kernel<E, NJ, true, (NJ == 1 ? 8 : 4) / RPI, DS, SCORES, RPI>), grid,  \
+                               dim3(kFuThreads), smem, st, q, page_table, lengths, qkt, out, ml, partial, S, D, ct,      \
+                               ml_per_row, nchunk, direct, arrivals);                                                     \
+        else                                                                                                             \
+            hipLaunchKernelGGL((fused_decode_scan_kernel<E, NJ, false, (NJ == 1 ? 8 : 4) / RPI, DS, SCORES, RPI>), grid, \
+                               dim3(kFuThreads), smem, st, q, page_table, lengths, qkt, out, ml, partial, S, D, ct,      \
+                               ml_per_row, nchunk, direct, arrivals);                                                     \
+    } while (0)
     if constexpr (kFp8) {
         if (phases & 1) {
-            if (rpi == 4) {
-                if (nt) MLI_FU_LAUNCH(1, true, 2, 2, 4, false, false, 4);
-                else MLI_FU_LAUNCH(1, false, 2, 2, 4, false, false, 4);
-            } else if (rpi == 2) {
-                if (nt) MLI_FU_LAUNCH(1, true, 4, 2, 4, false, false, 2);
-                else MLI_FU_LAUNCH(1, false, 4, 2, 4, false, false, 2);
-            } else if (nj == 1) {
-                if (nt) MLI_FU_LAUNCH(1, true, 8, 2, 4, false, false);
-                else MLI_FU_LAUNCH(1, false, 8, 2, 4, false, false);
-            } else {
-                if (nt) MLI_FU_LAUNCH(2, true, 4, 2, 4, false, false);
-                else MLI_FU_LAUNCH(2, false, 4, 2, 4, false, false);
-            }
-        }
-    } else if ((phases & 1) && lean) {
-        // the default register budget only (the variants are tuning experiments of the materialising form)
-        if (dsplit) {
-            if (nj_ds == 1) {
-                if (nt) MLI_FU_LAUNCH(1, true, 8, 2, 4, true, false);
-                else MLI_FU_LAUNCH(1, false, 8, 2, 4, true, false);
-            } else {
-                if (nt) MLI_FU_LAUNCH(2, true, 4, 2, 4, true, false);
-                else MLI_FU_LAUNCH(2, false, 4, 2, 4, true, false);
-            }
-        } else if (nj == 1) {
-            if (nt) MLI_FU_LAUNCH(1, true, 8, 2, 4, false, false);
-            else MLI_FU_LAUNCH(1, false, 8, 2, 4, false, false);
-        } else {
-            if (nt) MLI_FU_LAUNCH(2, true, 4, 2, 4, false, false);
-            else MLI_FU_LAUNCH(2, false, 4, 2, 4, false, false);
+            if (rpi == 4) MLI_FU_LAUNCH(1, false, false, 4);
+            else if (rpi == 2) MLI_FU_LAUNCH(1, false, false, 2);
+            else if (nj == 1) MLI_FU_LAUNCH(1, false, false, 1);
+            else MLI_FU_LAUNCH(2, false, false, 1);
         }
     } else if (phases & 1) {
-        if (dsplit) {
-            if (nj_ds == 1) {
-                if (nt) MLI_FU_LAUNCH(1, true, 8, 2, 4, true);
-                else MLI_FU_LAUNCH(1, false, 8, 2, 4, true);
+        const auto launch = [&](auto scores) {  // SCORES: the materialising form
+            constexpr bool SC = decltype(scores)::value;
+            if (dsplit) {
+                if (nj_ds == 1) MLI_FU_LAUNCH(1, true, SC, 1);
+                else MLI_FU_LAUNCH(2, true, SC, 1);
+            } else if (nj == 1) {
+                MLI_FU_LAUNCH(1, false, SC, 1);
             } else {
-                if (nt) MLI_FU_LAUNCH(2, true, 4, 2, 4, true);
-                else MLI_FU_LAUNCH(2, false, 4, 2, 4, true);
+                MLI_FU_LAUNCH(2, false, SC, 1);
             }
-        } else if (nj == 1) {
-            if (!nt) MLI_FU_LAUNCH(1, false, 8, 2, 4);
-            else if (solo) MLI_FU_LAUNCH(1, true, 8, 2, 1);
-            else if (g_flash_variant == 2) MLI_FU_LAUNCH(1, true, 4, 4, 4);
-            else MLI_FU_LAUNCH(1, true, 8, 2, 4);
-        } else {
-            if (!nt) MLI_FU_LAUNCH(2, false, 4, 2, 4);
-            else if (solo) MLI_FU_LAUNCH(2, true, 4, 2, 1);
-            else if (g_flash_variant == 2) MLI_FU_LAUNCH(2, true, 2, 4, 4);
-            else MLI_FU_LAUNCH(2, true, 4, 2, 4);
-        }
+        };
+        if (lean) launch(std::false_type{});
+        else launch(std::true_type{});
     }
 #undef MLI_FU_LAUNCH
     int rc = launch_status();
@@ -341,7 +258,7 @@ static int launch_fused_decode(const float* q, const void* const* page_table, co
     if (!direct && (phases & 2) && arrivals == nullptr) {
         // lean: one part per row, no score pass (qkt == nullptr)
         hipLaunchKernelGGL(fused_decode_combine_kernel, dim3(B, lean ? 1 : kCombineParts), dim3(kFuThreads), 0, st, ml,
-                           partial, lengths, lean ? nullptr : qkt, out, S, D, ct, ml_per_row, slots, tail);
+                           partial, lengths, lean ? nullptr : qkt, out, S, D, ct, ml_per_row, nchunk);
         rc = launch_status();
         if (rc) return rc > 0 ? rc + 1 : rc;
     }

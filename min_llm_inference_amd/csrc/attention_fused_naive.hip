@@ -189,16 +189,13 @@ __global__ __launch_bounds__(kNvThreads) void naive_decode_scan_kernel(
                                   &last_sh);
 }
 
-static thread_local int g_naive_fused = 1;  // mli_tune "naive_scan_fused": 0 = the lean contiguous composition is not offered
-void set_naive_fused(int v) { g_naive_fused = v != 0; }
-
 static inline bool aligned16_nv(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // 1 = ran, 0 = shape not covered (the caller takes the three-launch composition), else an error (+1 if positive).
 // ws = workspace BODY (the arrival counters sit in front of it).
 int launch_fused_decode_naive(const float* q, const float* kt, const float* v, const int* lengths, float* out, int B,
                               int S, int D, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (!g_naive_fused || B <= 0 || D % 4 != 0 || S % 4 != 0 || D <= 0 || S <= 0) return 0;
+    if (B <= 0 || D % 4 != 0 || S % 4 != 0 || D <= 0 || S <= 0) return 0;
     if (!aligned16_nv(kt) || !aligned16_nv(v) || !aligned16_nv(out)) return 0;
     const int nchunk = ceil_div_i(S, kNvChunk);
     // the last arriver keeps the row's chunk statistics in the 4 KiB score-partial buffer: 512 (max, sum) pairs

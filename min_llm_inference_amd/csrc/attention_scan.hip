@@ -21,36 +21,27 @@ constexpr int kMaxChunkTokens = 1024;
 constexpr int kMinChunkTokens = 64;
 
 void set_bf16_native_mfma(int v);  // proj_gemm.hip
-void set_flash_decode(int v);      // attention_fused.hip
-void set_flash_variant(int v);
-void set_scan_merge(int v);
+void set_scan_merge(int v);        // attention_fused.hip
 void set_gemm_panel(int v);
-void set_tail_tokens(int v);
 void set_scan_stream(int v);
 void set_scan_stream_min(int v);
 void set_stream_dyn_pct(int v);
 void set_stream_granule(int v);
-void set_dynamic_items(int v);
-void set_partial_last(int v);
 void set_gemm_split(int v);
 void set_row_order(int v);
 void set_bf16_split(int v);
 void set_prefill_fused(int v);
-void set_naive_fused(int v);
 void set_gemm_tall_tiles(int v);
-void set_deep_k_tiles(int v);
 void set_fill_compact(int v);
 void set_latest_compact(int v);
 
 // Tuning knobs (mli_tune): 0 = use the built-in heuristic / default.
 static thread_local int g_chunk_tokens = 0;
 static thread_local int g_nt_loads = 2;  // 0 = default cache policy, 1 = non-temporal, 2 = by working set (nt_loads_for)
-static thread_local int g_qkt_token_batch = 8;
 
 // Sequence chunk (tokens per workgroup) for the split-sequence kernels: the largest power of two in
 // [64, 1024] that still yields >= min_units work units.  With rows as the fast grid dimension the choice is
 // worth a few percent (measured on MI355X at B=1024, S=4096: q.K^T 256, softmax.V 512).
-// MLI_CHUNK_TOKENS (power of two in [64, 1024]) overrides the heuristic for tuning runs.
 constexpr int kQktUnits = 16384;  // q.K^T is insensitive to the chunk size (341-349 us for 64..512 tokens at config 4)
 // softmax.V: at most 512 tokens (fewer partial sums to write and combine than q.K^T's chunks), shrunk until there are
 // >= 2048 units.  Measured: B=1024, S=4096 -> 512 (8192 units); B=256, S=1024 -> 128 (26.5 us; 64: 32.8, 256: 27.8,
@@ -59,12 +50,6 @@ constexpr int kSvUnits = 2048;
 constexpr int kSvMaxChunkTokens = 512;
 
 static int pick_chunk_tokens(int n_batch, int n_sequence, int min_units = kQktUnits, int max_ct = kMaxChunkTokens) {
-    static const int forced = [] {
-        const char* e = getenv("MLI_CHUNK_TOKENS");
-        const int v = e ? atoi(e) : 0;
-        return (v >= kMinChunkTokens && v <= kMaxChunkTokens && (v & (v - 1)) == 0) ? v : 0;
-    }();
-    if (forced) return forced;
     if (g_chunk_tokens) return g_chunk_tokens;
     int ct = max_ct;
     while (ct > kMinChunkTokens && (int64_t)n_batch * ceil_div_i(n_sequence, ct) < min_units) ct >>= 1;
@@ -82,7 +67,7 @@ static int pick_chunk_tokens(int n_batch, int n_sequence, int min_units = kQktUn
 // ------------------------------------------------------------------------------------------
 // qkt, paged layout.  grid = (B, ceil(S / ct)), block = 256.  Each wave takes whole pages.
 // ------------------------------------------------------------------------------------------
-template <int TB, bool NT>
+template <bool NT>
 __global__ __launch_bounds__(kScanThreads) void qkt_paged_kernel(
     const float* __restrict__ q, const float* const* __restrict__ page_table,
     const int* __restrict__ lengths, float* __restrict__ qkt, int S, int D, int ct, SoftmaxStats st) {
@@ -114,6 +99,7 @@ __global__ __launch_bounds__(kScanThreads) void qkt_paged_kernel(
     const int wave = threadIdx.x >> 6;
     const float scale = sqrtf((float)D);  // the reference divides by sqrtf(dim), so do we
     const int nj = (D4 + kWave - 1) / kWave;
+    constexpr int TB = 8;  // K rows in flight per load batch
 
     float run_m = -INFINITY, run_l = 0.f;
     for (int pi = wave; pi < npages; pi += kScanWaves) {
@@ -491,7 +477,7 @@ int nt_loads_for(int B, int S, int D, int esize) {
     if (g_nt_loads != 2) return g_nt_loads;
     return (int64_t)B * S * D * esize * 2 > kNtMinKvBytes;
 }
-int tuned_chunk_tokens() { return (getenv("MLI_CHUNK_TOKENS") && atoi(getenv("MLI_CHUNK_TOKENS")) > 0) ? atoi(getenv("MLI_CHUNK_TOKENS")) : g_chunk_tokens; }
+int tuned_chunk_tokens() { return g_chunk_tokens; }
 
 int launch_softmax_v_combine(const float* partial, const int* lengths, float* out, int B, int S, int D, int ct,
                              int nchunk, hipStream_t st) {
@@ -558,12 +544,10 @@ int launch_qkt_paged_stats(const float* q, const float* const* page_table, const
     const int ct = pick_chunk_tokens(B, S);
     const size_t smem = (size_t)D * 4 + (size_t)(ct / kPage) * 8;
     dim3 grid(B, ceil_div_i(S, ct));
-#define MLI_QKT_LAUNCH(TB, NT) \
-    hipLaunchKernelGGL((qkt_paged_kernel<TB, NT>), grid, dim3(kScanThreads), smem, st, q, page_table, lengths, qkt, S, D, ct, stats)
-    const bool nt_kv = nt_loads_for(B, S, D, 4);
-    if (g_qkt_token_batch == 16) { if (nt_kv) MLI_QKT_LAUNCH(16, true); else MLI_QKT_LAUNCH(16, false); }
-    else if (g_qkt_token_batch == 4) { if (nt_kv) MLI_QKT_LAUNCH(4, true); else MLI_QKT_LAUNCH(4, false); }
-    else { if (nt_kv) MLI_QKT_LAUNCH(8, true); else MLI_QKT_LAUNCH(8, false); }
+#define MLI_QKT_LAUNCH(NT) \
+    hipLaunchKernelGGL((qkt_paged_kernel<NT>), grid, dim3(kScanThreads), smem, st, q, page_table, lengths, qkt, S, D, ct, stats)
+    if (nt_loads_for(B, S, D, 4)) MLI_QKT_LAUNCH(true);
+    else MLI_QKT_LAUNCH(false);
 #undef MLI_QKT_LAUNCH
     return launch_status();
 }
@@ -723,12 +707,8 @@ int mli_tune(const char* key, int value) {
         mli::set_fill_compact(value);
     } else if (k == "gemm_panel") {
         mli::set_gemm_panel(value);
-    } else if (k == "gemm_deep_k") {
-        mli::set_deep_k_tiles(value);
     } else if (k == "gemm_tall_tiles") {
         mli::set_gemm_tall_tiles(value);
-    } else if (k == "naive_scan_fused") {
-        mli::set_naive_fused(value);
     } else if (k == "gemm_bf16_split") {
         mli::set_bf16_split(value);
     } else if (k == "prefill_fused") {
@@ -737,8 +717,6 @@ int mli_tune(const char* key, int value) {
         mli::set_row_order(value);
     } else if (k == "gemm_split") {
         mli::set_gemm_split(value);
-    } else if (k == "scan_partial_last") {
-        mli::set_partial_last(value);
     } else if (k == "scan_stream") {
         mli::set_scan_stream(value);
     } else if (k == "scan_stream_dynamic_pct") {
@@ -747,24 +725,12 @@ int mli_tune(const char* key, int value) {
         mli::set_stream_granule(value);
     } else if (k == "scan_stream_min_tokens") {
         mli::set_scan_stream_min(value);
-    } else if (k == "scan_tail_tokens") {
-        if (value != 0 && (value < 64 || value > 1024 || (value & (value - 1)))) return MLI_ERR_BAD_ARG;
-        mli::set_tail_tokens(value);
-    } else if (k == "scan_dynamic_items") {
-        mli::set_dynamic_items(value);
     } else if (k == "scan_merge") {
         mli::set_scan_merge(value);
-    } else if (k == "flash_variant") {
-        mli::set_flash_variant(value);
-    } else if (k == "flash_decode") {
-        mli::set_flash_decode(value);
     } else if (k == "fused_softmax") {
         mli::g_fused_softmax = value < 0 ? -1 : (value != 0);
     } else if (k == "bf16_native_mfma") {
         mli::set_bf16_native_mfma(value);
-    } else if (k == "qkt_token_batch") {
-        if (value != 4 && value != 8 && value != 16) return MLI_ERR_BAD_ARG;
-        mli::g_qkt_token_batch = value;
     } else {
         return MLI_ERR_BAD_ARG;
     }

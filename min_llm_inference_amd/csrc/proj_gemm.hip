@@ -402,9 +402,6 @@ int latest_compact(int n_batch, int k_dim) {
     return g_latest_compact == 2 || k_dim >= 1024 ? 1 : 0;
 }
 
-static thread_local int g_deep_k_tiles = 1;  // mli_tune "gemm_deep_k" (bf16 kernel): 0 = 32-deep staged tiles everywhere
-void set_deep_k_tiles(int v) { g_deep_k_tiles = v != 0; }
-int deep_k_tiles_enabled() { return g_deep_k_tiles; }
 // mli_tune "prefill_fused": which form mli_[paged_]prefill runs: 1 (default) = the encoder as the fill GEMM's prologue up to
 // emb_dim 512 and encoder + fill as two launches beyond, 0 = always the two launches, 2 = always the prologue form
 static thread_local int g_prefill_fused = 1;

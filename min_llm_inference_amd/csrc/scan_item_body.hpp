@@ -21,15 +21,7 @@ __device__ unsigned long long mli_scan_trace[kTraceSlots * 8];
 constexpr int kFuThreads = 256;
 constexpr int kFuWaves = kFuThreads / kWave;
 
-// number of (m, l, partial) triples a row of length L produces: full chunks + pieces of the remainder
-__host__ __device__ __forceinline__ int row_items(int L, int ct, int tail) {
-    if (tail == 0) return (L + ct - 1) / ct;
-    const int nf = L / ct;
-    return nf + (L - nf * ct + tail - 1) / tail;
-}
-
-// TBR = rows per load batch, MINW = waves per SIMD the register allocator must leave room for
-// WAVES = waves per workgroup (each wave owns whole pages; 1 = every wave is its own scheduling unit)
+// TBR = rows per load batch
 // DS = false: a wave owns whole pages (rows of up to NJ * 64 lane loads) and the waves are merged at the end;
 // DS = true ("D-split", wide rows): every wave visits every page of the chunk but owns a slice of NJ * 64 lane loads
 //      of each row; the 16 partial scores of a page are exchanged through LDS (one barrier per page, double
@@ -118,18 +110,18 @@ __device__ __forceinline__ void row_publish_merge(float m, float l, float2* ml_r
 // b, c: the item (row, grid row); first_grid_row: this workgroup is the one that writes the zero result of an empty row.
 // RPI = token slots per load instruction (scan_common.hpp; 1 except for narrow fp8 rows): a batch is TBR instructions =
 //   TBR * RPI slots
-template <class E, int NJ, bool NT, int TBR, int WAVES, bool DS, bool SCORES, int RPI = 1>
+template <class E, int NJ, bool NT, int TBR, bool DS, bool SCORES, int RPI>
 __device__ __forceinline__ void fused_scan_item(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ qkt, float* __restrict__ out, float2* ml, float* partial,
-    int S, int D, int ct, int ml_per_row, int nchunk_max, int direct, int tail,
-    int slots, unsigned* arrivals, int b, int c, bool first_grid_row, int trace_stride, unsigned char* smem_raw) {
+    int S, int D, int ct, int ml_per_row, int nchunk_max, int direct, unsigned* arrivals, int b, int c,
+    bool first_grid_row, int trace_stride, unsigned char* smem_raw) {
     constexpr int EPL = E::EPL;
     constexpr int LPR = kWave / RPI;   // lanes per token row
     static_assert(RPI == 1 || (NJ == 1 && !DS), "several rows per instruction: rows of one lane load, whole pages per wave");
     const void** ptr_sh = reinterpret_cast<const void**>(smem_raw);                       // ct/16 page pointers
     float* red = reinterpret_cast<float*>(smem_raw + (size_t)(ct / kPage) * 8);            // [waves][NJ*64*EPL]
-    __shared__ float2 wave_ml[WAVES];
+    __shared__ float2 wave_ml[kFuWaves];
 
 #ifdef MLI_SCAN_TRACE
     const int trace_id = b + trace_stride * c;
@@ -146,7 +138,7 @@ __device__ __forceinline__ void fused_scan_item(
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     const int W = S / kPage;
-    const bool early = !tail || c < nchunk_max;
+    const bool early = c < nchunk_max;
     const void* early_ptr = nullptr;
     if (early && (int)threadIdx.x < ct / kPage && c * (ct / kPage) + (int)threadIdx.x < W)
         early_ptr = page_table[(int64_t)b * W + c * (ct / kPage) + threadIdx.x];
@@ -171,33 +163,33 @@ __device__ __forceinline__ void fused_scan_item(
     if (arrivals != nullptr && L == 0) {
         // in-kernel merge: no workgroup arrives for an empty row, so its zero result is written here, once
         if (first_grid_row) {
-            for (int i = threadIdx.x; i < D; i += (WAVES * kWave)) out[(int64_t)b * D + i] = 0.f;
+            for (int i = threadIdx.x; i < D; i += kFuThreads) out[(int64_t)b * D + i] = 0.f;
         }
         return;
     }
-    // Items of a row, in token order: its full chunks, then (tail > 0) the remainder cut into pieces of `tail` tokens.
-    // Largest items first: grid rows 0 .. nchunk-1 run only the FULL chunks, the grid rows behind them the pieces of
-    // every row's remainder.  In plain chunk order the last workgroups to start are often full ones and the launch
-    // ends with a long stretch at a fraction of the bandwidth (tools/scan_trace.py); with the pieces last, what is
-    // still running when the queue runs dry is at most `tail` tokens long.
+    // Items of a row, in token order: its full chunks, then its remainder (if any) as one item.
+    // Largest items first: grid rows 0 .. nchunk-1 run only the FULL chunks, grid row nchunk every row's remainder.
+    // In plain chunk order the last workgroups to start are often full ones and the launch ends with a long stretch
+    // at a fraction of the bandwidth (tools/scan_trace.py); with the remainders last, what is still running when the
+    // queue runs dry is shorter than a chunk.
     int s0 = c * ct, s1 = min(s0 + ct, L);
-    if (tail) {
+    if (!direct) {
         const int nf = L / ct;
         if (c < nchunk_max) {
-            if (c >= nf) return;                // empty, or part of the remainder (the grid rows behind take it)
+            if (c >= nf) return;                // empty, or the remainder (grid row nchunk takes it)
         } else {
-            s0 = nf * ct + (c - nchunk_max) * tail;
+            s0 = nf * ct;
             if (s0 >= L) return;                // (covers the empty row)
-            s1 = min(s0 + tail, L);
-            c = nf + (c - nchunk_max);          // its slot among the row's items
+            s1 = L;
+            c = nf;                             // its slot among the row's items
         }
     }
     float* qkt_row = qkt + (int64_t)b * S;
 
     if (s0 >= L) {
         if (direct) {  // single-chunk problem: this workgroup owns the whole (empty) row
-            if (SCORES) for (int i = threadIdx.x; i < S; i += (WAVES * kWave)) qkt_row[i] = 0.f;
-            for (int i = threadIdx.x; i < D; i += (WAVES * kWave)) out[(int64_t)b * D + i] = 0.f;
+            if (SCORES) for (int i = threadIdx.x; i < S; i += kFuThreads) qkt_row[i] = 0.f;
+            for (int i = threadIdx.x; i < D; i += kFuThreads) out[(int64_t)b * D + i] = 0.f;
         }
         return;
     }
@@ -206,7 +198,7 @@ __device__ __forceinline__ void fused_scan_item(
     if (early) {
         if ((int)threadIdx.x < npages) ptr_sh[threadIdx.x] = early_ptr;   // npages <= ct / 16 <= 64 < threads
     } else {
-        for (int i = threadIdx.x; i < npages; i += (WAVES * kWave))
+        for (int i = threadIdx.x; i < npages; i += kFuThreads)
             ptr_sh[i] = page_table[(int64_t)b * W + s0 / kPage + i];
     }
     __syncthreads();
@@ -255,7 +247,7 @@ __device__ __forceinline__ void fused_scan_item(
                 buf[bi][t][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[j], base + t * RPI * (int)row_bytes, NT ? 2 : 0);
     };
 
-    constexpr int PSTEP = DS ? 1 : WAVES;
+    constexpr int PSTEP = DS ? 1 : kFuWaves;
     const int p_first = DS ? 0 : wave;
     const char* page = p_first < npages ? page_ptr(p_first) : nullptr;
     if (p_first < npages) {   // (not "page != nullptr": a null table entry is a page too -- it reads as zeros)
@@ -293,12 +285,12 @@ __device__ __forceinline__ void fused_scan_item(
                     const int slot = rpi_slot_of_lane<RPI>(lane);
                     if constexpr (DS) {
                         // complete the dot products across the waves' row slices (fixed order: identical in every wave)
-                        float* xs = red + (pi & 1) * (WAVES * 16);
+                        float* xs = red + (pi & 1) * (kFuWaves * 16);
                         if ((lane & 3) == 0) xs[wave * 16 + slot] = tot;
                         __syncthreads();
                         tot = 0.f;
 #pragma unroll
-                        for (int w = 0; w < WAVES; ++w) tot += xs[w * 16 + slot];
+                        for (int w = 0; w < kFuWaves; ++w) tot += xs[w * 16 + slot];
                     }
                     const bool valid = slot < nt;
                     const float score = tot / scale;
@@ -348,7 +340,7 @@ __device__ __forceinline__ void fused_scan_item(
     // DS: every wave already holds the chunk's (max, sum) and its own slice of the output.
     // otherwise: the waves (each owns whole pages) are merged in wave order through LDS.
     const bool publish = arrivals != nullptr;  // lean mode, several chunks per row: in-kernel merge by the last arriver
-    float* o = direct ? out + (int64_t)b * D : partial + ((int64_t)b * slots + c) * D;
+    float* o = direct ? out + (int64_t)b * D : partial + ((int64_t)b * nchunk_max + c) * D;
     float m, l;
     if constexpr (DS) {
         m = run_m;
@@ -385,24 +377,24 @@ __device__ __forceinline__ void fused_scan_item(
         __syncthreads();
         m = -INFINITY;
 #pragma unroll
-        for (int w = 0; w < WAVES; ++w) m = fmaxf(m, wave_ml[w].x);
-        float wsc[WAVES];
+        for (int w = 0; w < kFuWaves; ++w) m = fmaxf(m, wave_ml[w].x);
+        float wsc[kFuWaves];
         l = 0.f;
 #pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
+        for (int w = 0; w < kFuWaves; ++w) {
             wsc[w] = wave_ml[w].x == -INFINITY ? 0.f : expf(wave_ml[w].x - m);
             l += wave_ml[w].y * wsc[w];
         }
         const float norm = direct ? 1.f / l : 1.f;
         const __amdgpu_buffer_rsrc_t orow = __builtin_amdgcn_make_buffer_rsrc(o, 0, D * (int)sizeof(float), 0x00020000);
         // element i of the row lives at red[...][i] by construction; D % 4 == 0
-        for (int i = 4 * threadIdx.x; i < D; i += 4 * (WAVES * kWave)) {
+        for (int i = 4 * threadIdx.x; i < D; i += 4 * kFuThreads) {
             float r[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float t = 0.f;
 #pragma unroll
-                for (int w = 0; w < WAVES; ++w) t += red[w * kRowF + i + k] * wsc[w];
+                for (int w = 0; w < kFuWaves; ++w) t += red[w * kRowF + i + k] * wsc[w];
                 r[k] = t * norm;
             }
             if (publish) {
@@ -419,15 +411,15 @@ __device__ __forceinline__ void fused_scan_item(
             // whole row handled by this workgroup: normalise the scores in place and write the zero tail
             __syncthreads();  // raw scores written by other waves of this workgroup are visible after the barrier
             const float inv_l = 1.f / l;
-            for (int i = threadIdx.x; i < S; i += (WAVES * kWave)) qkt_row[i] = i < L ? expf(qkt_row[i] - m) * inv_l : 0.f;
+            for (int i = threadIdx.x; i < S; i += kFuThreads) qkt_row[i] = i < L ? expf(qkt_row[i] - m) * inv_l : 0.f;
         }
     } else if (!publish) {
         if (threadIdx.x == 0) ml[(int64_t)b * ml_per_row + c] = make_float2(m, l);
     } else {
         // ---- publish the triple, count the arrival; the workgroup that completes the row merges it ----
-        row_publish_merge<WAVES * kWave>(m, l, ml + (int64_t)b * ml_per_row, c, row_items(L, ct, tail), arrivals + b,
-                                         partial + (int64_t)b * slots * D, D, out + (int64_t)b * D, red,
-                                         reinterpret_cast<int*>(wave_ml));
+        row_publish_merge<kFuThreads>(m, l, ml + (int64_t)b * ml_per_row, c, (L + ct - 1) / ct, arrivals + b,
+                                      partial + (int64_t)b * nchunk_max * D, D, out + (int64_t)b * D, red,
+                                      reinterpret_cast<int*>(wave_ml));
     }
     MLI_TRACE(4);
 #ifdef MLI_SCAN_TRACE

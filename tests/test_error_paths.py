@@ -48,8 +48,20 @@ def test_tune_rejects_unknown_keys_and_values(mli):
     assert mli.mli_tune(b"no_such_knob", 1) == BAD_ARG
     assert mli.mli_tune(b"chunk_tokens", 100) == BAD_ARG      # not a power of two
     assert mli.mli_tune(b"chunk_tokens", 4096) == BAD_ARG     # beyond the largest chunk
-    assert mli.mli_tune(b"qkt_token_batch", 5) == BAD_ARG
     assert mli.mli_tune(b"chunk_tokens", 0) == 0
+    # retired tuning keys are unknown keys now
+    for key in (b"flash_variant", b"flash_decode", b"scan_dynamic_items", b"scan_partial_last", b"scan_tail_tokens",
+                b"qkt_token_batch", b"gemm_deep_k", b"naive_scan_fused"):
+        assert mli.mli_tune(key, 0) == BAD_ARG, key
+        assert mli.mli_tune(key, 1) == BAD_ARG, key
+    # every kept key takes its default value
+    defaults = {b"chunk_tokens": 0, b"nt_loads": 2, b"scan_merge": 1, b"scan_stream": 1,
+                b"scan_stream_min_tokens": 1 << 21, b"scan_stream_dynamic_pct": 4, b"scan_stream_granule": 64,
+                b"scan_row_order": 1, b"fused_softmax": -1, b"fill_compact": 1, b"latest_compact": 1, b"gemm_split": 1,
+                b"gemm_bf16_split": 1, b"prefill_fused": 1, b"gemm_panel": 1, b"gemm_tall_tiles": 1,
+                b"bf16_native_mfma": 1}
+    for key, value in defaults.items():
+        assert mli.mli_tune(key, value) == 0, key
 
 
 def test_engine_rejects_bad_configurations(mli):

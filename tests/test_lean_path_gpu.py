@@ -168,8 +168,8 @@ def test_lean_scan_equal_page_shares_with_the_largest_dynamic_part(oracle, mli, 
     assert (outs[0][3] == 0).all()
 
 
-@pytest.mark.parametrize("chunk,tail", [(64, 0), (128, 0), (256, 0), (512, 64), (512, 128), (1024, 256), (256, 256)])
-def test_lean_scan_many_chunks_per_row(oracle, mli, dev, chunk, tail):
+@pytest.mark.parametrize("chunk", [64, 128, 256, 512, 1024])
+def test_lean_scan_many_chunks_per_row(oracle, mli, dev, chunk):
     """Small chunks: up to 64 arrivals per row, rows of every chunk count side by side (uneven load)."""
     from min_llm_inference_amd import ops
     B, S, D = 96, 4096, 128
@@ -178,7 +178,6 @@ def test_lean_scan_many_chunks_per_row(oracle, mli, dev, chunk, tail):
     lengths[:8] = [0, 1, chunk - 1, chunk, chunk + 1, S - 1, 2 * chunk, 17]
     c, d = _prepare(oracle, dev, 141, B, S, D, conditioned=True, lengths=lengths)
     assert mli.mli_tune(b"chunk_tokens", chunk) == 0
-    assert mli.mli_tune(b"scan_tail_tokens", tail) == 0
     try:
         ops.decode_scan_paged(d["q_output"], d["page_table"], d["lengths"], d["qkt_output"], d["attention_result"], False)
         full = host(d["attention_result"]).copy()
@@ -189,7 +188,6 @@ def test_lean_scan_many_chunks_per_row(oracle, mli, dev, chunk, tail):
             assert_equal(host(d["attention_result"]), full, what=f"lean == materialising at {chunk}-token chunks")
     finally:
         mli.mli_tune(b"chunk_tokens", 0)
-        mli.mli_tune(b"scan_tail_tokens", 0)
     oracle.qkt_host(c["q_output"], c["kt_cache"], c["lengths"], c["qkt_output"])
     oracle.softmax_in_place_with_lengths_host(c["qkt_output"], c["lengths"])
     oracle.softmax_v_host(c["qkt_output"], c["v_cache"], c["attention_result"], c["lengths"])

@@ -19,13 +19,10 @@ ks = wl.kernels()
 qk = [k for k in ks if k.startswith("qkt")][0]
 sk = [k for k in ks if k.startswith("softmax_v")][0]
 print(f"workload {name}: qkt bytes {alg['qkt']/1e9:.3f} GB, sv bytes {alg['softmax_v']/1e9:.3f} GB")
-for ct, nt, tb in itertools.product([0, 64, 128, 256, 512, 1024], [1, 0], [8]):
+for ct, nt in itertools.product([0, 64, 128, 256, 512, 1024], [1, 0]):
     assert lib.mli_tune(b"chunk_tokens", ct) == 0
     assert lib.mli_tune(b"nt_loads", nt) == 0
-    assert lib.mli_tune(b"qkt_token_batch", tb) == 0
     tq = bench.time_kernel(ks[qk], 20)
-    line = f"ct {ct:5d} nt {nt} tb {tb:2d}: qkt {tq*1e3:8.1f} us {alg['qkt']/tq/1e6:7.0f} GB/s"
-    if tb == 8:
-        ts = bench.time_kernel(ks[sk], 20)
-        line += f" | sv {ts*1e3:8.1f} us {alg['softmax_v']/ts/1e6:7.0f} GB/s"
-    print(line, flush=True)
+    ts = bench.time_kernel(ks[sk], 20)
+    print(f"ct {ct:5d} nt {nt}: qkt {tq*1e3:8.1f} us {alg['qkt']/tq/1e6:7.0f} GB/s"
+          f" | sv {ts*1e3:8.1f} us {alg['softmax_v']/ts/1e6:7.0f} GB/s", flush=True)
