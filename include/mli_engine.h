@@ -120,6 +120,15 @@ void mli_engine_set_step_graphs(int enabled);
  * it is.  (The fp8 engine has the lean compositions only.) */
 int mli_engine_configure(mli_engine* engine, int lean_layers, int step_graphs);
 
+/* EXTENSION: multi-head attention (mli_kernels.h: mli_paged_attention_lean_heads).  n_heads heads of
+ * head_dim = emb_dim / n_heads, head h owning columns [h * head_dim, (h + 1) * head_dim) of q, K and V; one softmax per
+ * head over q_h . K_h / sqrtf(head_dim).  Before the first step or run; kinds MLI_ENGINE_PAGED, MLI_ENGINE_PAGED_GEMM and
+ * MLI_ENGINE_PAGED_BF16.  -1 with a message for another kind, an unsupported (emb_dim, n_heads) -- head_dim 32, 64, 128 or
+ * 256, emb_dim <= 512 (fp32) / 1024 (bf16) --, an engine configured with lean_layers = 0 (mli_engine_configure(e, 0, ...)
+ * afterwards is refused likewise) or a call after the first step.  n_heads = 1 is accepted everywhere and changes
+ * nothing.  Loops, step graphs, preemption, sampling and n_forward_rounds work as with one head. */
+int mli_engine_set_heads(mli_engine* engine, int n_heads);
+
 const char* mli_engine_last_error(void);
 
 #ifdef __cplusplus

@@ -201,6 +201,35 @@ int mli_paged_attention_lean(void* const* page_table, const int* lengths,
                              int n_batch, int n_sequence, int emb_dim, int n_new_items, int elem_bf16,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* EXTENSION: MULTI-HEAD attention for the lean paged composition and its scan.  n_heads = H >= 1, head_dim = hd =
+ * emb_dim / H; head h owns columns [h * hd, (h + 1) * hd) of q_output and of the K and V segments of every page slot:
+ *     x[h][s] = sum_{d < hd} q[b, h*hd + d] * K[b, s, h*hd + d] / sqrtf(hd),  p[h][.] = softmax over s < lengths[b],
+ *     attention_result[b, h*hd + d] = sum_s p[h][s] * V[b, s, h*hd + d]
+ * (no output projection: the model has none).  Rows of length 0 give zeros, slots >= lengths[b] are never multiplied, a
+ * null page reads as zeros.  Fill, projection, page layout and q_output do not depend on H.  H == 1 is exactly
+ * mli_paged_attention_lean / mli_decode_scan_paged(phases 7): same kernels, same bits.  For H > 1 -- one scan launch, no
+ * scores materialised, chunked grid, in-kernel merge per head; of the mli_tune keys "chunk_tokens", "nt_loads" and
+ * "scan_row_order" apply -- the supported shapes are: emb_dim % H == 0; hd in {32, 64, 128, 256}; elem MLI_ELEM_F32 with
+ * emb_dim <= 512 or MLI_ELEM_BF16 with emb_dim <= 1024; n_sequence % 16 == 0; n_batch <= 16384.  Everything else (and
+ * MLI_ELEM_FP8 with any H) is MLI_ERR_BAD_ARG, decided before anything is launched.
+ *
+ * Workspace: mli_attention_heads_workspace_bytes >= mli_attention_workspace_bytes of the same shape (equal at H == 1), so
+ * one buffer serves both kinds of call; 0 for an unsupported combination.  Same layout rule (the 64 KiB counter region in
+ * front, zeroed once by mli_attention_workspace_init, zero again after every call); too small: MLI_ERR_WORKSPACE. */
+size_t mli_attention_heads_workspace_bytes(int n_batch, int n_sequence, int dim, int n_heads);
+
+/* The multi-head scan on its own: q_output from the projection in, attention_result out. */
+int mli_decode_scan_paged_heads(const float* q_output, const void* const* page_table, const int* lengths,
+                                float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                int elem, void* workspace, size_t workspace_bytes, void* stream);
+
+/* mli_paged_attention_lean with n_heads heads: fill (n_new_items rows) -> latest -> multi-head scan. */
+int mli_paged_attention_lean_heads(void* const* page_table, const int* lengths,
+                                   const void* wk, const void* wq, const void* wv, const int* new_batch_idx,
+                                   float* q_output, float* attention_result,
+                                   int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int elem,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */

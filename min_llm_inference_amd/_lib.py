@@ -64,6 +64,9 @@ SIGNATURES = {
     "mli_paged_decoder_multi_rounds_bf16": [_P] * 7 + [_I] * 6 + [_P],
     "mli_decode_scan_paged": [_P] * 5 + [_I] * 5 + [_P, _Z, _P],
     "mli_paged_attention_lean": [_P] * 8 + [_I] * 5 + [_P, _Z, _P],
+    "mli_attention_heads_workspace_bytes": [_I, _I, _I, _I],
+    "mli_decode_scan_paged_heads": [_P] * 4 + [_I] * 5 + [_P, _Z, _P],
+    "mli_paged_attention_lean_heads": [_P] * 8 + [_I] * 6 + [_P, _Z, _P],
     "mli_get_latest_k_q_v_paged_lean": [_P] * 6 + [_I] * 4 + [_P],
     "mli_self_attention_lean": [_P] * 10 + [_I] * 5 + [_P, _Z, _P],
     "mli_decode_scan_contiguous": [_P] * 5 + [_I] * 3 + [_P, _Z, _P],
@@ -121,6 +124,7 @@ ENGINE_SIGNATURES = {
     "mli_engine_decoder_result": [_P, _PP, _IP],
     "mli_engine_get_finished": [_P, _I, _IP, _P, _I, _IP],
     "mli_engine_configure": [_P, _I, _I],
+    "mli_engine_set_heads": [_P, _I],
     "mli_engine_set_lean_layers": [_I],
     "mli_engine_set_step_graphs": [_I],
     "mli_engine_last_error": [],
@@ -145,7 +149,8 @@ class ShardStats(ctypes.Structure):
 
 
 _RESTYPES = {"mli_shard_last_error": ctypes.c_char_p, "mli_shard_group_destroy": None, "mli_shard_group_engine": _P,
-             "mli_attention_workspace_bytes": _Z, "mli_decoder_scratch_bytes": _Z,
+             "mli_attention_workspace_bytes": _Z, "mli_attention_heads_workspace_bytes": _Z,
+             "mli_decoder_scratch_bytes": _Z,
              "mli_sample_scratch_bytes": _Z, "mli_decoder_sampled_scratch_bytes": _Z, "mli_engine_last_error": ctypes.c_char_p,
              "mli_engine_destroy": None, "mli_engine_set_lean_layers": None,
              "mli_engine_set_step_graphs": None}

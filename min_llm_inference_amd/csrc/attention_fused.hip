@@ -12,6 +12,7 @@
 //   scan    grid = (B, chunks) rows fast (XCD balance), 256 threads; a wave owns whole pages
 //   combine grid = B, 256 threads
 #include "scan_item_body.hpp"
+#include "scan_row_order.hpp"
 
 namespace mli {
 
@@ -24,73 +25,6 @@ template <class E>
 bool stream_decode_applies(int B, int S, int D);
 size_t stats_region_bytes_for(int B, int S);
 int nt_loads_for(int B, int S, int D, int esize);
-
-// One workgroup per row (short sequences: the whole row is one item): workgroups start in grid order and the rows' lengths
-// are ragged, so whichever long rows happen to sit at the end of the grid run alone at the end (README workload, B=1024,
-// S=128, D=2048: 5.3 TB/s against 6.4 with equal lengths).  This hands the rows out LONGEST FIRST instead: workgroup r takes
-// the row of rank r by page count (descending; equal counts in row order).  Every workgroup derives the same ranking from
-// the lengths -- a histogram over the page counts, then the j-th row of its bucket by a block-wide count --: ~2 us of
-// prologue per workgroup, no pre-pass, deterministic.  All kFuThreads threads call it; n_batch <= kMaxOrderedRows.
-constexpr int kMaxOrderedRows = 2048;
-constexpr int kMaxOrderedPages = 64;
-__device__ __forceinline__ int longest_first_row(const int* __restrict__ lengths, int n_batch, int S, int rank) {
-    __shared__ int hist[kMaxOrderedPages + 1];
-    __shared__ int wave_cnt[kFuWaves];
-    __shared__ int found_row;
-    constexpr int kPer = kMaxOrderedRows / kFuThreads;
-    const int tid = threadIdx.x;
-    const int per = (n_batch + kFuThreads - 1) / kFuThreads;  // rows per thread, a contiguous segment
-    if (tid <= kMaxOrderedPages) hist[tid] = 0;
-    __syncthreads();
-    int pages[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-        const int row = tid * per + j;
-        pages[j] = -1;
-        if (j < per && row < n_batch) {
-            pages[j] = (min(max(lengths[row], 0), S) + kPage - 1) / kPage;
-            atomicAdd(&hist[pages[j]], 1);
-        }
-    }
-    __syncthreads();
-    // the bucket of this rank (page counts descending) and the rank inside it
-    int bucket = 0, before = 0;
-    for (int p = kMaxOrderedPages; p >= 0; --p) {
-        const int h = hist[p];
-        if (rank < before + h) {
-            bucket = p;
-            break;
-        }
-        before += h;
-    }
-    const int j_in_bucket = rank - before;
-    // the j-th row of the bucket in row order: matches per thread segment, exclusive prefix over the threads
-    int mine = 0;
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) mine += pages[j] == bucket;
-    int incl = mine;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const int up = __shfl_up(incl, off, kWave);
-        if ((tid & (kWave - 1)) >= off) incl += up;
-    }
-    if ((tid & (kWave - 1)) == kWave - 1) wave_cnt[tid / kWave] = incl;
-    __syncthreads();
-    int base = incl - mine;
-    for (int w = 0; w < tid / kWave; ++w) base += wave_cnt[w];
-    if (j_in_bucket >= base && j_in_bucket < base + mine) {
-        int seen = base;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-            if (pages[j] == bucket) {
-                if (seen == j_in_bucket) found_row = tid * per + j;
-                ++seen;
-            }
-        }
-    }
-    __syncthreads();
-    return found_row;
-}
 
 template <class E, int NJ, bool NT, int TBR, bool DS, bool SCORES, int RPI>
 __global__ __launch_bounds__(kFuThreads, 2) void fused_decode_scan_kernel(
@@ -149,6 +83,7 @@ __global__ __launch_bounds__(kFuThreads) void fused_decode_combine_kernel(
 
 static thread_local int g_row_order = 1;  // mli_tune "scan_row_order": 0 = one-workgroup-per-row grids take the rows in grid order
 void set_row_order(int v) { g_row_order = v != 0; }
+int scan_row_order() { return g_row_order; }   // attention_heads.hip
 // mli_tune "scan_merge" (lean mode only): 1 (default) = the workgroup that completes a row merges its chunks inside
 // the scan launch, 0 = the separate combine launch (bit-identical results)
 static thread_local int g_scan_merge = 1;
@@ -159,7 +94,7 @@ void set_scan_merge(int v) { g_scan_merge = v != 0; }
 // holds.  Measured: B=1024, S=4096 -> 512 (256: +2.4 %, 1024: +1 % with ragged lengths); B=256, S=1024 -> 128 (round 2,
 // scan launch: 46.9 us against 49.6 at 256 and 54.3 at 512, where 384 items of very unequal size cannot even fill the
 // 512 slots once; lean form 52.5 / 53.1 / 56.2).
-static int fused_chunk_tokens(int B, int S) {
+int fused_chunk_tokens(int B, int S) {   // (also attention_heads.hip)
     if (tuned_chunk_tokens() != 0) return sv_chunk_tokens_for(B, S);  // forced (mli_tune)
     int ct = 512;
     while (ct > 64 && (int64_t)B * ceil_div_i(S, ct) < 2048) ct >>= 1;

@@ -37,22 +37,11 @@ constexpr int kFuWaves = kFuThreads / kWave;
 //      same order as fused_decode_combine_kernel, so the result is bit-identical to the two-launch form -- and puts
 //      the counter back to zero for the next launch.  (MI355X_MICROARCH.md, inter-workgroup visibility: sc1 payload +
 //      every storing wave's vmcnt(0) + barrier + counter add; consumer: agent acquire + vmcnt(0) + barrier, then loads.)
-// The tail of every item of a row that has several: the item's partial output row has been stored write-through (sc1)
-// at partial_row[c]; here its (m, l) pair follows, the arrival is counted, and the workgroup whose arrival completes the
-// row merges the row's nc triples in item order into out_row (MI355X_MICROARCH.md, inter-workgroup visibility: sc1
-// payload + every storing wave's vmcnt(0) + barrier + counter add; the last arriver: agent acquire + vmcnt(0) + barrier,
-// then loads) and puts the counter back to zero.  All THREADS threads call it.  lds: >= nc float2 of scratch no thread
-// still reads; last_sh: one LDS int.
-template <int THREADS>
-__device__ __forceinline__ void row_publish_merge(float m, float l, float2* ml_row, int c, int nc, unsigned* arrival,
-                                                  const float* partial_row, int D, float* out_row, float* lds,
-                                                  int* last_sh) {
-    typedef unsigned long long __attribute__((address_space(1)))* gu64_ptr;
+// The hand-off itself, shared with the multi-head scan (heads_item_body.hpp): every thread of the workgroup calls it after
+// its write-through (sc1) stores of the item's payload.  Returns true, in every thread, in the workgroup whose arrival
+// completes the row's nc items -- after the acquire, with the counter back at zero.  last_sh: one LDS int.
+__device__ __forceinline__ bool row_arrive(unsigned* arrival, int nc, int* last_sh) {
     typedef unsigned __attribute__((address_space(1)))* gu32_ptr;
-    if (threadIdx.x == 0) {
-        const unsigned long long packed = ((unsigned long long)__float_as_uint(l) << 32) | __float_as_uint(m);
-        __hip_atomic_store((gu64_ptr)(ml_row + c), packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1 store
-    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // EVERY storing wave: its write-through stores have left
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -66,7 +55,25 @@ __device__ __forceinline__ void row_publish_merge(float m, float l, float2* ml_r
         *last_sh = last;
     }
     __syncthreads();
-    if (!*last_sh) return;
+    return *last_sh != 0;
+}
+
+// The tail of every item of a row that has several: the item's partial output row has been stored write-through (sc1)
+// at partial_row[c]; here its (m, l) pair follows, the arrival is counted, and the workgroup whose arrival completes the
+// row merges the row's nc triples in item order into out_row (MI355X_MICROARCH.md, inter-workgroup visibility: sc1
+// payload + every storing wave's vmcnt(0) + barrier + counter add; the last arriver: agent acquire + vmcnt(0) + barrier,
+// then loads) and puts the counter back to zero.  All THREADS threads call it.  lds: >= nc float2 of scratch no thread
+// still reads; last_sh: one LDS int.
+template <int THREADS>
+__device__ __forceinline__ void row_publish_merge(float m, float l, float2* ml_row, int c, int nc, unsigned* arrival,
+                                                  const float* partial_row, int D, float* out_row, float* lds,
+                                                  int* last_sh) {
+    typedef unsigned long long __attribute__((address_space(1)))* gu64_ptr;
+    if (threadIdx.x == 0) {
+        const unsigned long long packed = ((unsigned long long)__float_as_uint(l) << 32) | __float_as_uint(m);
+        __hip_atomic_store((gu64_ptr)(ml_row + c), packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1 store
+    }
+    if (!row_arrive(arrival, nc, last_sh)) return;
     // item statistics -> LDS; sc1 loads: served by L2 / memory, never L1
     float2* ml_sh = reinterpret_cast<float2*>(lds);
     for (int i = threadIdx.x; i < nc; i += THREADS) {

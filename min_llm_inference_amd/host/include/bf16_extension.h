@@ -47,11 +47,14 @@ public:
     void prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
                  TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
                  int n_new_items);
+    // attention heads of the lean forward (default 1: one softmax over emb_dim)
+    void set_n_heads(int n_heads) { n_heads_ = n_heads; }
 
 private:
     TensorBf16 wk_, wq_, wv_;
     TensorFloat q_output_;
     TensorFloat qkt_output_;
+    int n_heads_ = 1;
 };
 
 class PagedAttentionBf16InferenceModel : public NonCopyableNonClonable {
@@ -63,6 +66,7 @@ public:
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
     // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling)
     void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }
+    void set_n_heads(int n_heads) { attention_layer_.set_n_heads(n_heads); }
 
 private:
     PagedAttentionBf16Layer attention_layer_;

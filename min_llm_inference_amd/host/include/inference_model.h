@@ -36,6 +36,7 @@ public:
                  TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
     void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
+    void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
 
 private:
     PagedAttentionLayer paged_attention_layer_;
@@ -56,6 +57,7 @@ public:
                  TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table, GemmHandle handle);
     void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
+    void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
 
 private:
     PagedAttentionCublasLayer paged_attention_layer_;

@@ -36,6 +36,13 @@ void paged_attention_lean(TensorFloatPoint& page_table, const TensorInt& lengths
                           TensorFloat& q_output, TensorFloat& qkt_output, TensorFloat& attention_result,
                           int n_new_items, int n_sequence);
 
+// EXTENSION: paged_attention_lean with n_heads attention heads (head h owns columns [h * emb_dim / n_heads, ...) of q, K
+// and V; one softmax per head).  Pages and q_output are those of paged_attention_lean.  Throws on an unsupported shape.
+void paged_attention_lean_heads(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                                const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                                TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
+                                int n_heads);
+
 // EXTENSION: launch_paged_attention_encoder_kernel + launch_fill_new_k_v_cache_paged_attention in one
 // launch -- the embedding lookup is the fill GEMM's prologue; pages bit-identical to the two-launch form.
 void launch_paged_prefill(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,

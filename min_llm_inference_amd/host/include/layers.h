@@ -38,10 +38,14 @@ public:
                  TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
                  int n_new_items);
 
+    // EXTENSION: attention heads of the lean forward (default 1 = the reference's single softmax over emb_dim)
+    void set_n_heads(int n_heads) { n_heads_ = n_heads; }
+
 private:
     TensorFloat wk_, wq_, wv_;
     TensorFloat q_output_;
     TensorFloat qkt_output_;
+    int n_heads_ = 1;
 };
 
 class PagedAttentionCublasLayer : public NonCopyableNonClonable {
@@ -54,10 +58,14 @@ public:
                  TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
                  int n_new_items);  // extension, as PagedAttentionLayer::prefill
 
+    // EXTENSION: attention heads of the lean forward (default 1 = the reference's single softmax over emb_dim)
+    void set_n_heads(int n_heads) { n_heads_ = n_heads; }
+
 private:
     TensorFloat wk_, wq_, wv_;
     TensorFloat q_output_;
     TensorFloat qkt_output_;
+    int n_heads_ = 1;
     TensorFloat latest_emb_;        // kept for signature parity with the reference; unused by the MFMA path
     TensorFloat temp_placeholder_;
 };

@@ -23,7 +23,8 @@ struct Scratch {
     void* ptr;
     size_t bytes;
 };
-Scratch attention_scratch(int n_batch, int n_sequence, int emb_dim);
+// n_heads > 1 (EXTENSION, multi-head scan): sized by mli_attention_heads_workspace_bytes, which covers the single-head need
+Scratch attention_scratch(int n_batch, int n_sequence, int emb_dim, int n_heads = 1);
 void release_attention_scratch(void* stream) noexcept;  // frees the buffers tied to a stream that is going away
 
 // The three switches below are PER THREAD, like the device and the compute stream: they apply to what the calling thread

@@ -20,9 +20,14 @@
 #include "inferencer.h"
 #include "kernels/decoder.h"
 #include "mli_engine.h"
+#include "mli_kernels.h"
 #include "pipelined_engine.h"
 #include "runtime.h"
 #include "throughput_counter.h"
+
+namespace mli {
+int heads_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int elem);  // attention_heads.hip
+}
 
 namespace {
 
@@ -73,6 +78,7 @@ struct mli_engine {
     void* stream = nullptr;     // private compute stream (mli_engine_use_private_stream), else the thread's
     bool lean_layers = g_default_lean_layers.load();   // this engine's composition and replay switches (runtime.h)
     bool step_graphs = g_default_step_graphs.load();
+    int n_heads = 1;            // mli_engine_set_heads
 
     // EXTENSION: sampled decoding (mli_engine_add_item_sampled).  The parameters live here, keyed by item
     // id, so a preempted item keeps its stream; the decoder head reads them from per-slot device arrays, filled when an
@@ -381,10 +387,35 @@ void mli_engine_set_step_graphs(int enabled) { g_default_step_graphs.store(enabl
 int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
     MLI_GUARD({
         if (e->started) throw std::runtime_error("mli_engine_configure after the engine has started");
+        if (e->n_heads > 1 && lean_layers == 0)   // refused before anything is changed
+            throw std::runtime_error("multi-head attention (mli_engine_set_heads) has the lean compositions only");
         if (lean_layers >= 0) e->lean_layers = lean_layers != 0;
         if (step_graphs >= 0) e->step_graphs = step_graphs != 0;
         if (e->cfg.kind == MLI_ENGINE_PAGED_FP8 && !e->lean_layers)
             throw std::runtime_error("the fp8 engine has the lean compositions only");
+    })
+}
+
+int mli_engine_set_heads(mli_engine* e, int n_heads) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (n_heads < 1) throw std::runtime_error("mli_engine_set_heads: n_heads must be >= 1");
+        if (n_heads != e->n_heads) {
+            if (e->started) throw std::runtime_error("mli_engine_set_heads after the engine has started");
+            const int kind = e->cfg.kind;
+            if (kind != MLI_ENGINE_PAGED && kind != MLI_ENGINE_PAGED_GEMM && kind != MLI_ENGINE_PAGED_BF16)
+                throw std::runtime_error("mli_engine_set_heads: multi-head attention serves the fp32 and bf16 paged engines");
+            if (n_heads > 1 && !e->lean_layers)
+                throw std::runtime_error("mli_engine_set_heads: multi-head attention has the lean compositions only");
+            const int elem = kind == MLI_ENGINE_PAGED_BF16 ? MLI_ELEM_BF16 : MLI_ELEM_F32;
+            if (n_heads > 1 && !mli::heads_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, elem))
+                throw std::runtime_error("mli_engine_set_heads: unsupported (emb_dim, n_heads): head_dim must be 32, 64, 128 or "
+                                         "256 and emb_dim at most 512 (fp32) / 1024 (bf16)");
+            if (e->paged_model) e->paged_model->set_n_heads(n_heads);
+            if (e->gemm_model) e->gemm_model->set_n_heads(n_heads);
+            if (e->bf16_model) e->bf16_model->set_n_heads(n_heads);
+            e->n_heads = n_heads;
+        }
     })
 }
 

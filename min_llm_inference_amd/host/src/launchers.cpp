@@ -30,10 +30,10 @@ void mli::runtime::release_attention_scratch(void* stream) noexcept {
     for (auto it = g_scratch.begin(); it != g_scratch.end();) it = it->first.second == stream ? g_scratch.erase(it) : std::next(it);
 }
 
-mli::runtime::Scratch mli::runtime::attention_scratch(int n_batch, int n_sequence, int dim) {
+mli::runtime::Scratch mli::runtime::attention_scratch(int n_batch, int n_sequence, int dim, int n_heads) {
     std::mutex& mu = g_scratch_mu;
     auto& per_device = g_scratch;
-    const size_t need = mli_attention_workspace_bytes(n_batch, n_sequence, dim);
+    const size_t need = mli_attention_heads_workspace_bytes(n_batch, n_sequence, dim, n_heads);  // n_heads 1: the plain size
     if (need == 0) return {nullptr, 0};
     std::lock_guard<std::mutex> lock(mu);
     auto& slot = per_device[{mli::runtime::current_device(), mli::runtime::compute_stream()}];
@@ -284,6 +284,19 @@ void paged_attention_lean(TensorFloatPoint& page_table, const TensorInt& lengths
         return;
     }
     HIP_CHECK(rc);
+}
+
+// EXTENSION: the lean composition with n_heads attention heads (mli_paged_attention_lean_heads); an unsupported shape throws
+void paged_attention_lean_heads(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                                const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                                TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
+                                int n_heads) {
+    const int B = (int)page_table.shape()[0], D = (int)wk.shape()[0];
+    const Scratch ws = mli::runtime::attention_scratch(B, n_sequence, D, n_heads);
+    HIP_CHECK(mli_paged_attention_lean_heads(reinterpret_cast<void* const*>(pages(page_table)), lengths.data(), wk.data(),
+                                             wq.data(), wv.data(), new_batch_idx.data(), q_output.data(),
+                                             attention_result.data(), B, n_sequence, D, n_new_items, n_heads, MLI_ELEM_F32,
+                                             ws.ptr, ws.bytes, stream()));
 }
 
 void paged_attention_with_cublas(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,

@@ -45,10 +45,14 @@ def _check(rc, what):
         raise MliError(f"Hip Failure: {what} returned {rc}")
 
 
-def workspace_for(n_batch, n_sequence, dim, device):
-    """Caller-owned scratch for the split-sequence kernels (grown on demand, never inside a timed region)."""
+def workspace_for(n_batch, n_sequence, dim, device, n_heads=1):
+    """Caller-owned scratch for the split-sequence kernels (grown on demand, never inside a timed region).  n_heads > 1:
+    sized for the multi-head scan (mli_attention_heads_workspace_bytes), which covers the single-head calls too."""
     lib = load_library()
-    need = int(lib.mli_attention_workspace_bytes(n_batch, n_sequence, dim))
+    if n_heads == 1:
+        need = int(lib.mli_attention_workspace_bytes(n_batch, n_sequence, dim))
+    else:
+        need = int(lib.mli_attention_heads_workspace_bytes(n_batch, n_sequence, dim, int(n_heads)))
     # one buffer per (device, stream), as the C++ side keys its scratch (host/src/memory_hip.cpp): the split-sequence
     # kernels of two streams must not share partial sums.  A buffer that has to grow is replaced only after the
     # stream that used the old one has drained.
@@ -273,12 +277,30 @@ def _elem_of(wk, elem):
     return int(wk.dtype == torch.bfloat16) if elem is None else int(elem)
 
 
+def decode_scan_paged_heads(q_output, page_table, lengths, attention_result, n_heads, elem, n_sequence):
+    """The multi-head single-pass scan (mli_decode_scan_paged_heads): head h owns columns [h * D / n_heads, ...) of q, K and V,
+    one softmax per head; lean form.  n_heads = 1 is decode_scan_paged(phases=7)."""
+    B, D = q_output.shape
+    ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+    _check(load_library().mli_decode_scan_paged_heads(_p(q_output), _p(page_table), _p(lengths), _p(attention_result), B,
+                                                      n_sequence, D, int(n_heads), int(elem), _p(ws), need, _stream()),
+           "mli_decode_scan_paged_heads")
+
+
 def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_new_items,
-                         n_sequence, elem=None):
+                         n_sequence, elem=None, n_heads=1):
     """What the attention layers run: the paged composition without materialising scores / probabilities
-    (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype."""
+    (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads > 1: the
+    multi-head form (mli_paged_attention_lean_heads)."""
     B = page_table.shape[0]
     D = wk.shape[0]
+    if n_heads != 1:
+        ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+        _check(load_library().mli_paged_attention_lean_heads(_p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv),
+                                                             _p(new_batch_idx), _p(q_output), _p(attention_result), B,
+                                                             n_sequence, D, n_new_items, int(n_heads), _elem_of(wk, elem),
+                                                             _p(ws), need, _stream()), "mli_paged_attention_lean_heads")
+        return
     ws, need = workspace_for(B, n_sequence, D, q_output.device)
     _check(load_library().mli_paged_attention_lean(_p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv),
                                                    _p(new_batch_idx), _p(q_output), _p(attention_result), B, n_sequence,
