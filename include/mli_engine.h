@@ -129,6 +129,17 @@ int mli_engine_configure(mli_engine* engine, int lean_layers, int step_graphs);
  * nothing.  Loops, step graphs, preemption, sampling and n_forward_rounds work as with one head. */
 int mli_engine_set_heads(mli_engine* engine, int n_heads);
 
+/* EXTENSION: sliding-window attention (mli_kernels.h: mli_paged_attention_lean_window).  Every row attends its newest
+ * `window` tokens only.  The window changes which slots the scan reads and nothing else: admission, page growth,
+ * preemption, re-prefill, n_forward_rounds (the window follows the device-side length), step graphs, sampling and the
+ * pipelined loop work as without one, and no page is returned to the pool early.  Before the first step or run; kinds
+ * MLI_ENGINE_PAGED, MLI_ENGINE_PAGED_GEMM, MLI_ENGINE_PAGED_BF16 and MLI_ENGINE_PAGED_FP8; combines with
+ * mli_engine_set_heads in either order (each call validates the combination).  -1 with a message for another kind,
+ * window < 1, a call after the engine has started, an engine configured with lean_layers = 0
+ * (mli_engine_configure(e, 0, ...) afterwards is refused likewise) or a shape the windowed scan does not take.
+ * window >= n_sequence is accepted everywhere and changes nothing. */
+int mli_engine_set_window(mli_engine* engine, int window);
+
 const char* mli_engine_last_error(void);
 
 #ifdef __cplusplus

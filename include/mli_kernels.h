@@ -230,6 +230,32 @@ int mli_paged_attention_lean_heads(void* const* page_table, const int* lengths,
                                    int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int elem,
                                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* EXTENSION: SLIDING-WINDOW attention for the lean paged composition and its scan.  window = W >= 1; for row b with
+ * L = min(lengths[b], n_sequence) and lo = max(0, L - W) the row attends slots s in [lo, L) -- its newest W tokens, the
+ * newest one (slot L - 1) always among them -- with the scores scaled as without a window (1 / sqrtf(emb_dim) with one
+ * head, 1 / sqrtf(head_dim) per head).  L == 0 gives zeros; W == 1 gives the fp32 value of V's row L - 1 bit for bit.
+ * No byte of a slot outside [lo, L) influences the result: slots >= L and slots < lo of the first live page are never
+ * multiplied, and the page-table entries of the pages wholly below lo (index < lo / 16) are never read -- they may be
+ * null or stale.  Fill, projection, page layout and q_output do not depend on W.
+ * W >= n_sequence is "no window": the call IS mli_decode_scan_paged(phases 7) / mli_paged_attention_lean, or the _heads
+ * forms for n_heads > 1 -- same kernels, same bits.  For W < n_sequence -- one scan launch, chunked grid sized by the
+ * min(n_sequence, 16 * (ceil(W / 16) + 1)) tokens a windowed row can span, in-kernel merge; of the mli_tune keys
+ * "chunk_tokens", "nt_loads" and "scan_row_order" apply -- the supported shapes are: n_heads == 1: what the lean chunked
+ * scan takes (n_sequence % 16 == 0; MLI_ELEM_F32 to emb_dim 2048, MLI_ELEM_BF16 to 4096, MLI_ELEM_FP8 with emb_dim % 16
+ * == 0 to 2048) with n_batch <= 16384; n_heads > 1: what mli_decode_scan_paged_heads takes.  Everything else, window < 1
+ * and n_heads < 1 are MLI_ERR_BAD_ARG, decided before anything is launched.
+ * Workspace: mli_attention_workspace_bytes (n_heads == 1) / mli_attention_heads_workspace_bytes of the same
+ * (n_batch, n_sequence, emb_dim, n_heads): one buffer serves windowed and plain calls; same layout and counter rule. */
+int mli_decode_scan_paged_window(const float* q_output, const void* const* page_table, const int* lengths,
+                                 float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                 int window, int elem, void* workspace, size_t workspace_bytes, void* stream);
+
+/* mli_paged_attention_lean[_heads] with a window: fill (n_new_items rows) -> latest -> windowed scan. */
+int mli_paged_attention_lean_window(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                    const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                    int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int window,
+                                    int elem, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */

@@ -15,13 +15,6 @@ int fused_chunk_tokens(int B, int S);   // attention_fused.hip
 int scan_row_order();
 int tuned_chunk_tokens();               // attention_scan.hip
 int nt_loads_for(int B, int S, int D, int esize);
-int launch_latest_paged(float* const*, const int*, const float*, const float*, const float*, float*, int, int, int,
-                        hipStream_t);   // proj_gemm.hip
-int launch_fill_paged(float* const*, const int*, const int*, const float*, const float*, int, int, int, int, hipStream_t);
-int launch_latest_paged_bf16(uint16_t* const*, const int*, const uint16_t*, const uint16_t*, const uint16_t*, float*, int,
-                             int, int, hipStream_t);   // proj_gemm_bf16.hip
-int launch_fill_paged_bf16(uint16_t* const*, const int*, const int*, const uint16_t*, const uint16_t*, int, int, int, int,
-                           hipStream_t);
 
 template <class E, int NJ, bool NT>
 __global__ __launch_bounds__(kFuThreads, 2) void heads_decode_scan_kernel(
@@ -45,8 +38,8 @@ constexpr int kMaxItemTokens = 1024;
 constexpr int kMaxMergeStats = 4096;   // float2 entries
 
 // The supported combinations (everything else is MLI_ERR_BAD_ARG before anything is launched).  Returns log2 of the lanes
-// per head, or -1.
-static int heads_lanes_log2(int B, int S, int D, int H, int elem) {
+// per head, or -1.  (This and the two sizing rules below: also attention_window.hip.)
+int heads_lanes_log2(int B, int S, int D, int H, int elem) {
     if (B <= 0 || B > kMaxArrivalRows || S <= 0 || S % kPage != 0 || D <= 0 || H < 1 || D % H != 0) return -1;
     if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) return -1;
     const int hd = D / H;
@@ -67,14 +60,14 @@ int heads_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads,
 // Tokens per item: the single-head scan's choice, raised where a row's (items x heads) statistics would not fit the
 // 32 KiB of LDS the last arriver stages them in (n_sequence 16384 with 32 heads and a small batch).  A size exists for
 // every shape heads_lanes_log2 accepts.
-static int heads_chunk_tokens(int B, int S, int H) {
+int heads_chunk_tokens(int B, int S, int H) {
     int ct = (S <= 128 && B >= 256 && tuned_chunk_tokens() == 0) ? 128 : fused_chunk_tokens(B, S);
     while (ct < kMaxItemTokens && (int64_t)ceil_div_i(S, ct) * H > kMaxMergeStats) ct <<= 1;
     return ct;
 }
 
 // body = [(m, l) per row, item and head: B * ceil(S / 64) * H float2, 256-B aligned][partial rows: B * ceil(S / 64) * D]
-static size_t heads_stats_bytes(int B, int S, int H) {
+size_t heads_stats_bytes(int B, int S, int H) {
     const size_t n = (size_t)B * ceil_div_i(S, 64) * H * sizeof(float2);
     return (n + 255) & ~(size_t)255;
 }
@@ -168,18 +161,8 @@ int mli_paged_attention_lean_heads(void* const* page_table, const int* lengths, 
     if (lg < 0) return MLI_ERR_BAD_ARG;
     hipStream_t st = mli::as_stream(stream);
     // fill and projection: the launches of mli_paged_attention_lean (pages and q_output do not depend on n_heads)
-    int rc;
-    if (elem == MLI_ELEM_BF16) {
-        mli_bf16* const* pt = reinterpret_cast<mli_bf16* const*>(page_table);
-        const mli_bf16 *k = static_cast<const mli_bf16*>(wk), *q = static_cast<const mli_bf16*>(wq), *v = static_cast<const mli_bf16*>(wv);
-        rc = mli::launch_fill_paged_bf16(pt, new_batch_idx, lengths, k, v, n_batch, n_sequence, emb_dim, n_new_items, st);
-        if (!rc) rc = mli::launch_latest_paged_bf16(pt, lengths, k, q, v, q_output, n_batch, n_sequence, emb_dim, st);
-    } else {
-        float* const* pt = reinterpret_cast<float* const*>(page_table);
-        const float *k = static_cast<const float*>(wk), *q = static_cast<const float*>(wq), *v = static_cast<const float*>(wv);
-        rc = mli::launch_fill_paged(pt, new_batch_idx, lengths, k, v, n_batch, n_sequence, emb_dim, n_new_items, st);
-        if (!rc) rc = mli::launch_latest_paged(pt, lengths, k, q, v, q_output, n_batch, n_sequence, emb_dim, st);
-    }
+    const int rc = mli::launch_fill_and_latest(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, n_batch,
+                                               n_sequence, emb_dim, n_new_items, st);
     if (rc) return rc;
     return mli::launch_heads_decode_elem(q_output, reinterpret_cast<const void* const*>(page_table), lengths,
                                          attention_result, n_batch, n_sequence, emb_dim, n_heads, lg, elem, workspace,

@@ -51,6 +51,32 @@ int launch_fill_paged_fp8_embed(const float*, const float*, const int*, uint8_t*
 int launch_fused_decode_fp8(const float*, const uint8_t* const*, const int*, float*, int, int, int, void*, size_t, hipStream_t);
 int launch_softmax_v_paged_bf16(const float*, const uint16_t* const*, const int*, float*, int, int, int, void*, size_t,
                                 hipStream_t);
+
+int launch_fill_and_latest(int elem, void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                           const void* wv, const int* new_batch_idx, float* q_output, int n_batch, int n_sequence,
+                           int emb_dim, int n_new_items, hipStream_t st) {
+    int rc;
+    if (elem == MLI_ELEM_FP8) {
+        uint8_t* const* pt = reinterpret_cast<uint8_t* const*>(page_table);
+        const mli_bf16 *k = static_cast<const mli_bf16*>(wk), *q = static_cast<const mli_bf16*>(wq), *v = static_cast<const mli_bf16*>(wv);
+        rc = launch_fill_paged_fp8_embed(nullptr, nullptr, nullptr, pt, new_batch_idx, lengths, k, v, n_batch, n_sequence,
+                                         emb_dim, n_new_items, st);
+        if (!rc) rc = launch_latest_paged_fp8(pt, lengths, k, q, v, q_output, n_batch, n_sequence, emb_dim, st);
+    } else if (elem == MLI_ELEM_BF16) {
+        mli_bf16* const* pt = reinterpret_cast<mli_bf16* const*>(page_table);
+        const mli_bf16 *k = static_cast<const mli_bf16*>(wk), *q = static_cast<const mli_bf16*>(wq), *v = static_cast<const mli_bf16*>(wv);
+        rc = launch_fill_paged_bf16(pt, new_batch_idx, lengths, k, v, n_batch, n_sequence, emb_dim, n_new_items, st);
+        if (!rc) rc = launch_latest_paged_bf16(pt, lengths, k, q, v, q_output, n_batch, n_sequence, emb_dim, st);
+    } else if (elem == MLI_ELEM_F32) {
+        float* const* pt = reinterpret_cast<float* const*>(page_table);
+        const float *k = static_cast<const float*>(wk), *q = static_cast<const float*>(wq), *v = static_cast<const float*>(wv);
+        rc = launch_fill_paged(pt, new_batch_idx, lengths, k, v, n_batch, n_sequence, emb_dim, n_new_items, st);
+        if (!rc) rc = launch_latest_paged(pt, lengths, k, q, v, q_output, n_batch, n_sequence, emb_dim, st);
+    } else {
+        rc = MLI_ERR_BAD_ARG;
+    }
+    return rc;
+}
 }  // namespace mli
 
 extern "C" {
@@ -65,34 +91,20 @@ int mli_paged_attention_lean(void* const* page_table, const int* lengths, const 
                              size_t workspace_bytes, void* stream) {
     { const mli::WsBody body = mli::ws_body(workspace, workspace_bytes); workspace = body.ptr; workspace_bytes = body.bytes; }
     hipStream_t st = mli::as_stream(stream);
-    int rc, fused;
     if (elem_bf16 < MLI_ELEM_F32 || elem_bf16 > MLI_ELEM_FP8) return MLI_ERR_BAD_ARG;
-    if (elem_bf16 == MLI_ELEM_FP8) {
-        uint8_t* const* pt = reinterpret_cast<uint8_t* const*>(page_table);
-        const mli_bf16 *k = static_cast<const mli_bf16*>(wk), *q = static_cast<const mli_bf16*>(wq), *v = static_cast<const mli_bf16*>(wv);
-        rc = mli::launch_fill_paged_fp8_embed(nullptr, nullptr, nullptr, pt, new_batch_idx, lengths, k, v, n_batch, n_sequence,
-                                              emb_dim, n_new_items, st);
-        if (!rc) rc = mli::launch_latest_paged_fp8(pt, lengths, k, q, v, q_output, n_batch, n_sequence, emb_dim, st);
-        if (rc) return rc;
-        fused = mli::launch_fused_decode_fp8(q_output, pt, lengths, attention_result, n_batch, n_sequence, emb_dim, workspace,
-                                             workspace_bytes, st);
-    } else if (elem_bf16) {
-        mli_bf16* const* pt = reinterpret_cast<mli_bf16* const*>(page_table);
-        const mli_bf16 *k = static_cast<const mli_bf16*>(wk), *q = static_cast<const mli_bf16*>(wq), *v = static_cast<const mli_bf16*>(wv);
-        rc = mli::launch_fill_paged_bf16(pt, new_batch_idx, lengths, k, v, n_batch, n_sequence, emb_dim, n_new_items, st);
-        if (!rc) rc = mli::launch_latest_paged_bf16(pt, lengths, k, q, v, q_output, n_batch, n_sequence, emb_dim, st);
-        if (rc) return rc;
-        fused = mli::launch_fused_decode_bf16(q_output, pt, lengths, nullptr, attention_result, n_batch, n_sequence,
-                                              emb_dim, workspace, workspace_bytes, st);
-    } else {
-        float* const* pt = reinterpret_cast<float* const*>(page_table);
-        const float *k = static_cast<const float*>(wk), *q = static_cast<const float*>(wq), *v = static_cast<const float*>(wv);
-        rc = mli::launch_fill_paged(pt, new_batch_idx, lengths, k, v, n_batch, n_sequence, emb_dim, n_new_items, st);
-        if (!rc) rc = mli::launch_latest_paged(pt, lengths, k, q, v, q_output, n_batch, n_sequence, emb_dim, st);
-        if (rc) return rc;
-        fused = mli::launch_fused_decode_f32(q_output, pt, lengths, nullptr, attention_result, n_batch, n_sequence,
-                                             emb_dim, workspace, workspace_bytes, st);
-    }
+    const int rc = mli::launch_fill_and_latest(elem_bf16, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, n_batch,
+                                               n_sequence, emb_dim, n_new_items, st);
+    if (rc) return rc;
+    int fused;
+    if (elem_bf16 == MLI_ELEM_FP8)
+        fused = mli::launch_fused_decode_fp8(q_output, reinterpret_cast<uint8_t* const*>(page_table), lengths, attention_result,
+                                             n_batch, n_sequence, emb_dim, workspace, workspace_bytes, st);
+    else if (elem_bf16 == MLI_ELEM_BF16)
+        fused = mli::launch_fused_decode_bf16(q_output, reinterpret_cast<mli_bf16* const*>(page_table), lengths, nullptr,
+                                              attention_result, n_batch, n_sequence, emb_dim, workspace, workspace_bytes, st);
+    else
+        fused = mli::launch_fused_decode_f32(q_output, reinterpret_cast<float* const*>(page_table), lengths, nullptr,
+                                             attention_result, n_batch, n_sequence, emb_dim, workspace, workspace_bytes, st);
     if (fused == 1) return 0;
     // rows too wide for the single-pass kernel (or no workspace): the caller takes the materialising composition
     if (fused == 0) return MLI_ERR_BAD_ARG;

@@ -50,11 +50,13 @@ __device__ __forceinline__ void heads_xor_step(float (&v)[NJ][16]) {
 // ml: [B][nchunk_max][H] (max, sum) per item and head; partial: [B][nchunk_max][D] un-normalised partial rows.
 // TBR = rows per load batch, PD = batches in flight (of four register buffers).
 // smem_raw: ct / 16 page pointers | max(4 waves x (NJ * 64 * EPL floats + NJ * 64 float2), nchunk_max * H float2)
-template <class E, int NJ, bool NT, int TBR, int PD>
+// WIN = true (EXTENSION, attention_window.hip): the row attends its newest `window` tokens -- fused_scan_item's window
+// switch: the row is taken from its first live page p0 on, and that page's slots below the window are masked.
+template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false>
 __device__ __forceinline__ void heads_scan_item(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ out, float2* ml, float* partial, int S, int D, int lg, int H, int ct, int nchunk_max, int direct,
-    unsigned* arrivals, int b, int c, bool first_grid_row, unsigned char* smem_raw) {
+    unsigned* arrivals, int b, int c, bool first_grid_row, unsigned char* smem_raw, int window = 0) {
     constexpr int EPL = E::EPL;
     constexpr int kRowF = NJ * kWave * EPL;   // floats one wave parks
     constexpr int kRowU = NJ * kWave;         // lane units of a row
@@ -67,7 +69,7 @@ __device__ __forceinline__ void heads_scan_item(
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     const int W = S / kPage;
-    const bool early = c < nchunk_max;
+    const bool early = !WIN && c < nchunk_max;   // (a windowed row's first page depends on its length)
     const void* early_ptr = nullptr;
     if (early && (int)threadIdx.x < ct / kPage && c * (ct / kPage) + (int)threadIdx.x < W)
         early_ptr = page_table[(int64_t)b * W + c * (ct / kPage) + threadIdx.x];
@@ -83,7 +85,10 @@ __device__ __forceinline__ void heads_scan_item(
 #pragma unroll
         for (int e = 0; e < EPL; ++e) qr[j][e] = live ? q[(int64_t)b * D + u * EPL + e] : 0.f;
     }
-    const int L = min(lengths[b], S);
+    const int L_row = min(lengths[b], S);
+    const int lo = WIN ? max(0, L_row - window) : 0;   // first slot the row attends
+    const int p0 = lo / kPage;                         // ... and the page it lies in
+    const int L = L_row - p0 * kPage;                  // the row from that page on
     if (L <= 0) {
         // no workgroup arrives for an empty row: its zero result is written here, once
         if (first_grid_row)
@@ -109,7 +114,7 @@ __device__ __forceinline__ void heads_scan_item(
         if ((int)threadIdx.x < npages) ptr_sh[threadIdx.x] = early_ptr;   // npages <= ct / 16 <= 64 < threads
     } else {
         for (int i = threadIdx.x; i < npages; i += kFuThreads)
-            ptr_sh[i] = page_table[(int64_t)b * W + s0 / kPage + i];
+            ptr_sh[i] = page_table[(int64_t)b * W + p0 + s0 / kPage + i];
     }
     __syncthreads();
 
@@ -165,6 +170,7 @@ __device__ __forceinline__ void heads_scan_item(
         const bool has_next = pi + kFuWaves < npages;
         const char* next = has_next ? page_ptr(pi + kFuWaves) : nullptr;
         const int nt = min(kPage, ntok - pi * kPage);  // live tokens in this page (>= 1)
+        const int nlo = (WIN && pi == 0 && s0 == 0) ? lo - p0 * kPage : 0;   // slots below the window (row's first live page)
         float sp[NJ][16];   // partial scores, then scores, then the page's probabilities (of the lane's head for j)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
@@ -201,14 +207,14 @@ __device__ __forceinline__ void heads_scan_item(
 #pragma unroll
                         for (int t = 0; t < 16; ++t) {
                             sp[j][t] = div_by(sp[j][t], scale, inv_scale);
-                            pm = t < nt ? fmaxf(pm, sp[j][t]) : pm;
+                            pm = slot_live<WIN>(t, nt, nlo) ? fmaxf(pm, sp[j][t]) : pm;
                         }
                         const float m_new = fmaxf(run_m[j], pm);
                         const float alpha = run_m[j] == -INFINITY ? 0.f : expf(run_m[j] - m_new);
                         float psum = 0.f;
 #pragma unroll
                         for (int t = 0; t < 16; ++t) {
-                            sp[j][t] = t < nt ? expf(sp[j][t] - m_new) : 0.f;
+                            sp[j][t] = slot_live<WIN>(t, nt, nlo) ? expf(sp[j][t] - m_new) : 0.f;
                             psum += sp[j][t];
                         }
                         run_l[j] = run_l[j] * alpha + psum;
@@ -222,7 +228,8 @@ __device__ __forceinline__ void heads_scan_item(
                 constexpr int first = (pos - NB) * TBR;
 #pragma unroll
                 for (int t = 0; t < TBR; ++t) {
-                    if (first + t < nt) {  // wave-uniform: never multiply unwritten page memory, even by zero
+                    // wave-uniform: never multiply unwritten page memory (or a slot below the window), even by zero
+                    if (slot_live<WIN>(first + t, nt, nlo)) {
 #pragma unroll
                         for (int j = 0; j < NJ; ++j) ElemMath<E>::axpy(buf[bi][t][j], sp[j][first + t], acc[j]);
                     }

@@ -114,15 +114,29 @@ __device__ __forceinline__ void row_publish_merge(float m, float l, float2* ml_r
     }
 }
 
+// Is slot t of a page attended?  nt: the page's slots inside the row; nlo (WIN, attention_window.hip): its slots below the
+// row's window.
+template <bool WIN>
+__device__ __forceinline__ bool slot_live(int t, int nt, int nlo) {
+    if constexpr (WIN) return t < nt && t >= nlo;
+    else return t < nt;
+}
+
 // b, c: the item (row, grid row); first_grid_row: this workgroup is the one that writes the zero result of an empty row.
 // RPI = token slots per load instruction (scan_common.hpp; 1 except for narrow fp8 rows): a batch is TBR instructions =
 //   TBR * RPI slots
-template <class E, int NJ, bool NT, int TBR, bool DS, bool SCORES, int RPI>
+// WIN = true (EXTENSION, attention_window.hip; lean form only): the row attends its newest `window` tokens, slots
+//   [lo, L) with lo = max(0, L - window).  Its first live page is p0 = lo / 16; everything below is done on the row as it
+//   looks from token 16 * p0 on (relative length L - 16 * p0 <= window + 15; page pointers from page_table[b][p0 + ...], an
+//   entry below p0 is never read), and in the row's first live page the slots t < lo - 16 * p0 are masked exactly as the
+//   slots >= nt of its last one are.  WIN = false ignores `window`.
+template <class E, int NJ, bool NT, int TBR, bool DS, bool SCORES, int RPI, bool WIN = false>
 __device__ __forceinline__ void fused_scan_item(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ qkt, float* __restrict__ out, float2* ml, float* partial,
     int S, int D, int ct, int ml_per_row, int nchunk_max, int direct, unsigned* arrivals, int b, int c,
-    bool first_grid_row, int trace_stride, unsigned char* smem_raw) {
+    bool first_grid_row, int trace_stride, unsigned char* smem_raw, int window = 0) {
+    static_assert(!WIN || !SCORES, "the window exists in the lean form only");
     constexpr int EPL = E::EPL;
     constexpr int LPR = kWave / RPI;   // lanes per token row
     static_assert(RPI == 1 || (NJ == 1 && !DS), "several rows per instruction: rows of one lane load, whole pages per wave");
@@ -145,7 +159,7 @@ __device__ __forceinline__ void fused_scan_item(
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     const int W = S / kPage;
-    const bool early = c < nchunk_max;
+    const bool early = !WIN && c < nchunk_max;   // (a windowed row's first page depends on its length)
     const void* early_ptr = nullptr;
     if (early && (int)threadIdx.x < ct / kPage && c * (ct / kPage) + (int)threadIdx.x < W)
         early_ptr = page_table[(int64_t)b * W + c * (ct / kPage) + threadIdx.x];
@@ -166,7 +180,10 @@ __device__ __forceinline__ void fused_scan_item(
 #pragma unroll
         for (int e = 0; e < EPLc; ++e) qr[j][e] = live[j] ? q[(int64_t)b * D + u * EPLc + e] : 0.f;
     }
-    const int L = min(lengths[b], S);
+    const int L_row = min(lengths[b], S);
+    const int lo = WIN ? max(0, L_row - window) : 0;   // first slot the row attends
+    const int p0 = lo / kPage;                         // ... and the page it lies in
+    const int L = L_row - p0 * kPage;                  // the row from that page on
     if (arrivals != nullptr && L == 0) {
         // in-kernel merge: no workgroup arrives for an empty row, so its zero result is written here, once
         if (first_grid_row) {
@@ -206,7 +223,7 @@ __device__ __forceinline__ void fused_scan_item(
         if ((int)threadIdx.x < npages) ptr_sh[threadIdx.x] = early_ptr;   // npages <= ct / 16 <= 64 < threads
     } else {
         for (int i = threadIdx.x; i < npages; i += kFuThreads)
-            ptr_sh[i] = page_table[(int64_t)b * W + s0 / kPage + i];
+            ptr_sh[i] = page_table[(int64_t)b * W + p0 + s0 / kPage + i];
     }
     __syncthreads();
     MLI_TRACE(1);
@@ -266,6 +283,7 @@ __device__ __forceinline__ void fused_scan_item(
         const bool has_next = pi + PSTEP < npages;
         const char* next = has_next ? page_ptr(pi + PSTEP) : nullptr;
         const int nt = min(kPage, ntok - pi * kPage);  // live tokens in this page (>= 1)
+        const int nlo = (WIN && pi == 0 && s0 == 0) ? lo - p0 * kPage : 0;   // slots below the window (row's first live page)
         float sacc[16 / RPI];
 #pragma unroll
         for (int t = 0; t < 16 / RPI; ++t) sacc[t] = 0.f;
@@ -299,7 +317,7 @@ __device__ __forceinline__ void fused_scan_item(
 #pragma unroll
                         for (int w = 0; w < kFuWaves; ++w) tot += xs[w * 16 + slot];
                     }
-                    const bool valid = slot < nt;
+                    const bool valid = slot_live<WIN>(slot, nt, nlo);
                     const float score = tot / scale;
                     if (SCORES && valid && (lane & 3) == 0 && (!DS || wave == 0))
                         qkt_row[s0 + pi * kPage + slot] = score;  // raw; normalised later
@@ -322,12 +340,14 @@ __device__ __forceinline__ void fused_scan_item(
                 for (int t = 0; t < TBR; ++t) {
                     // the slot's probability sits in lane 4 * slot: broadcast through an SGPR
                     const float p = rpi_prob<RPI>(p_lane, first + t, lane);
-                    if (RPI * (first + t) < nt) {  // wave-uniform: never multiply unwritten page memory, even by zero
+                    // wave-uniform: never multiply unwritten page memory (or a slot outside the window), even by zero; the
+                    // instruction is skipped when its first slot lies beyond the row or its last one below the window
+                    if (slot_live<WIN>(RPI * (first + t), nt, nlo - (RPI - 1))) {
 #pragma unroll
                         for (int j = 0; j < NJ; ++j) {
                             fu_u32x4 raw = buf[bi][t][j];
                             if constexpr (RPI > 1) {   // (per lane group: a slot beyond the row reads as zeros)
-                                const bool ok = RPI * (first + t) + lane_grp < nt;
+                                const bool ok = slot_live<WIN>(RPI * (first + t) + lane_grp, nt, nlo);
                                 raw.x = ok ? raw.x : 0u; raw.y = ok ? raw.y : 0u; raw.z = ok ? raw.z : 0u; raw.w = ok ? raw.w : 0u;
                             }
                             ElemMath<E>::axpy(raw, p, acc[j]);

@@ -12,8 +12,11 @@ namespace mli {
 // the lengths -- a histogram over the page counts, then the j-th row of its bucket by a block-wide count --: ~2 us of
 // prologue per workgroup, no pre-pass, deterministic.  All kFuThreads threads call it; n_batch <= kMaxOrderedRows.
 constexpr int kMaxOrderedRows = 2048;
+// WIN = true (attention_window.hip): the rows are ranked by the pages their window leaves live, ceil(L / 16) - lo / 16 with
+// lo = max(0, L - window); S / 16 may then exceed kMaxOrderedPages as long as the window's span does not.
 constexpr int kMaxOrderedPages = 64;
-__device__ __forceinline__ int longest_first_row(const int* __restrict__ lengths, int n_batch, int S, int rank) {
+template <bool WIN = false>
+__device__ __forceinline__ int longest_first_row(const int* __restrict__ lengths, int n_batch, int S, int rank, int window = 0) {
     __shared__ int hist[kMaxOrderedPages + 1];
     __shared__ int wave_cnt[kFuWaves];
     __shared__ int found_row;
@@ -28,7 +31,8 @@ __device__ __forceinline__ int longest_first_row(const int* __restrict__ lengths
         const int row = tid * per + j;
         pages[j] = -1;
         if (j < per && row < n_batch) {
-            pages[j] = (min(max(lengths[row], 0), S) + kPage - 1) / kPage;
+            const int len = min(max(lengths[row], 0), S);
+            pages[j] = (len + kPage - 1) / kPage - (WIN ? max(0, len - window) / kPage : 0);
             atomicAdd(&hist[pages[j]], 1);
         }
     }

@@ -38,7 +38,7 @@ def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
 
 class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
-                 n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1):
+                 n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -48,6 +48,8 @@ class Engine:
         self._check(self._lib.mli_engine_create(ctypes.byref(self.cfg), *[k[1] for k in keep], ctypes.byref(self._h)))
         if n_heads != 1:
             self.set_heads(n_heads)
+        if window is not None:
+            self.set_window(window)
 
     def _check(self, rc):
         if rc != 0:
@@ -56,6 +58,11 @@ class Engine:
     def set_heads(self, n_heads):
         """Multi-head attention (mli_engine_set_heads): before the first step or run, fp32 / bf16 paged kinds."""
         self._check(self._lib.mli_engine_set_heads(self._h, int(n_heads)))
+
+    def set_window(self, window):
+        """Sliding-window attention (mli_engine_set_window): every row attends its newest `window` tokens.  Before the
+        first step or run, paged kinds; window >= n_sequence changes nothing."""
+        self._check(self._lib.mli_engine_set_window(self._h, int(window)))
 
     def use_private_stream(self):
         self._check(self._lib.mli_engine_use_private_stream(self._h))

@@ -49,12 +49,15 @@ public:
                  int n_new_items);
     // attention heads of the lean forward (default 1: one softmax over emb_dim)
     void set_n_heads(int n_heads) { n_heads_ = n_heads; }
+    // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
+    void set_window(int window) { window_ = window; }
 
 private:
     TensorBf16 wk_, wq_, wv_;
     TensorFloat q_output_;
     TensorFloat qkt_output_;
     int n_heads_ = 1;
+    int window_ = 0;
 };
 
 class PagedAttentionBf16InferenceModel : public NonCopyableNonClonable {
@@ -67,6 +70,7 @@ public:
     // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling)
     void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }
     void set_n_heads(int n_heads) { attention_layer_.set_n_heads(n_heads); }
+    void set_window(int window) { attention_layer_.set_window(window); }
 
 private:
     PagedAttentionBf16Layer attention_layer_;

@@ -24,11 +24,14 @@ public:
     void prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
                  TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
                  int n_new_items);
+    // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
+    void set_window(int window) { window_ = window; }
 
 private:
     TensorBf16 wk_, wq_, wv_;
     TensorFloat q_output_;
     size_t n_sequence_;
+    int window_ = 0;
 };
 
 class PagedAttentionFp8InferenceModel : public NonCopyableNonClonable {
@@ -41,6 +44,7 @@ public:
     // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling); allocates the
     // logits buffer the sampled head needs
     void set_sampling(const SlotSampling* sampling);
+    void set_window(int window) { attention_layer_.set_window(window); }
 
 private:
     PagedAttentionFp8Layer attention_layer_;

@@ -37,6 +37,7 @@ public:
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
     void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
     void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
+    void set_window(int window) { paged_attention_layer_.set_window(window); }                        // EXTENSION
 
 private:
     PagedAttentionLayer paged_attention_layer_;
@@ -58,6 +59,7 @@ public:
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table, GemmHandle handle);
     void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
     void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
+    void set_window(int window) { paged_attention_layer_.set_window(window); }                        // EXTENSION
 
 private:
     PagedAttentionCublasLayer paged_attention_layer_;

@@ -43,6 +43,14 @@ void paged_attention_lean_heads(TensorFloatPoint& page_table, const TensorInt& l
                                 TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
                                 int n_heads);
 
+// EXTENSION: paged_attention_lean[_heads] with a sliding window: row b attends its newest `window` tokens (slots
+// [max(0, L - window), L), L = min(lengths[b], n_sequence)).  Pages and q_output are those of paged_attention_lean;
+// window >= n_sequence is the un-windowed call.  Throws on an unsupported shape.
+void paged_attention_lean_window(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                                 const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                                 TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
+                                 int n_heads, int window);
+
 // EXTENSION: launch_paged_attention_encoder_kernel + launch_fill_new_k_v_cache_paged_attention in one
 // launch -- the embedding lookup is the fill GEMM's prologue; pages bit-identical to the two-launch form.
 void launch_paged_prefill(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,

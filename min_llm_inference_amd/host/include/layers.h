@@ -40,12 +40,15 @@ public:
 
     // EXTENSION: attention heads of the lean forward (default 1 = the reference's single softmax over emb_dim)
     void set_n_heads(int n_heads) { n_heads_ = n_heads; }
+    // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
+    void set_window(int window) { window_ = window; }
 
 private:
     TensorFloat wk_, wq_, wv_;
     TensorFloat q_output_;
     TensorFloat qkt_output_;
     int n_heads_ = 1;
+    int window_ = 0;
 };
 
 class PagedAttentionCublasLayer : public NonCopyableNonClonable {
@@ -60,12 +63,15 @@ public:
 
     // EXTENSION: attention heads of the lean forward (default 1 = the reference's single softmax over emb_dim)
     void set_n_heads(int n_heads) { n_heads_ = n_heads; }
+    // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
+    void set_window(int window) { window_ = window; }
 
 private:
     TensorFloat wk_, wq_, wv_;
     TensorFloat q_output_;
     TensorFloat qkt_output_;
     int n_heads_ = 1;
+    int window_ = 0;
     TensorFloat latest_emb_;        // kept for signature parity with the reference; unused by the MFMA path
     TensorFloat temp_placeholder_;
 };

@@ -76,6 +76,16 @@ void PagedAttentionBf16Layer::forward(TensorFloatPoint& page_table, const Tensor
                                       const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                       int n_new_items) {
     const int n_sequence = static_cast<int>(qkt_output_.shape()[1]);
+    if (window_ > 0 && window_ < n_sequence) {
+        if (!mli::runtime::lean_layers()) throw std::runtime_error("sliding-window attention exists in the lean composition only");
+        const int B = (int)page_table.shape()[0], D = (int)wk_.shape()[0];
+        const mli::runtime::Scratch ws = mli::runtime::attention_scratch(B, n_sequence, D, n_heads_);
+        HIP_CHECK(mli_paged_attention_lean_window(reinterpret_cast<void* const*>(page_table.data()), lengths.data(), wk_.data(),
+                                                  wq_.data(), wv_.data(), new_batch_idx.data(), q_output_.data(),
+                                                  attention_result.data(), B, n_sequence, D, n_new_items, n_heads_, window_,
+                                                  MLI_ELEM_BF16, ws.ptr, ws.bytes, mli::runtime::compute_stream()));
+        return;
+    }
     if (n_heads_ > 1) {
         if (!mli::runtime::lean_layers()) throw std::runtime_error("multi-head attention exists in the lean composition only");
         const int B = (int)page_table.shape()[0], D = (int)wk_.shape()[0];

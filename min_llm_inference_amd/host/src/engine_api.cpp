@@ -27,6 +27,7 @@
 
 namespace mli {
 int heads_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int elem);  // attention_heads.hip
+int window_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int elem);  // attention_window.hip
 }
 
 namespace {
@@ -79,6 +80,7 @@ struct mli_engine {
     bool lean_layers = g_default_lean_layers.load();   // this engine's composition and replay switches (runtime.h)
     bool step_graphs = g_default_step_graphs.load();
     int n_heads = 1;            // mli_engine_set_heads
+    int window = 0;             // mli_engine_set_window (0: none)
 
     // EXTENSION: sampled decoding (mli_engine_add_item_sampled).  The parameters live here, keyed by item
     // id, so a preempted item keeps its stream; the decoder head reads them from per-slot device arrays, filled when an
@@ -389,6 +391,8 @@ int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
         if (e->started) throw std::runtime_error("mli_engine_configure after the engine has started");
         if (e->n_heads > 1 && lean_layers == 0)   // refused before anything is changed
             throw std::runtime_error("multi-head attention (mli_engine_set_heads) has the lean compositions only");
+        if (e->window > 0 && e->window < e->cfg.n_sequence && lean_layers == 0)
+            throw std::runtime_error("sliding-window attention (mli_engine_set_window) has the lean compositions only");
         if (lean_layers >= 0) e->lean_layers = lean_layers != 0;
         if (step_graphs >= 0) e->step_graphs = step_graphs != 0;
         if (e->cfg.kind == MLI_ENGINE_PAGED_FP8 && !e->lean_layers)
@@ -411,10 +415,44 @@ int mli_engine_set_heads(mli_engine* e, int n_heads) {
             if (n_heads > 1 && !mli::heads_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, elem))
                 throw std::runtime_error("mli_engine_set_heads: unsupported (emb_dim, n_heads): head_dim must be 32, 64, 128 or "
                                          "256 and emb_dim at most 512 (fp32) / 1024 (bf16)");
+            if (e->window > 0 && e->window < e->cfg.n_sequence &&
+                !mli::window_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, elem))
+                throw std::runtime_error("mli_engine_set_heads: the windowed scan (mli_engine_set_window) does not take this shape");
             if (e->paged_model) e->paged_model->set_n_heads(n_heads);
             if (e->gemm_model) e->gemm_model->set_n_heads(n_heads);
             if (e->bf16_model) e->bf16_model->set_n_heads(n_heads);
             e->n_heads = n_heads;
+        }
+    })
+}
+
+int mli_engine_set_window(mli_engine* e, int window) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (window < 1) throw std::runtime_error("mli_engine_set_window: window must be >= 1");
+        // what counts is the window the scan would see: n_sequence or more is none, accepted everywhere, changing nothing
+        const int S = e->cfg.n_sequence;
+        const int now = e->window > 0 && e->window < S ? e->window : S;
+        const int then = window < S ? window : S;
+        if (then != now) {
+            const int kind = e->cfg.kind;
+            if (kind != MLI_ENGINE_PAGED && kind != MLI_ENGINE_PAGED_GEMM && kind != MLI_ENGINE_PAGED_BF16 &&
+                kind != MLI_ENGINE_PAGED_FP8)
+                throw std::runtime_error("mli_engine_set_window: sliding-window attention serves the paged engines");
+            if (e->started) throw std::runtime_error("mli_engine_set_window after the engine has started");
+            if (then < S) {
+                if (!e->lean_layers)
+                    throw std::runtime_error("mli_engine_set_window: sliding-window attention has the lean compositions only");
+                const int elem = kind == MLI_ENGINE_PAGED_FP8 ? MLI_ELEM_FP8 : kind == MLI_ENGINE_PAGED_BF16 ? MLI_ELEM_BF16 : MLI_ELEM_F32;
+                if (!mli::window_shape_supported(e->cfg.n_batch, S, e->cfg.emb_dim, e->n_heads, elem))
+                    throw std::runtime_error("mli_engine_set_window: the windowed scan does not take this (n_batch, n_sequence, "
+                                             "emb_dim, n_heads)");
+            }
+            if (e->paged_model) e->paged_model->set_window(then);
+            if (e->gemm_model) e->gemm_model->set_window(then);
+            if (e->bf16_model) e->bf16_model->set_window(then);
+            if (e->fp8_model) e->fp8_model->set_window(then);
+            e->window = then;
         }
     })
 }

@@ -16,6 +16,13 @@ void PagedAttentionFp8Layer::forward(TensorFloatPoint& page_table, const TensorI
                                      const TensorInt& new_batch_idx, TensorFloat& attention_result, int n_new_items) {
     const int B = (int)page_table.shape()[0], D = (int)wk_.shape()[0], S = (int)n_sequence_;
     const mli::runtime::Scratch ws = mli::runtime::attention_scratch(B, S, D);
+    if (window_ > 0 && window_ < S) {
+        HIP_CHECK(mli_paged_attention_lean_window(reinterpret_cast<void* const*>(page_table.data()), lengths.data(), wk_.data(),
+                                                  wq_.data(), wv_.data(), new_batch_idx.data(), q_output_.data(),
+                                                  attention_result.data(), B, S, D, n_new_items, /*n_heads=*/1, window_,
+                                                  MLI_ELEM_FP8, ws.ptr, ws.bytes, mli::runtime::compute_stream()));
+        return;
+    }
     HIP_CHECK(mli_paged_attention_lean(reinterpret_cast<void* const*>(page_table.data()), lengths.data(), wk_.data(),
                                        wq_.data(), wv_.data(), new_batch_idx.data(), q_output_.data(),
                                        attention_result.data(), B, S, D, n_new_items, MLI_ELEM_FP8, ws.ptr, ws.bytes,

@@ -299,6 +299,19 @@ void paged_attention_lean_heads(TensorFloatPoint& page_table, const TensorInt& l
                                              ws.ptr, ws.bytes, stream()));
 }
 
+// EXTENSION: the lean composition with a sliding window (mli_paged_attention_lean_window); an unsupported shape throws
+void paged_attention_lean_window(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                                 const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                                 TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
+                                 int n_heads, int window) {
+    const int B = (int)page_table.shape()[0], D = (int)wk.shape()[0];
+    const Scratch ws = mli::runtime::attention_scratch(B, n_sequence, D, n_heads);
+    HIP_CHECK(mli_paged_attention_lean_window(reinterpret_cast<void* const*>(pages(page_table)), lengths.data(), wk.data(),
+                                              wq.data(), wv.data(), new_batch_idx.data(), q_output.data(),
+                                              attention_result.data(), B, n_sequence, D, n_new_items, n_heads, window,
+                                              MLI_ELEM_F32, ws.ptr, ws.bytes, stream()));
+}
+
 void paged_attention_with_cublas(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
                                  const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
                                  TensorFloat& q_output, TensorFloat& qkt_output, TensorFloat& attention_result,

@@ -287,13 +287,31 @@ def decode_scan_paged_heads(q_output, page_table, lengths, attention_result, n_h
            "mli_decode_scan_paged_heads")
 
 
+def decode_scan_paged_window(q_output, page_table, lengths, attention_result, n_heads, window, elem, n_sequence):
+    """The sliding-window scan (mli_decode_scan_paged_window): row b attends slots [max(0, L - window), L) only; lean
+    form, n_heads heads.  window >= n_sequence is decode_scan_paged(phases=7) / decode_scan_paged_heads."""
+    B, D = q_output.shape
+    ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+    _check(load_library().mli_decode_scan_paged_window(_p(q_output), _p(page_table), _p(lengths), _p(attention_result), B,
+                                                       n_sequence, D, int(n_heads), int(window), int(elem), _p(ws), need,
+                                                       _stream()), "mli_decode_scan_paged_window")
+
+
 def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_new_items,
-                         n_sequence, elem=None, n_heads=1):
+                         n_sequence, elem=None, n_heads=1, window=None):
     """What the attention layers run: the paged composition without materialising scores / probabilities
     (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads > 1: the
     multi-head form (mli_paged_attention_lean_heads)."""
     B = page_table.shape[0]
     D = wk.shape[0]
+    if window is not None:   # the sliding-window form (mli_paged_attention_lean_window)
+        ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+        _check(load_library().mli_paged_attention_lean_window(_p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv),
+                                                              _p(new_batch_idx), _p(q_output), _p(attention_result), B,
+                                                              n_sequence, D, n_new_items, int(n_heads), int(window),
+                                                              _elem_of(wk, elem), _p(ws), need, _stream()),
+               "mli_paged_attention_lean_window")
+        return
     if n_heads != 1:
         ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
         _check(load_library().mli_paged_attention_lean_heads(_p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv),
