@@ -25,15 +25,12 @@ import torch
 import f64_model as fm
 from accuracy_cases import (FAMILIES, SCAN_SHAPES, STREAM_CASES, apply_family, base_case, edge_lengths, fill_pages,
                             oracle_scan, poison_contiguous)
+from accuracy_gpu import (ELEM, REPORT as _report, SENTINEL, Checker, elems_for as _elems_for, lean as _lean,
+                          lean_twice as _lean_twice, paged_inputs as _paged_inputs, to_device as _t)
 from gpu_util import host
 from helpers import assert_equal, paged_case
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 12345.0
-ELEM = {"f32": 0, "bf16": 1, "fp8": 2}
-ESIZE = {"f32": 4, "bf16": 2, "fp8": 1}
-_report = {}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -45,35 +42,6 @@ def _write_report():
             json.dump({" | ".join(k): v for k, v in sorted(_report.items())}, f, indent=1)
 
 
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-class Checker:
-    """Collects the comparisons of one test: every figure is printed and recorded before anything is asserted."""
-
-    def __init__(self, family, elem="f32"):
-        self.family, self.elem, self.failures = family, elem, []
-
-    def check(self, path, what, err_rows, e_oracle_rows):
-        tol = fm.tolerance(e_oracle_rows)
-        worst = float(np.max(err_rows)) if len(err_rows) else 0.0
-        e_or = float(np.max(e_oracle_rows)) if len(e_oracle_rows) else 0.0
-        print(f"ACCURACY {path} | {self.elem} | {self.family} | {what}: kernel {worst:.3e}  oracle {e_or:.3e}  tol {tol:.3e}")
-        rec = _report.setdefault((path, self.elem, self.family, what), {"kernel": 0.0, "oracle": 0.0, "ratio": 0.0, "cases": 0})
-        rec["kernel"] = max(rec["kernel"], worst) if np.isfinite(worst) else float("inf")
-        rec["oracle"] = max(rec["oracle"], e_or)
-        rec["ratio"] = max(rec["ratio"], worst / tol)
-        rec["cases"] += 1
-        if not worst <= tol:
-            bad = np.nonzero(~(np.asarray(err_rows) <= tol))[0]
-            self.failures.append(f"{path} [{self.elem}, {self.family}] {what}: {worst:.3e} > tol {tol:.3e} "
-                                 f"(oracle {e_or:.3e}) in rows {bad[:8].tolist()}")
-
-    def done(self):
-        assert not self.failures, "\n".join(self.failures)
-
-
 @functools.lru_cache(maxsize=2)
 def _base(seed, B, S, D, chunks, lengths=None):
     if isinstance(lengths, tuple):
@@ -83,72 +51,19 @@ def _base(seed, B, S, D, chunks, lengths=None):
     return base_case(seed, B, S, D, L)
 
 
-def _pages_on_device(oracle, dev, c, q, kt, v, elem, poison):
-    """(device pool in the page element type, float32 values the pages hold).  The fp32 pool is converted ON THE DEVICE --
-    torch's round-to-nearest-even cast for bf16, the library's own mli_f32_to_fp8 for fp8, both checked against the numpy
-    definitions elsewhere in the suite -- and read back, so the model sees exactly what the kernels will read."""
-    from helpers import fp8_decode
-    from min_llm_inference_amd import ops
-    pool32, off = fill_pages(oracle, c, q, kt, v, finite_poison=poison == "finite")
-    t = _t(pool32, dev)
-    offs = _t(off, dev) if poison == "nan" and len(off) else None
-    if elem == "f32":
-        pool, values = t, pool32                     # (the model never reads a dead slot)
-        if offs is not None:
-            pool[offs] = float("nan")
-    elif elem == "bf16":
-        pool = t.to(torch.bfloat16)
-        values = pool.float().cpu().numpy()
-        if offs is not None:
-            pool.view(torch.int16)[offs] = 0x7FC0
-    else:
-        assert poison == "nan"
-        pool = ops.f32_to_fp8(t)
-        lut = _t(fp8_decode(np.arange(256, dtype=np.uint8)), dev)
-        values = lut[pool.long()].cpu().numpy()
-        if offs is not None:
-            pool[offs] = 0x7f
-    return pool, values
+def _two_rows_of_S_tokens(L, S):
+    """The length vector with its two long random rows (>= 3/4 S) made full: L == n_sequence, all S / 16 pages present.
+    Every paged scan clamps with min(L, S); the reference's own wrapper never goes beyond S - 1."""
+    L = L.copy()
+    rows = np.nonzero((L >= 3 * S // 4) & (L < S - 2))[0][:2]
+    assert len(rows) == 2
+    L[rows] = S
+    return L
 
 
-def _paged_inputs(oracle, dev, c, family, elem, poison="nan"):
-    """Pages of the family on the device, the float64 model of what they hold, and the oracle's scan of the same."""
-    q, kt = apply_family(c, family)
-    B, D, S = kt.shape
-    L = c["lengths"]
-    pool, values = _pages_on_device(oracle, dev, c, q, kt, c["v_cache"], elem, poison)
-    s_live = max(-(-int(L.max()) // 16) * 16, 16)          # the model and the oracle never look beyond the longest row
-    k_rows = fm.gather_pages(values, c["table"], L, s_live, D, 1)
-    v_rows = fm.gather_pages(values, c["table"], L, s_live, D, 2)
-    ktm = k_rows.transpose(0, 2, 1)
-    model = fm.Model(q, ktm, v_rows, L)
-    table = _t(np.where(c["table"] >= 0, pool.data_ptr() + ESIZE[elem] * c["table"], 0).astype(np.int64), dev)
-    return SimpleNamespace(q=_t(q, dev), L=_t(L, dev), page_table=table, pool=pool, model=model, B=B, S=S, D=D,
-                           oracle=oracle_scan(oracle, q, ktm, v_rows, L), lengths=L, k_rows=k_rows, v_rows=v_rows, q_host=q)
-
-
-def _elems_for(D):
-    from min_llm_inference_amd import ops
-    out = ["f32"]
-    if D % 8 == 0:
-        out.append("bf16")
-    if D % 16 == 0 and ops.has_fp8():
-        out.append("fp8")
-    return out
-
-
-def _lean(ops, x, elem, out=None):
-    out = torch.full((x.B, x.D), SENTINEL, device=x.q.device) if out is None else out.fill_(SENTINEL)
-    ops.decode_scan_paged(x.q, x.page_table, x.L, None, out, ELEM[elem], phases=7, n_sequence=x.S)
-    return host(out).copy()
-
-
-def _lean_twice(ops, x, elem, what):
-    """Two launches: the second finds the arrival counters back at zero, and gives the same bits."""
-    a = _lean(ops, x, elem)
-    b = _lean(ops, x, elem)
-    assert_equal(b, a, what=f"{what}: second launch")
-    return a
+@functools.lru_cache(maxsize=1)
+def _base_to_S(seed, B, S, D, chunks):
+    return base_case(seed, B, S, D, _two_rows_of_S_tokens(edge_lengths(seed, B, S, chunks), S))
 
 
 # ---- the single-pass paged scan (chunked grid): materialising and lean, fp32 / bf16 / fp8 pages ---------------------------
@@ -187,6 +102,32 @@ def test_paged_scan(oracle, mli, dev, seed, B, S, D, chunks, family):
             mli.mli_tune(b"scan_merge", 1)
             mli.mli_tune(b"nt_loads", 2)
             mli.mli_tune(b"scan_row_order", 1)
+        ck.done()
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+def test_paged_scan_with_rows_of_S_tokens(oracle, mli, dev, family):
+    """mli_decode_scan_paged, materialising and lean (chunked grid), on the S = 1024 shape with two rows of 1024 tokens."""
+    from min_llm_inference_amd import ops
+    seed, B, S, D, chunks = SCAN_SHAPES[1]
+    c = _base_to_S(seed, B, S, D, chunks)
+    for elem in _elems_for(D):
+        ck = Checker(family, elem)
+        x = _paged_inputs(oracle, dev, c, family, elem)
+        assert x.lengths.max() == S and (x.lengths == S).sum() == 2 and x.lengths.min() == 0
+        e_o, e_p = fm.attention_error(x.oracle[2], x.model), fm.probability_error(x.oracle[1], x.model)
+        try:
+            assert mli.mli_tune(b"scan_stream", 0) == 0
+            if elem != "fp8":
+                qkt = torch.full((B, S), SENTINEL, device=dev)
+                out = torch.full((B, D), SENTINEL, device=dev)
+                ops.decode_scan_paged(x.q, x.page_table, x.L, qkt, out, ELEM[elem], phases=3)
+                ck.check("paged scan, materialising, L = S", "attention", fm.attention_error(host(out), x.model), e_o)
+                ck.check("paged scan, materialising, L = S", "probabilities", fm.probability_error(host(qkt), x.model), e_p)
+            got = _lean_twice(ops, x, elem, "lean, rows of S tokens")
+            ck.check("paged scan, lean, L = S", "attention", fm.attention_error(got, x.model), e_o)
+        finally:
+            mli.mli_tune(b"scan_stream", 1)
         ck.done()
 
 

@@ -46,6 +46,11 @@ def _base(seed, B, S, D, chunks):
     return base_case(seed, B, S, D, edge_lengths(seed, B, S, chunks))
 
 
+@functools.lru_cache(maxsize=1)
+def _base_with(seed, B, S, D, lengths):
+    return base_case(seed, B, S, D, np.asarray(lengths, np.int32))
+
+
 def _poisoned_pool(pool32, off, elem, dev):
     """(device pool of the page type with NaN in the dead K / V slots, the float32 values the live slots hold)"""
     t = _t(pool32, dev)
@@ -120,6 +125,27 @@ def test_heads_scan(oracle, mli, dev, seed, B, S, D, H, elem, chunks, assignment
         mli.mli_tune(b"nt_loads", 2)
         mli.mli_tune(b"scan_row_order", 1)
     hm.assert_within(results, f"B{B} S{S} D{D} H{H} {elem}")
+
+
+@pytest.mark.parametrize("assignment", hm.ASSIGNMENTS)
+@pytest.mark.parametrize("H,elem", [(2, "f32"), (8, "bf16")])
+def test_heads_scan_with_rows_of_S_tokens(oracle, mli, dev, H, elem, assignment):
+    """The S = 1024 shape with its two long random rows made full: L == n_sequence, all S / 16 pages present (the scan clamps
+    with min(L, S); every other case stops at S - 1)."""
+    from min_llm_inference_amd import ops
+    seed, B, S, D, _, _, chunks = hm.HEAD_SHAPES[3]
+    L = edge_lengths(seed, B, S, chunks)
+    rows = np.nonzero((L >= 3 * S // 4) & (L < S - 2))[0][:2]
+    assert len(rows) == 2
+    L[rows] = S
+    x = _inputs(oracle, dev, _base_with(seed, B, S, D, tuple(L.tolist())), H, assignment, elem)
+    assert x.lengths.min() == 0 and x.lengths.max() == S and (x.lengths == S).sum() == 2
+    what = f"B{B} S{S} D{D} H{H} {elem}, rows of S tokens"
+    got = _scan(ops, x, elem)
+    results = hm.compare(got, x.oracle, x.model, assignment, what=what)
+    assert_equal(_scan(ops, x, elem), got, what=f"{what}: second launch")
+    _counters_are_zero(ops, x, H)
+    hm.assert_within(results, what)
 
 
 @pytest.mark.parametrize("seed,B,S,D,elem", [(302, 24, 256, 512, "f32"), (304, 20, 1024, 256, "bf16")])

@@ -60,6 +60,11 @@ def _base(seed, B, S, D, W, chunks, part):
     return base_case(seed, B, S, D, wm.window_lengths(seed, B, S, W, chunks)[part])
 
 
+@functools.lru_cache(maxsize=1)
+def _base_with(seed, B, S, D, lengths):
+    return base_case(seed, B, S, D, np.asarray(lengths, np.int32))
+
+
 def _poisoned_pool(pool32, off, elem, dev):
     """(device pool of the page type with NaN at the element offsets `off`, the float32 values the other slots hold)"""
     offs = _t(off, dev) if len(off) else None
@@ -184,6 +189,28 @@ def test_window_scan(oracle, mli, dev, seed, B, S, D, H, elem, W, forced, chunks
     assert np.isfinite(want).all() and (want != SENTINEL).all()
     for no_window in (S, S + 1000):
         assert_equal(_scan(ops, x, elem, table=x.page_table, window=no_window), want, what=f"window {no_window} >= n_sequence")
+
+
+@pytest.mark.parametrize("assignment", hm.ASSIGNMENTS)
+@pytest.mark.parametrize("H,elem,W", [(1, "f32", 100), (2, "bf16", 513)])
+def test_window_scan_with_rows_of_S_tokens(oracle, mli, dev, H, elem, W, assignment):
+    """The S = 1024 shape with its two long random rows made full: L == n_sequence, all S / 16 pages present, the window
+    [S - W, S) (the scan clamps with min(L, S); every other case stops at S - 1)."""
+    from min_llm_inference_amd import ops
+    seed, B, S, D, _, _, _, _, chunks = wm.WINDOW_SHAPES[2]
+    L = wm.window_lengths(seed, B, S, W, chunks)[0].copy()
+    rows = np.nonzero((L >= 3 * S // 4) & (L < S - 2))[0][:2]
+    assert len(rows) == 2
+    L[rows] = S
+    x = _inputs(oracle, dev, _base_with(seed, B, S, D, tuple(L.tolist())), H, W, assignment, elem)
+    assert x.lengths.min() == 0 and x.lengths.max() == S and (x.lengths == S).sum() == 2
+    what = f"B{B} S{S} D{D} H{H} W{W} {elem}, rows of S tokens"
+    got = _scan(ops, x, elem)
+    results = hm.compare(got, x.oracle, x.model, assignment, what=what)
+    assert_equal(_scan(ops, x, elem, table=x.table_null), got, what=f"{what}: null page-table entries below the window")
+    assert_equal(_scan(ops, x, elem), got, what=f"{what}: second launch")
+    _counters_are_zero(ops, x)
+    hm.assert_within(results, what)
 
 
 def test_a_plain_call_of_another_shape_shares_the_buffer(oracle, mli, dev):
