@@ -14,12 +14,9 @@
 // kernel's pass; the K^T and V bytes are read once each either way.  BASELINE config 2 (B=256, D=256, S=1024):
 // qkt 27 us + softmax_v 27 us + combine 5 us -> one launch.
 // Results differ from the materialising composition by fp32 rounding of the merge only (tested: <= 1e-5).
-#include "scan_item_body.hpp"
+#include "scan_launch.hpp"
 
 namespace mli {
-
-size_t stats_region_bytes_for(int B, int S);             // attention_scan.hip
-int nt_loads_for(int B, int S, int D, int esize);
 
 constexpr int kNvThreads = 256;
 constexpr int kNvWaves = kNvThreads / kWave;
@@ -206,7 +203,7 @@ int launch_fused_decode_naive(const float* q, const float* kt, const float* v, c
     float* partial = nullptr;
     unsigned* arrivals = nullptr;
     if (!direct) {
-        const size_t stats_bytes = stats_region_bytes_for(B, S);
+        const size_t stats_bytes = scan_stats_bytes(B, S);
         if (ws == nullptr || ws_bytes < stats_bytes + (size_t)B * nchunk * D * sizeof(float) || B > kMaxArrivalRows / 2) return 0;
         ml = reinterpret_cast<float2*>(ws);
         partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + stats_bytes);

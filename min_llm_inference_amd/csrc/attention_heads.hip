@@ -7,14 +7,10 @@
 //
 //   grid = (B, chunks + 1) rows fast, 256 threads, a wave owns whole pages; one launch, no combine kernel
 #include "heads_item_body.hpp"
+#include "scan_launch.hpp"
 #include "scan_row_order.hpp"
 
 namespace mli {
-
-int fused_chunk_tokens(int B, int S);   // attention_fused.hip
-int scan_row_order();
-int tuned_chunk_tokens();               // attention_scan.hip
-int nt_loads_for(int B, int S, int D, int esize);
 
 template <class E, int NJ, bool NT>
 __global__ __launch_bounds__(kFuThreads, 2) void heads_decode_scan_kernel(
@@ -34,89 +30,29 @@ __global__ __launch_bounds__(kFuThreads, 2) void heads_decode_scan_kernel(
                                                     direct, arrivals, b, c, c == 0, smem_raw);
 }
 
-constexpr int kMaxItemTokens = 1024;
-constexpr int kMaxMergeStats = 4096;   // float2 entries
-
-// The supported combinations (everything else is MLI_ERR_BAD_ARG before anything is launched).  Returns log2 of the lanes
-// per head, or -1.  (This and the two sizing rules below: also attention_window.hip.)
-int heads_lanes_log2(int B, int S, int D, int H, int elem) {
-    if (B <= 0 || B > kMaxArrivalRows || S <= 0 || S % kPage != 0 || D <= 0 || H < 1 || D % H != 0) return -1;
-    if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) return -1;
-    const int hd = D / H;
-    if (hd != 32 && hd != 64 && hd != 128 && hd != 256) return -1;
-    const int epl = elem == MLI_ELEM_BF16 ? 8 : 4;
-    if (D / epl > 2 * kWave) return -1;   // rows of at most two lane loads: whole pages per wave
-    // the last arriver stages a row's (items x heads) statistics in LDS: even at the largest item size they must fit
-    if ((int64_t)ceil_div_i(S, kMaxItemTokens) * H > kMaxMergeStats) return -1;
-    int lg = 0;
-    while ((epl << lg) < hd) ++lg;
-    return lg;
-}
-
-int heads_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int elem) {   // engine_api.cpp
-    return heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem) >= 0;
-}
-
-// Tokens per item: the single-head scan's choice, raised where a row's (items x heads) statistics would not fit the
-// 32 KiB of LDS the last arriver stages them in (n_sequence 16384 with 32 heads and a small batch).  A size exists for
-// every shape heads_lanes_log2 accepts.
-int heads_chunk_tokens(int B, int S, int H) {
-    int ct = (S <= 128 && B >= 256 && tuned_chunk_tokens() == 0) ? 128 : fused_chunk_tokens(B, S);
-    while (ct < kMaxItemTokens && (int64_t)ceil_div_i(S, ct) * H > kMaxMergeStats) ct <<= 1;
-    return ct;
-}
-
-// body = [(m, l) per row, item and head: B * ceil(S / 64) * H float2, 256-B aligned][partial rows: B * ceil(S / 64) * D]
-size_t heads_stats_bytes(int B, int S, int H) {
-    const size_t n = (size_t)B * ceil_div_i(S, 64) * H * sizeof(float2);
-    return (n + 255) & ~(size_t)255;
-}
-
+// Grid, item size, workspace and LDS: scan_plan.hpp (the supported shapes: heads_lanes_log2 there).
 template <class E>
-static int launch_heads_decode(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S,
-                               int D, int H, int lg, void* ws, size_t ws_bytes, hipStream_t st) {
+static int launch_heads_decode_t(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S,
+                                 int D, int H, int lg, void* ws, size_t ws_bytes, hipStream_t st) {
     const int nj = ceil_div_i(D / E::EPL, kWave);   // 1 or 2
-    const int ct = heads_chunk_tokens(B, S, H);
-    const int nchunk = ceil_div_i(S, ct);
-    const bool ordered = scan_row_order() && nchunk == 1 && B > 512 && B <= kMaxOrderedRows && S / kPage <= kMaxOrderedPages;
-    const int direct = nchunk == 1 ? (ordered ? 2 : 1) : 0;
-    float2* ml = nullptr;
-    float* partial = nullptr;
-    unsigned* arrivals = nullptr;
-    if (!direct) {
-        const size_t stats_bytes = heads_stats_bytes(B, S, H);
-        if (ws == nullptr || ws_bytes < stats_bytes + (size_t)B * nchunk * D * sizeof(float)) return MLI_ERR_WORKSPACE;
-        ml = reinterpret_cast<float2*>(ws);
-        partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + stats_bytes);
-        arrivals = ws_arrivals(ws);
-    }
+    const ScanPlan p = plan_chunked_scan(scan_tune(), B, S, S, D, H, E::kBytes);
+    ScanWs w;
+    if (!carve_scan_ws(p, ws, ws_bytes, &w)) return MLI_ERR_WORKSPACE;
     // page pointers of the item | the waves' parked rows and statistics, later the row's (item, head) statistics
-    const size_t park_bytes = (size_t)kFuWaves * nj * kWave * (E::EPL * sizeof(float) + sizeof(float2));
-    const size_t stat_bytes = (size_t)nchunk * H * sizeof(float2);
-    const size_t smem = (size_t)(ct / kPage) * 8 + (park_bytes > stat_bytes ? park_bytes : stat_bytes);
-    const dim3 grid(B, direct ? 1 : nchunk + 1);
-    const bool nt = nt_loads_for(B, S, D, E::kBytes);
-#define MLI_HEADS_LAUNCH(NJ, NT)                                                                                          \
-    hipLaunchKernelGGL((heads_decode_scan_kernel<E, NJ, NT>), grid, dim3(kFuThreads), smem, st, q, page_table, lengths, out, \
-                       ml, partial, S, D, lg, H, ct, nchunk, direct, arrivals)
-    if (nj == 1) {
-        if (nt) MLI_HEADS_LAUNCH(1, true);
-        else MLI_HEADS_LAUNCH(1, false);
-    } else {
-        if (nt) MLI_HEADS_LAUNCH(2, true);
-        else MLI_HEADS_LAUNCH(2, false);
-    }
-#undef MLI_HEADS_LAUNCH
+    const size_t smem = scan_lds_bytes(p.ct, heads_reduction_bytes(nj, E::EPL), heads_merge_stat_bytes(p.nchunk, H));
+    dispatch_scan_variant<E>(ScanVariant{nj, false, 1}, p.nt, [&](auto NJ, auto, auto, auto NT) {
+        hipLaunchKernelGGL((heads_decode_scan_kernel<E, NJ(), NT()>), dim3(B, p.grid_y), dim3(kFuThreads), smem, st, q,
+                           page_table, lengths, out, w.ml, w.partial, S, D, lg, H, p.ct, p.nchunk, p.direct, w.arrivals);
+    });
     return launch_status();
 }
 
-static int launch_heads_decode_elem(const float* q, const void* const* page_table, const int* lengths, float* out, int B,
-                                    int S, int D, int H, int lg, int elem, void* workspace, size_t workspace_bytes,
-                                    hipStream_t st) {
-    const WsBody body = ws_body(workspace, workspace_bytes);
-    return elem == MLI_ELEM_BF16
-               ? launch_heads_decode<ElemBF16>(q, page_table, lengths, out, B, S, D, H, lg, body.ptr, body.bytes, st)
-               : launch_heads_decode<ElemF32>(q, page_table, lengths, out, B, S, D, H, lg, body.ptr, body.bytes, st);
+int launch_heads_decode(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
+                        int H, int elem, void* ws, size_t ws_bytes, hipStream_t st) {
+    const int lg = heads_lanes_log2(B, S, D, H, elem);
+    if (lg < 0) return MLI_ERR_BAD_ARG;
+    return elem == MLI_ELEM_BF16 ? launch_heads_decode_t<ElemBF16>(q, page_table, lengths, out, B, S, D, H, lg, ws, ws_bytes, st)
+                                 : launch_heads_decode_t<ElemF32>(q, page_table, lengths, out, B, S, D, H, lg, ws, ws_bytes, st);
 }
 
 }  // namespace mli
@@ -130,43 +66,32 @@ size_t mli_attention_heads_workspace_bytes(int n_batch, int n_sequence, int dim,
         mli::heads_lanes_log2(n_batch, n_sequence, dim, n_heads, MLI_ELEM_BF16) < 0)
         return 0;
     const size_t nchunk = (size_t)mli::ceil_div_i(n_sequence, 64);
-    const size_t heads = mli::kArrivalRegionBytes + mli::heads_stats_bytes(n_batch, n_sequence, n_heads) +
+    const size_t heads = mli::kArrivalRegionBytes + mli::scan_stats_bytes(n_batch, n_sequence, n_heads) +
                          (nchunk <= 1 ? 0 : (size_t)n_batch * nchunk * (size_t)dim * sizeof(float));
     const size_t plain = mli_attention_workspace_bytes(n_batch, n_sequence, dim);
     return heads > plain ? heads : plain;
 }
 
+// n_heads == 1 is the single-head scan (mli_decode_scan_paged, phases 7), unchanged
 int mli_decode_scan_paged_heads(const float* q_output, const void* const* page_table, const int* lengths,
                                 float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int elem,
                                 void* workspace, size_t workspace_bytes, void* stream) {
     if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) return MLI_ERR_BAD_ARG;
-    if (n_heads == 1)   // today's code path, unchanged
-        return mli_decode_scan_paged(q_output, page_table, lengths, nullptr, attention_result, n_batch, n_sequence, emb_dim,
-                                     elem, 7, workspace, workspace_bytes, stream);
-    const int lg = mli::heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem);
-    if (lg < 0) return MLI_ERR_BAD_ARG;
-    return mli::launch_heads_decode_elem(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim,
-                                         n_heads, lg, elem, workspace, workspace_bytes, mli::as_stream(stream));
+    if (n_heads != 1 && mli::heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem) < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads, 0,
+                                 elem, workspace, workspace_bytes, mli::as_stream(stream));
 }
 
+// n_heads == 1 is mli_paged_attention_lean; fill and projection do not depend on n_heads
 int mli_paged_attention_lean_heads(void* const* page_table, const int* lengths, const void* wk, const void* wq,
                                    const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
                                    int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int elem,
                                    void* workspace, size_t workspace_bytes, void* stream) {
     if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) return MLI_ERR_BAD_ARG;
-    if (n_heads == 1)
-        return mli_paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_batch,
-                                        n_sequence, emb_dim, n_new_items, elem, workspace, workspace_bytes, stream);
-    const int lg = mli::heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem);
-    if (lg < 0) return MLI_ERR_BAD_ARG;
-    hipStream_t st = mli::as_stream(stream);
-    // fill and projection: the launches of mli_paged_attention_lean (pages and q_output do not depend on n_heads)
-    const int rc = mli::launch_fill_and_latest(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, n_batch,
-                                               n_sequence, emb_dim, n_new_items, st);
-    if (rc) return rc;
-    return mli::launch_heads_decode_elem(q_output, reinterpret_cast<const void* const*>(page_table), lengths,
-                                         attention_result, n_batch, n_sequence, emb_dim, n_heads, lg, elem, workspace,
-                                         workspace_bytes, st);
+    if (n_heads != 1 && mli::heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem) < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_lean_attention(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
+                                      n_batch, n_sequence, emb_dim, n_new_items, n_heads, 0, workspace, workspace_bytes,
+                                      mli::as_stream(stream));
 }
 
 }  // extern "C"

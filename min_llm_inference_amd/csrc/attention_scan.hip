@@ -12,6 +12,7 @@
 #include <string>
 
 #include "device_common.hpp"
+#include "scan_plan.hpp"
 
 namespace mli {
 
@@ -28,7 +29,6 @@ void set_scan_stream_min(int v);
 void set_stream_dyn_pct(int v);
 void set_stream_granule(int v);
 void set_gemm_split(int v);
-void set_row_order(int v);
 void set_bf16_split(int v);
 void set_prefill_fused(int v);
 void set_gemm_tall_tiles(int v);
@@ -37,7 +37,8 @@ void set_latest_compact(int v);
 
 // Tuning knobs (mli_tune): 0 = use the built-in heuristic / default.
 static thread_local int g_chunk_tokens = 0;
-static thread_local int g_nt_loads = 2;  // 0 = default cache policy, 1 = non-temporal, 2 = by working set (nt_loads_for)
+static thread_local int g_nt_loads = 2;  // 0 = default cache policy, 1 = non-temporal, 2 = by working set (nt_loads_rule)
+static thread_local int g_row_order = 1; // 0 = one-workgroup-per-row grids of the chunked paged scans take the rows in grid order
 
 // Sequence chunk (tokens per workgroup) for the split-sequence kernels: the largest power of two in
 // [64, 1024] that still yields >= min_units work units.  With rows as the fast grid dimension the choice is
@@ -468,16 +469,8 @@ __global__ __launch_bounds__(kScanThreads) void stream_read_kernel(const float4*
 // ------------------------------------------------------------------------------------------
 int chunk_tokens_for(int n_batch, int n_sequence) { return pick_chunk_tokens(n_batch, n_sequence); }
 int sv_chunk_tokens_for(int n_batch, int n_sequence) { return pick_chunk_tokens(n_batch, n_sequence, kSvUnits, kSvMaxChunkTokens); }
-// K/V loads: non-temporal where the rows' K/V (upper bound B * S * D * e * 2 bytes) is far beyond the 256 MiB
-// Infinity Cache -- every byte is read once per step and nothing survives to the next one --, default policy where a
-// good part of it can stay on-die between two steps.  Measured (lean scan, fp32, D=256, S=1024, lengths U[S/4, 3S/4]):
-// B=128 / 256: default policy 6 / 5 % faster; B=512 / 1024 / 2048: non-temporal 6 / 11 / 10 % faster.
-constexpr int64_t kNtMinKvBytes = (int64_t)768 << 20;
-int nt_loads_for(int B, int S, int D, int esize) {
-    if (g_nt_loads != 2) return g_nt_loads;
-    return (int64_t)B * S * D * esize * 2 > kNtMinKvBytes;
-}
-int tuned_chunk_tokens() { return g_chunk_tokens; }
+int nt_loads_for(int B, int S, int D, int esize) { return nt_loads_rule(g_nt_loads, B, S, D, esize); }
+ScanTune scan_tune() { return ScanTune{g_chunk_tokens, g_row_order, g_nt_loads}; }   // scan_plan.hpp
 
 int launch_softmax_v_combine(const float* partial, const int* lengths, float* out, int B, int S, int D, int ct,
                              int nchunk, hipStream_t st) {
@@ -488,10 +481,7 @@ int launch_softmax_v_combine(const float* partial, const int* lengths, float* ou
 
 // Workspace layout (mli_attention_workspace_bytes): [row arrival counters: kArrivalRegionBytes, device_common.hpp] then the
 // body every launcher here sees: [chunk statistics: B * ceil(S/64) float2, 256-B aligned][partial sums: B * nchunk * D floats].
-static size_t stats_region_bytes(int B, int S) {
-    const size_t n = (size_t)B * ceil_div_i(S, kMinChunkTokens) * sizeof(float2);
-    return (n + 255) & ~(size_t)255;
-}
+static size_t stats_region_bytes(int B, int S) { return scan_stats_bytes(B, S); }
 
 static SoftmaxStats stats_view(void* workspace, int B, int S, int chunk_tokens) {
     SoftmaxStats st;
@@ -634,8 +624,6 @@ int launch_scores_softmax_v_naive(const float* q, const float* kt, const float* 
     return launch_softmax_v_impl<1, false>(qkt, v_cache, lengths, out, B, S, D, ws, ws_bytes, stats, st);
 }
 
-// exported to attention_scan_bf16.hip
-size_t stats_region_bytes_for(int B, int S) { return stats_region_bytes(B, S); }
 static size_t partial_region_bytes(int B, int S, int D) {
     const size_t nchunk = (size_t)ceil_div_i(S, kMinChunkTokens);
     return nchunk <= 1 ? 0 : (size_t)B * nchunk * (size_t)D * sizeof(float);
@@ -714,7 +702,7 @@ int mli_tune(const char* key, int value) {
     } else if (k == "prefill_fused") {
         mli::set_prefill_fused(value);
     } else if (k == "scan_row_order") {
-        mli::set_row_order(value);
+        mli::g_row_order = value != 0;
     } else if (k == "gemm_split") {
         mli::set_gemm_split(value);
     } else if (k == "scan_stream") {

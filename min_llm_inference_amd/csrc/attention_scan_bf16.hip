@@ -4,6 +4,7 @@
 // 16-byte lane load, so one load instruction covers a 512-element row (D=512 -> exactly one K or V row).
 // The reference has no bf16 path; these kernels extend include/mli_kernels.h (see the header's bf16 section).
 #include "device_common.hpp"
+#include "scan_plan.hpp"
 
 namespace mli {
 
@@ -14,7 +15,6 @@ int chunk_tokens_for(int n_batch, int n_sequence);  // attention_scan.hip (same 
 int sv_chunk_tokens_for(int n_batch, int n_sequence);
 int nt_loads_for(int B, int S, int D, int esize);
 int fused_softmax_wanted(int B, int S);
-size_t stats_region_bytes_for(int B, int S);
 int launch_softmax(float*, const int*, int, int, hipStream_t);
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
@@ -288,9 +288,9 @@ static int launch_softmax_v_paged_bf16_stats(float* probs, const uint16_t* const
     const int direct = nchunk == 1;
     float* dst = out;
     if (!direct) {
-        const size_t need = stats_region_bytes_for(B, S) + (size_t)B * nchunk * D * sizeof(float);
+        const size_t need = scan_stats_bytes(B, S) + (size_t)B * nchunk * D * sizeof(float);
         if (workspace == nullptr || ws_bytes < need) return MLI_ERR_WORKSPACE;
-        dst = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + stats_region_bytes_for(B, S));
+        dst = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + scan_stats_bytes(B, S));
     }
     const size_t smem = (size_t)ct * 4 + (size_t)(ct / kPage) * 8 + (size_t)kBfWaves * slice_u * 8 * 4;
     dim3 grid(B, nchunk);
@@ -315,7 +315,7 @@ int launch_softmax_v_paged_bf16(const float* probs, const uint16_t* const* page_
 int launch_scores_softmax_v_paged_bf16(const float* q, const uint16_t* const* page_table, const int* lengths,
                                        float* qkt, float* out, int B, int S, int D, void* ws, size_t ws_bytes,
                                        hipStream_t st) {
-    if (!fused_softmax_wanted(B, S) || ws == nullptr || ws_bytes < stats_region_bytes_for(B, S) ||
+    if (!fused_softmax_wanted(B, S) || ws == nullptr || ws_bytes < scan_stats_bytes(B, S) ||
         ceil_div_i(S, chunk_tokens_for(B, S)) > 256) {
         int rc = launch_qkt_paged_bf16(q, page_table, lengths, qkt, B, S, D, st);
         if (!rc) rc = launch_softmax(qkt, lengths, B, S, st);

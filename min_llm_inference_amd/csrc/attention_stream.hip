@@ -20,7 +20,7 @@
 //
 // Replaces, inside mli_paged_attention_lean / mli_decode_scan_paged(lean), launch_qkt_paged_attention +
 // launch_softmax_in_place_with_lengths + launch_softmax_v_paged_attention (reference paged_attention.cu:270-345).
-#include "scan_common.hpp"
+#include "scan_launch.hpp"
 
 namespace mli {
 
@@ -45,9 +45,6 @@ __device__ unsigned long long mli_stream_trace[kStTraceSlots * 8];
 #else
 #define MLI_ST_TRACE(i) do { } while (0)
 #endif
-
-int nt_loads_for(int B, int S, int D, int esize);             // attention_scan.hip
-size_t stats_region_bytes_for(int B, int S);
 
 // MAXSEG = segments (rows touched) a workgroup finishes per group: their wave partials wait in LDS for the group's merge
 // RPI = token slots per load instruction (scan_common.hpp; 1 for the reference's fp32 and for bf16), TBR = load
@@ -533,7 +530,7 @@ int launch_stream_decode(const float* q, const void* const* page_table, const in
     // spilled -- 543 / 894 us against 338; decoding and multiplying in pairs (v_pk_fma_f32): 338.8 against 338.0 us.)
     const int G = 2 * n_cu;
     const int ml_per_row = ceil_div_i(S, 64);
-    const size_t stats_bytes = stats_region_bytes_for(B, S);
+    const size_t stats_bytes = scan_stats_bytes(B, S);
     if (ws == nullptr || ws_bytes < stats_bytes + (size_t)B * ml_per_row * D * sizeof(float)) return 0;
     float2* ml = reinterpret_cast<float2*>(ws);
     float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + stats_bytes);

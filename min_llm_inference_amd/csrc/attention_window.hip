@@ -11,18 +11,10 @@
 //
 //   grid = (B, items of the span + 1) rows fast, 256 threads; one launch, no combine kernel
 #include "heads_item_body.hpp"
+#include "scan_launch.hpp"
 #include "scan_row_order.hpp"
 
 namespace mli {
-
-int fused_chunk_tokens(int B, int S);   // attention_fused.hip
-int scan_row_order();
-int tuned_chunk_tokens();               // attention_scan.hip
-int nt_loads_for(int B, int S, int D, int esize);
-size_t stats_region_bytes_for(int B, int S);
-int heads_lanes_log2(int B, int S, int D, int H, int elem);   // attention_heads.hip
-int heads_chunk_tokens(int B, int S, int H);
-size_t heads_stats_bytes(int B, int S, int H);
 
 template <class E, int NJ, bool NT, int TBR, bool DS, int RPI>
 __global__ __launch_bounds__(kFuThreads, 2) void window_decode_scan_kernel(
@@ -53,85 +45,20 @@ __global__ __launch_bounds__(kFuThreads, 2) void window_heads_scan_kernel(
                                                           nchunk_max, direct, arrivals, b, c, c == 0, smem_raw, window);
 }
 
-// The tokens a windowed row can span: its window plus the part of the first live page below it, whole pages.
-static int window_span(int S, int window) {
-    const int64_t span = (int64_t)kPage * (ceil_div_i(window, kPage) + 1);
-    return span < S ? (int)span : S;
-}
-
-// One head: what the lean chunked scan takes (launch_fused_decode), with the rows the arrival counters can count.
-static bool window_plain_shape_ok(int B, int S, int D, int elem) {
-    if (B <= 0 || B > kMaxArrivalRows || S <= 0 || S % kPage != 0 || D <= 0) return false;
-    if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16 && elem != MLI_ELEM_FP8) return false;
-    const int epl = elem == MLI_ELEM_FP8 ? 16 : elem == MLI_ELEM_BF16 ? 8 : 4;
-    if (D % epl != 0) return false;
-    const int nj = ceil_div_i(D / epl, kWave);
-    return elem == MLI_ELEM_FP8 ? nj <= 2 : nj <= 8;
-}
-
-int window_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int elem) {   // engine_api.cpp
-    if (n_heads < 1) return 0;
-    return n_heads == 1 ? window_plain_shape_ok(n_batch, n_sequence, emb_dim, elem)
-                        : heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem) >= 0;
-}
-
+// The un-windowed launchers' plan (scan_plan.hpp) at the span the window leaves; the workspace layout stays n_sequence's.
 template <class E>
 static int launch_window_decode(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S,
                                 int D, int window, void* ws, size_t ws_bytes, hipStream_t st) {
-    constexpr bool kFp8 = std::is_same<E, ElemFP8>::value;
-    const int Du = D / E::EPL;
-    const int nj = ceil_div_i(Du, kWave);
-    const int rpi = kFp8 ? (Du <= 16 ? 4 : Du <= 32 ? 2 : 1) : 1;
-    const bool dsplit = nj > 2;
-    const int nj_ds = ceil_div_i(Du, kWave * kFuWaves);
-    // grid and item size: launch_fused_decode's choices at the span the window leaves
-    const int span = window_span(S, window);
-    const int ct = (span <= 128 && B >= 256 && tuned_chunk_tokens() == 0) ? 128 : fused_chunk_tokens(B, span);
-    const int nchunk = ceil_div_i(span, ct);
-    const bool ordered = scan_row_order() && nchunk == 1 && B > 512 && B <= kMaxOrderedRows && span / kPage <= kMaxOrderedPages;
-    const int direct = nchunk == 1 ? (ordered ? 2 : 1) : 0;
-    // the un-windowed workspace layout: statistics with the row stride of n_sequence, then the partial rows
-    const size_t stats_bytes = stats_region_bytes_for(B, S);
-    const int ml_per_row = ceil_div_i(S, 64);
-    float2* ml = nullptr;
-    float* partial = nullptr;
-    unsigned* arrivals = nullptr;
-    if (!direct) {
-        if (ws == nullptr || ws_bytes < stats_bytes + (size_t)B * nchunk * D * sizeof(float)) return MLI_ERR_WORKSPACE;
-        ml = reinterpret_cast<float2*>(ws);
-        partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + stats_bytes);
-        arrivals = ws_arrivals(ws);
-    }
-    const size_t red_bytes = (dsplit ? (size_t)2 * kFuWaves * 16 : (size_t)kFuWaves * nj * (kWave / rpi) * E::EPL) * sizeof(float);
-    const size_t stat_bytes_row = (size_t)nchunk * 8;
-    const size_t smem = (size_t)(ct / kPage) * 8 + (red_bytes > stat_bytes_row ? red_bytes : stat_bytes_row);
-    const dim3 grid(B, direct ? 1 : nchunk + 1);
-    const bool nt = nt_loads_for(B, span, D, E::kBytes);
-#define MLI_WIN_LAUNCH(NJ, DS, RPI)                                                                                       \
-    do {                                                                                                                 \
-        if (nt)                                                                                                          \
-            hipLaunchKernelGGL((window_decode_scan_kernel<E, NJ, true, (NJ == 1 ? 8 : 4) / RPI, DS, RPI>), grid,         \
-                               dim3(kFuThreads), smem, st, q, page_table, lengths, out, ml, partial, S, D, ct, ml_per_row, \
-                               nchunk, direct, arrivals, window);                                                         \
-        else                                                                                                             \
-            hipLaunchKernelGGL((window_decode_scan_kernel<E, NJ, false, (NJ == 1 ? 8 : 4) / RPI, DS, RPI>), grid,        \
-                               dim3(kFuThreads), smem, st, q, page_table, lengths, out, ml, partial, S, D, ct, ml_per_row, \
-                               nchunk, direct, arrivals, window);                                                         \
-    } while (0)
-    if constexpr (kFp8) {
-        if (rpi == 4) MLI_WIN_LAUNCH(1, false, 4);
-        else if (rpi == 2) MLI_WIN_LAUNCH(1, false, 2);
-        else if (nj == 1) MLI_WIN_LAUNCH(1, false, 1);
-        else MLI_WIN_LAUNCH(2, false, 1);
-    } else if (dsplit) {
-        if (nj_ds == 1) MLI_WIN_LAUNCH(1, true, 1);
-        else MLI_WIN_LAUNCH(2, true, 1);
-    } else if (nj == 1) {
-        MLI_WIN_LAUNCH(1, false, 1);
-    } else {
-        MLI_WIN_LAUNCH(2, false, 1);
-    }
-#undef MLI_WIN_LAUNCH
+    const ScanVariant v = plain_scan_variant(D, E::EPL);
+    const ScanPlan p = plan_chunked_scan(scan_tune(), B, S, window_span(S, window), D, 1, E::kBytes);
+    ScanWs w;
+    if (!carve_scan_ws(p, ws, ws_bytes, &w)) return MLI_ERR_WORKSPACE;
+    const size_t smem = scan_lds_bytes(p.ct, plain_reduction_bytes(v, E::EPL), window_merge_stat_bytes(p.nchunk));
+    dispatch_scan_variant<E>(v, p.nt, [&](auto NJ, auto DS, auto RPI, auto NT) {
+        hipLaunchKernelGGL((window_decode_scan_kernel<E, NJ(), NT(), (NJ() == 1 ? 8 : 4) / RPI(), DS(), RPI()>), dim3(B, p.grid_y),
+                           dim3(kFuThreads), smem, st, q, page_table, lengths, out, w.ml, w.partial, S, D, p.ct,
+                           ceil_div_i(S, 64), p.nchunk, p.direct, w.arrivals, window);
+    });
     return launch_status();
 }
 
@@ -139,66 +66,41 @@ template <class E>
 static int launch_window_heads(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S,
                                int D, int H, int lg, int window, void* ws, size_t ws_bytes, hipStream_t st) {
     const int nj = ceil_div_i(D / E::EPL, kWave);   // 1 or 2
-    const int span = window_span(S, window);
-    const int ct = heads_chunk_tokens(B, span, H);
-    const int nchunk = ceil_div_i(span, ct);
-    const bool ordered = scan_row_order() && nchunk == 1 && B > 512 && B <= kMaxOrderedRows && span / kPage <= kMaxOrderedPages;
-    const int direct = nchunk == 1 ? (ordered ? 2 : 1) : 0;
-    float2* ml = nullptr;
-    float* partial = nullptr;
-    unsigned* arrivals = nullptr;
-    if (!direct) {
-        const size_t stats_bytes = heads_stats_bytes(B, S, H);   // the un-windowed layout
-        if (ws == nullptr || ws_bytes < stats_bytes + (size_t)B * nchunk * D * sizeof(float)) return MLI_ERR_WORKSPACE;
-        ml = reinterpret_cast<float2*>(ws);
-        partial = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + stats_bytes);
-        arrivals = ws_arrivals(ws);
-    }
-    const size_t park_bytes = (size_t)kFuWaves * nj * kWave * (E::EPL * sizeof(float) + sizeof(float2));
-    const size_t stat_bytes = (size_t)nchunk * H * sizeof(float2);
-    const size_t smem = (size_t)(ct / kPage) * 8 + (park_bytes > stat_bytes ? park_bytes : stat_bytes);
-    const dim3 grid(B, direct ? 1 : nchunk + 1);
-    const bool nt = nt_loads_for(B, span, D, E::kBytes);
-#define MLI_WIN_HEADS_LAUNCH(NJ, NT)                                                                                      \
-    hipLaunchKernelGGL((window_heads_scan_kernel<E, NJ, NT>), grid, dim3(kFuThreads), smem, st, q, page_table, lengths, out, \
-                       ml, partial, S, D, lg, H, ct, nchunk, direct, arrivals, window)
-    if (nj == 1) {
-        if (nt) MLI_WIN_HEADS_LAUNCH(1, true);
-        else MLI_WIN_HEADS_LAUNCH(1, false);
-    } else {
-        if (nt) MLI_WIN_HEADS_LAUNCH(2, true);
-        else MLI_WIN_HEADS_LAUNCH(2, false);
-    }
-#undef MLI_WIN_HEADS_LAUNCH
+    const ScanPlan p = plan_chunked_scan(scan_tune(), B, S, window_span(S, window), D, H, E::kBytes);
+    ScanWs w;
+    if (!carve_scan_ws(p, ws, ws_bytes, &w)) return MLI_ERR_WORKSPACE;
+    const size_t smem = scan_lds_bytes(p.ct, heads_reduction_bytes(nj, E::EPL), heads_merge_stat_bytes(p.nchunk, H));
+    dispatch_scan_variant<E>(ScanVariant{nj, false, 1}, p.nt, [&](auto NJ, auto, auto, auto NT) {
+        hipLaunchKernelGGL((window_heads_scan_kernel<E, NJ(), NT()>), dim3(B, p.grid_y), dim3(kFuThreads), smem, st, q,
+                           page_table, lengths, out, w.ml, w.partial, S, D, lg, H, p.ct, p.nchunk, p.direct, w.arrivals, window);
+    });
     return launch_status();
 }
 
 // window < n_sequence, shape already accepted by window_shape_supported
-static int launch_window_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S,
-                              int D, int H, int window, int elem, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    const WsBody body = ws_body(workspace, workspace_bytes);
+int launch_window_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
+                       int H, int window, int elem, void* ws, size_t ws_bytes, hipStream_t st) {
     if (H > 1) {
         const int lg = heads_lanes_log2(B, S, D, H, elem);
         return elem == MLI_ELEM_BF16
-                   ? launch_window_heads<ElemBF16>(q, page_table, lengths, out, B, S, D, H, lg, window, body.ptr, body.bytes, st)
-                   : launch_window_heads<ElemF32>(q, page_table, lengths, out, B, S, D, H, lg, window, body.ptr, body.bytes, st);
+                   ? launch_window_heads<ElemBF16>(q, page_table, lengths, out, B, S, D, H, lg, window, ws, ws_bytes, st)
+                   : launch_window_heads<ElemF32>(q, page_table, lengths, out, B, S, D, H, lg, window, ws, ws_bytes, st);
     }
-    if (elem == MLI_ELEM_FP8)
-        return launch_window_decode<ElemFP8>(q, page_table, lengths, out, B, S, D, window, body.ptr, body.bytes, st);
-    if (elem == MLI_ELEM_BF16)
-        return launch_window_decode<ElemBF16>(q, page_table, lengths, out, B, S, D, window, body.ptr, body.bytes, st);
-    return launch_window_decode<ElemF32>(q, page_table, lengths, out, B, S, D, window, body.ptr, body.bytes, st);
+    if (elem == MLI_ELEM_FP8) return launch_window_decode<ElemFP8>(q, page_table, lengths, out, B, S, D, window, ws, ws_bytes, st);
+    if (elem == MLI_ELEM_BF16) return launch_window_decode<ElemBF16>(q, page_table, lengths, out, B, S, D, window, ws, ws_bytes, st);
+    return launch_window_decode<ElemF32>(q, page_table, lengths, out, B, S, D, window, ws, ws_bytes, st);
 }
 
 }  // namespace mli
 
 extern "C" {
 
+// window >= n_sequence is no window: the un-windowed entry points, with their own refusals
 int mli_decode_scan_paged_window(const float* q_output, const void* const* page_table, const int* lengths,
                                  float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int window,
                                  int elem, void* workspace, size_t workspace_bytes, void* stream) {
     if (window < 1 || n_heads < 1) return MLI_ERR_BAD_ARG;
-    if (window >= n_sequence) {   // no window: today's code paths, unchanged
+    if (window >= n_sequence) {
         if (n_heads == 1)
             return mli_decode_scan_paged(q_output, page_table, lengths, nullptr, attention_result, n_batch, n_sequence,
                                          emb_dim, elem, 7, workspace, workspace_bytes, stream);
@@ -206,10 +108,11 @@ int mli_decode_scan_paged_window(const float* q_output, const void* const* page_
                                            n_heads, elem, workspace, workspace_bytes, stream);
     }
     if (!mli::window_shape_supported(n_batch, n_sequence, emb_dim, n_heads, elem)) return MLI_ERR_BAD_ARG;
-    return mli::launch_window_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
-                                   window, elem, workspace, workspace_bytes, mli::as_stream(stream));
+    return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
+                                 window, elem, workspace, workspace_bytes, mli::as_stream(stream));
 }
 
+// fill and projection do not depend on the window
 int mli_paged_attention_lean_window(void* const* page_table, const int* lengths, const void* wk, const void* wq,
                                     const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
                                     int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int window,
@@ -224,13 +127,9 @@ int mli_paged_attention_lean_window(void* const* page_table, const int* lengths,
                                               workspace_bytes, stream);
     }
     if (!mli::window_shape_supported(n_batch, n_sequence, emb_dim, n_heads, elem)) return MLI_ERR_BAD_ARG;
-    hipStream_t st = mli::as_stream(stream);
-    // fill and projection: the launches of mli_paged_attention_lean (pages and q_output do not depend on the window)
-    const int rc = mli::launch_fill_and_latest(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, n_batch,
-                                               n_sequence, emb_dim, n_new_items, st);
-    if (rc) return rc;
-    return mli::launch_window_scan(q_output, reinterpret_cast<const void* const*>(page_table), lengths, attention_result,
-                                   n_batch, n_sequence, emb_dim, n_heads, window, elem, workspace, workspace_bytes, st);
+    return mli::launch_lean_attention(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
+                                      n_batch, n_sequence, emb_dim, n_new_items, n_heads, window, workspace, workspace_bytes,
+                                      mli::as_stream(stream));
 }
 
 }  // extern "C"

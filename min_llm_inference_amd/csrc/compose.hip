@@ -2,7 +2,7 @@
 // order, issued back to back on one stream.
 //   src/kernels/self_attention_inference_optimized.cu:282-301
 //   src/kernels/paged_attention.cu:358-377, src/kernels/paged_attention_cublas.cu:260-280
-#include "device_common.hpp"
+#include "scan_launch.hpp"
 
 namespace mli {
 int launch_latest_naive(const float*, const int*, const float*, const float*, const float*, float*, float*, float*,
@@ -48,11 +48,12 @@ int launch_latest_paged_fp8(uint8_t* const*, const int*, const uint16_t*, const 
                             int, hipStream_t);
 int launch_fill_paged_fp8_embed(const float*, const float*, const int*, uint8_t* const*, const int*, const int*,
                                 const uint16_t*, const uint16_t*, int, int, int, int, hipStream_t);
-int launch_fused_decode_fp8(const float*, const uint8_t* const*, const int*, float*, int, int, int, void*, size_t, hipStream_t);
 int launch_softmax_v_paged_bf16(const float*, const uint16_t* const*, const int*, float*, int, int, int, void*, size_t,
                                 hipStream_t);
 
-int launch_fill_and_latest(int elem, void* const* page_table, const int* lengths, const void* wk, const void* wq,
+// What every lean paged composition starts with, by page element type (MLI_ELEM_*; bf16 weights for bf16 and fp8 pages):
+// fill the n_new_items new rows, then project every non-empty row's last token (k, v appended, q to q_output)
+static int launch_fill_and_latest(int elem, void* const* page_table, const int* lengths, const void* wk, const void* wq,
                            const void* wv, const int* new_batch_idx, float* q_output, int n_batch, int n_sequence,
                            int emb_dim, int n_new_items, hipStream_t st) {
     int rc;
@@ -77,6 +78,26 @@ int launch_fill_and_latest(int elem, void* const* page_table, const int* lengths
     }
     return rc;
 }
+
+int launch_lean_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
+                     int n_heads, int window, int elem, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const WsBody body = ws_body(workspace, workspace_bytes);
+    if (window > 0 && window < S)
+        return launch_window_scan(q, page_table, lengths, out, B, S, D, n_heads, window, elem, body.ptr, body.bytes, st);
+    if (n_heads > 1) return launch_heads_decode(q, page_table, lengths, out, B, S, D, n_heads, elem, body.ptr, body.bytes, st);
+    // not applicable (rows too wide for the single-pass kernel, or no workspace) is a bad argument: the host layers then
+    // take the materialising composition
+    return fused_status(launch_fused_decode_elem(elem, q, page_table, lengths, nullptr, out, B, S, D, body.ptr, body.bytes, st, 7));
+}
+
+int launch_lean_attention(int elem, void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                          const void* wv, const int* new_batch_idx, float* q_output, float* out, int B, int S, int D,
+                          int n_new_items, int n_heads, int window, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const int rc = launch_fill_and_latest(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, B, S, D, n_new_items, st);
+    if (rc) return rc;
+    return launch_lean_scan(q_output, reinterpret_cast<const void* const*>(page_table), lengths, out, B, S, D, n_heads, window,
+                            elem, workspace, workspace_bytes, st);
+}
 }  // namespace mli
 
 extern "C" {
@@ -89,26 +110,10 @@ int mli_paged_attention_lean(void* const* page_table, const int* lengths, const 
                              const int* new_batch_idx, float* q_output, float* attention_result, int n_batch,
                              int n_sequence, int emb_dim, int n_new_items, int elem_bf16, void* workspace,
                              size_t workspace_bytes, void* stream) {
-    { const mli::WsBody body = mli::ws_body(workspace, workspace_bytes); workspace = body.ptr; workspace_bytes = body.bytes; }
-    hipStream_t st = mli::as_stream(stream);
     if (elem_bf16 < MLI_ELEM_F32 || elem_bf16 > MLI_ELEM_FP8) return MLI_ERR_BAD_ARG;
-    const int rc = mli::launch_fill_and_latest(elem_bf16, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, n_batch,
-                                               n_sequence, emb_dim, n_new_items, st);
-    if (rc) return rc;
-    int fused;
-    if (elem_bf16 == MLI_ELEM_FP8)
-        fused = mli::launch_fused_decode_fp8(q_output, reinterpret_cast<uint8_t* const*>(page_table), lengths, attention_result,
-                                             n_batch, n_sequence, emb_dim, workspace, workspace_bytes, st);
-    else if (elem_bf16 == MLI_ELEM_BF16)
-        fused = mli::launch_fused_decode_bf16(q_output, reinterpret_cast<mli_bf16* const*>(page_table), lengths, nullptr,
-                                              attention_result, n_batch, n_sequence, emb_dim, workspace, workspace_bytes, st);
-    else
-        fused = mli::launch_fused_decode_f32(q_output, reinterpret_cast<float* const*>(page_table), lengths, nullptr,
-                                             attention_result, n_batch, n_sequence, emb_dim, workspace, workspace_bytes, st);
-    if (fused == 1) return 0;
-    // rows too wide for the single-pass kernel (or no workspace): the caller takes the materialising composition
-    if (fused == 0) return MLI_ERR_BAD_ARG;
-    return fused < 0 ? fused : fused - 1;
+    return mli::launch_lean_attention(elem_bf16, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
+                                      n_batch, n_sequence, emb_dim, n_new_items, 1, 0, workspace, workspace_bytes,
+                                      mli::as_stream(stream));
 }
 
 int mli_get_latest_k_q_v_paged_lean(void* const* page_table, const int* lengths, const void* wk, const void* wq,

@@ -180,10 +180,4 @@ inline int launch_status() {
 
 inline int ceil_div_i(int a, int b) { return (a + b - 1) / b; }
 
-// compose.hip: what every lean paged composition starts with, by page element type (MLI_ELEM_*; bf16 weights for bf16 and
-// fp8 pages): fill the n_new_items new rows, then project every non-empty row's last token (k, v appended, q to q_output)
-int launch_fill_and_latest(int elem, void* const* page_table, const int* lengths, const void* wk, const void* wq,
-                           const void* wv, const int* new_batch_idx, float* q_output, int n_batch, int n_sequence,
-                           int emb_dim, int n_new_items, hipStream_t st);
-
 }  // namespace mli

@@ -1,0 +1,178 @@
+// The launch plan of the chunked paged scans -- the single-head scan (attention_fused.hip), the multi-head scan
+// (attention_heads.hip) and their sliding-window forms (attention_window.hip): every rule that decides how such a scan is
+// launched, once.  Plain C++ over int / size_t / bool, no HIP types and no global state (tests/cpp/scan_plan_test.cpp
+// compiles it alone); the mli_tune values the rules depend on come in as a ScanTune.
+#pragma once
+
+#include <cstddef>
+
+#include "mli_kernels.h"
+
+namespace mli {
+
+// device_common.hpp / scan_item_body.hpp: kPage, kWave, kFuWaves, kMaxArrivalRows (scan_launch.hpp holds them equal)
+constexpr int kPlanPage = MLI_PAGE_BLOCK_SIZE;
+constexpr int kPlanWave = 64;
+constexpr int kPlanWaves = 4;
+constexpr int kPlanMaxRows = 16384;
+
+constexpr int kMaxOrderedRows = 2048;   // longest-first row order (scan_row_order.hpp): rows it can rank ...
+constexpr int kMaxOrderedPages = 64;    // ... and live pages per row its histogram covers
+constexpr int kMaxItemTokens = 1024;
+constexpr int kMaxMergeStats = 4096;    // float2 entries: the 32 KiB of LDS the last arriver stages a row's statistics in
+
+inline int plan_ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// The calling thread's mli_tune values (scan_tune(), attention_scan.hip)
+struct ScanTune {
+    int chunk_tokens;   // "chunk_tokens": 0 = the heuristic, else the forced item size (what sv_chunk_tokens_for then returns)
+    int row_order;      // "scan_row_order": 0 = one-workgroup-per-row grids take the rows in grid order
+    int nt_loads;       // "nt_loads": 0 = default cache policy, 1 = non-temporal, 2 = by working set
+};
+
+// K/V loads: non-temporal where the rows' K/V (upper bound B * S * D * e * 2 bytes) is far beyond the 256 MiB
+// Infinity Cache -- every byte is read once per step and nothing survives to the next one --, default policy where a
+// good part of it can stay on-die between two steps.  Measured (lean scan, fp32, D=256, S=1024, lengths U[S/4, 3S/4]):
+// B=128 / 256: default policy 6 / 5 % faster; B=512 / 1024 / 2048: non-temporal 6 / 11 / 10 % faster.
+inline bool nt_loads_rule(int setting, int B, int S, int D, int esize) {
+    if (setting != 2) return setting != 0;
+    return (long long)B * S * D * esize * 2 > ((long long)768 << 20);
+}
+
+// The tokens a windowed row can span: its window plus the part of the first live page below it, whole pages
+// (1 <= window < S: the entry points hand everything else on).
+inline int window_span(int S, int window) {
+    const long long span = (long long)kPlanPage * (plan_ceil_div(window, kPlanPage) + 1);
+    return span < S ? (int)span : S;
+}
+
+// Tokens per item over rows of `span` tokens (n_sequence, or the span a window leaves).
+//   Short sequences with a full batch: one workgroup per row (no partials, no combine launch) beats two 64-token chunks
+//   (README workload, S = 128: 200 vs 209 us).
+//   Otherwise the largest power of two <= 512 that still cuts the batch into >= 2048 (row, item) slots, i.e. with ragged
+//   lengths about two rounds of real items for the 512 workgroups the chip holds.  Measured: B=1024, S=4096 -> 512 (256:
+//   +2.4 %, 1024: +1 % with ragged lengths); B=256, S=1024 -> 128 (round 2, scan launch: 46.9 us against 49.6 at 256 and 54.3
+//   at 512, where 384 items of very unequal size cannot even fill the 512 slots once; lean form 52.5 / 53.1 / 56.2).
+//   Several heads: raised where a row's (items x heads) statistics would not fit the LDS the last arriver stages them in
+//   (n_sequence 16384 with 32 heads and a small batch); a size exists for every shape heads_lanes_log2 accepts.
+inline int scan_item_tokens(const ScanTune& t, int B, int span, int H) {
+    int ct;
+    if (t.chunk_tokens != 0) {
+        ct = t.chunk_tokens;
+    } else if (span <= 128 && B >= 256) {
+        ct = 128;
+    } else {
+        ct = 512;
+        while (ct > 64 && (long long)B * plan_ceil_div(span, ct) < 2048) ct >>= 1;
+    }
+    if (H > 1)
+        while (ct < kMaxItemTokens && (long long)plan_ceil_div(span, ct) * H > kMaxMergeStats) ct <<= 1;
+    return ct;
+}
+
+// Workspace body = [(m, l) per row, 64 tokens and head: B * ceil(S / 64) * H float2, 256-B aligned][partial rows].  The row
+// stride is n_sequence's whatever the item size or the window: calls of different shapes share one layout.
+inline size_t scan_stats_bytes(int B, int S, int H = 1) {
+    const size_t n = (size_t)B * plan_ceil_div(S, 64) * H * 8;
+    return (n + 255) & ~(size_t)255;
+}
+
+struct ScanPlan {
+    int ct;              // tokens per item
+    int nchunk;          // items a row can have
+    int direct;          // 0 = several items per row, 1 = one workgroup per row in grid order, 2 = ... longest row first
+    int grid_y;          // grid = (B, grid_y): rows 0 .. nchunk-1 run the full items, row nchunk every row's remainder
+    size_t stats_bytes;  // the statistics region in front of the partial rows
+    size_t body_bytes;   // what the workspace body must hold unless direct
+    bool nt;             // non-temporal K/V loads
+};
+
+// S = n_sequence; span = S, or window_span(S, window); esize = bytes per page element
+inline ScanPlan plan_chunked_scan(const ScanTune& t, int B, int S, int span, int D, int H, int esize) {
+    ScanPlan p;
+    p.ct = scan_item_tokens(t, B, span, H);
+    p.nchunk = plan_ceil_div(span, p.ct);
+    // one workgroup per row: hand the rows out longest first where the batch has more rows than the chip has workgroup slots
+    const bool ordered = t.row_order && p.nchunk == 1 && B > 512 && B <= kMaxOrderedRows && span / kPlanPage <= kMaxOrderedPages;
+    p.direct = p.nchunk == 1 ? (ordered ? 2 : 1) : 0;
+    p.grid_y = p.direct ? 1 : p.nchunk + 1;
+    p.stats_bytes = scan_stats_bytes(B, S, H);
+    p.body_bytes = p.stats_bytes + (size_t)B * p.nchunk * D * sizeof(float);
+    p.nt = nt_loads_rule(t.nt_loads, B, span, D, esize);
+    return p;
+}
+
+// The single-head kernel variant.  epl = elements per 16-byte lane load: 4 (fp32), 8 (bf16), 16 (fp8).
+struct ScanVariant {
+    int nj;    // template NJ: lane loads per row and wave, 1 or 2
+    bool ds;   // D-split (rows of more than two lane loads): the four waves split the row instead of the pages
+    int rpi;   // token slots per load instruction: fp8 rows narrower than one instruction take 2 or 4 (scan_common.hpp)
+};
+inline ScanVariant plain_scan_variant(int D, int epl) {
+    const int Du = D / epl;
+    const int nj = plan_ceil_div(Du, kPlanWave);
+    ScanVariant v;
+    v.ds = nj > 2;
+    v.nj = v.ds ? plan_ceil_div(Du, kPlanWave * kPlanWaves) : nj;
+    v.rpi = epl == 16 ? (Du <= 16 ? 4 : Du <= 32 ? 2 : 1) : 1;
+    return v;
+}
+
+// Dynamic LDS of a workgroup: the item's page pointers | the reduction buffer, which also holds the row's statistics
+// during the in-kernel merge (so the larger of the two).
+inline size_t scan_lds_bytes(int ct, size_t reduction_bytes, size_t merge_stat_bytes) {
+    return (size_t)(ct / kPlanPage) * 8 + (reduction_bytes > merge_stat_bytes ? reduction_bytes : merge_stat_bytes);
+}
+// single head: the waves' partial output rows, or with the D-split two buffers of the 16 partial scores of a page
+inline size_t plain_reduction_bytes(const ScanVariant& v, int epl) {
+    return (v.ds ? (size_t)2 * kPlanWaves * 16 : (size_t)kPlanWaves * v.nj * (kPlanWave / v.rpi) * epl) * sizeof(float);
+}
+// several heads: the waves' parked rows and (m, l) pairs
+inline size_t heads_reduction_bytes(int nj, int epl) {
+    return (size_t)kPlanWaves * nj * kPlanWave * (epl * sizeof(float) + 8);
+}
+// The merge statistics' bound is a different expression in each launcher; each sets the dynamic LDS of existing launches
+// and stays as it is.
+// Single head, no window: one pair per 64 tokens of n_sequence -- the workspace's row stride, an upper bound at every item
+// size; the merge stages one pair per item, so nchunk pairs would do, and why the stride was taken cannot be told from the code.
+inline size_t plain_merge_stat_bytes(int S) { return (size_t)plan_ceil_div(S, 64) * 8; }
+// Single head, window: one pair per item of the span -- what the merge stages.
+inline size_t window_merge_stat_bytes(int nchunk) { return (size_t)nchunk * 8; }
+// Several heads, with or without a window: one pair per (item, head) -- what the merge stages; scan_item_tokens keeps it
+// within kMaxMergeStats.
+inline size_t heads_merge_stat_bytes(int nchunk, int H) { return (size_t)nchunk * H * 8; }
+
+// ---- shapes the scans take (everything else is MLI_ERR_BAD_ARG before anything is launched) -------------------------------
+// Several heads: log2 of the lanes per head, or -1.
+inline int heads_lanes_log2(int B, int S, int D, int H, int elem) {
+    if (B <= 0 || B > kPlanMaxRows || S <= 0 || S % kPlanPage != 0 || D <= 0 || H < 1 || D % H != 0) return -1;
+    if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) return -1;
+    const int hd = D / H;
+    if (hd != 32 && hd != 64 && hd != 128 && hd != 256) return -1;
+    const int epl = elem == MLI_ELEM_BF16 ? 8 : 4;
+    if (D / epl > 2 * kPlanWave) return -1;   // rows of at most two lane loads: whole pages per wave
+    // the last arriver stages a row's (items x heads) statistics in LDS: even at the largest item size they must fit
+    if ((long long)plan_ceil_div(S, kMaxItemTokens) * H > kMaxMergeStats) return -1;
+    int lg = 0;
+    while ((epl << lg) < hd) ++lg;
+    return lg;
+}
+inline int heads_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int elem) {
+    return heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem) >= 0;
+}
+// One head under a window: what the lean chunked scan takes, with the rows the arrival counters can count.
+inline bool window_plain_shape_ok(int B, int S, int D, int elem) {
+    if (B <= 0 || B > kPlanMaxRows || S <= 0 || S % kPlanPage != 0 || D <= 0) return false;
+    if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16 && elem != MLI_ELEM_FP8) return false;
+    const int epl = elem == MLI_ELEM_FP8 ? 16 : elem == MLI_ELEM_BF16 ? 8 : 4;
+    if (D % epl != 0) return false;
+    const int nj = plan_ceil_div(D / epl, kPlanWave);
+    return elem == MLI_ELEM_FP8 ? nj <= 2 : nj <= 8;
+}
+inline int window_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int elem) {
+    if (n_heads < 1) return 0;
+    return n_heads == 1 ? window_plain_shape_ok(n_batch, n_sequence, emb_dim, elem)
+                        : heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem) >= 0;
+}
+
+}  // namespace mli

@@ -1,7 +1,8 @@
-// Longest-first row order of the one-workgroup-per-row grids (attention_fused.hip; the multi-head scan, attention_heads.hip).
+// Longest-first row order of the one-workgroup-per-row grids of the chunked paged scans (when it applies: scan_plan.hpp).
 #pragma once
 
 #include "scan_item_body.hpp"
+#include "scan_plan.hpp"
 
 namespace mli {
 
@@ -11,10 +12,8 @@ namespace mli {
 // the row of rank r by page count (descending; equal counts in row order).  Every workgroup derives the same ranking from
 // the lengths -- a histogram over the page counts, then the j-th row of its bucket by a block-wide count --: ~2 us of
 // prologue per workgroup, no pre-pass, deterministic.  All kFuThreads threads call it; n_batch <= kMaxOrderedRows.
-constexpr int kMaxOrderedRows = 2048;
 // WIN = true (attention_window.hip): the rows are ranked by the pages their window leaves live, ceil(L / 16) - lo / 16 with
 // lo = max(0, L - window); S / 16 may then exceed kMaxOrderedPages as long as the window's span does not.
-constexpr int kMaxOrderedPages = 64;
 template <bool WIN = false>
 __device__ __forceinline__ int longest_first_row(const int* __restrict__ lengths, int n_batch, int S, int rank, int window = 0) {
     __shared__ int hist[kMaxOrderedPages + 1];

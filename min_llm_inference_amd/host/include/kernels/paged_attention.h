@@ -51,6 +51,13 @@ void paged_attention_lean_window(TensorFloatPoint& page_table, const TensorInt& 
                                  TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
                                  int n_heads, int window);
 
+// What the three functions above share, and what the fp32 layers call: n_heads heads, window <= 0 or >= n_sequence = none;
+// qkt_output (may be null) serves one head without a window as in paged_attention_lean.
+void paged_attention_lean_layer(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                                const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                                TensorFloat& q_output, TensorFloat* qkt_output, TensorFloat& attention_result,
+                                int n_new_items, int n_sequence, int n_heads, int window);
+
 // EXTENSION: launch_paged_attention_encoder_kernel + launch_fill_new_k_v_cache_paged_attention in one
 // launch -- the embedding lookup is the fill GEMM's prologue; pages bit-identical to the two-launch form.
 void launch_paged_prefill(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,

@@ -1,7 +1,6 @@
 #include "bf16_extension.h"
 
 #include <cstring>
-#include <stdexcept>
 #include <utility>
 
 #include "kernels/decoder.h"
@@ -76,34 +75,13 @@ void PagedAttentionBf16Layer::forward(TensorFloatPoint& page_table, const Tensor
                                       const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                       int n_new_items) {
     const int n_sequence = static_cast<int>(qkt_output_.shape()[1]);
-    if (window_ > 0 && window_ < n_sequence) {
-        if (!mli::runtime::lean_layers()) throw std::runtime_error("sliding-window attention exists in the lean composition only");
-        const int B = (int)page_table.shape()[0], D = (int)wk_.shape()[0];
-        const mli::runtime::Scratch ws = mli::runtime::attention_scratch(B, n_sequence, D, n_heads_);
-        HIP_CHECK(mli_paged_attention_lean_window(reinterpret_cast<void* const*>(page_table.data()), lengths.data(), wk_.data(),
-                                                  wq_.data(), wv_.data(), new_batch_idx.data(), q_output_.data(),
-                                                  attention_result.data(), B, n_sequence, D, n_new_items, n_heads_, window_,
-                                                  MLI_ELEM_BF16, ws.ptr, ws.bytes, mli::runtime::compute_stream()));
-        return;
-    }
-    if (n_heads_ > 1) {
-        if (!mli::runtime::lean_layers()) throw std::runtime_error("multi-head attention exists in the lean composition only");
-        const int B = (int)page_table.shape()[0], D = (int)wk_.shape()[0];
-        const mli::runtime::Scratch ws = mli::runtime::attention_scratch(B, n_sequence, D, n_heads_);
-        HIP_CHECK(mli_paged_attention_lean_heads(reinterpret_cast<void* const*>(page_table.data()), lengths.data(), wk_.data(),
-                                                 wq_.data(), wv_.data(), new_batch_idx.data(), q_output_.data(),
-                                                 attention_result.data(), B, n_sequence, D, n_new_items, n_heads_,
-                                                 MLI_ELEM_BF16, ws.ptr, ws.bytes, mli::runtime::compute_stream()));
-        return;
-    }
-    if (mli::runtime::lean_layers()) {
-        const int B = (int)page_table.shape()[0], D = (int)wk_.shape()[0];
-        const mli::runtime::Scratch ws = mli::runtime::attention_scratch(B, n_sequence, D);
-        const int rc = mli_paged_attention_lean(reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
-                                                wk_.data(), wq_.data(), wv_.data(), new_batch_idx.data(),
-                                                q_output_.data(), attention_result.data(), B, n_sequence, D,
-                                                n_new_items, /*elem_bf16=*/1, ws.ptr, ws.bytes,
-                                                mli::runtime::compute_stream());
+    if (mli::runtime::lean_paged_wanted(n_heads_, window_, n_sequence)) {
+        const int D = (int)wk_.shape()[0];
+        const int rc = mli::runtime::lean_paged_attention(MLI_ELEM_BF16, n_heads_, window_,
+                                                          reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
+                                                          wk_.data(), wq_.data(), wv_.data(), new_batch_idx.data(),
+                                                          q_output_.data(), attention_result.data(),
+                                                          (int)page_table.shape()[0], n_sequence, D, n_new_items);
         if (rc != MLI_ERR_BAD_ARG || D <= 4096) {  // rows wider than the single-pass kernel covers: fall through
             HIP_CHECK(rc);
             return;

@@ -23,12 +23,8 @@
 #include "mli_kernels.h"
 #include "pipelined_engine.h"
 #include "runtime.h"
+#include "scan_plan.hpp"   // heads_shape_supported, window_shape_supported
 #include "throughput_counter.h"
-
-namespace mli {
-int heads_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int elem);  // attention_heads.hip
-int window_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int elem);  // attention_window.hip
-}
 
 namespace {
 

@@ -6,6 +6,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 
 #include "constants.h"
 #include "kernels/decoder.h"
@@ -266,50 +267,75 @@ void launch_prefill(const TensorFloat& emb_table, const TensorFloat& wpe, const 
                           (int)s[1], (int)s[2], (int)wk.shape()[1], n_new_items, stream()));
 }
 
-// EXTENSION: the composition without the scores (include/mli_kernels.h: mli_paged_attention_lean).  Rows too wide for
-// the single-pass kernel take the materialising composition into the caller's qkt_output scratch instead.
-void paged_attention_lean(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
-                          const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
-                          TensorFloat& q_output, TensorFloat& qkt_output, TensorFloat& attention_result,
-                          int n_new_items, int n_sequence) {
+bool mli::runtime::lean_paged_wanted(int n_heads, int window, int n_sequence) {
+    const bool lean = lean_layers();
+    if (n_heads > 1 && !lean) throw std::runtime_error("multi-head attention exists in the lean composition only");
+    if (window > 0 && window < n_sequence && !lean)
+        throw std::runtime_error("sliding-window attention exists in the lean composition only");
+    return lean;
+}
+
+int mli::runtime::lean_paged_attention(int elem, int n_heads, int window, void* const* page_table, const int* lengths,
+                                       const void* wk, const void* wq, const void* wv, const int* new_batch_idx,
+                                       float* q_output, float* attention_result, int B, int S, int D, int n_new_items) {
+    const Scratch ws = attention_scratch(B, S, D, n_heads > 1 ? n_heads : 1);
+    if (window > 0 && window < S) {
+        HIP_CHECK(mli_paged_attention_lean_window(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B,
+                                                  S, D, n_new_items, n_heads, window, elem, ws.ptr, ws.bytes, stream()));
+        return 0;
+    }
+    if (n_heads > 1) {
+        HIP_CHECK(mli_paged_attention_lean_heads(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B,
+                                                 S, D, n_new_items, n_heads, elem, ws.ptr, ws.bytes, stream()));
+        return 0;
+    }
+    return mli_paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B, S, D,
+                                    n_new_items, elem, ws.ptr, ws.bytes, stream());
+}
+
+// EXTENSION: the composition without the scores, with n_heads heads and a sliding window (kernels/paged_attention.h).  One
+// head without a window, rows too wide for the single-pass kernel: the materialising composition into the caller's
+// qkt_output scratch (if given) instead.  Every other unsupported shape throws.
+void paged_attention_lean_layer(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                                const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                                TensorFloat& q_output, TensorFloat* qkt_output, TensorFloat& attention_result,
+                                int n_new_items, int n_sequence, int n_heads, int window) {
     const int B = (int)page_table.shape()[0], D = (int)wk.shape()[0];
-    const Scratch ws = scratch_for(B, n_sequence, D);
-    const int rc = mli_paged_attention_lean(reinterpret_cast<void* const*>(pages(page_table)), lengths.data(), wk.data(),
-                                            wq.data(), wv.data(), new_batch_idx.data(), q_output.data(),
-                                            attention_result.data(), B, n_sequence, D, n_new_items, /*elem_bf16=*/0,
-                                            ws.ptr, ws.bytes, stream());
-    if (rc == MLI_ERR_BAD_ARG && D > 2048 && D % 4 == 0) {
-        paged_attention(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, qkt_output, attention_result,
+    const int rc = mli::runtime::lean_paged_attention(MLI_ELEM_F32, n_heads, window, reinterpret_cast<void* const*>(pages(page_table)),
+                                                      lengths.data(), wk.data(), wq.data(), wv.data(), new_batch_idx.data(),
+                                                      q_output.data(), attention_result.data(), B, n_sequence, D, n_new_items);
+    if (rc == MLI_ERR_BAD_ARG && qkt_output != nullptr && D > 2048 && D % 4 == 0) {
+        paged_attention(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, *qkt_output, attention_result,
                         n_new_items, n_sequence);
         return;
     }
     HIP_CHECK(rc);
 }
 
-// EXTENSION: the lean composition with n_heads attention heads (mli_paged_attention_lean_heads); an unsupported shape throws
+void paged_attention_lean(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                          const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                          TensorFloat& q_output, TensorFloat& qkt_output, TensorFloat& attention_result,
+                          int n_new_items, int n_sequence) {
+    paged_attention_lean_layer(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, &qkt_output, attention_result,
+                               n_new_items, n_sequence, 1, 0);
+}
+
 void paged_attention_lean_heads(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
                                 const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
                                 TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
                                 int n_heads) {
-    const int B = (int)page_table.shape()[0], D = (int)wk.shape()[0];
-    const Scratch ws = mli::runtime::attention_scratch(B, n_sequence, D, n_heads);
-    HIP_CHECK(mli_paged_attention_lean_heads(reinterpret_cast<void* const*>(pages(page_table)), lengths.data(), wk.data(),
-                                             wq.data(), wv.data(), new_batch_idx.data(), q_output.data(),
-                                             attention_result.data(), B, n_sequence, D, n_new_items, n_heads, MLI_ELEM_F32,
-                                             ws.ptr, ws.bytes, stream()));
+    if (n_heads < 1) HIP_CHECK(MLI_ERR_BAD_ARG);   // as mli_paged_attention_lean_heads
+    paged_attention_lean_layer(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, nullptr, attention_result,
+                               n_new_items, n_sequence, n_heads, 0);
 }
 
-// EXTENSION: the lean composition with a sliding window (mli_paged_attention_lean_window); an unsupported shape throws
 void paged_attention_lean_window(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
                                  const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
                                  TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
                                  int n_heads, int window) {
-    const int B = (int)page_table.shape()[0], D = (int)wk.shape()[0];
-    const Scratch ws = mli::runtime::attention_scratch(B, n_sequence, D, n_heads);
-    HIP_CHECK(mli_paged_attention_lean_window(reinterpret_cast<void* const*>(pages(page_table)), lengths.data(), wk.data(),
-                                              wq.data(), wv.data(), new_batch_idx.data(), q_output.data(),
-                                              attention_result.data(), B, n_sequence, D, n_new_items, n_heads, window,
-                                              MLI_ELEM_F32, ws.ptr, ws.bytes, stream()));
+    if (window < 1 || n_heads < 1) HIP_CHECK(MLI_ERR_BAD_ARG);   // as mli_paged_attention_lean_window; the layers' "no window" is 0
+    paged_attention_lean_layer(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, nullptr, attention_result,
+                               n_new_items, n_sequence, n_heads, window);
 }
 
 void paged_attention_with_cublas(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,

@@ -1,6 +1,5 @@
 #include "layers.h"
 
-#include <stdexcept>
 #include <utility>
 
 #include "kernels/decoder.h"
@@ -50,20 +49,9 @@ PagedAttentionLayer::PagedAttentionLayer(TensorFloat&& wk, TensorFloat&& wq, Ten
 void PagedAttentionLayer::forward(TensorFloatPoint& page_table, const TensorInt& lengths,
                                   const TensorInt& new_batch_idx, TensorFloat& attention_result, int n_new_items) {
     const int n_sequence = static_cast<int>(qkt_output_.shape()[1]);
-    const bool windowed = window_ > 0 && window_ < n_sequence;
-    if (n_heads_ > 1 && !mli::runtime::lean_layers())
-        throw std::runtime_error("multi-head attention exists in the lean composition only");
-    if (windowed && !mli::runtime::lean_layers())
-        throw std::runtime_error("sliding-window attention exists in the lean composition only");
-    if (windowed)
-        paged_attention_lean_window(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, attention_result,
-                                    n_new_items, n_sequence, n_heads_, window_);
-    else if (n_heads_ > 1)
-        paged_attention_lean_heads(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, attention_result,
-                                   n_new_items, n_sequence, n_heads_);
-    else if (mli::runtime::lean_layers())
-        paged_attention_lean(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, qkt_output_,
-                             attention_result, n_new_items, n_sequence);
+    if (mli::runtime::lean_paged_wanted(n_heads_, window_, n_sequence))
+        paged_attention_lean_layer(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, &qkt_output_,
+                                   attention_result, n_new_items, n_sequence, n_heads_, window_);
     else
         paged_attention(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, qkt_output_, attention_result,
                         n_new_items, n_sequence);
@@ -93,20 +81,9 @@ void PagedAttentionCublasLayer::forward(TensorFloatPoint& page_table, const Tens
                                         const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                         int n_new_items, GemmHandle& handle) {
     const int n_sequence = static_cast<int>(qkt_output_.shape()[1]);
-    const bool windowed = window_ > 0 && window_ < n_sequence;
-    if (n_heads_ > 1 && !mli::runtime::lean_layers())
-        throw std::runtime_error("multi-head attention exists in the lean composition only");
-    if (windowed && !mli::runtime::lean_layers())
-        throw std::runtime_error("sliding-window attention exists in the lean composition only");
-    if (windowed)
-        paged_attention_lean_window(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, attention_result,
-                                    n_new_items, n_sequence, n_heads_, window_);
-    else if (n_heads_ > 1)
-        paged_attention_lean_heads(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, attention_result,
-                                   n_new_items, n_sequence, n_heads_);
-    else if (mli::runtime::lean_layers())
-        paged_attention_lean(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, qkt_output_,
-                             attention_result, n_new_items, n_sequence);
+    if (mli::runtime::lean_paged_wanted(n_heads_, window_, n_sequence))
+        paged_attention_lean_layer(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, &qkt_output_,
+                                   attention_result, n_new_items, n_sequence, n_heads_, window_);
     else
         paged_attention_with_cublas(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, qkt_output_,
                                     attention_result, latest_emb_, temp_placeholder_, n_new_items, n_sequence, handle);

@@ -277,53 +277,43 @@ def _elem_of(wk, elem):
     return int(wk.dtype == torch.bfloat16) if elem is None else int(elem)
 
 
+def _lean_call(name, front, B, n_sequence, D, extra, n_heads, elem, device):
+    """One lean entry point: the workspace for n_heads heads, then name(*front, B, n_sequence, D, *extra, elem, workspace)."""
+    ws, need = workspace_for(B, n_sequence, D, device, n_heads)
+    _check(getattr(load_library(), name)(*map(_p, front), B, n_sequence, D, *map(int, extra), int(elem), _p(ws), need,
+                                         _stream()), name)
+
+
 def decode_scan_paged_heads(q_output, page_table, lengths, attention_result, n_heads, elem, n_sequence):
     """The multi-head single-pass scan (mli_decode_scan_paged_heads): head h owns columns [h * D / n_heads, ...) of q, K and V,
     one softmax per head; lean form.  n_heads = 1 is decode_scan_paged(phases=7)."""
     B, D = q_output.shape
-    ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
-    _check(load_library().mli_decode_scan_paged_heads(_p(q_output), _p(page_table), _p(lengths), _p(attention_result), B,
-                                                      n_sequence, D, int(n_heads), int(elem), _p(ws), need, _stream()),
-           "mli_decode_scan_paged_heads")
+    _lean_call("mli_decode_scan_paged_heads", (q_output, page_table, lengths, attention_result), B, n_sequence, D, (n_heads,),
+               n_heads, elem, q_output.device)
 
 
 def decode_scan_paged_window(q_output, page_table, lengths, attention_result, n_heads, window, elem, n_sequence):
     """The sliding-window scan (mli_decode_scan_paged_window): row b attends slots [max(0, L - window), L) only; lean
     form, n_heads heads.  window >= n_sequence is decode_scan_paged(phases=7) / decode_scan_paged_heads."""
     B, D = q_output.shape
-    ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
-    _check(load_library().mli_decode_scan_paged_window(_p(q_output), _p(page_table), _p(lengths), _p(attention_result), B,
-                                                       n_sequence, D, int(n_heads), int(window), int(elem), _p(ws), need,
-                                                       _stream()), "mli_decode_scan_paged_window")
+    _lean_call("mli_decode_scan_paged_window", (q_output, page_table, lengths, attention_result), B, n_sequence, D,
+               (n_heads, window), n_heads, elem, q_output.device)
 
 
 def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_new_items,
                          n_sequence, elem=None, n_heads=1, window=None):
     """What the attention layers run: the paged composition without materialising scores / probabilities
-    (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads > 1: the
-    multi-head form (mli_paged_attention_lean_heads)."""
-    B = page_table.shape[0]
-    D = wk.shape[0]
-    if window is not None:   # the sliding-window form (mli_paged_attention_lean_window)
-        ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
-        _check(load_library().mli_paged_attention_lean_window(_p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv),
-                                                              _p(new_batch_idx), _p(q_output), _p(attention_result), B,
-                                                              n_sequence, D, n_new_items, int(n_heads), int(window),
-                                                              _elem_of(wk, elem), _p(ws), need, _stream()),
-               "mli_paged_attention_lean_window")
-        return
-    if n_heads != 1:
-        ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
-        _check(load_library().mli_paged_attention_lean_heads(_p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv),
-                                                             _p(new_batch_idx), _p(q_output), _p(attention_result), B,
-                                                             n_sequence, D, n_new_items, int(n_heads), _elem_of(wk, elem),
-                                                             _p(ws), need, _stream()), "mli_paged_attention_lean_heads")
-        return
-    ws, need = workspace_for(B, n_sequence, D, q_output.device)
-    _check(load_library().mli_paged_attention_lean(_p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv),
-                                                   _p(new_batch_idx), _p(q_output), _p(attention_result), B, n_sequence,
-                                                   D, n_new_items, _elem_of(wk, elem), _p(ws), need,
-                                                   _stream()), "mli_paged_attention_lean")
+    (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads != 1: the
+    multi-head form (mli_paged_attention_lean_heads); window given: the sliding-window form
+    (mli_paged_attention_lean_window)."""
+    if window is not None:
+        name, extra = "mli_paged_attention_lean_window", (n_new_items, n_heads, window)
+    elif n_heads != 1:
+        name, extra = "mli_paged_attention_lean_heads", (n_new_items, n_heads)
+    else:
+        name, extra = "mli_paged_attention_lean", (n_new_items,)
+    _lean_call(name, (page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result), page_table.shape[0],
+               n_sequence, wk.shape[0], extra, n_heads, _elem_of(wk, elem), q_output.device)
 
 
 def paged_prefill(emb_table, wpe, inp, page_table, lengths, new_item_indices, wk, wv, n_new_items, elem=None):

@@ -8,7 +8,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BAD_ARG, F32, BF16, FP8 = -22, 0, 1, 2
+BAD_ARG, WORKSPACE, F32, BF16, FP8 = -22, -12, 0, 1, 2
 SYMBOLS = ("mli_attention_heads_workspace_bytes", "mli_decode_scan_paged_heads", "mli_paged_attention_lean_heads",
            "mli_engine_set_heads")
 
@@ -52,6 +52,14 @@ def test_unsupported_shapes_are_refused_before_any_launch(mli, what, B, S, D, H,
     assert mli.mli_decode_scan_paged_heads(None, None, None, None, B, S, D, H, elem, None, 0, None) == BAD_ARG
     assert mli.mli_paged_attention_lean_heads(None, None, None, None, None, None, None, None, B, S, D, 0, H, elem, None, 0,
                                               None) == BAD_ARG
+
+
+def test_a_missing_workspace_on_a_multi_item_shape_is_a_workspace_error(mli):
+    """B 8, S 1024: several items per row, so the scans need the workspace body; validation precedes every launch.  The
+    multi-head scan says MLI_ERR_WORKSPACE, the plain lean scan "not applicable", which its entry point reports as a bad
+    argument."""
+    assert mli.mli_decode_scan_paged_heads(None, None, None, None, 8, 1024, 128, 2, F32, None, 0, None) == WORKSPACE
+    assert mli.mli_decode_scan_paged(None, None, None, None, None, 8, 1024, 128, F32, 7, None, 0, None) == BAD_ARG
 
 
 def test_headers_still_compile_as_c99_and_cxx17(tmp_path):

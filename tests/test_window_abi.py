@@ -8,7 +8,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BAD_ARG, F32, BF16, FP8 = -22, 0, 1, 2
+BAD_ARG, WORKSPACE, F32, BF16, FP8 = -22, -12, 0, 1, 2
 SYMBOLS = ("mli_decode_scan_paged_window", "mli_paged_attention_lean_window", "mli_engine_set_window")
 
 
@@ -64,6 +64,12 @@ def test_unsupported_shapes_are_refused_before_any_launch(mli, what, B, S, D, H,
     for W in (1, 12, S - 1):
         assert _scan(mli, B, S, D, H, W, elem) == BAD_ARG, W
         assert _lean(mli, B, S, D, H, W, elem) == BAD_ARG, W
+
+
+@pytest.mark.parametrize("H", [1, 2])
+def test_a_missing_workspace_on_a_multi_item_shape_is_a_workspace_error(mli, H):
+    """B 8, S 1024, W 256: several items per row, so the scan needs the workspace body; validation precedes every launch."""
+    assert _scan(mli, 8, 1024, 128, H, 256, F32) == WORKSPACE
 
 
 def test_headers_still_compile_as_c99_and_cxx17(tmp_path):
