@@ -140,6 +140,16 @@ int mli_engine_set_heads(mli_engine* engine, int n_heads);
  * window >= n_sequence is accepted everywhere and changes nothing. */
 int mli_engine_set_window(mli_engine* engine, int window);
 
+/* EXTENSION: attention sinks beside the window (mli_kernels.h: mli_paged_attention_lean_sinks).  Every row attends its
+ * first n_sink tokens as well as its newest `window`.  Like the window, sinks change which slots the scan reads and
+ * nothing else: admission, growth, preemption, re-prefill, n_forward_rounds, step graphs, sampling and the pipelined loop
+ * work as without them, and no page is returned to the pool early.  Before the first step or run; the four paged kinds;
+ * combines with mli_engine_set_heads and mli_engine_set_window in any order (each call validates the combination).
+ * Without an effective window (none set, or window >= n_sequence) it is accepted and changes nothing until one is set.
+ * -1 with a message for MLI_ENGINE_CONTIGUOUS, n_sink < 0, a call after the engine has started, or an engine configured
+ * with lean_layers = 0. */
+int mli_engine_set_sinks(mli_engine* engine, int n_sink);
+
 const char* mli_engine_last_error(void);
 
 #ifdef __cplusplus

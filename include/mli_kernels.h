@@ -256,6 +256,28 @@ int mli_paged_attention_lean_window(void* const* page_table, const int* lengths,
                                     int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int window,
                                     int elem, void* workspace, size_t workspace_bytes, void* stream);
 
+/* EXTENSION: ATTENTION SINKS beside the sliding window.  n_sink = K >= 0, window = W >= 1; for row b with
+ * L = min(lengths[b], n_sequence) and lo = max(0, L - W) the row attends the slots s < L with s < K or s >= lo -- its first
+ * K tokens and its newest W (W is not reduced by K); a row with lo <= K attends all of [0, L).  Scores are scaled as without
+ * sinks; L == 0 gives zeros.  No byte of a slot outside the attended set influences the result: the gap slots [K, lo) and
+ * the slots >= L are never multiplied, not even inside a page they share with attended slots, and the page-table entries
+ * of the pages wholly inside the gap (ceil(K / 16) <= index < lo / 16) are never read -- they may be null or stale.  Fill,
+ * projection, page layout and q_output depend neither on W nor on K.
+ * Hand-offs, before anything else, same kernels and same bits: K == 0 IS the _window call; K + W >= n_sequence or
+ * W >= n_sequence (no row can have a gap) IS mli_decode_scan_paged(phases 7) / mli_paged_attention_lean, or the _heads forms
+ * for n_heads > 1.  Otherwise one scan launch, chunked grid sized by the min(n_sequence, 16 * (ceil(K / 16) + ceil(W / 16)
+ * + 1)) tokens a row's two page runs can span, in-kernel merge; supported shapes, mli_tune keys and the workspace are
+ * mli_decode_scan_paged_window's.  K < 0, W < 1 and n_heads < 1 are MLI_ERR_BAD_ARG, decided before anything is launched. */
+int mli_decode_scan_paged_sinks(const float* q_output, const void* const* page_table, const int* lengths,
+                                float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int window,
+                                int n_sink, int elem, void* workspace, size_t workspace_bytes, void* stream);
+
+/* mli_paged_attention_lean_window with sinks: fill (n_new_items rows) -> latest -> sink-windowed scan. */
+int mli_paged_attention_lean_sinks(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                   const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                   int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int window,
+                                   int n_sink, int elem, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */

@@ -69,6 +69,8 @@ SIGNATURES = {
     "mli_paged_attention_lean_heads": [_P] * 8 + [_I] * 6 + [_P, _Z, _P],
     "mli_decode_scan_paged_window": [_P] * 4 + [_I] * 6 + [_P, _Z, _P],
     "mli_paged_attention_lean_window": [_P] * 8 + [_I] * 7 + [_P, _Z, _P],
+    "mli_decode_scan_paged_sinks": [_P] * 4 + [_I] * 7 + [_P, _Z, _P],
+    "mli_paged_attention_lean_sinks": [_P] * 8 + [_I] * 8 + [_P, _Z, _P],
     "mli_get_latest_k_q_v_paged_lean": [_P] * 6 + [_I] * 4 + [_P],
     "mli_self_attention_lean": [_P] * 10 + [_I] * 5 + [_P, _Z, _P],
     "mli_decode_scan_contiguous": [_P] * 5 + [_I] * 3 + [_P, _Z, _P],
@@ -128,6 +130,7 @@ ENGINE_SIGNATURES = {
     "mli_engine_configure": [_P, _I, _I],
     "mli_engine_set_heads": [_P, _I],
     "mli_engine_set_window": [_P, _I],
+    "mli_engine_set_sinks": [_P, _I],
     "mli_engine_set_lean_layers": [_I],
     "mli_engine_set_step_graphs": [_I],
     "mli_engine_last_error": [],

@@ -52,11 +52,14 @@ __device__ __forceinline__ void heads_xor_step(float (&v)[NJ][16]) {
 // smem_raw: ct / 16 page pointers | max(4 waves x (NJ * 64 * EPL floats + NJ * 64 float2), nchunk_max * H float2)
 // WIN = true (EXTENSION, attention_window.hip): the row attends its newest `window` tokens -- fused_scan_item's window
 // switch: the row is taken from its first live page p0 on, and that page's slots below the window are masked.
-template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false>
+// SINK = true (EXTENSION, attention_sinks.hip; with WIN): fused_scan_item's sink switch -- the first n_sink tokens are attended
+// too, on the virtual row of sink pages + window pages; the mask is per slot of the lane's 16.
+template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false, bool SINK = false>
 __device__ __forceinline__ void heads_scan_item(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ out, float2* ml, float* partial, int S, int D, int lg, int H, int ct, int nchunk_max, int direct,
-    unsigned* arrivals, int b, int c, bool first_grid_row, unsigned char* smem_raw, int window = 0) {
+    unsigned* arrivals, int b, int c, bool first_grid_row, unsigned char* smem_raw, int window = 0, int n_sink = 0) {
+    static_assert(!SINK || WIN, "sinks exist beside a window only");
     constexpr int EPL = E::EPL;
     constexpr int kRowF = NJ * kWave * EPL;   // floats one wave parks
     constexpr int kRowU = NJ * kWave;         // lane units of a row
@@ -88,7 +91,9 @@ __device__ __forceinline__ void heads_scan_item(
     const int L_row = min(lengths[b], S);
     const int lo = WIN ? max(0, L_row - window) : 0;   // first slot the row attends
     const int p0 = lo / kPage;                         // ... and the page it lies in
-    const int L = L_row - p0 * kPage;                  // the row from that page on
+    const int ps = SINK ? (n_sink + kPage - 1) / kPage : 0;   // sink pages
+    const int skip = SINK ? max(0, p0 - ps) : p0;             // pages dropped in front of the window's first page
+    const int L = L_row - skip * kPage;                // the row from that page on (SINK: the virtual row)
     if (L <= 0) {
         // no workgroup arrives for an empty row: its zero result is written here, once
         if (first_grid_row)
@@ -113,8 +118,12 @@ __device__ __forceinline__ void heads_scan_item(
     if (early) {
         if ((int)threadIdx.x < npages) ptr_sh[threadIdx.x] = early_ptr;   // npages <= ct / 16 <= 64 < threads
     } else {
-        for (int i = threadIdx.x; i < npages; i += kFuThreads)
-            ptr_sh[i] = page_table[(int64_t)b * W + p0 + s0 / kPage + i];
+        for (int i = threadIdx.x; i < npages; i += kFuThreads) {
+            // (the old statement stays verbatim in the else branch: folded into one expression with a SINK operand, the
+            // 64-bit address sum of the existing kernels re-associates and their device code changes)
+            if constexpr (SINK) ptr_sh[i] = page_table[(int64_t)b * W + sink_page(s0 / kPage + i, ps, skip)];
+            else ptr_sh[i] = page_table[(int64_t)b * W + p0 + s0 / kPage + i];
+        }
     }
     __syncthreads();
 
@@ -170,7 +179,15 @@ __device__ __forceinline__ void heads_scan_item(
         const bool has_next = pi + kFuWaves < npages;
         const char* next = has_next ? page_ptr(pi + kFuWaves) : nullptr;
         const int nt = min(kPage, ntok - pi * kPage);  // live tokens in this page (>= 1)
-        const int nlo = (WIN && pi == 0 && s0 == 0) ? lo - p0 * kPage : 0;   // slots below the window (row's first live page)
+        int nlo = (WIN && pi == 0 && s0 == 0) ? lo - p0 * kPage : 0;   // slots below the window (row's first live page)
+        int nk = 0;                                                         // slots among the sinks
+        // (SINK overwrites the nlo above, which is dead there: the line stays as it was so that the existing kernels' device
+        // code does not change)
+        if constexpr (SINK) {
+            const int first = sink_page(s0 / kPage + pi, ps, skip) * kPage;   // the page's first slot in the row
+            nlo = lo - first;
+            nk = n_sink - first;
+        }
         float sp[NJ][16];   // partial scores, then scores, then the page's probabilities (of the lane's head for j)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
@@ -207,14 +224,14 @@ __device__ __forceinline__ void heads_scan_item(
 #pragma unroll
                         for (int t = 0; t < 16; ++t) {
                             sp[j][t] = div_by(sp[j][t], scale, inv_scale);
-                            pm = slot_live<WIN>(t, nt, nlo) ? fmaxf(pm, sp[j][t]) : pm;
+                            pm = slot_live<WIN, SINK>(t, nt, nlo, nk) ? fmaxf(pm, sp[j][t]) : pm;
                         }
                         const float m_new = fmaxf(run_m[j], pm);
                         const float alpha = run_m[j] == -INFINITY ? 0.f : expf(run_m[j] - m_new);
                         float psum = 0.f;
 #pragma unroll
                         for (int t = 0; t < 16; ++t) {
-                            sp[j][t] = slot_live<WIN>(t, nt, nlo) ? expf(sp[j][t] - m_new) : 0.f;
+                            sp[j][t] = slot_live<WIN, SINK>(t, nt, nlo, nk) ? expf(sp[j][t] - m_new) : 0.f;
                             psum += sp[j][t];
                         }
                         run_l[j] = run_l[j] * alpha + psum;
@@ -229,7 +246,7 @@ __device__ __forceinline__ void heads_scan_item(
 #pragma unroll
                 for (int t = 0; t < TBR; ++t) {
                     // wave-uniform: never multiply unwritten page memory (or a slot below the window), even by zero
-                    if (slot_live<WIN>(first + t, nt, nlo)) {
+                    if (slot_live<WIN, SINK>(first + t, nt, nlo, nk)) {
 #pragma unroll
                         for (int j = 0; j < NJ; ++j) ElemMath<E>::axpy(buf[bi][t][j], sp[j][first + t], acc[j]);
                     }

@@ -115,12 +115,17 @@ __device__ __forceinline__ void row_publish_merge(float m, float l, float2* ml_r
 }
 
 // Is slot t of a page attended?  nt: the page's slots inside the row; nlo (WIN, attention_window.hip): its slots below the
-// row's window.
-template <bool WIN>
-__device__ __forceinline__ bool slot_live(int t, int nt, int nlo) {
-    if constexpr (WIN) return t < nt && t >= nlo;
+// row's window; nk (SINK, attention_sinks.hip): its slots among the row's sink tokens, attended whatever the window.
+template <bool WIN, bool SINK = false>
+__device__ __forceinline__ bool slot_live(int t, int nt, int nlo, int nk = 0) {
+    if constexpr (SINK) return t < nt && (t < nk || t >= nlo);
+    else if constexpr (WIN) return t < nt && t >= nlo;
     else return t < nt;
 }
+
+// SINK: the physical page of page v of the row's virtual row -- the ps sink pages, then the pages from the window's first
+// one on, `skip` pages dropped between the two runs.
+__device__ __forceinline__ int sink_page(int v, int ps, int skip) { return v < ps ? v : v + skip; }
 
 // b, c: the item (row, grid row); first_grid_row: this workgroup is the one that writes the zero result of an empty row.
 // RPI = token slots per load instruction (scan_common.hpp; 1 except for narrow fp8 rows): a batch is TBR instructions =
@@ -130,13 +135,21 @@ __device__ __forceinline__ bool slot_live(int t, int nt, int nlo) {
 //   looks from token 16 * p0 on (relative length L - 16 * p0 <= window + 15; page pointers from page_table[b][p0 + ...], an
 //   entry below p0 is never read), and in the row's first live page the slots t < lo - 16 * p0 are masked exactly as the
 //   slots >= nt of its last one are.  WIN = false ignores `window`.
-template <class E, int NJ, bool NT, int TBR, bool DS, bool SCORES, int RPI, bool WIN = false>
+// SINK = true (EXTENSION, attention_sinks.hip; with WIN): the row attends its first n_sink tokens as well, slots s < L with
+//   s < n_sink or s >= lo.  Its ps = ceil(n_sink / 16) sink pages stay, skip = max(0, p0 - ps) pages between them and page p0
+//   are dropped, and everything below is done on the virtual row of L - 16 * skip tokens whose page v is physical page
+//   sink_page(v): items are cut over the virtual row (one may straddle the joint), page pointers are staged through that
+//   mapping (an entry inside the dropped run is never read), and slot t of physical page P is live iff t < nt and
+//   (16 P + t < n_sink or 16 P + t >= lo) -- the hole may lie inside a page, straddle a page edge, or be the dropped run.
+//   A row with lo <= n_sink attends all of [0, L).  SINK = false ignores `n_sink`.
+template <class E, int NJ, bool NT, int TBR, bool DS, bool SCORES, int RPI, bool WIN = false, bool SINK = false>
 __device__ __forceinline__ void fused_scan_item(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ qkt, float* __restrict__ out, float2* ml, float* partial,
     int S, int D, int ct, int ml_per_row, int nchunk_max, int direct, unsigned* arrivals, int b, int c,
-    bool first_grid_row, int trace_stride, unsigned char* smem_raw, int window = 0) {
+    bool first_grid_row, int trace_stride, unsigned char* smem_raw, int window = 0, int n_sink = 0) {
     static_assert(!WIN || !SCORES, "the window exists in the lean form only");
+    static_assert(!SINK || WIN, "sinks exist beside a window only");
     constexpr int EPL = E::EPL;
     constexpr int LPR = kWave / RPI;   // lanes per token row
     static_assert(RPI == 1 || (NJ == 1 && !DS), "several rows per instruction: rows of one lane load, whole pages per wave");
@@ -183,7 +196,9 @@ __device__ __forceinline__ void fused_scan_item(
     const int L_row = min(lengths[b], S);
     const int lo = WIN ? max(0, L_row - window) : 0;   // first slot the row attends
     const int p0 = lo / kPage;                         // ... and the page it lies in
-    const int L = L_row - p0 * kPage;                  // the row from that page on
+    const int ps = SINK ? (n_sink + kPage - 1) / kPage : 0;   // sink pages
+    const int skip = SINK ? max(0, p0 - ps) : p0;             // pages dropped in front of the window's first page
+    const int L = L_row - skip * kPage;                // the row from that page on (SINK: the virtual row)
     if (arrivals != nullptr && L == 0) {
         // in-kernel merge: no workgroup arrives for an empty row, so its zero result is written here, once
         if (first_grid_row) {
@@ -222,8 +237,12 @@ __device__ __forceinline__ void fused_scan_item(
     if (early) {
         if ((int)threadIdx.x < npages) ptr_sh[threadIdx.x] = early_ptr;   // npages <= ct / 16 <= 64 < threads
     } else {
-        for (int i = threadIdx.x; i < npages; i += kFuThreads)
-            ptr_sh[i] = page_table[(int64_t)b * W + p0 + s0 / kPage + i];
+        for (int i = threadIdx.x; i < npages; i += kFuThreads) {
+            // (the old statement stays verbatim in the else branch: folded into one expression with a SINK operand, the
+            // 64-bit address sum of the existing kernels re-associates and their device code changes)
+            if constexpr (SINK) ptr_sh[i] = page_table[(int64_t)b * W + sink_page(s0 / kPage + i, ps, skip)];
+            else ptr_sh[i] = page_table[(int64_t)b * W + p0 + s0 / kPage + i];
+        }
     }
     __syncthreads();
     MLI_TRACE(1);
@@ -283,7 +302,15 @@ __device__ __forceinline__ void fused_scan_item(
         const bool has_next = pi + PSTEP < npages;
         const char* next = has_next ? page_ptr(pi + PSTEP) : nullptr;
         const int nt = min(kPage, ntok - pi * kPage);  // live tokens in this page (>= 1)
-        const int nlo = (WIN && pi == 0 && s0 == 0) ? lo - p0 * kPage : 0;   // slots below the window (row's first live page)
+        int nlo = (WIN && pi == 0 && s0 == 0) ? lo - p0 * kPage : 0;   // slots below the window (row's first live page)
+        int nk = 0;                                                         // slots among the sinks
+        // (SINK overwrites the nlo above, which is dead there: the line stays as it was so that the existing kernels' device
+        // code does not change)
+        if constexpr (SINK) {
+            const int first = sink_page(s0 / kPage + pi, ps, skip) * kPage;   // the page's first slot in the row
+            nlo = lo - first;
+            nk = n_sink - first;
+        }
         float sacc[16 / RPI];
 #pragma unroll
         for (int t = 0; t < 16 / RPI; ++t) sacc[t] = 0.f;
@@ -317,7 +344,7 @@ __device__ __forceinline__ void fused_scan_item(
 #pragma unroll
                         for (int w = 0; w < kFuWaves; ++w) tot += xs[w * 16 + slot];
                     }
-                    const bool valid = slot_live<WIN>(slot, nt, nlo);
+                    const bool valid = slot_live<WIN, SINK>(slot, nt, nlo, nk);
                     const float score = tot / scale;
                     if (SCORES && valid && (lane & 3) == 0 && (!DS || wave == 0))
                         qkt_row[s0 + pi * kPage + slot] = score;  // raw; normalised later
@@ -342,12 +369,12 @@ __device__ __forceinline__ void fused_scan_item(
                     const float p = rpi_prob<RPI>(p_lane, first + t, lane);
                     // wave-uniform: never multiply unwritten page memory (or a slot outside the window), even by zero; the
                     // instruction is skipped when its first slot lies beyond the row or its last one below the window
-                    if (slot_live<WIN>(RPI * (first + t), nt, nlo - (RPI - 1))) {
+                    if (slot_live<WIN, SINK>(RPI * (first + t), nt, nlo - (RPI - 1), nk)) {
 #pragma unroll
                         for (int j = 0; j < NJ; ++j) {
                             fu_u32x4 raw = buf[bi][t][j];
                             if constexpr (RPI > 1) {   // (per lane group: a slot beyond the row reads as zeros)
-                                const bool ok = slot_live<WIN>(RPI * (first + t) + lane_grp, nt, nlo);
+                                const bool ok = slot_live<WIN, SINK>(RPI * (first + t) + lane_grp, nt, nlo, nk);
                                 raw.x = ok ? raw.x : 0u; raw.y = ok ? raw.y : 0u; raw.z = ok ? raw.z : 0u; raw.w = ok ? raw.w : 0u;
                             }
                             ElemMath<E>::axpy(raw, p, acc[j]);

@@ -1,7 +1,8 @@
 // The launch plan of the chunked paged scans -- the single-head scan (attention_fused.hip), the multi-head scan
-// (attention_heads.hip) and their sliding-window forms (attention_window.hip): every rule that decides how such a scan is
-// launched, once.  Plain C++ over int / size_t / bool, no HIP types and no global state (tests/cpp/scan_plan_test.cpp
-// compiles it alone); the mli_tune values the rules depend on come in as a ScanTune.
+// (attention_heads.hip), their sliding-window forms (attention_window.hip) and those with sinks (attention_sinks.hip):
+// every rule that decides how such a scan is launched, once.  Plain C++ over int / size_t / bool, no HIP types and no
+// global state (tests/cpp/scan_plan_test.cpp compiles it alone); the mli_tune values the rules depend on come in as a
+// ScanTune.
 #pragma once
 
 #include <cstddef>
@@ -46,6 +47,23 @@ inline int window_span(int S, int window) {
     return span < S ? (int)span : S;
 }
 
+// ... and with n_sink sink tokens in front (1 <= n_sink, n_sink + window < S): the sink pages, the window's pages and the
+// part of the window's first page below it -- the longest virtual row (scan_item_body.hpp, SINK).
+inline int sink_span(int S, int window, int n_sink) {
+    const long long span = (long long)kPlanPage * (plan_ceil_div(n_sink, kPlanPage) + plan_ceil_div(window, kPlanPage) + 1);
+    return span < S ? (int)span : S;
+}
+
+// Which scan a lean call with (window, n_sink) is -- the hand-offs of the entry points, once: no window (<= 0, or >=
+// n_sequence) is the plain scan whatever n_sink; no sinks is the windowed scan; sinks and window that together cover
+// n_sequence leave no row a gap and are the plain scan again.
+enum ScanKind { kScanPlain, kScanWindow, kScanSinks };
+inline ScanKind lean_scan_kind(int S, int window, int n_sink) {
+    if (window <= 0 || window >= S) return kScanPlain;
+    if (n_sink <= 0) return kScanWindow;
+    return (long long)n_sink + window >= S ? kScanPlain : kScanSinks;
+}
+
 // Tokens per item over rows of `span` tokens (n_sequence, or the span a window leaves).
 //   Short sequences with a full batch: one workgroup per row (no partials, no combine launch) beats two 64-token chunks
 //   (README workload, S = 128: 200 vs 209 us).
@@ -87,7 +105,7 @@ struct ScanPlan {
     bool nt;             // non-temporal K/V loads
 };
 
-// S = n_sequence; span = S, or window_span(S, window); esize = bytes per page element
+// S = n_sequence; span = S, window_span(S, window) or sink_span(S, window, n_sink); esize = bytes per page element
 inline ScanPlan plan_chunked_scan(const ScanTune& t, int B, int S, int span, int D, int H, int esize) {
     ScanPlan p;
     p.ct = scan_item_tokens(t, B, span, H);

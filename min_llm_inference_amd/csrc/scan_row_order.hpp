@@ -14,8 +14,10 @@ namespace mli {
 // prologue per workgroup, no pre-pass, deterministic.  All kFuThreads threads call it; n_batch <= kMaxOrderedRows.
 // WIN = true (attention_window.hip): the rows are ranked by the pages their window leaves live, ceil(L / 16) - lo / 16 with
 // lo = max(0, L - window); S / 16 may then exceed kMaxOrderedPages as long as the window's span does not.
-template <bool WIN = false>
-__device__ __forceinline__ int longest_first_row(const int* __restrict__ lengths, int n_batch, int S, int rank, int window = 0) {
+// SINK = true (attention_sinks.hip; with WIN): ... by the pages of the virtual row, ceil(L / 16) - max(0, lo / 16 - ceil(n_sink / 16)).
+template <bool WIN = false, bool SINK = false>
+__device__ __forceinline__ int longest_first_row(const int* __restrict__ lengths, int n_batch, int S, int rank, int window = 0,
+                                                 int n_sink = 0) {
     __shared__ int hist[kMaxOrderedPages + 1];
     __shared__ int wave_cnt[kFuWaves];
     __shared__ int found_row;
@@ -31,7 +33,12 @@ __device__ __forceinline__ int longest_first_row(const int* __restrict__ lengths
         pages[j] = -1;
         if (j < per && row < n_batch) {
             const int len = min(max(lengths[row], 0), S);
-            pages[j] = (len + kPage - 1) / kPage - (WIN ? max(0, len - window) / kPage : 0);
+            // (the old expression stays verbatim in the else branch: with the pages below the window as a named value the
+            // windowed kernels' instruction order changes)
+            if constexpr (SINK)
+                pages[j] = (len + kPage - 1) / kPage - max(0, max(0, len - window) / kPage - (n_sink + kPage - 1) / kPage);
+            else
+                pages[j] = (len + kPage - 1) / kPage - (WIN ? max(0, len - window) / kPage : 0);
             atomicAdd(&hist[pages[j]], 1);
         }
     }

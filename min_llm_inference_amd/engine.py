@@ -38,7 +38,7 @@ def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
 
 class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
-                 n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None):
+                 n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -50,6 +50,8 @@ class Engine:
             self.set_heads(n_heads)
         if window is not None:
             self.set_window(window)
+        if sinks is not None:
+            self.set_sinks(sinks)
 
     def _check(self, rc):
         if rc != 0:
@@ -63,6 +65,11 @@ class Engine:
         """Sliding-window attention (mli_engine_set_window): every row attends its newest `window` tokens.  Before the
         first step or run, paged kinds; window >= n_sequence changes nothing."""
         self._check(self._lib.mli_engine_set_window(self._h, int(window)))
+
+    def set_sinks(self, n_sink):
+        """Attention sinks (mli_engine_set_sinks): beside the window every row keeps its first `n_sink` tokens attended.
+        Before the first step or run, paged kinds; without a window below n_sequence it changes nothing."""
+        self._check(self._lib.mli_engine_set_sinks(self._h, int(n_sink)))
 
     def use_private_stream(self):
         self._check(self._lib.mli_engine_use_private_stream(self._h))

@@ -51,6 +51,8 @@ public:
     void set_n_heads(int n_heads) { n_heads_ = n_heads; }
     // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
     void set_window(int window) { window_ = window; }
+    // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
+    void set_sinks(int n_sink) { n_sink_ = n_sink; }
 
 private:
     TensorBf16 wk_, wq_, wv_;
@@ -58,6 +60,7 @@ private:
     TensorFloat qkt_output_;
     int n_heads_ = 1;
     int window_ = 0;
+    int n_sink_ = 0;
 };
 
 class PagedAttentionBf16InferenceModel : public NonCopyableNonClonable {
@@ -71,6 +74,7 @@ public:
     void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }
     void set_n_heads(int n_heads) { attention_layer_.set_n_heads(n_heads); }
     void set_window(int window) { attention_layer_.set_window(window); }
+    void set_sinks(int n_sink) { attention_layer_.set_sinks(n_sink); }
 
 private:
     PagedAttentionBf16Layer attention_layer_;

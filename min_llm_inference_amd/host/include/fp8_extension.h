@@ -26,12 +26,15 @@ public:
                  int n_new_items);
     // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
     void set_window(int window) { window_ = window; }
+    // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
+    void set_sinks(int n_sink) { n_sink_ = n_sink; }
 
 private:
     TensorBf16 wk_, wq_, wv_;
     TensorFloat q_output_;
     size_t n_sequence_;
     int window_ = 0;
+    int n_sink_ = 0;
 };
 
 class PagedAttentionFp8InferenceModel : public NonCopyableNonClonable {
@@ -45,6 +48,7 @@ public:
     // logits buffer the sampled head needs
     void set_sampling(const SlotSampling* sampling);
     void set_window(int window) { attention_layer_.set_window(window); }
+    void set_sinks(int n_sink) { attention_layer_.set_sinks(n_sink); }
 
 private:
     PagedAttentionFp8Layer attention_layer_;

@@ -38,6 +38,7 @@ public:
     void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
     void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
     void set_window(int window) { paged_attention_layer_.set_window(window); }                        // EXTENSION
+    void set_sinks(int n_sink) { paged_attention_layer_.set_sinks(n_sink); }                          // EXTENSION
 
 private:
     PagedAttentionLayer paged_attention_layer_;
@@ -60,6 +61,7 @@ public:
     void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
     void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
     void set_window(int window) { paged_attention_layer_.set_window(window); }                        // EXTENSION
+    void set_sinks(int n_sink) { paged_attention_layer_.set_sinks(n_sink); }                          // EXTENSION
 
 private:
     PagedAttentionCublasLayer paged_attention_layer_;

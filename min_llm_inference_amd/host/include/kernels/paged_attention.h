@@ -51,12 +51,20 @@ void paged_attention_lean_window(TensorFloatPoint& page_table, const TensorInt& 
                                  TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
                                  int n_heads, int window);
 
-// What the three functions above share, and what the fp32 layers call: n_heads heads, window <= 0 or >= n_sequence = none;
-// qkt_output (may be null) serves one head without a window as in paged_attention_lean.
+// EXTENSION: paged_attention_lean_window with attention sinks: row b attends its first n_sink tokens as well as its newest
+// `window` (slots s < L with s < n_sink or s >= max(0, L - window)).  n_sink == 0 is paged_attention_lean_window; n_sink +
+// window >= n_sequence is the un-windowed call.  Throws on an unsupported shape.
+void paged_attention_lean_sinks(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                                const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                                TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
+                                int n_heads, int window, int n_sink);
+
+// What the four functions above share, and what the fp32 layers call: n_heads heads, window <= 0 or >= n_sequence = none,
+// n_sink sinks beside a window; qkt_output (may be null) serves one head without a window as in paged_attention_lean.
 void paged_attention_lean_layer(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
                                 const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
                                 TensorFloat& q_output, TensorFloat* qkt_output, TensorFloat& attention_result,
-                                int n_new_items, int n_sequence, int n_heads, int window);
+                                int n_new_items, int n_sequence, int n_heads, int window, int n_sink);
 
 // EXTENSION: launch_paged_attention_encoder_kernel + launch_fill_new_k_v_cache_paged_attention in one
 // launch -- the embedding lookup is the fill GEMM's prologue; pages bit-identical to the two-launch form.

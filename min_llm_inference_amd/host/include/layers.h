@@ -42,6 +42,8 @@ public:
     void set_n_heads(int n_heads) { n_heads_ = n_heads; }
     // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
     void set_window(int window) { window_ = window; }
+    // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
+    void set_sinks(int n_sink) { n_sink_ = n_sink; }
 
 private:
     TensorFloat wk_, wq_, wv_;
@@ -49,6 +51,7 @@ private:
     TensorFloat qkt_output_;
     int n_heads_ = 1;
     int window_ = 0;
+    int n_sink_ = 0;
 };
 
 class PagedAttentionCublasLayer : public NonCopyableNonClonable {
@@ -65,6 +68,8 @@ public:
     void set_n_heads(int n_heads) { n_heads_ = n_heads; }
     // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
     void set_window(int window) { window_ = window; }
+    // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
+    void set_sinks(int n_sink) { n_sink_ = n_sink; }
 
 private:
     TensorFloat wk_, wq_, wv_;
@@ -72,6 +77,7 @@ private:
     TensorFloat qkt_output_;
     int n_heads_ = 1;
     int window_ = 0;
+    int n_sink_ = 0;
     TensorFloat latest_emb_;        // kept for signature parity with the reference; unused by the MFMA path
     TensorFloat temp_placeholder_;
 };

@@ -41,13 +41,15 @@ bool lean_layers();
 // The one lean dispatch of the paged attention layers (fp32, bf16 and fp8 pages: elem = MLI_ELEM_*).
 // lean_paged_wanted: does the layer run the lean composition?  Multi-head and sliding-window attention (0 < window <
 // n_sequence) exist there only: with lean layers off they throw.
-// lean_paged_attention: sizes the scratch and calls the one entry point that serves (n_heads, window) -- window <= 0 or >=
-// n_sequence: none.  One head without a window returns the entry point's status (MLI_ERR_BAD_ARG where the rows are too
-// wide for the single-pass kernel: the caller may take its materialising composition); every other form throws on failure.
+// lean_paged_attention: sizes the scratch and calls the one entry point that serves (n_heads, window, n_sink), chosen by
+// lean_scan_kind (scan_plan.hpp) -- window <= 0 or >= n_sequence: none; n_sink counts beside a window only (attention
+// sinks: the first n_sink tokens stay attended).  One head without a window returns the entry point's status
+// (MLI_ERR_BAD_ARG where the rows are too wide for the single-pass kernel: the caller may take its materialising
+// composition); every other form throws on failure.
 bool lean_paged_wanted(int n_heads, int window, int n_sequence);
-int lean_paged_attention(int elem, int n_heads, int window, void* const* page_table, const int* lengths, const void* wk,
-                         const void* wq, const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
-                         int n_batch, int n_sequence, int emb_dim, int n_new_items);
+int lean_paged_attention(int elem, int n_heads, int window, int n_sink, void* const* page_table, const int* lengths,
+                         const void* wk, const void* wq, const void* wv, const int* new_batch_idx, float* q_output,
+                         float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_new_items);
 
 // Which loop start_paged_attention_*_inference_engine runs (default false): the pipelined loop
 // (pipelined_engine.h: the host one step behind the GPU, same tokens per item) wherever it applies -- up to

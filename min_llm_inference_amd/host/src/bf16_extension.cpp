@@ -77,7 +77,7 @@ void PagedAttentionBf16Layer::forward(TensorFloatPoint& page_table, const Tensor
     const int n_sequence = static_cast<int>(qkt_output_.shape()[1]);
     if (mli::runtime::lean_paged_wanted(n_heads_, window_, n_sequence)) {
         const int D = (int)wk_.shape()[0];
-        const int rc = mli::runtime::lean_paged_attention(MLI_ELEM_BF16, n_heads_, window_,
+        const int rc = mli::runtime::lean_paged_attention(MLI_ELEM_BF16, n_heads_, window_, n_sink_,
                                                           reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
                                                           wk_.data(), wq_.data(), wv_.data(), new_batch_idx.data(),
                                                           q_output_.data(), attention_result.data(),

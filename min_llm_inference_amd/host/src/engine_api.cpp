@@ -77,6 +77,7 @@ struct mli_engine {
     bool step_graphs = g_default_step_graphs.load();
     int n_heads = 1;            // mli_engine_set_heads
     int window = 0;             // mli_engine_set_window (0: none)
+    int n_sink = 0;             // mli_engine_set_sinks (0: none; counts beside a window only)
 
     // EXTENSION: sampled decoding (mli_engine_add_item_sampled).  The parameters live here, keyed by item
     // id, so a preempted item keeps its stream; the decoder head reads them from per-slot device arrays, filled when an
@@ -449,6 +450,29 @@ int mli_engine_set_window(mli_engine* e, int window) {
             if (e->bf16_model) e->bf16_model->set_window(then);
             if (e->fp8_model) e->fp8_model->set_window(then);
             e->window = then;
+        }
+    })
+}
+
+// Sinks ride on the window: the shapes are the windowed scan's (validated by set_window / set_heads, with or without sinks),
+// and without an effective window the layers ignore the value.
+int mli_engine_set_sinks(mli_engine* e, int n_sink) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (n_sink < 0) throw std::runtime_error("mli_engine_set_sinks: n_sink must be >= 0");
+        const int kind = e->cfg.kind;
+        if (kind != MLI_ENGINE_PAGED && kind != MLI_ENGINE_PAGED_GEMM && kind != MLI_ENGINE_PAGED_BF16 &&
+            kind != MLI_ENGINE_PAGED_FP8)
+            throw std::runtime_error("mli_engine_set_sinks: attention sinks serve the paged engines");
+        if (n_sink != e->n_sink) {
+            if (e->started) throw std::runtime_error("mli_engine_set_sinks after the engine has started");
+            if (!e->lean_layers)
+                throw std::runtime_error("mli_engine_set_sinks: attention sinks have the lean compositions only");
+            if (e->paged_model) e->paged_model->set_sinks(n_sink);
+            if (e->gemm_model) e->gemm_model->set_sinks(n_sink);
+            if (e->bf16_model) e->bf16_model->set_sinks(n_sink);
+            if (e->fp8_model) e->fp8_model->set_sinks(n_sink);
+            e->n_sink = n_sink;
         }
     })
 }

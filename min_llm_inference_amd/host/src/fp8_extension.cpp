@@ -15,8 +15,8 @@ PagedAttentionFp8Layer::PagedAttentionFp8Layer(TensorBf16&& wk, TensorBf16&& wq,
 void PagedAttentionFp8Layer::forward(TensorFloatPoint& page_table, const TensorInt& lengths,
                                      const TensorInt& new_batch_idx, TensorFloat& attention_result, int n_new_items) {
     const int B = (int)page_table.shape()[0], D = (int)wk_.shape()[0], S = (int)n_sequence_;
-    // fp8 pages have the lean composition only: one head, with or without a window
-    HIP_CHECK(mli::runtime::lean_paged_attention(MLI_ELEM_FP8, /*n_heads=*/1, window_,
+    // fp8 pages have the lean composition only: one head, with or without a window and sinks
+    HIP_CHECK(mli::runtime::lean_paged_attention(MLI_ELEM_FP8, /*n_heads=*/1, window_, n_sink_,
                                                  reinterpret_cast<void* const*>(page_table.data()), lengths.data(), wk_.data(),
                                                  wq_.data(), wv_.data(), new_batch_idx.data(), q_output_.data(),
                                                  attention_result.data(), B, S, D, n_new_items));

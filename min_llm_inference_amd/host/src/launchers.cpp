@@ -15,6 +15,7 @@
 #include "kernels/self_attention_inference_optimized.h"
 #include "mli_kernels.h"
 #include "runtime.h"
+#include "scan_plan.hpp"   // lean_scan_kind
 #include "step_graph.h"
 #include "utils.h"
 
@@ -275,11 +276,18 @@ bool mli::runtime::lean_paged_wanted(int n_heads, int window, int n_sequence) {
     return lean;
 }
 
-int mli::runtime::lean_paged_attention(int elem, int n_heads, int window, void* const* page_table, const int* lengths,
-                                       const void* wk, const void* wq, const void* wv, const int* new_batch_idx,
-                                       float* q_output, float* attention_result, int B, int S, int D, int n_new_items) {
+int mli::runtime::lean_paged_attention(int elem, int n_heads, int window, int n_sink, void* const* page_table,
+                                       const int* lengths, const void* wk, const void* wq, const void* wv,
+                                       const int* new_batch_idx, float* q_output, float* attention_result, int B, int S, int D,
+                                       int n_new_items) {
     const Scratch ws = attention_scratch(B, S, D, n_heads > 1 ? n_heads : 1);
-    if (window > 0 && window < S) {
+    const mli::ScanKind kind = mli::lean_scan_kind(S, window, n_sink);
+    if (kind == mli::kScanSinks) {
+        HIP_CHECK(mli_paged_attention_lean_sinks(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B,
+                                                 S, D, n_new_items, n_heads, window, n_sink, elem, ws.ptr, ws.bytes, stream()));
+        return 0;
+    }
+    if (kind == mli::kScanWindow) {
         HIP_CHECK(mli_paged_attention_lean_window(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B,
                                                   S, D, n_new_items, n_heads, window, elem, ws.ptr, ws.bytes, stream()));
         return 0;
@@ -293,15 +301,15 @@ int mli::runtime::lean_paged_attention(int elem, int n_heads, int window, void* 
                                     n_new_items, elem, ws.ptr, ws.bytes, stream());
 }
 
-// EXTENSION: the composition without the scores, with n_heads heads and a sliding window (kernels/paged_attention.h).  One
+// EXTENSION: the composition without the scores, with n_heads heads, a sliding window and sinks (kernels/paged_attention.h).  One
 // head without a window, rows too wide for the single-pass kernel: the materialising composition into the caller's
 // qkt_output scratch (if given) instead.  Every other unsupported shape throws.
 void paged_attention_lean_layer(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
                                 const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
                                 TensorFloat& q_output, TensorFloat* qkt_output, TensorFloat& attention_result,
-                                int n_new_items, int n_sequence, int n_heads, int window) {
+                                int n_new_items, int n_sequence, int n_heads, int window, int n_sink) {
     const int B = (int)page_table.shape()[0], D = (int)wk.shape()[0];
-    const int rc = mli::runtime::lean_paged_attention(MLI_ELEM_F32, n_heads, window, reinterpret_cast<void* const*>(pages(page_table)),
+    const int rc = mli::runtime::lean_paged_attention(MLI_ELEM_F32, n_heads, window, n_sink, reinterpret_cast<void* const*>(pages(page_table)),
                                                       lengths.data(), wk.data(), wq.data(), wv.data(), new_batch_idx.data(),
                                                       q_output.data(), attention_result.data(), B, n_sequence, D, n_new_items);
     if (rc == MLI_ERR_BAD_ARG && qkt_output != nullptr && D > 2048 && D % 4 == 0) {
@@ -317,7 +325,7 @@ void paged_attention_lean(TensorFloatPoint& page_table, const TensorInt& lengths
                           TensorFloat& q_output, TensorFloat& qkt_output, TensorFloat& attention_result,
                           int n_new_items, int n_sequence) {
     paged_attention_lean_layer(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, &qkt_output, attention_result,
-                               n_new_items, n_sequence, 1, 0);
+                               n_new_items, n_sequence, 1, 0, 0);
 }
 
 void paged_attention_lean_heads(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
@@ -326,7 +334,7 @@ void paged_attention_lean_heads(TensorFloatPoint& page_table, const TensorInt& l
                                 int n_heads) {
     if (n_heads < 1) HIP_CHECK(MLI_ERR_BAD_ARG);   // as mli_paged_attention_lean_heads
     paged_attention_lean_layer(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, nullptr, attention_result,
-                               n_new_items, n_sequence, n_heads, 0);
+                               n_new_items, n_sequence, n_heads, 0, 0);
 }
 
 void paged_attention_lean_window(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
@@ -335,7 +343,16 @@ void paged_attention_lean_window(TensorFloatPoint& page_table, const TensorInt& 
                                  int n_heads, int window) {
     if (window < 1 || n_heads < 1) HIP_CHECK(MLI_ERR_BAD_ARG);   // as mli_paged_attention_lean_window; the layers' "no window" is 0
     paged_attention_lean_layer(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, nullptr, attention_result,
-                               n_new_items, n_sequence, n_heads, window);
+                               n_new_items, n_sequence, n_heads, window, 0);
+}
+
+void paged_attention_lean_sinks(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                                const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                                TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
+                                int n_heads, int window, int n_sink) {
+    if (n_sink < 0 || window < 1 || n_heads < 1) HIP_CHECK(MLI_ERR_BAD_ARG);   // as mli_paged_attention_lean_sinks
+    paged_attention_lean_layer(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, nullptr, attention_result,
+                               n_new_items, n_sequence, n_heads, window, n_sink);
 }
 
 void paged_attention_with_cublas(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,

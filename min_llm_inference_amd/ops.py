@@ -300,13 +300,27 @@ def decode_scan_paged_window(q_output, page_table, lengths, attention_result, n_
                (n_heads, window), n_heads, elem, q_output.device)
 
 
+def decode_scan_paged_sinks(q_output, page_table, lengths, attention_result, n_heads, window, sinks, elem, n_sequence):
+    """The sliding-window scan with attention sinks (mli_decode_scan_paged_sinks): row b attends its first `sinks` slots and
+    slots [max(0, L - window), L); lean form, n_heads heads.  sinks = 0 is decode_scan_paged_window; sinks + window >=
+    n_sequence is decode_scan_paged(phases=7) / decode_scan_paged_heads."""
+    B, D = q_output.shape
+    _lean_call("mli_decode_scan_paged_sinks", (q_output, page_table, lengths, attention_result), B, n_sequence, D,
+               (n_heads, window, sinks), n_heads, elem, q_output.device)
+
+
 def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_new_items,
-                         n_sequence, elem=None, n_heads=1, window=None):
+                         n_sequence, elem=None, n_heads=1, window=None, sinks=None):
     """What the attention layers run: the paged composition without materialising scores / probabilities
     (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads != 1: the
     multi-head form (mli_paged_attention_lean_heads); window given: the sliding-window form
-    (mli_paged_attention_lean_window)."""
-    if window is not None:
+    (mli_paged_attention_lean_window); sinks given as well: the first `sinks` tokens of every row stay attended
+    (mli_paged_attention_lean_sinks)."""
+    if sinks is not None:
+        if window is None:
+            raise ValueError("sinks exist beside a window: pass window= as well")
+        name, extra = "mli_paged_attention_lean_sinks", (n_new_items, n_heads, window, sinks)
+    elif window is not None:
         name, extra = "mli_paged_attention_lean_window", (n_new_items, n_heads, window)
     elif n_heads != 1:
         name, extra = "mli_paged_attention_lean_heads", (n_new_items, n_heads)

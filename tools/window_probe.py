@@ -1,5 +1,5 @@
-"""What a sliding window costs and gains the lean paged scan (mli_decode_scan_paged_window), on the same pages, in the same
-process.
+"""What a sliding window costs and gains the lean paged scan (mli_decode_scan_paged_window), and what attention sinks
+(mli_decode_scan_paged_sinks) cost beside it, on the same pages, in the same process.
 
   config-4 shape  bf16, B = 1024, S = 4096, D = 512, lengths U[S/4, 3S/4]
   config-3 shape  fp32, B = 256, S = 1024, D = 256 (W = 1024 is "no window" there: the un-windowed kernels)
@@ -8,11 +8,14 @@ process.
     H{H}_base_W{W}   the un-windowed lean chunked scan (H = 1: scan_stream 0; H = 8: the multi-head scan) with the lengths
                      replaced by min(L, W): the same bytes to within 15 tokens a row, no window logic.  time / this = the PRICE
     H{H}_full        the un-windowed scan on the true lengths, as a caller gets it by default.  time / this = the GAIN
+    H{H}_W{W}_K4     the windowed scan with 4 sinks on the true lengths: one more page a row (the sink page), the two-run page
+                     mapping and the second mask.  time / H{H}_W{W} = what the sinks cost (where K + W >= S, config-3 shape
+                     at W = 1024, both are the un-windowed kernels)
   engine          PAGED_BF16, B = 1024, S = 4096, D = 512, 2048 items, window 1024 against none, tokens/s
 
-TB/s is on the bytes the window leaves, sum of 2 min(L, W) D e.  HIP events on the launch stream; after a warm-up, five
-regions of >= 20 launches per variant, the variants interleaved region by region; median / min / max of the regions'
-per-launch time.
+TB/s is on the bytes the window leaves, sum of 2 min(L, W) D e (with sinks: 2 min(L, W + K) D e).  HIP events on the launch
+stream; after a warm-up, five regions of >= 20 launches per variant, the variants interleaved region by region; median /
+min / max of the regions' per-launch time.
 
   python tools/window_probe.py [--out profiles/window_probe.json] [--no-engine] [--regions 5] [--launches 20]
 Under rocprofv3 --kernel-trace --stats use --no-engine --regions 1."""
@@ -31,6 +34,7 @@ from min_llm_inference_amd import engine as eng, load_library, ops  # noqa: E402
 
 WINDOWS = (256, 1024)
 HEADS = (1, 8)
+SINKS = 4
 
 
 def region(fn, launches, stream):
@@ -51,6 +55,7 @@ def scan_table(lib, name, dtype, args, dev, side):
     cut = {W: torch.clamp(wl.lengths, max=W) for W in WINDOWS}
     kv_bytes = {W: int(2 * np.minimum(wl.lengths_host, W).astype(np.int64).sum() * wl.D * wl.esize) for W in WINDOWS}
     kv_full = int(2 * wl.lengths_host.astype(np.int64).sum() * wl.D * wl.esize)
+    kv_sinks = {W: int(2 * np.minimum(wl.lengths_host, W + SINKS).astype(np.int64).sum() * wl.D * wl.esize) for W in WINDOWS}
 
     def plain(lengths, H):
         if H == 1:
@@ -62,6 +67,10 @@ def scan_table(lib, name, dtype, args, dev, side):
         return lambda: ops.decode_scan_paged_window(wl.q_output, wl.page_table, wl.lengths, wl.attention_result, H, W, wl.elem,
                                                     wl.S)
 
+    def with_sinks(H, W):
+        return lambda: ops.decode_scan_paged_sinks(wl.q_output, wl.page_table, wl.lengths, wl.attention_result, H, W, SINKS,
+                                                   wl.elem, wl.S)
+
     # name -> (scan_stream setting, set once before the variant's launches and never inside a timed region; launch; bytes)
     variants = {}
     for H in HEADS:
@@ -69,6 +78,7 @@ def scan_table(lib, name, dtype, args, dev, side):
         for W in WINDOWS:
             variants[f"H{H}_W{W}"] = (1, windowed(H, W), kv_bytes[W])
             variants[f"H{H}_base_W{W}"] = (0, plain(cut[W], H), kv_bytes[W])
+            variants[f"H{H}_W{W}_K{SINKS}"] = (1, with_sinks(H, W), kv_sinks[W])
     ops.workspace_for(wl.B, wl.S, wl.D, dev, max(HEADS))   # grown once, before anything is timed
     times = {k: [] for k in variants}
     try:
@@ -85,12 +95,15 @@ def scan_table(lib, name, dtype, args, dev, side):
         lib.mli_tune(b"scan_stream", 1)
     med = {k: float(np.median(t)) for k, t in times.items()}
     out = {"shape": {"dtype": dtype, "B": wl.B, "S": wl.S, "D": wl.D}, "kv_MB_full": round(kv_full / 1e6, 1),
-           "kv_MB_in_window": {str(W): round(kv_bytes[W] / 1e6, 1) for W in WINDOWS}, "regions": args.regions,
-           "launches_per_region": args.launches, "variants": {}}
+           "kv_MB_in_window": {str(W): round(kv_bytes[W] / 1e6, 1) for W in WINDOWS},
+           "kv_MB_in_window_and_sinks": {str(W): round(kv_sinks[W] / 1e6, 1) for W in WINDOWS}, "n_sink": SINKS,
+           "regions": args.regions, "launches_per_region": args.launches, "variants": {}}
     for k, t in times.items():
         row = {"us_median": round(med[k], 1), "us_min": round(min(t), 1), "us_max": round(max(t), 1),
                "TBps": round(variants[k][2] / med[k] / 1e6, 3)}
-        if "_W" in k and "_base_" not in k:
+        if k.endswith(f"_K{SINKS}"):
+            row["time_vs_window"] = round(med[k] / med[k[:-len(f"_K{SINKS}")]], 3)
+        elif "_W" in k and "_base_" not in k:
             H, W = k.split("_W")
             row["price_time_vs_base"] = round(med[k] / med[f"{H}_base_W{W}"], 3)
             row["gain_time_vs_full"] = round(med[k] / med[f"{H}_full"], 3)
