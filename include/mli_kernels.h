@@ -477,6 +477,12 @@ int mli_f32_to_fp8(const float* src, uint8_t* dst, size_t n, void* stream);
  *   "nt_loads"         non-temporal hint on the K/V stream: 2 (default) = where the rows' K/V (n_batch * n_sequence *
  *                      emb_dim * 2 elements) exceeds 768 MiB, i.e. nothing of it survives in the 256 MiB Infinity Cache
  *                      until the next step; 1 = always, 0 = never (plain loads)
+ *   "scan_resident_mib"  (equal page shares, where the K/V stream is non-temporal) MiB of the launch's K/V, 0 .. 240 (default
+ *                      192), that are loaded with the default policy instead: a slice of the pages chosen by address, the
+ *                      same in every step, which the non-temporal loads of the rest leave in the Infinity Cache, so a
+ *                      decode step finds it on die.  0 = every load non-temporal.  Identical results for every value.
+ *                      (Rows wider than 64 16-byte lane loads keep their loads non-temporal and touch the lines of a
+ *                      kept page with default-policy loads first.)
  *   "scan_stream"      (lean mode) 1 (default) = batches that fill the chip (n_batch * n_sequence >= 2^21, n_batch <= 2048,
  *                      n_sequence >= 256) are scanned in EQUAL PAGE SHARES: the pages of all rows form one sequence
  *                      that 2 x CUs workgroups split evenly, each streaming its share across row boundaries and merging
@@ -519,6 +525,13 @@ int mli_f32_to_fp8(const float* src, uint8_t* dst, size_t n, void* stream);
  *                      to fp32 + fp32 MFMA (bit-identical to a sequential fp32 sum; differs from 1 only by the
  *                      rounding order of the fp32 accumulation) */
 int mli_tune(const char* key, int value);
+
+/* The resident slice of "scan_resident_mib", restated for tests and tools.  mli_scan_resident_threshold: the threshold
+ * (0 .. 65536) of a launch whose rows hold total_pages pages in all (elem: MLI_ELEM_*; MLI_ERR_BAD_ARG for another tag, a
+ * negative page count or emb_dim <= 0).  mli_scan_resident_keeps: 1 if that launch loads the page at page_ptr with the
+ * default policy, 0 if non-temporal; a function of the address and the threshold only, monotone in the threshold. */
+int mli_scan_resident_threshold(long long total_pages, int emb_dim, int elem, int resident_mib);
+int mli_scan_resident_keeps(const void* page_ptr, int thr);
 
 /* float4 device copy (kept for tools; a copy is not a ceiling for a read stream). */
 int mli_stream_copy(const float* src, float* dst, size_t n_floats, void* stream);

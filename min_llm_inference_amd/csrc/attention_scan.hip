@@ -28,6 +28,7 @@ void set_scan_stream(int v);
 void set_scan_stream_min(int v);
 void set_stream_dyn_pct(int v);
 void set_stream_granule(int v);
+void set_scan_resident_mib(int v);
 void set_gemm_split(int v);
 void set_bf16_split(int v);
 void set_prefill_fused(int v);
@@ -711,6 +712,8 @@ int mli_tune(const char* key, int value) {
         mli::set_stream_dyn_pct(value);
     } else if (k == "scan_stream_granule") {
         mli::set_stream_granule(value);
+    } else if (k == "scan_resident_mib") {
+        mli::set_scan_resident_mib(value);
     } else if (k == "scan_stream_min_tokens") {
         mli::set_scan_stream_min(value);
     } else if (k == "scan_merge") {

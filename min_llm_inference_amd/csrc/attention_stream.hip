@@ -53,7 +53,7 @@ template <class E, int NJ, bool NT, int TBR, int MAXSEG, int RPI = 1>
 __global__ __launch_bounds__(kStThreads, 2) void fused_decode_stream_kernel(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ out, float2* ml, float* partial, unsigned* arrivals, unsigned* ticket, int B, int S, int D,
-    int ml_per_row, int max_pages_wg, int dyn_pct, int gran) {
+    int ml_per_row, int max_pages_wg, int dyn_pct, int gran, int resident_mib) {
     constexpr int EPL = E::EPL;
     constexpr int LPR = kWave / RPI;         // lanes per token row
     static_assert(RPI == 1 || NJ == 1, "several rows per instruction only for rows of one lane load");
@@ -175,6 +175,21 @@ __global__ __launch_bounds__(kStThreads, 2) void fused_decode_stream_kernel(
     auto page_ptr = [&](int pi) {
         return reinterpret_cast<const char*>(wave_uniform(reinterpret_cast<const float*>(ptr_sh[pi])));
     };
+    // Non-temporal stream with a resident slice (scan_plan.hpp): the pages whose address hashes under res_thr -- resident_mib
+    // MiB of this launch's P pages -- are loaded with the default policy and stay in the Infinity Cache until the next step,
+    // which reads the same pages; the non-temporal loads of all the others pass them by.  The flag is wave-uniform like the
+    // pointer it is computed from, the policy an immediate of the load: a scalar branch around the same loads into the same
+    // registers.  It is recomputed at every batch (four scalar instructions) rather than carried beside `page` and `next`:
+    // the kernel has no SGPRs to spare.  Only the variants with one lane load per row (NJ = 1) have the branch: with two,
+    // hipcc spills 100 .. 340 VGPRs around it (fp32, emb_dim 512, config 4: 1924 us against 1278); those keep every
+    // 16-byte load non-temporal and touch a kept page's lines once per page instead (touch_page below).  hipcc lays the two arms out as two conditional
+    // blocks in a row and, seeing a path through neither, waits with vmcnt(0) before a batch where it counted before;
+    // measured, that costs nothing (bf16, config 4, nothing kept: 638 us against 644): 8 waves per CU with one batch
+    // each in flight are still more than HBM needs.
+    constexpr bool RES = NT && NJ == 1;
+    constexpr bool TOUCH = NT && NJ == 2;
+    unsigned res_thr = 0;
+    if constexpr (NT) res_thr = resident_threshold(P, (long long)2 * kPage * D * E::kBytes, resident_mib);
     auto issue = [&](auto POS, const char* pg) {
         constexpr int pos = decltype(POS)::value;
         constexpr int bi = pos % 4;
@@ -182,11 +197,43 @@ __global__ __launch_bounds__(kStThreads, 2) void fused_decode_stream_kernel(
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(upg), 0, upg != nullptr ? block_bytes : 0, 0x00020000);
         const int base = (pos < NB ? (int)seg_bytes : 2 * (int)seg_bytes) + (pos % NB) * TBR * RPI * (int)row_bytes;
+        auto load = [&](auto STREAM) {   // the cache policy is an immediate: 2 = non-temporal, 0 = default
 #pragma unroll
-        for (int t = 0; t < TBR; ++t)
+            for (int t = 0; t < TBR; ++t)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j)
-                buf[bi][t][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[j], base + t * RPI * (int)row_bytes, NT ? 2 : 0);
+                for (int j = 0; j < NJ; ++j)
+                    buf[bi][t][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[j], base + t * RPI * (int)row_bytes,
+                                                                          decltype(STREAM)::value ? 2 : 0);
+        };
+        if constexpr (RES) {
+            if (resident_keeps((unsigned long long)reinterpret_cast<uintptr_t>(upg), res_thr)) load(std::false_type{});
+            else load(std::true_type{});
+        } else {
+            load(std::integral_constant<bool, NT>{});
+        }
+    };
+
+    // NJ = 2: once per kept page, before its first batch is issued, one default-policy dword load per 128-byte line of its
+    // K and V (adjacent in a token slot: at most 32 lines, so two slots per instruction, eight instructions; a lane beyond
+    // the row points outside the descriptor's range and fetches nothing).  The miss allocates the line in the Infinity
+    // Cache, and the non-temporal loads that follow are served by it.  The results are combined and handed to an empty
+    // asm so that the loads stay: the wave waits for them here, once per kept page.  This sits outside the batches on
+    // purpose: any conditional block inside `issue` makes hipcc spill 60 .. 190 VGPRs in these variants.
+    auto touch_page = [&](const char* pg) {
+        if constexpr (TOUCH) {
+            if (pg != nullptr && resident_keeps((unsigned long long)reinterpret_cast<uintptr_t>(pg), res_thr)) {
+                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pg), 0, block_bytes, 0x00020000);
+                const unsigned line = (unsigned)(lane & 31) * 128u;
+                const unsigned off = line < 2u * (unsigned)seg_bytes
+                                         ? (unsigned)(lane >> 5) * (unsigned)row_bytes + (unsigned)seg_bytes + line
+                                         : 0x40000000u;
+                unsigned seen = 0;
+#pragma unroll
+                for (int r = 0; r < kPage / 2; ++r)
+                    seen |= __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, r * 2 * (int)row_bytes, 0);
+                asm volatile("" ::"v"(seen));
+            }
+        }
     };
 
     typedef unsigned long long __attribute__((address_space(1)))* gu64_ptr;
@@ -240,6 +287,7 @@ __global__ __launch_bounds__(kStThreads, 2) void fused_decode_stream_kernel(
         const int p_first = pg_lo + wave;
         const char* page = p_first < pg_hi ? page_ptr(p_first) : nullptr;
         if (p_first < pg_hi) {
+            touch_page(page);
             issue(std::integral_constant<int, 0>{}, page);
             issue(std::integral_constant<int, 1>{}, page);
             issue(std::integral_constant<int, 2>{}, page);
@@ -247,6 +295,7 @@ __global__ __launch_bounds__(kStThreads, 2) void fused_decode_stream_kernel(
         for (int pi = p_first; pi < pg_hi; pi += kStWaves) {
             const bool has_next = pi + kStWaves < pg_hi;
             const char* next = has_next ? page_ptr(pi + kStWaves) : nullptr;
+            touch_page(next);
             if (pi >= cur_end) {   // the wave enters another row (wave-uniform): park its state, take the new row's q
                 flush();
                 int b = cur < 0 ? r0 : cur + 1;
@@ -488,6 +537,10 @@ static thread_local int g_stream_dyn_pct = 4;
 static thread_local int g_stream_granule = 64;
 void set_stream_dyn_pct(int v) { g_stream_dyn_pct = v < 0 ? 0 : (v > 60 ? 60 : v); }
 void set_stream_granule(int v) { g_stream_granule = v < 16 ? 16 : (v > 256 ? 256 : v); }
+// mli_tune "scan_resident_mib": MiB of the non-temporal K/V stream that are loaded with the default policy instead and so
+// stay in the 256 MiB Infinity Cache from step to step (scan_plan.hpp: resident_threshold / resident_keeps); 0 = none.
+static thread_local int g_scan_resident_mib = 192;
+void set_scan_resident_mib(int v) { g_scan_resident_mib = v < 0 ? 0 : (v > 240 ? 240 : v); }
 static thread_local int g_scan_stream_min = 1 << 21;   // mli_tune "scan_stream_min_tokens": n_batch * n_sequence from which it is used
 void set_scan_stream_min(int v) { g_scan_stream_min = v < 0 ? 0 : v; }
 
@@ -556,7 +609,7 @@ int launch_stream_decode(const float* q, const void* const* page_table, const in
         }                                                                                                                \
         hipLaunchKernelGGL(kern, dim3(G), dim3(kStThreads), smem, st, q, page_table, lengths, out, ml, partial, arrivals, \
                            arrivals + (kMaxArrivalRows - 1), B, S, D, ml_per_row, max_pages_wg, g_stream_dyn_pct,     \
-                           g_stream_granule);                                                                            \
+                           g_stream_granule, g_scan_resident_mib);                                                       \
     } while (0)
     if constexpr (std::is_same<E, ElemFP8>::value) {
         if (rpi == 4) {
@@ -592,6 +645,20 @@ template int launch_stream_decode<ElemBF16>(const float*, const void* const*, co
 template int launch_stream_decode<ElemFP8>(const float*, const void* const*, const int*, float*, int, int, int, void*, size_t, hipStream_t);
 
 }  // namespace mli
+
+extern "C" {
+
+int mli_scan_resident_threshold(long long total_pages, int emb_dim, int elem, int resident_mib) {
+    if (total_pages < 0 || emb_dim <= 0 || (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16 && elem != MLI_ELEM_FP8)) return MLI_ERR_BAD_ARG;
+    const long long esize = elem == MLI_ELEM_FP8 ? 1 : elem == MLI_ELEM_BF16 ? 2 : 4;
+    return (int)mli::resident_threshold(total_pages, 2LL * mli::kPage * emb_dim * esize, resident_mib);
+}
+
+int mli_scan_resident_keeps(const void* page_ptr, int thr) {
+    return thr > 0 && mli::resident_keeps((unsigned long long)reinterpret_cast<uintptr_t>(page_ptr), (unsigned)thr) ? 1 : 0;
+}
+
+}  // extern "C"
 
 #ifdef MLI_SCAN_TRACE
 extern "C" int mli_debug_stream_trace(unsigned long long* host, int n_slots) {

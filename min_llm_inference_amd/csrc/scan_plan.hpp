@@ -40,6 +40,27 @@ inline bool nt_loads_rule(int setting, int B, int S, int D, int esize) {
     return (long long)B * S * D * esize * 2 > ((long long)768 << 20);
 }
 
+// The resident slice of the equal-shares scan (attention_stream.hip, mli_tune "scan_resident_mib").  Where the K/V stream is
+// non-temporal, a fixed slice of the pages, sized to fit the Infinity Cache, is loaded with the default policy instead and
+// stays on die from one decode step to the next (tools/membench.hip `resident`: non-temporal loads leave such lines alone).
+// Both functions are constexpr so that the kernel and a host program (tests/cpp/scan_resident_test.cpp) compile this text.
+//   resident_threshold: the share of the launch's K/V bytes that resident_mib MiB are, as a value in 0 .. 65536.
+//   page_kv_bytes = 2 * 16 * D * e (the x segment of a page is not read by the scan); 64-bit throughout (2048 rows x 256
+//   pages x 64 KiB = 2^35 bytes at the largest shape the kernel takes).
+constexpr unsigned resident_threshold(long long total_pages, long long page_kv_bytes, int resident_mib) {
+    if (resident_mib <= 0) return 0u;
+    if (total_pages <= 0 || page_kv_bytes <= 0) return 65536u;
+    const unsigned long long t = (((unsigned long long)resident_mib << 20) * 65536ull) /
+                                 ((unsigned long long)total_pages * (unsigned long long)page_kv_bytes);
+    return t > 65536ull ? 65536u : (unsigned)t;
+}
+//   resident_keeps: whether a page belongs to the slice.  A multiplicative hash of the page's address (4-KiB granularity)
+//   against the threshold: the same page gets the same answer in every step, whatever the partition, the row's length or
+//   the batch's composition, and as the threshold falls (the batch grows) pages only leave the slice.
+constexpr bool resident_keeps(unsigned long long page_ptr, unsigned thr) {
+    return (((unsigned)(page_ptr >> 12) * 2654435761u) >> 16) < thr;
+}
+
 // The tokens a windowed row can span: its window plus the part of the first live page below it, whole pages
 // (1 <= window < S: the entry points hand everything else on).
 inline int window_span(int S, int window) {

@@ -3,6 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <ctime>
+#include <string>
+#include <unistd.h>
 #include <vector>
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
@@ -96,6 +100,67 @@ __global__ __launch_bounds__(256) void read_blocks_kv_order(const float4* __rest
         }
     }
     if (acc == 12345.678f) sink[0] = acc;
+}
+
+// read_blocks_kv_order with a MIXED cache policy -- the question behind `membench resident`: can a fixed slice of a
+// working set far larger than the 256 MiB Infinity Cache be kept on die from pass to pass while the rest streams by?
+// A block whose address hashes under `thr` (of 65536) is read with default-policy loads, every other block with nt;
+// the choice depends on the block's address only, so the same blocks are kept in every pass.  `salt` != 0 picks another
+// slice of the same size.  The loads are the scan's (16 bytes per lane through a buffer descriptor, cache policy as the
+// immediate), the branch between the two arms is wave-uniform.
+// TOUCH > 0 is the branch-free form: EVERY 16-byte load is nt, and in front of each batch of a kept block goes one
+// default-policy dword load per TOUCH bytes of the batch (TOUCH = 128: one instruction for the 64 lines of a batch, 64: two);
+// for a block that is not kept the same instruction points outside the descriptor's range and fetches nothing.  The
+// question there: does the default-policy miss allocate the line on die although the nt load of the same line follows
+// at once, and does one dword per line do?
+__device__ __forceinline__ bool block_kept(const void* p, unsigned thr, unsigned salt) {
+    return ((((unsigned)((unsigned long long)p >> 12) ^ salt) * 2654435761u) >> 16) < thr;
+}
+template <int TOUCH>
+__global__ __launch_bounds__(256) void read_blocks_kv_mixed(const float4* __restrict__ src, float* __restrict__ sink,
+                                                             const int* __restrict__ perm, int nblocks, long stride_f4,
+                                                             unsigned thr, unsigned salt) {
+    typedef unsigned u4v __attribute__((ext_vector_type(4)));
+    const int lane = threadIdx.x & 63;
+    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
+    const int block_bytes = (int)(16 * stride_f4 * 16);
+    unsigned acc = 0;
+    for (long bi = wave; bi < nblocks; bi += nwaves) {
+        const int blk = __builtin_amdgcn_readfirstlane(perm[bi]);
+        const char* pg = reinterpret_cast<const char*>(src) + (long)blk * block_bytes;
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pg), 0, block_bytes, 0x00020000);
+        const bool keep = block_kept(pg, thr, salt);   // wave-uniform
+#pragma unroll
+        for (int phase = 0; phase < 4; ++phase) {
+            const int seg = phase < 2 ? 1 : 2;           // K, K, V, V
+            const int r0 = (phase & 1) * 8;
+            u4v v[8];
+            if constexpr (TOUCH > 0) {
+                constexpr int per_row = 1024 / TOUCH;   // touches per 1-KiB row segment
+#pragma unroll
+                for (int k = 0; k < 8 * per_row / 64; ++k) {
+                    const int i = lane + 64 * k;        // touch i of the batch: row i / per_row, chunk i % per_row
+                    const unsigned off = (unsigned)(((r0 + i / per_row) * stride_f4 + seg * 64) * 16 + (i % per_row) * TOUCH);
+                    acc ^= __builtin_amdgcn_raw_buffer_load_b32(rsrc, keep ? off : 0x40000000u, 0, 0);
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (unsigned)lane * 16u, (int)(((r0 + u) * stride_f4 + seg * 64) * 16), 2);
+            } else if (keep) {
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (unsigned)lane * 16u, (int)(((r0 + u) * stride_f4 + seg * 64) * 16), 0);
+            } else {
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (unsigned)lane * 16u, (int)(((r0 + u) * stride_f4 + seg * 64) * 16), 2);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc += v[u].x ^ v[u].y ^ v[u].z ^ v[u].w;
+        }
+    }
+    if (acc == 0x12345678u) sink[0] = (float)acc;
 }
 
 // the decode scan's WORKGROUP structure around the same loads: an item = 32 blocks for the 4 waves of a workgroup
@@ -223,9 +288,96 @@ float time_ms(F f, int reps) {
 // the decode scan kernel) without touching the kernels
 static unsigned g_lds = 0;
 
-int main() {
+// `membench resident [out.json]`: the mixed-policy probe alone.  4.2 GB of K|V in shuffled 48-KiB blocks (bf16, D = 512:
+// 32 KiB read of every block), 20 passes per timing, R MiB of it under the default policy.  Forms per R:
+//   reuse   every pass reads the same buffer: the kept slice can be served from the Infinity Cache
+//   control passes alternate between two such buffers: the same policy mix, but a kept block comes round only after the
+//           other buffer's pass (two slices, 2 R MiB, compete for the cache)
+//   fresh   the same buffer, another slice of the same size every pass (salted hash): a pass finds the PREVIOUS pass's slice
+//           on die and reads nearly all of it with nt loads -- what it gains, nt loads gain from lines they did not allocate
+//   touch128 / touch64, reuse and control: the same two forms for the branch-free kernel (TOUCH above)
+static int resident_probe(const char* out_path) {
+    const long stride_f4 = 192;                              // a token slot: x | K | V, 3 KiB
+    const long block_f4 = 16 * stride_f4;                    // 48 KiB
+    const int nblocks = (int)(4.2e9 / (16 * 2048));          // 32 KiB of K|V per block
+    const double bytes = (double)nblocks * 16 * 2048;
+    const int grid = 8192, passes = 20, rounds = 3;
+    float4* buf[2]; float* sink; int* dperm[2];
+    CK(hipMalloc(&sink, 4));
+    for (int b = 0; b < 2; ++b) {
+        CK(hipMalloc(&buf[b], (size_t)nblocks * block_f4 * 16));
+        CK(hipMemset(buf[b], 1 + b, (size_t)nblocks * block_f4 * 16));
+        std::vector<int> shuf(nblocks);
+        for (int i = 0; i < nblocks; ++i) shuf[i] = i;
+        unsigned long long seed = 88172645463325252ULL + 977ULL * b;
+        for (int i = nblocks - 1; i > 0; --i) {
+            seed ^= seed << 13; seed ^= seed >> 7; seed ^= seed << 17;
+            int j = (int)(seed % (unsigned long long)(i + 1));
+            int t = shuf[i]; shuf[i] = shuf[j]; shuf[j] = t;
+        }
+        CK(hipMalloc(&dperm[b], sizeof(int) * nblocks));
+        CK(hipMemcpy(dperm[b], shuf.data(), sizeof(int) * nblocks, hipMemcpyHostToDevice));   // (every index < nblocks)
+    }
+    const int Rs[] = {0, 64, 128, 160, 192, 224};
+    const int nR = 6;
+    const char* forms[] = {"reuse", "control", "fresh", "touch128_reuse", "touch128_control", "touch64_reuse", "touch64_control"};
+    const int nforms = 7;
+    double tbps[7][6][3];
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    for (int round = 0; round < rounds; ++round)
+        for (int k = 0; k < nR; ++k) {
+            const int ri = (round & 1) ? nR - 1 - k : k;     // alternating order
+            const unsigned long long rb = (unsigned long long)Rs[ri] << 20;
+            unsigned long long t = rb * 65536ULL / (unsigned long long)bytes;
+            const unsigned thr = (unsigned)(t > 65536ULL ? 65536ULL : t);
+            for (int form = 0; form < nforms; ++form) {
+                auto pass = [&](int i) {
+                    const int b = form == 1 || form == 4 || form == 6 ? (i & 1) : 0;
+                    const unsigned salt = form == 2 ? 0x9E3779B9u * (unsigned)(i + 1) : 0u;
+                    auto kern = form < 3 ? read_blocks_kv_mixed<0> : form < 5 ? read_blocks_kv_mixed<128> : read_blocks_kv_mixed<64>;
+                    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), g_lds, 0, buf[b], sink, dperm[b], nblocks, stride_f4, thr, salt);
+                };
+                pass(0); pass(1);                            // warm: both buffers' slices have been read once
+                CK(hipDeviceSynchronize());
+                CK(hipEventRecord(e0));
+                for (int i = 0; i < passes; ++i) pass(i + 2);
+                CK(hipEventRecord(e1));
+                CK(hipEventSynchronize(e1));
+                float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                tbps[form][ri][round] = bytes / (ms / passes) / 1e9;
+            }
+        }
+    std::string js = "{\n \"what\": \"membench resident: mixed cache policy over 4.2 GB of shuffled 48-KiB blocks\",\n";
+    char line[512], host[128] = "?", date[32];
+    gethostname(host, sizeof host - 1);
+    time_t now = time(nullptr);
+    strftime(date, sizeof date, "%Y-%m-%d", gmtime(&now));
+    snprintf(line, sizeof line, " \"box\": \"%s\",\n \"date\": \"%s\",\n \"kv_MB\": %.1f,\n \"blocks\": %d,\n \"passes_per_timing\": %d,\n \"grid\": %d,\n \"lds_bytes\": %u,\n \"TBps_per_round\": {\n",
+             host, date, bytes / 1e6, nblocks, passes, grid, g_lds);
+    js += line;
+    for (int form = 0; form < nforms; ++form) {
+        snprintf(line, sizeof line, "  \"%s\": {\n", forms[form]); js += line;
+        for (int ri = 0; ri < nR; ++ri) {
+            const double* v = tbps[form][ri];
+            printf("resident %-16s R %3d MiB: %.3f %.3f %.3f TB/s\n", forms[form], Rs[ri], v[0], v[1], v[2]);
+            snprintf(line, sizeof line, "   \"%d\": [%.3f, %.3f, %.3f]%s\n", Rs[ri], v[0], v[1], v[2], ri + 1 < nR ? "," : ""); js += line;
+        }
+        js += form + 1 < nforms ? "  },\n" : "  }\n";
+    }
+    js += " }\n}\n";
+    if (out_path) {
+        FILE* f = fopen(out_path, "w");
+        if (!f) { printf("cannot write %s\n", out_path); return 1; }
+        fputs(js.c_str(), f); fclose(f);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
     if (const char* e = getenv("MEMBENCH_LDS")) g_lds = (unsigned)atoi(e);
     std::printf("dynamic LDS per workgroup: %u bytes\n", g_lds);
+    if (argc > 1 && strcmp(argv[1], "resident") == 0) return resident_probe(argc > 2 ? argv[2] : nullptr);
     const long n4 = 1L << 28;  // 4 GiB source
     float4 *src, *dst; float* sink;
     CK(hipMalloc(&src, n4 * 16)); CK(hipMalloc(&dst, n4 * 16)); CK(hipMalloc(&sink, 4));
