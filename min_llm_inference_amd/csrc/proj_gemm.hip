@@ -404,6 +404,7 @@ int latest_compact(int n_batch, int k_dim) {
 
 // mli_tune "prefill_fused": which form mli_[paged_]prefill runs: 1 (default) = the encoder as the fill GEMM's prologue up to
 // emb_dim 512 and encoder + fill as two launches beyond, 0 = always the two launches, 2 = always the prologue form
+// (mli_prefill: an input_dim that is no multiple of 4 has the prologue form only, under every setting)
 static thread_local int g_prefill_fused = 1;
 void set_prefill_fused(int v) { g_prefill_fused = v < 0 ? 0 : (v > 2 ? 2 : v); }
 bool prefill_fuses(int emb_dim) { return g_prefill_fused == 2 || (g_prefill_fused == 1 && emb_dim <= 512); }
@@ -656,7 +657,9 @@ int mli_prefill(const float* emb_table, const float* wpe, const int* inp, float*
                 const int* new_item_indices, const float* wk, const float* wv, float* kt_cache, float* v_cache,
                 int n_batch, int n_sequence, int input_dim, int output_dim, int n_new_items, void* stream) {
     if (emb_table == nullptr || wpe == nullptr || inp == nullptr) return MLI_ERR_BAD_ARG;
-    if (!mli::prefill_fuses(input_dim)) {   // wide models: encoder + fill as two launches (see mli_paged_prefill)
+    // wide models: encoder + fill as two launches (see mli_paged_prefill).  The encoder kernel moves float4, so a width
+    // that is no multiple of 4 has the prologue form only (its scalar-load instantiation), whatever "prefill_fused" says
+    if (!mli::prefill_fuses(input_dim) && input_dim % 4 == 0) {
         int rc = mli_inference_optimized_encoder(emb_table, wpe, inp, inp_embedding, lengths, new_item_indices, n_batch,
                                                  n_sequence, input_dim, n_new_items, stream);
         if (rc) return rc;
