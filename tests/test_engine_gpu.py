@@ -8,6 +8,7 @@ the same tokens per item, and the same tokens as the CPU engine built from the o
 import numpy as np
 import pytest
 
+import replay_model as rm
 from engine_sim import make_items, make_model, run_cpu_engine
 
 pytestmark = pytest.mark.gpu
@@ -97,7 +98,9 @@ def test_bf16_engine_matches_cpu_engine_on_bf16_rounded_state(oracle, mli, dev):
     embeddings, K and V rounded to bfloat16 where the GPU stores them.  With the operands widened to the exact fp32
     MFMA (bf16_native_mfma = 0) K/V bits equal the CPU's, so tokens must agree item for item; the native bf16 MFMA
     accumulates in a different order, a K/V element can round the other way and a near-tie argmax can flip, so there
-    the bar is: every item finishes with its prompt intact and at least 90 % of the items are token-identical."""
+    the bar is: every item finishes with its prompt intact and at least 90 % of the items are token-identical.  Both runs
+    are also audited token by token against the float64 replay (tests/replay_model.py): an item that leaves the CPU engine's
+    path must do so on a near-tie, and every later token is judged along the engine's own path."""
     from min_llm_inference_amd import engine as eng
     B, S, D, V = 16, 128, 64, 1024
     model = make_model(49, V, S, D)
@@ -105,9 +108,10 @@ def test_bf16_engine_matches_cpu_engine_on_bf16_rounded_state(oracle, mli, dev):
     cpu, _ = run_cpu_engine(oracle, model, items, B, S, bf16=True)
     try:
         assert mli.mli_tune(b"bf16_native_mfma", 0) == 0
-        _, exact = _run(eng.PAGED_BF16, model, items, B, S, n_blocks=4 * B)   # tight pool: preemption happens
+        st_exact, exact = _run(eng.PAGED_BF16, model, items, B, S, n_blocks=4 * B)   # tight pool: preemption happens
     finally:
         mli.mli_tune(b"bf16_native_mfma", 1)
+    rm.audit(model, items, exact, rm.Spec("bf16"), S, total_tokens=st_exact.total_tokens, what="bf16 engine, exact MFMA").assert_ok()
     for item_id, _ in items:
         assert len(exact[item_id]) == len(cpu[item_id]) and (exact[item_id] == cpu[item_id]).all(), item_id
     st, native = _run(eng.PAGED_BF16, model, items, B, S, n_blocks=8 * B, rounds=2)
@@ -117,6 +121,9 @@ def test_bf16_engine_matches_cpu_engine_on_bf16_rounded_state(oracle, mli, dev):
         assert (native[item_id][:len(toks)] == toks).all()
         same += len(native[item_id]) == len(cpu[item_id]) and bool((native[item_id] == cpu[item_id]).all())
     assert same >= 0.9 * len(items), same
+    native_spec = rm.Spec("bf16", flips=True)
+    rm.audit(model, items, native, native_spec, S, total_tokens=st.total_tokens, what="bf16 engine, native MFMA").assert_ok()
+    rm.first_divergences(model, items, native, cpu, native_spec, what="bf16 engine, native MFMA")
 
 
 def test_two_engines_on_private_streams_overlap_safely(oracle, mli, dev):

@@ -1,0 +1,243 @@
+"""Every token the engines emit, audited against a float64 replay (tests/replay_model.py, DESIGN 6 "Engine replay audit").
+
+Each engine run is judged token by token: a greedy token may fall short of the float64 model's maximum logit by at most the
+item's tolerance, a drawn token must be the reference's draw wherever the draw is well-posed, and the bookkeeping (prompt,
+end of stream, token range, every item exactly once, total_tokens) must be exact.  The workloads are drawn freely -- no seed
+search; a near-tie costs one token a deficit of a few 1e-5 and the audit carries on along the engine's own path.
+
+  base shape   n_batch 16, n_sequence 128, emb_dim 64, n_vocab 1024, 40 items with prompts of 1 .. 60 tokens; all five kinds;
+               the paged ones on the sequential loop, the pipelined loop with 4 pages per slot (growth and preemption),
+               n_forward_rounds 3 and step graphs on a private stream; PAGED_BF16 with bf16_native_mfma 0 and 1; PAGED and
+               PAGED_GEMM also on the reference's launch sequence (lean_layers 0).  The contiguous engine has the sequential
+               loop alone (no rounds, no pipelined loop, no step graphs).
+  big shape    n_batch 8, n_sequence 256, emb_dim 128, 24 items with prompts of 3 .. 100 tokens, window 40 (three to four
+               pages, no multiple of 16), 4 sinks, 1 and 4 heads; full pool, half the worst-case pool, 2 rounds, step graphs;
+               and window alone, heads alone, sinks without a window.
+  wide rows    n_batch 8, n_sequence 256, emb_dim 512 (split-sequence scratch), 16 items, pipelined loop, tight pool.
+  sampled      replay_model.sampled_workload: half the items greedy, half drawn (T 0.8 top_k 40; T 0.8 top_p 0.95), each
+               with its own seed; sequential, pipelined with preemption, 2 rounds.  Draws are audited on the bit-exact kinds
+               only (fp32 pages, bf16 with bf16_native_mfma 0); on the native bf16 MFMA and on fp8 pages a sampled item gets
+               the bookkeeping judge alone (a rounding flip moves a perturbed score by more than the draws' gaps).
+  shard group  one loopback group of 2 ranks on one device, every rank's finished items audited.
+  wrong engine reference_length_reset_quirk = True (rows attend their prompt only) must be REJECTED by 4 tolerances.
+
+Every test prints its figures; MLI_REPLAY_REPORT=<file> collects them as JSON."""
+import functools
+
+import pytest
+
+import replay_model as rm
+from engine_sim import make_items, make_model
+
+pytestmark = pytest.mark.gpu
+
+BASE = dict(B=16, S=128, D=64, V=1024)
+BIG = dict(B=8, S=256, D=128, V=1024)
+WIDE = dict(B=8, S=256, D=512, V=1024)
+W, K = 40, 4
+
+
+@functools.lru_cache(maxsize=None)
+def _workload(name):
+    if name == "base":
+        return make_model(9201, BASE["V"], BASE["S"], BASE["D"]), make_items(9202, 40, 1, 60)
+    if name == "big":
+        return make_model(9211, BIG["V"], BIG["S"], BIG["D"]), make_items(9212, 24, 3, 100)
+    return make_model(9221, WIDE["V"], WIDE["S"], WIDE["D"]), make_items(9222, 16, 1, 100)
+
+
+def _kind(variant):
+    """("PAGED_BF16 exact" -> PAGED_BF16 with bf16_native_mfma 0)"""
+    return variant.split()[0], not variant.endswith("exact")
+
+
+def _run(kind_name, model, items, shape, n_blocks, rounds=1, pipelined=False, graphs=False, lean=None, n_heads=1, window=None,
+         sinks=None, sampling=None, quirk=False):
+    from min_llm_inference_amd import engine as eng
+    kind = getattr(eng, kind_name)
+    e = eng.Engine(kind, shape["B"], shape["S"], shape["D"], shape["V"], model["emb_table"], model["pos_table"], model["wk"],
+                   model["wq"], model["wv"], n_blocks=0 if kind == eng.CONTIGUOUS else n_blocks, n_forward_rounds=rounds,
+                   reference_length_reset_quirk=quirk, n_heads=n_heads, window=window, sinks=sinks)
+    try:
+        if lean is not None:
+            e.configure(lean_layers=lean)
+        if graphs:
+            e.use_private_stream()
+            e.configure(step_graphs=True)
+        if kind != eng.CONTIGUOUS:
+            e.set_pipelined(bool(pipelined))
+        for item_id, toks in items:
+            if sampling and item_id in sampling:
+                T, top_k, top_p, seed = sampling[item_id]
+                e.add_item(item_id, toks, temperature=T, top_k=top_k, top_p=top_p, seed=seed)
+            else:
+                e.add_item(item_id, toks)
+        st = e.run()
+        return st, e.finished()
+    finally:
+        e.close()
+
+
+def _audited(what, variant, workload, shape, n_heads=1, window=None, sinks=None, sampling=None, **kw):
+    """Run one engine and audit it; returns the figures (asserted)."""
+    kind_name, native = _kind(variant)
+    model, items = workload
+    spec = rm.spec_of_kind(kind_name, n_heads, window, sinks if window is not None else 0, native=native)
+    st, finished = _run(kind_name, model, items, shape, n_heads=n_heads, window=window, sinks=sinks, sampling=sampling, **kw)
+    fig = rm.audit(model, items, finished, spec, shape["S"], total_tokens=st.total_tokens, sampling=sampling,
+                   what=f"{variant}, {what}")
+    assert st.finished == len(items) and st.waiting == 0 and st.in_flight == 0
+    fig.assert_ok()
+    assert fig.items == len(items)
+    return fig
+
+
+class _Native:
+    """bf16_native_mfma for the duration of a test, restored afterwards"""
+
+    def __init__(self, mli, variant):
+        self.mli, self.value = mli, int(_kind(variant)[1])
+
+    def __enter__(self):
+        assert self.mli.mli_tune(b"bf16_native_mfma", self.value) == 0
+
+    def __exit__(self, *exc):
+        self.mli.mli_tune(b"bf16_native_mfma", 1)
+
+
+PAGED_VARIANTS = ["PAGED", "PAGED_GEMM", "PAGED_BF16 exact", "PAGED_BF16", "PAGED_FP8"]
+
+
+def test_contiguous_engine(mli, dev):
+    _audited("sequential loop", "CONTIGUOUS", _workload("base"), BASE, n_blocks=0)
+
+
+@pytest.mark.parametrize("variant", PAGED_VARIANTS)
+def test_paged_engine_on_every_loop(mli, dev, variant):
+    B = BASE["B"]
+    wl = _workload("base")
+    with _Native(mli, variant):
+        _audited("sequential loop", variant, wl, BASE, n_blocks=8 * B)
+        _audited("pipelined loop, 4 pages per slot", variant, wl, BASE, n_blocks=4 * B, pipelined=True)
+        _audited("3 rounds", variant, wl, BASE, n_blocks=8 * B, rounds=3)
+        _audited("3 rounds, pipelined, 4 pages per slot", variant, wl, BASE, n_blocks=4 * B, rounds=3, pipelined=True)
+        _audited("step graphs", variant, wl, BASE, n_blocks=8 * B, graphs=True)
+        _audited("step graphs, pipelined, 4 pages per slot", variant, wl, BASE, n_blocks=4 * B, graphs=True, pipelined=True)
+
+
+@pytest.mark.parametrize("kind_name", ["PAGED", "PAGED_GEMM"])
+def test_paged_engine_on_the_reference_launch_sequence(mli, dev, kind_name):
+    B = BASE["B"]
+    wl = _workload("base")
+    _audited("lean_layers 0, sequential loop", kind_name, wl, BASE, n_blocks=8 * B, lean=0)
+    _audited("lean_layers 0, pipelined loop, 4 pages per slot", kind_name, wl, BASE, n_blocks=4 * B, lean=0, pipelined=True)
+    _audited("lean_layers 0, 3 rounds", kind_name, wl, BASE, n_blocks=4 * B, lean=0, rounds=3)
+
+
+BIG_CASES = [(v, h) for v in ("PAGED", "PAGED_GEMM", "PAGED_BF16 exact", "PAGED_BF16") for h in (1, 4)] + [("PAGED_FP8", 1)]
+
+
+@pytest.mark.parametrize("variant,n_heads", BIG_CASES)
+def test_heads_window_and_sinks_beyond_the_toy_size(mli, dev, variant, n_heads):
+    full = BIG["B"] * BIG["S"] // 16
+    wl = _workload("big")
+    kw = dict(n_heads=n_heads, window=W, sinks=K)
+    with _Native(mli, variant):
+        _audited(f"{n_heads} head(s), full pool", variant, wl, BIG, n_blocks=full, **kw)
+        _audited(f"{n_heads} head(s), half the pool, pipelined", variant, wl, BIG, n_blocks=full // 2, pipelined=True, **kw)
+        _audited(f"{n_heads} head(s), half the pool, sequential", variant, wl, BIG, n_blocks=full // 2, **kw)
+        _audited(f"{n_heads} head(s), 2 rounds", variant, wl, BIG, n_blocks=full, rounds=2, **kw)
+        _audited(f"{n_heads} head(s), step graphs", variant, wl, BIG, n_blocks=full, graphs=True, **kw)
+
+
+@pytest.mark.parametrize("variant,n_heads", BIG_CASES)
+def test_window_alone_heads_alone_and_sinks_without_a_window(mli, dev, variant, n_heads):
+    half = BIG["B"] * BIG["S"] // 32
+    wl = _workload("big")
+    with _Native(mli, variant):
+        _audited(f"{n_heads} head(s), window alone", variant, wl, BIG, n_blocks=half, pipelined=True, n_heads=n_heads, window=W)
+        _audited(f"{n_heads} head(s), no window (sinks change nothing)", variant, wl, BIG, n_blocks=half, pipelined=True,
+                 n_heads=n_heads, sinks=K)
+
+
+@pytest.mark.parametrize("variant", ["PAGED_GEMM", "PAGED_BF16 exact", "PAGED_BF16"])
+def test_wide_rows_with_a_tight_pool(mli, dev, variant):
+    with _Native(mli, variant):
+        _audited("emb_dim 512, pipelined, 6 pages per slot", variant, _workload("wide"), WIDE, n_blocks=6 * WIDE["B"] + 16,
+                 pipelined=True)
+
+
+SAMPLED_CASES = [("PAGED_GEMM", 1, None), ("PAGED_BF16 exact", 4, rm.SAMPLED_SHAPE["W"])]
+
+
+@pytest.mark.parametrize("which", sorted(rm.SAMPLED_PARAMS))
+@pytest.mark.parametrize("variant,n_heads,window", SAMPLED_CASES)
+def test_sampled_engine_draws_what_the_reference_draws(mli, dev, variant, n_heads, window, which):
+    """The engine owns the per-slot parameters, the position counter and the seed after a preemption: every well-posed draw
+    equals sampling_ref.sample_row at the item's seed and the row's length before the draw; the greedy half of the batch is
+    judged by its deficits.  (The masked-draw share of the reference alone: tests/test_replay_model_cpu.py.)"""
+    s = rm.SAMPLED_SHAPE
+    shape = dict(B=s["B"], S=s["S"], D=s["D"], V=s["V"])
+    model, items, sampling = rm.sampled_workload(which)
+    kw = dict(n_heads=n_heads, window=window, sampling=sampling)
+    full = shape["B"] * shape["S"] // 16
+    with _Native(mli, variant):
+        fig = _audited(f"sampled {which}, sequential", variant, (model, items), shape, n_blocks=full, **kw)
+        assert fig.draws > 0 and fig.draws < fig.tokens
+        _audited(f"sampled {which}, pipelined, 4 pages per slot", variant, (model, items), shape, n_blocks=4 * shape["B"],
+                 pipelined=True, **kw)
+        _audited(f"sampled {which}, 2 rounds", variant, (model, items), shape, n_blocks=full, rounds=2, **kw)
+        _audited(f"sampled {which}, 2 rounds, pipelined, 4 pages per slot", variant, (model, items), shape,
+                 n_blocks=4 * shape["B"], rounds=2, pipelined=True, **kw)
+
+
+@pytest.mark.parametrize("variant", ["PAGED_BF16", "PAGED_FP8"])
+def test_sampled_items_of_the_kinds_with_rounding_flips_get_the_bookkeeping_judge(mli, dev, variant):
+    s = rm.SAMPLED_SHAPE
+    shape = dict(B=s["B"], S=s["S"], D=s["D"], V=s["V"])
+    model, items, sampling = rm.sampled_workload("top-k")
+    fig = _audited("sampled top-k, pipelined, 4 pages per slot", variant, (model, items), shape, n_blocks=4 * shape["B"],
+                   pipelined=True, sampling=sampling)
+    assert fig.draws == 0 and fig.tokens > 0
+
+
+def test_loopback_shard_group_of_two_ranks(mli, dev):
+    from min_llm_inference_amd import engine as eng
+    model, items = _workload("base")
+    B = BASE["B"] // 2
+    g = eng.ShardGroup(eng.PAGED_GEMM, B, BASE["S"], BASE["D"], BASE["V"], model["emb_table"], model["pos_table"], model["wk"],
+                       model["wq"], model["wv"], devices=[0], n_blocks=4 * B, loopback_ranks=2)
+    try:
+        for item_id, toks in items:
+            g.add_item(item_id, toks)
+        st = g.run()
+        assert st.ranks_seen == 2 and st.finished == len(items)
+        total = 0
+        for r in range(2):
+            e = g.engine(r)
+            mine = [(i, t) for i, t in items if i % 2 == r]
+            fig = rm.audit(model, mine, e.finished(), rm.spec_of_kind("PAGED_GEMM"), BASE["S"],
+                           total_tokens=e.stats().total_tokens, what=f"loopback group, rank {r}")
+            fig.assert_ok()
+            assert fig.items == len(mine)
+            total += fig.tokens
+        assert st.total_tokens == total
+    finally:
+        g.close()
+
+
+def test_the_audit_rejects_the_engine_whose_rows_attend_their_prompt_only(mli, dev):
+    """reference_length_reset_quirk = True is a wrong engine the project ships: the device-side length is reset to the
+    prompt's, so rows attend over their prompt only while the host counts tokens correctly.  The audit must see it -- a token
+    that misses the model's maximum by at least 4 tol -- while its bookkeeping passes: the engine-level counterpart of
+    test_the_comparison_sees_a_scan_that_stops_one_token_early."""
+    model, items = _workload("base")
+    B = BASE["B"]
+    st, finished = _run("PAGED", model, items, BASE, n_blocks=4 * B, quirk=True)
+    fig = rm.audit(model, items, finished, rm.spec_of_kind("PAGED"), BASE["S"], total_tokens=st.total_tokens,
+                   what="PAGED, reference_length_reset_quirk")
+    print(f"REPLAY quirk engine: factor reached {fig.worst_ratio:.1f} ({len(fig.failures)} of {fig.tokens} tokens over tolerance)")
+    assert st.finished == len(items) and not fig.bookkeeping, fig.bookkeeping
+    assert fig.worst_ratio >= rm.MARGIN, fig.line()
+    with pytest.raises(AssertionError):
+        fig.assert_ok()

@@ -268,7 +268,10 @@ def test_fp8_engine_matches_cpu_engine_on_fp8_rounded_state(oracle, mli, dev):
     """MLI_ENGINE_PAGED_FP8 end to end (pipelined loop, tight pool: growth and preemption) against the CPU engine with
     bf16-rounded weights and fp8-rounded page contents.  A stored K / V element can land on the other side of a rounding
     boundary and a near-tie argmax can then flip, so the bar is the bf16 engine's: every item finishes with its prompt
-    intact and at least 85 % of the items are token-identical."""
+    intact and at least 85 % of the items are token-identical.  Every run is also audited token by token against the float64
+    replay (tests/replay_model.py), and the deficit at each diverging item's first divergence is printed: the flips are
+    near-ties."""
+    import replay_model as rm
     from engine_sim import make_items, make_model, run_cpu_engine
     from min_llm_inference_amd import engine as eng
     B, S, D, V = 16, 128, 64, 1024
@@ -292,6 +295,9 @@ def test_fp8_engine_matches_cpu_engine_on_fp8_rounded_state(oracle, mli, dev):
             assert len(got[item_id]) == S or got[item_id][-1] == 1023
             same += len(got[item_id]) == len(cpu[item_id]) and bool((got[item_id] == cpu[item_id]).all())
         assert same >= 0.85 * len(items), same
+        what = f"fp8 engine, {rounds} round(s), {'pipelined' if pipelined else 'sequential'}"
+        rm.audit(model, items, got, rm.Spec("fp8", flips=True), S, total_tokens=st.total_tokens, what=what).assert_ok()
+        rm.first_divergences(model, items, got, cpu, rm.Spec("fp8", flips=True), what=what)
         outs.append(got)
     # scheduling (rounds, pool size, loop order, preemption) never changes an item's tokens
     for item_id, _ in items:

@@ -18,6 +18,7 @@ import functools
 import numpy as np
 import pytest
 
+import replay_model as rm
 import sinks_model as sm
 import window_model as wm
 from engine_sim import make_items, make_model
@@ -54,8 +55,8 @@ def _engine(kind_name, **kw):
 
 
 def _run(kind_name, n_heads=1, window=W, sinks=K, n_blocks=WORST_CASE_BLOCKS, rounds=1, pipelined=False, graphs=False,
-         sampled=False, order=None):
-    _, items = _setup()
+         sampled=False, order=None, audit=False):
+    model, items = _setup()
     if order is None:
         e = _engine(kind_name, n_blocks=n_blocks, n_forward_rounds=rounds, n_heads=n_heads, window=window, sinks=sinks)
     else:           # the three setters in the order given
@@ -72,9 +73,15 @@ def _run(kind_name, n_heads=1, window=W, sinks=K, n_blocks=WORST_CASE_BLOCKS, ro
         else:
             e.add_item(item_id, toks)
     st = e.run()
-    out = dict(e.finished())
+    finished = e.finished()
+    out = dict(finished)
     e.close()
     assert st.finished == len(items)
+    if audit:
+        store = {"PAGED_BF16": "bf16", "PAGED_FP8": "fp8"}.get(kind_name, "f32")
+        spec = rm.Spec(store, n_heads, window, (sinks or 0) if window is not None else 0, flips=store == "fp8")
+        rm.audit(model, items, finished, spec, S, total_tokens=st.total_tokens,
+                 what=f"sinks engine {kind_name}, {rounds} round(s), {n_blocks} pages, pipelined {pipelined}").assert_ok()
     return out
 
 
@@ -102,20 +109,20 @@ def test_engine_with_sinks_decodes_what_the_cpu_engine_decodes(mli, dev, kind_na
         if bf16:     # K / V bits equal to the CPU's (tests/test_engine_gpu.py: the native bf16 MFMA sums in another order)
             assert mli.mli_tune(b"bf16_native_mfma", 0) == 0
         what = f"{kind_name}, {n_heads} head(s)"
-        base = _run(kind_name, n_heads)
+        base = _run(kind_name, n_heads, audit=True)
         _same(base, cpu, f"{what}: sequential loop against the CPU engine")
-        _same(_run(kind_name, n_heads, pipelined=True), base, f"{what}: pipelined loop")
-        _same(_run(kind_name, n_heads, rounds=2), base, f"{what}: n_forward_rounds 2 (sinks and window follow the device-side length)")
-        _same(_run(kind_name, n_heads, graphs=True), base, f"{what}: step graphs on a private stream")
-        _same(_run(kind_name, n_heads, n_blocks=WORST_CASE_BLOCKS // 2), base, f"{what}: half the pool (growth + preemption)")
+        _same(_run(kind_name, n_heads, pipelined=True, audit=True), base, f"{what}: pipelined loop")
+        _same(_run(kind_name, n_heads, rounds=2, audit=True), base, f"{what}: n_forward_rounds 2 (sinks and window follow the device-side length)")
+        _same(_run(kind_name, n_heads, graphs=True, audit=True), base, f"{what}: step graphs on a private stream")
+        _same(_run(kind_name, n_heads, n_blocks=WORST_CASE_BLOCKS // 2, audit=True), base, f"{what}: half the pool (growth + preemption)")
         for order in (("sinks", "window", "heads"), ("heads", "sinks", "window"), ("window", "heads", "sinks")):
-            _same(_run(kind_name, n_heads, order=order), base, f"{what}: set_* in the order {order}")
-        cut = _run(kind_name, n_heads, sinks=None)
+            _same(_run(kind_name, n_heads, order=order, audit=True), base, f"{what}: set_* in the order {order}")
+        cut = _run(kind_name, n_heads, sinks=None, audit=True)
         assert _differ(cut, base), "set_sinks is a no-op"
-        _same(_run(kind_name, n_heads, sinks=0), cut, f"{what}: n_sink = 0 is the window alone")
-        whole = _run(kind_name, n_heads, window=None, sinks=None)
-        _same(_run(kind_name, n_heads, window=None), whole, f"{what}: sinks without a window change nothing")
-        _same(_run(kind_name, n_heads, sinks=S - W), whole, f"{what}: n_sink + window = n_sequence is no window")
+        _same(_run(kind_name, n_heads, sinks=0, audit=True), cut, f"{what}: n_sink = 0 is the window alone")
+        whole = _run(kind_name, n_heads, window=None, sinks=None, audit=True)
+        _same(_run(kind_name, n_heads, window=None, audit=True), whole, f"{what}: sinks without a window change nothing")
+        _same(_run(kind_name, n_heads, sinks=S - W, audit=True), whole, f"{what}: n_sink + window = n_sequence is no window")
     finally:
         mli.mli_tune(b"bf16_native_mfma", 1)
 
@@ -123,7 +130,8 @@ def test_engine_with_sinks_decodes_what_the_cpu_engine_decodes(mli, dev, kind_na
 def test_fp8_engine_with_sinks(oracle, mli, dev):
     model, items = _setup()
     cpu, _ = sm.run_sinks_cpu_engine(oracle, model, items, B, S, 1, W, K, bf16="fp8")
-    outs = [_run("PAGED_FP8", pipelined=True, n_blocks=WORST_CASE_BLOCKS // 2), _run("PAGED_FP8", rounds=2)]
+    # audit=True: every item of these runs is judged token by token against the float64 replay (tests/replay_model.py)
+    outs = [_run("PAGED_FP8", pipelined=True, n_blocks=WORST_CASE_BLOCKS // 2, audit=True), _run("PAGED_FP8", rounds=2, audit=True)]
     for got in outs:
         same = 0
         for item_id, toks in items:
@@ -132,8 +140,9 @@ def test_fp8_engine_with_sinks(oracle, mli, dev):
             same += len(got[item_id]) == len(cpu[item_id]) and bool((got[item_id] == cpu[item_id]).all())
         print(f"SINKS fp8 engine: {same} of {len(items)} items token-identical to the CPU engine")
         assert same >= 0.85 * len(items), same
+        rm.first_divergences(model, items, got, cpu, rm.Spec("fp8", 1, W, K, flips=True), what="sinks fp8 engine")
     _same(outs[1], outs[0], "fp8: scheduling (rounds, pool size, loop, preemption) never changes an item's tokens")
-    assert _differ(_run("PAGED_FP8", sinks=None), outs[0]), "set_sinks is a no-op on the fp8 engine"
+    assert _differ(_run("PAGED_FP8", sinks=None, audit=True), outs[0]), "set_sinks is a no-op on the fp8 engine"
     _same(_run("PAGED_FP8", order=("sinks", "window")), outs[0], "fp8: set_sinks before set_window")
 
 

@@ -17,6 +17,7 @@ import functools
 import numpy as np
 import pytest
 
+import replay_model as rm
 import window_model as wm
 from engine_sim import make_items, make_model
 
@@ -43,7 +44,8 @@ def _cpu(n_heads, bf16):
     return tokens
 
 
-def _run(kind_name, n_heads=1, window=W, n_blocks=WORST_CASE_BLOCKS, rounds=1, pipelined=False, graphs=False, sampled=False):
+def _run(kind_name, n_heads=1, window=W, n_blocks=WORST_CASE_BLOCKS, rounds=1, pipelined=False, graphs=False, sampled=False,
+         audit=False):
     from min_llm_inference_amd import engine as eng
     model, items = _setup()
     e = eng.Engine(getattr(eng, kind_name), B, S, D, V, model["emb_table"], model["pos_table"], model["wk"], model["wq"],
@@ -58,9 +60,15 @@ def _run(kind_name, n_heads=1, window=W, n_blocks=WORST_CASE_BLOCKS, rounds=1, p
         else:
             e.add_item(item_id, toks)
     st = e.run()
-    out = dict(e.finished())
+    finished = e.finished()
+    out = dict(finished)
     e.close()
     assert st.finished == len(items)
+    if audit:
+        store = {"PAGED_BF16": "bf16", "PAGED_FP8": "fp8"}.get(kind_name, "f32")
+        spec = rm.Spec(store, n_heads, None if window in (None, S) else window, flips=store == "fp8")
+        rm.audit(model, items, finished, spec, S, total_tokens=st.total_tokens,
+                 what=f"window engine {kind_name}, {rounds} round(s), {n_blocks} pages, pipelined {pipelined}").assert_ok()
     return out
 
 
@@ -88,15 +96,15 @@ def test_engine_with_a_window_decodes_what_the_cpu_engine_decodes(mli, dev, kind
         if bf16:     # K / V bits equal to the CPU's (tests/test_engine_gpu.py: the native bf16 MFMA sums in another order)
             assert mli.mli_tune(b"bf16_native_mfma", 0) == 0
         what = f"{kind_name}, {n_heads} head(s)"
-        base = _run(kind_name, n_heads)
+        base = _run(kind_name, n_heads, audit=True)
         _same(base, cpu, f"{what}: sequential loop against the CPU engine")
-        _same(_run(kind_name, n_heads, pipelined=True), base, f"{what}: pipelined loop")
-        _same(_run(kind_name, n_heads, rounds=3), base, f"{what}: n_forward_rounds 3 (the window follows the device-side length)")
-        _same(_run(kind_name, n_heads, graphs=True), base, f"{what}: step graphs on a private stream")
-        _same(_run(kind_name, n_heads, n_blocks=WORST_CASE_BLOCKS // 2), base, f"{what}: half the pool (growth + preemption)")
-        whole = _run(kind_name, n_heads, window=None)
+        _same(_run(kind_name, n_heads, pipelined=True, audit=True), base, f"{what}: pipelined loop")
+        _same(_run(kind_name, n_heads, rounds=3, audit=True), base, f"{what}: n_forward_rounds 3 (the window follows the device-side length)")
+        _same(_run(kind_name, n_heads, graphs=True, audit=True), base, f"{what}: step graphs on a private stream")
+        _same(_run(kind_name, n_heads, n_blocks=WORST_CASE_BLOCKS // 2, audit=True), base, f"{what}: half the pool (growth + preemption)")
+        whole = _run(kind_name, n_heads, window=None, audit=True)
         assert _differ(whole, base), "set_window is a no-op"
-        _same(_run(kind_name, n_heads, window=S), whole, f"{what}: window = n_sequence is no window")
+        _same(_run(kind_name, n_heads, window=S, audit=True), whole, f"{what}: window = n_sequence is no window")
     finally:
         mli.mli_tune(b"bf16_native_mfma", 1)
 
@@ -105,7 +113,8 @@ def test_fp8_engine_with_a_window(oracle, mli, dev):
     from engine_sim import run_cpu_engine  # noqa: F401  (the fp8 mode of the CPU engine is CpuEngine's)
     model, items = _setup()
     cpu, _ = wm.run_window_cpu_engine(oracle, model, items, B, S, 1, W, bf16="fp8")
-    outs = [_run("PAGED_FP8", pipelined=True, n_blocks=WORST_CASE_BLOCKS // 2), _run("PAGED_FP8", rounds=2)]
+    # audit=True: every item of these runs is judged token by token against the float64 replay (tests/replay_model.py)
+    outs = [_run("PAGED_FP8", pipelined=True, n_blocks=WORST_CASE_BLOCKS // 2, audit=True), _run("PAGED_FP8", rounds=2, audit=True)]
     for got in outs:
         same = 0
         for item_id, toks in items:
@@ -114,8 +123,9 @@ def test_fp8_engine_with_a_window(oracle, mli, dev):
             same += len(got[item_id]) == len(cpu[item_id]) and bool((got[item_id] == cpu[item_id]).all())
         print(f"WINDOW fp8 engine: {same} of {len(items)} items token-identical to the CPU engine")
         assert same >= 0.85 * len(items), same
+        rm.first_divergences(model, items, got, cpu, rm.Spec("fp8", 1, W, flips=True), what="window fp8 engine")
     _same(outs[1], outs[0], "fp8: scheduling (rounds, pool size, loop, preemption) never changes an item's tokens")
-    assert _differ(_run("PAGED_FP8", window=None), outs[0]), "set_window is a no-op on the fp8 engine"
+    assert _differ(_run("PAGED_FP8", window=None, audit=True), outs[0]), "set_window is a no-op on the fp8 engine"
 
 
 def test_sampled_run_with_a_window_is_reproducible_and_loop_independent(mli, dev):
