@@ -132,7 +132,8 @@ int mli_engine_set_heads(mli_engine* engine, int n_heads);
 /* EXTENSION: sliding-window attention (mli_kernels.h: mli_paged_attention_lean_window).  Every row attends its newest
  * `window` tokens only.  The window changes which slots the scan reads and nothing else: admission, page growth,
  * preemption, re-prefill, n_forward_rounds (the window follows the device-side length), step graphs, sampling and the
- * pipelined loop work as without one, and no page is returned to the pool early.  Before the first step or run; kinds
+ * pipelined loop work as without one, and no page is returned to the pool early unless mli_engine_set_page_release.  Before
+ * the first step or run; kinds
  * MLI_ENGINE_PAGED, MLI_ENGINE_PAGED_GEMM, MLI_ENGINE_PAGED_BF16 and MLI_ENGINE_PAGED_FP8; combines with
  * mli_engine_set_heads in either order (each call validates the combination).  -1 with a message for another kind,
  * window < 1, a call after the engine has started, an engine configured with lean_layers = 0
@@ -143,12 +144,36 @@ int mli_engine_set_window(mli_engine* engine, int window);
 /* EXTENSION: attention sinks beside the window (mli_kernels.h: mli_paged_attention_lean_sinks).  Every row attends its
  * first n_sink tokens as well as its newest `window`.  Like the window, sinks change which slots the scan reads and
  * nothing else: admission, growth, preemption, re-prefill, n_forward_rounds, step graphs, sampling and the pipelined loop
- * work as without them, and no page is returned to the pool early.  Before the first step or run; the four paged kinds;
+ * work as without them, and no page is returned to the pool early unless mli_engine_set_page_release.  Before the first
+ * step or run; the four paged kinds;
  * combines with mli_engine_set_heads and mli_engine_set_window in any order (each call validates the combination).
  * Without an effective window (none set, or window >= n_sequence) it is accepted and changes nothing until one is set.
  * -1 with a message for MLI_ENGINE_CONTIGUOUS, n_sink < 0, a call after the engine has started, or an engine configured
  * with lean_layers = 0. */
 int mli_engine_set_sinks(mli_engine* engine, int n_sink);
+
+/* EXTENSION: early page release beside the window.  A row under a window of W tokens with K sinks never again reads the
+ * pages between its sink pages and its window's first page (index ceil(K / 16) <= i < max(0, n - W) / 16 at n tokens).
+ * With release on, those pages go back to the pool while the row decodes, a new or re-admitted item takes and prefills
+ * its live pages only (mli_kernels.h: mli_paged_prefill_window), and a row never holds more than
+ *   ceil(K / 16) + ceil((W + a) / 16) + 1 pages,   a = n_forward_rounds (sequential loop) or 2 n_forward_rounds (pipelined),
+ * whatever n_sequence: the same pool serves more rows with fewer preemptions, and a pool smaller than n_sequence / 16
+ * pages decodes a row to n_sequence.  Tokens are those of the engine without release.  Before the first step or run; the
+ * four paged kinds; combines with mli_engine_set_window, mli_engine_set_sinks and mli_engine_set_heads in any order (the
+ * switch is read at the first step or run).  Without an effective window (none set, window >= n_sequence, or n_sink +
+ * window >= n_sequence) it is accepted and changes nothing.  -1 with a message for MLI_ENGINE_CONTIGUOUS, a call after the
+ * engine has started, or an engine with reference_length_reset_quirk (the quirk moves device lengths backwards; release
+ * rests on lengths that only grow). */
+int mli_engine_set_page_release(mli_engine* engine, int enabled);
+
+/* EXTENSION: occupancy of the page pool, for every paged kind with or without release: pages the pool has, pages out of it
+ * now and at most so far, pages returned early by mli_engine_set_page_release, and rows pushed back to the queue because
+ * the pool ran dry.  -1 for MLI_ENGINE_CONTIGUOUS. */
+typedef struct {
+    int pool_pages, in_use, peak_in_use;
+    long long released_early, preemptions;
+} mli_engine_page_stats;
+int mli_engine_get_page_stats(mli_engine* engine, mli_engine_page_stats* stats);
 
 const char* mli_engine_last_error(void);
 

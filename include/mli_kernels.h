@@ -417,6 +417,19 @@ int mli_paged_prefill(const float* emb_table, const float* wpe, const int* inp, 
 int mli_prefill(const float* emb_table, const float* wpe, const int* inp, float* inp_embedding, const int* lengths,
                 const int* new_item_indices, const float* wk, const float* wv, float* kt_cache, float* v_cache,
                 int n_batch, int n_sequence, int input_dim, int output_dim, int n_new_items, void* stream);
+/* EXTENSION: mli_paged_prefill of the LIVE tokens of rows that decode under a sliding window with attention sinks (the
+ * scans of mli_paged_attention_lean_window / _sinks).  For a row of L tokens, p0 = max(0, L - window) / 16 and ps =
+ * ceil(n_sink / 16): pages ps <= i < p0 are dead -- no decode step of the row reads them, now or at any later length.
+ *   live pages receive the bits mli_paged_prefill writes to them (x, K and V segments), in the same form (prologue form, or
+ *     encoder + fill, by mli_tune "prefill_fused");
+ *   the table entry of a dead page is never read and no byte of the page is written: it may be null, stale, or name a page
+ *     of another row.  No GEMM tile is spent on a dead token: the cost follows min(L, n_sink + window).
+ * window == 0 (none), window >= n_sequence and n_sink + window >= n_sequence leave no row a dead page and ARE
+ * mli_paged_prefill; window < 0 or n_sink < 0 is MLI_ERR_BAD_ARG.  Shapes and element types are mli_paged_prefill's. */
+int mli_paged_prefill_window(const float* emb_table, const float* wpe, const int* inp, void* const* page_table,
+                             const int* lengths, const int* new_item_indices, const void* wk, const void* wv,
+                             int n_batch, int n_sequence, int emb_dim, int n_new_items, int window, int n_sink, int elem,
+                             void* stream);
 
 /* One whole decode step of the continuous batch (n_new_items = 0) in ONE call: what *InferenceModel::forward does per
  * round once the new rows are prefilled (reference src/inference_model.cpp:26-30, 68-72) -- lean attention

@@ -83,6 +83,7 @@ SIGNATURES = {
     "mli_decoder_sampled": [_P] * 6 + [_I] * 4 + [_P] * 4 + [_P, _Z, _P],
     "mli_paged_decoder_sampled": [_P] * 6 + [_I] * 7 + [_P] * 4 + [_P, _Z, _P],
     "mli_paged_prefill": [_P] * 8 + [_I] * 5 + [_P],
+    "mli_paged_prefill_window": [_P] * 8 + [_I] * 7 + [_P],
     "mli_prefill": [_P] * 10 + [_I] * 5 + [_P],
     "mli_paged_decode_step": [_P] * 10 + [_I] * 7 + [_P, _Z, _P, _Z, _P],
     "mli_decode_step": [_P] * 13 + [_I] * 4 + [_P, _Z, _P, _Z, _P],
@@ -115,6 +116,12 @@ class EngineStats(ctypes.Structure):
                 ("finished", _I), ("waiting", _I), ("in_flight", _I)]
 
 
+class EnginePageStats(ctypes.Structure):
+    """mli_engine_page_stats (include/mli_engine.h)."""
+    _fields_ = [("pool_pages", _I), ("in_use", _I), ("peak_in_use", _I), ("released_early", ctypes.c_longlong),
+                ("preemptions", ctypes.c_longlong)]
+
+
 _PP = ctypes.POINTER(ctypes.c_void_p)
 _IP = ctypes.POINTER(_I)
 ENGINE_SIGNATURES = {
@@ -133,6 +140,8 @@ ENGINE_SIGNATURES = {
     "mli_engine_set_heads": [_P, _I],
     "mli_engine_set_window": [_P, _I],
     "mli_engine_set_sinks": [_P, _I],
+    "mli_engine_set_page_release": [_P, _I],
+    "mli_engine_get_page_stats": [_P, ctypes.POINTER(EnginePageStats)],
     "mli_engine_set_lean_layers": [_I],
     "mli_engine_set_step_graphs": [_I],
     "mli_engine_last_error": [],

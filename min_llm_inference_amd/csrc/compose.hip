@@ -39,6 +39,17 @@ int launch_fill_paged_embed(const float*, const float*, const int*, float* const
 int launch_fill_paged_bf16_embed(const float*, const float*, const int*, uint16_t* const*, const int*, const int*,
                                  const uint16_t*, const uint16_t*, int, int, int, int, hipStream_t);
 bool prefill_fuses(int emb_dim);   // proj_gemm.hip: mli_tune "prefill_fused"
+// the windowed prefill (mli_paged_prefill_window): the same launches over a row's live tokens (page_live.hpp)
+int launch_fill_paged_window_embed(const float*, const float*, const int*, float* const*, const int*, const int*, const float*,
+                                   const float*, int, int, int, int, int, int, hipStream_t);
+int launch_fill_paged_bf16_window_embed(const float*, const float*, const int*, uint16_t* const*, const int*, const int*,
+                                        const uint16_t*, const uint16_t*, int, int, int, int, int, int, hipStream_t);
+int launch_fill_paged_bf16_window(uint16_t* const*, const int*, const int*, const uint16_t*, const uint16_t*, int, int, int,
+                                  int, int, int, hipStream_t);
+int launch_fill_paged_fp8_window_embed(const float*, const float*, const int*, uint8_t* const*, const int*, const int*,
+                                       const uint16_t*, const uint16_t*, int, int, int, int, int, int, hipStream_t);
+int launch_paged_encoder_window(const float*, const float*, const int*, void* const*, const int*, const int*, int, int, int,
+                                int, int, int, int, hipStream_t);
 // single-launch scan over the contiguous caches (attention_fused_naive.hip): 1 = ran, 0 = shape not covered, else error + (rc > 0)
 int launch_fused_decode_naive(const float*, const float*, const float*, const int*, float*, int, int, int, void*, size_t,
                               hipStream_t);
@@ -229,6 +240,44 @@ int mli_paged_prefill(const float* emb_table, const float* wpe, const int* inp, 
     return mli::launch_fill_paged_embed(emb_table, wpe, inp, reinterpret_cast<float* const*>(page_table), new_item_indices,
                                         lengths, static_cast<const float*>(wk), static_cast<const float*>(wv), n_batch,
                                         n_sequence, emb_dim, n_new_items, st);
+}
+
+int mli_paged_prefill_window(const float* emb_table, const float* wpe, const int* inp, void* const* page_table,
+                             const int* lengths, const int* new_item_indices, const void* wk, const void* wv, int n_batch,
+                             int n_sequence, int emb_dim, int n_new_items, int window, int n_sink, int elem, void* stream) {
+    if (window < 0 || n_sink < 0) return MLI_ERR_BAD_ARG;
+    if (mli::lean_scan_kind(n_sequence, window, n_sink) == mli::kScanPlain)   // no row has a dead page
+        return mli_paged_prefill(emb_table, wpe, inp, page_table, lengths, new_item_indices, wk, wv, n_batch, n_sequence,
+                                 emb_dim, n_new_items, elem, stream);
+    if (emb_table == nullptr || wpe == nullptr || inp == nullptr) return MLI_ERR_BAD_ARG;
+    hipStream_t st = mli::as_stream(stream);
+    if (elem < MLI_ELEM_F32 || elem > MLI_ELEM_FP8) return MLI_ERR_BAD_ARG;
+    const mli_bf16 *k16 = static_cast<const mli_bf16*>(wk), *v16 = static_cast<const mli_bf16*>(wv);
+    if (elem == MLI_ELEM_FP8)
+        return mli::launch_fill_paged_fp8_window_embed(emb_table, wpe, inp, reinterpret_cast<uint8_t* const*>(page_table),
+                                                       new_item_indices, lengths, k16, v16, n_batch, n_sequence, emb_dim,
+                                                       n_new_items, window, n_sink, st);
+    // the form is mli_paged_prefill's: the prologue form, or encoder + fill beyond emb_dim 512
+    if (!mli::prefill_fuses(emb_dim)) {
+        const int rc = mli::launch_paged_encoder_window(emb_table, wpe, inp, page_table, lengths, new_item_indices, n_batch,
+                                                        n_sequence, emb_dim, n_new_items, window, n_sink, elem, st);
+        if (rc) return rc;
+        return elem ? mli::launch_fill_paged_bf16_window(reinterpret_cast<mli_bf16* const*>(page_table), new_item_indices,
+                                                         lengths, k16, v16, n_batch, n_sequence, emb_dim, n_new_items, window,
+                                                         n_sink, st)
+                    : mli::launch_fill_paged_window_embed(nullptr, nullptr, nullptr, reinterpret_cast<float* const*>(page_table),
+                                                          new_item_indices, lengths, static_cast<const float*>(wk),
+                                                          static_cast<const float*>(wv), n_batch, n_sequence, emb_dim,
+                                                          n_new_items, window, n_sink, st);
+    }
+    if (elem)
+        return mli::launch_fill_paged_bf16_window_embed(emb_table, wpe, inp, reinterpret_cast<mli_bf16* const*>(page_table),
+                                                        new_item_indices, lengths, k16, v16, n_batch, n_sequence, emb_dim,
+                                                        n_new_items, window, n_sink, st);
+    return mli::launch_fill_paged_window_embed(emb_table, wpe, inp, reinterpret_cast<float* const*>(page_table),
+                                               new_item_indices, lengths, static_cast<const float*>(wk),
+                                               static_cast<const float*>(wv), n_batch, n_sequence, emb_dim, n_new_items,
+                                               window, n_sink, st);
 }
 
 int mli_graph_begin_capture(void* stream) {

@@ -6,6 +6,7 @@
 #include <cfloat>
 
 #include "embed_store.hpp"
+#include "page_live.hpp"
 
 namespace mli {
 
@@ -44,6 +45,53 @@ __global__ __launch_bounds__(kEdThreads) void encoder_new_rows_kernel(
         float* dst = !PAGED ? inp_embedding + ((int64_t)b * S + s) * D : page_row_ptr<BF16>(page_sh, s, D, kSegInp);
         for (int i = lane; i < D4; i += kWave) store_sum4<BF16>(dst, i, e[i], p[i]);
     }
+}
+
+// encoder_new_rows_kernel<true> for rows that decode under a sliding window with sinks (the windowed prefill): a page dead
+// at the row's length (page_live.hpp) is left before its table entry is read.  A kernel of its own rather than a switch
+// of the one above, whose parameter list and code object stay what they were.
+template <int BF16>
+__global__ __launch_bounds__(kEdThreads) void encoder_live_rows_kernel(
+    const float* __restrict__ emb_table, const float* __restrict__ wpe, const int* __restrict__ inp,
+    float* const* __restrict__ page_table, const int* __restrict__ lengths, const int* __restrict__ new_item_indices, int S,
+    int D, int window, int n_sink) {
+    __shared__ float* page_sh;
+    const int b = new_item_indices[blockIdx.y];
+    const int L = lengths[b];
+    const int s_base = blockIdx.x * kPage;
+    if (s_base >= L) return;
+    if (page_dead(blockIdx.x, min(L, S), window, n_sink)) return;
+    if (threadIdx.x == 0) page_sh = page_table[(int64_t)b * (S / kPage) + blockIdx.x];
+    __syncthreads();
+    if (page_sh == nullptr) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    const int D4 = D >> 2;
+    for (int t = wave; t < kPage; t += kEdThreads / kWave) {
+        const int s = s_base + t;
+        if (s >= L) break;
+        const int tok = inp[(int64_t)b * S + s];
+        const float4* e = reinterpret_cast<const float4*>(emb_table + (int64_t)tok * D);
+        const float4* p = reinterpret_cast<const float4*>(wpe + (int64_t)s * D);
+        float* dst = page_row_ptr<BF16>(page_sh, s, D, kSegInp);
+        for (int i = lane; i < D4; i += kWave) store_sum4<BF16>(dst, i, e[i], p[i]);
+    }
+}
+
+// the encoder of the windowed prefill's two-launch form (mli_paged_prefill_window, compose.hip); elem = MLI_ELEM_F32 / _BF16
+int launch_paged_encoder_window(const float* emb_table, const float* wpe, const int* inp, void* const* page_table,
+                                const int* lengths, const int* new_item_indices, int B, int S, int D, int n_new, int window,
+                                int n_sink, int elem, hipStream_t st) {
+    if (n_new == 0) return 0;
+    if (n_new < 0 || D % (elem == MLI_ELEM_BF16 ? 8 : 4) != 0 || S % kPage != 0 || B <= 0) return MLI_ERR_BAD_ARG;
+    float* const* pt = reinterpret_cast<float* const*>(page_table);
+    if (elem == MLI_ELEM_BF16)
+        hipLaunchKernelGGL((encoder_live_rows_kernel<MLI_ELEM_BF16>), dim3(S / kPage, n_new), dim3(kEdThreads), 0, st, emb_table,
+                           wpe, inp, pt, lengths, new_item_indices, S, D, window, n_sink);
+    else
+        hipLaunchKernelGGL((encoder_live_rows_kernel<0>), dim3(S / kPage, n_new), dim3(kEdThreads), 0, st, emb_table, wpe, inp,
+                           pt, lengths, new_item_indices, S, D, window, n_sink);
+    return launch_status();
 }
 
 // One workgroup per batch row.  argmax keeps the LOWEST index among equal maxima (the reference's

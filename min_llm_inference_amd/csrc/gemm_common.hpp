@@ -5,8 +5,11 @@
 #include <type_traits>
 
 #include "device_common.hpp"
+#include "page_live.hpp"
 
 namespace mli {
+
+static_assert(kLivePage == kPage, "page_live.hpp counts in pages of kPage tokens");
 
 enum GemmMode : int {
     kNaiveLatest = 0,
@@ -14,6 +17,11 @@ enum GemmMode : int {
     kPagedLatest = 2,
     kPagedFill = 3,
     kPlain = 4,  // C[M,N] = A[M,K] . B  (B is [K,N], or [N,K] when b_transposed)
+    // kPagedFill over a row's LIVE tokens under a sliding window with sinks (page_live.hpp; window and sinks in
+    // GemmArgs::fill_window / fill_sink): the flat list holds no pair for a token of a dead page, the per-row grid drops such
+    // a token before its page's table entry is read.  Only the windowed prefill launches it; inside the kernels it is
+    // kPagedFill with the switch WIN set.
+    kPagedFillLive = 5,
 };
 
 struct GemmArgs {
@@ -25,7 +33,10 @@ struct GemmArgs {
     // row sources / sinks
     const float* a_plain;  // kPlain: A
     float* c_plain;        // kPlain: C
-    int lda, ldc;
+    // kPlain: the row strides of A and C.  kPagedFillLive keeps its window and sink count in the same two ints, which no
+    // fill reads otherwise: the block every other kernel is compiled against keeps its layout.
+    union { int lda; int fill_window; };
+    union { int ldc; int fill_sink; };
     const float* inp_embedding;  // naive: [B, S, K]
     float* kt_cache;             // naive: [B, N, S]
     float* v_cache;              // naive: [B, S, N]
@@ -100,7 +111,8 @@ using NoFillIndex = FillIndexT<1>;  // placeholder of the kernels that do no pre
 // non-empty: a continuous batch that is 40 % empty slots (a dry page pool, the tail of a run) then multiplies 40 %
 // fewer rows.
 // all THREADS (a multiple of 64, <= 512) threads of the workgroup call this; returns the total number of pairs
-template <int THREADS, bool LATEST, class FI>
+// WIN (fill only): a row counts its live tokens (page_live.hpp) -- no pair, and so no tile, for a token of a dead page
+template <int THREADS, bool LATEST, bool WIN = false, class FI>
 __device__ __forceinline__ int build_fill_index(const GemmArgs& g, FI& fi) {
     const int tid = threadIdx.x;
     const int n_entries = LATEST ? g.B : g.n_new;
@@ -114,6 +126,7 @@ __device__ __forceinline__ int build_fill_index(const GemmArgs& g, FI& fi) {
         if (j < per && zz < n_entries) {
             if (LATEST) L = g.lengths[zz] > 0 ? 1 : 0;
             else L = min(max(g.lengths[g.new_batch_idx[zz]], 0), g.S);
+            if (WIN && !LATEST) L = live_tokens(L, g.fill_window, g.fill_sink);
         }
         local[j] = sum;
         sum += L;
@@ -155,6 +168,22 @@ __device__ __forceinline__ void fill_index_lookup(const FI& fi, int n_new, int i
     }
     z = lo;
     s = i - fi.prefix[lo];
+}
+// ... of the windowed fill: the pair's live index -> its token slot
+template <class FI>
+__device__ __forceinline__ void fill_index_lookup_live(const GemmArgs& g, const FI& fi, int i, int& z, int& s) {
+    fill_index_lookup(fi, g.n_new, i, z, s);
+    s = live_slot(s, min(max(g.lengths[g.new_batch_idx[z]], 0), g.S), g.fill_window, g.fill_sink);
+}
+// one grid row per new row (the non-compact form) under a window: whether token m of new row z lies in a dead page --
+// decided before the page's table entry is read
+__device__ __forceinline__ bool fill_token_dead(const GemmArgs& g, int m, int z) {
+    return page_dead(m / kPage, min(max(g.lengths[g.new_batch_idx[z]], 0), g.S), g.fill_window, g.fill_sink);
+}
+// ... and whether every page of the tile's `rows` (a multiple of 16) tokens from m0 is dead: the workgroup leaves
+__device__ __forceinline__ bool fill_tile_dead(const GemmArgs& g, int m0, int rows, int z) {
+    const int n = min(max(g.lengths[g.new_batch_idx[z]], 0), g.S);
+    return m0 / kPage >= live_sink_pages(g.fill_sink) && (m0 + rows) / kPage <= live_window_page(n, g.fill_window);
 }
 
 struct RowDesc {

@@ -35,8 +35,12 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 // KQ: 32-deep k slabs staged per tile.  Only KQ = 1 is instantiated: 128 k per barrier pair (KQ = 4) was measured
 // SLOWER for the latency-bound fp32 shapes (config 4 logits 23.8 -> 26.0 us, D = 2048 logits 61.8 -> 70.2 us) --
 // unlike the bf16 kernel, whose deep tile is a win (proj_gemm_bf16.hip).
-template <int MODE, bool BT, bool VEC4, bool BF16 = false, int MT = 1, bool SPLIT = false>
+// MODE_ = kPagedFillLive (launched by the windowed prefill only) is kPagedFill with WIN set: the fill of a row's live tokens
+// under a sliding window with sinks (gemm_common.hpp, page_live.hpp).
+template <int MODE_, bool BT, bool VEC4, bool BF16 = false, int MT = 1, bool SPLIT = false>
 __global__ __launch_bounds__(SPLIT ? 2 * kGemmThreads : kGemmThreads) void gemm_f32_mfma_kernel(GemmArgs g) {
+    constexpr bool WIN = MODE_ == kPagedFillLive;   // the windowed prefill's fill: kPagedFill over the live tokens
+    constexpr int MODE = WIN ? kPagedFill : MODE_;
     constexpr int BM = 64 * MT;   // shadows the namespace-level 64: rows per workgroup
     constexpr int BK = 32;        // k extent of a staged tile
     constexpr int KQ = 1;
@@ -67,10 +71,12 @@ __global__ __launch_bounds__(SPLIT ? 2 * kGemmThreads : kGemmThreads) void gemm_
     int fill_total = 0;
     if (kFill || kLatest) {
         if (g.compact) {
-            fill_total = build_fill_index<kThreads, kLatest>(g, fill_index[0]);
+            fill_total = build_fill_index<kThreads, kLatest, WIN>(g, fill_index[0]);
             if (m0 >= fill_total) return;  // workgroup-uniform
         } else if (kFill && m0 >= g.lengths[g.new_batch_idx[z]]) {
             return;  // whole tile beyond the row's length: nothing to do (reference …optimized.cu:43-45)
+        } else if (kFill && WIN && fill_tile_dead(g, m0, BM, z)) {
+            return;  // ... or wholly in dead pages
         }
     }
 
@@ -80,10 +86,11 @@ __global__ __launch_bounds__(SPLIT ? 2 * kGemmThreads : kGemmThreads) void gemm_
         if ((kFill || kLatest) && g.compact) {
             if (m0 + tid < fill_total) {
                 int zz, ss;
-                fill_index_lookup(fill_index[0], kLatest ? g.B : g.n_new, m0 + tid, zz, ss);
+                if (WIN) fill_index_lookup_live(g, fill_index[0], m0 + tid, zz, ss);
+                else fill_index_lookup(fill_index[0], kLatest ? g.B : g.n_new, m0 + tid, zz, ss);
                 r = kLatest ? resolve_row<MODE, BF16>(g, zz, 0, out_id) : resolve_row<MODE, BF16>(g, ss, zz, out_id);
             }
-        } else {
+        } else if (!WIN || !fill_token_dead(g, m0 + tid, z)) {
             r = resolve_row<MODE, BF16>(g, m0 + tid, z, out_id);
         }
         a_ptr[tid] = r.a;
@@ -439,7 +446,7 @@ static int launch_gemm(const GemmArgs& g, int rows, int z, bool vec4, hipStream_
         return launch_status();
     }
     dim3 grid(tiles_x, ceil_div_i(rows, BM), z);
-    if (g.compact && (MODE == kNaiveFill || MODE == kPagedFill))
+    if (g.compact && (MODE == kNaiveFill || MODE == kPagedFill || MODE == kPagedFillLive))
         grid = dim3(tiles_x, ceil_div_i(rows * z, BM), 1);  // flat (new row, token) list: upper bound
     // a reduction long enough to pipeline: loader waves + MFMA waves (512 threads).  Measured at D = 2048: logits of 1024
     // rows 61 -> 52 us, prefill of 128 / 256 / 512 / 4096 prompt tokens 60 -> 49 / 63 -> 52 / 96 -> 86 / 593 -> 588 us,
@@ -506,9 +513,11 @@ int launch_latest_paged(float* const* page_table, const int* lengths, const floa
     return launch_gemm<kPagedLatest, false>(g, B, 1, vec4, st);
 }
 
-int launch_fill_paged_embed(const float* emb_table, const float* wpe, const int* tokens, float* const* page_table,
+// WIN: the windowed prefill's fill (1 <= window, 0 <= n_sink, n_sink + window < S: the entry point hands everything else on)
+template <bool WIN>
+static int fill_paged_embed(const float* emb_table, const float* wpe, const int* tokens, float* const* page_table,
                             const int* new_idx, const int* lengths, const float* wk, const float* wv, int B, int S, int D,
-                            int n_new, hipStream_t st) {
+                            int n_new, int window, int n_sink, hipStream_t st) {
     if (n_new == 0) return 0;  // reference paged_attention.cu:100-102
     if (n_new < 0 || B <= 0 || S % kPage != 0 || D % 4 != 0) return MLI_ERR_BAD_ARG;
     GemmArgs g{};
@@ -520,7 +529,22 @@ int launch_fill_paged_embed(const float* emb_table, const float* wpe, const int*
     g.B = B; g.S = S;
     g.n_new = n_new; g.compact = fill_compact(n_new);
     const bool vec4 = aligned16(wk) && aligned16(wv) && (emb_table == nullptr || (aligned16(emb_table) && aligned16(wpe)));
-    return launch_gemm<kPagedFill, false>(g, S, n_new, vec4, st);
+    if (!WIN) return launch_gemm<kPagedFill, false>(g, S, n_new, vec4, st);
+    g.fill_window = window; g.fill_sink = n_sink;
+    // the flat list is at most live_tokens_bound pairs per row; the per-row grid keeps the row's extent
+    return launch_gemm<kPagedFillLive, false>(g, g.compact ? live_tokens_bound(S, window, n_sink) : S, n_new, vec4, st);
+}
+
+int launch_fill_paged_embed(const float* emb_table, const float* wpe, const int* tokens, float* const* page_table,
+                            const int* new_idx, const int* lengths, const float* wk, const float* wv, int B, int S, int D,
+                            int n_new, hipStream_t st) {
+    return fill_paged_embed<false>(emb_table, wpe, tokens, page_table, new_idx, lengths, wk, wv, B, S, D, n_new, 0, 0, st);
+}
+
+int launch_fill_paged_window_embed(const float* emb_table, const float* wpe, const int* tokens, float* const* page_table,
+                                   const int* new_idx, const int* lengths, const float* wk, const float* wv, int B, int S,
+                                   int D, int n_new, int window, int n_sink, hipStream_t st) {
+    return fill_paged_embed<true>(emb_table, wpe, tokens, page_table, new_idx, lengths, wk, wv, B, S, D, n_new, window, n_sink, st);
 }
 
 int launch_fill_paged(float* const* page_table, const int* new_idx, const int* lengths, const float* wk,
@@ -554,11 +578,18 @@ int launch_latest_paged_bf16(uint16_t* const* page_table, const int* lengths, co
     return launch_status();
 }
 
-int launch_fill_paged_bf16(uint16_t* const* page_table, const int* new_idx, const int* lengths, const uint16_t* wk,
-                           const uint16_t* wv, int B, int S, int D, int n_new, hipStream_t st) {
+int launch_fill_paged_bf16_window_embed(const float*, const float*, const int*, uint16_t* const*, const int*, const int*,
+                                        const uint16_t*, const uint16_t*, int, int, int, int, int, int, hipStream_t);
+
+template <bool WIN>
+static int fill_paged_bf16(uint16_t* const* page_table, const int* new_idx, const int* lengths, const uint16_t* wk,
+                           const uint16_t* wv, int B, int S, int D, int n_new, int window, int n_sink, hipStream_t st) {
     if (n_new == 0) return 0;
     if (n_new < 0 || B <= 0 || S % kPage != 0 || D % 8 != 0) return MLI_ERR_BAD_ARG;
-    if (g_bf16_native_mfma) return launch_fill_paged_bf16_native(page_table, new_idx, lengths, wk, wv, B, S, D, n_new, st);
+    if (g_bf16_native_mfma)
+        return WIN ? launch_fill_paged_bf16_window_embed(nullptr, nullptr, nullptr, page_table, new_idx, lengths, wk, wv, B, S,
+                                                         D, n_new, window, n_sink, st)
+                   : launch_fill_paged_bf16_native(page_table, new_idx, lengths, wk, wv, B, S, D, n_new, st);
     GemmArgs g{};
     g.w[0] = reinterpret_cast<const float*>(wk); g.w[1] = reinterpret_cast<const float*>(wv); g.n_out = 2;
     g.out_id[0] = 0; g.out_id[1] = 2;
@@ -567,9 +598,25 @@ int launch_fill_paged_bf16(uint16_t* const* page_table, const int* new_idx, cons
     g.B = B; g.S = S;
     g.n_new = n_new; g.compact = fill_compact(n_new);
     dim3 grid(ceil_div_i(D, BN) * 2, ceil_div_i(S, BM), n_new);
-    if (g.compact) grid = dim3(ceil_div_i(D, BN) * 2, ceil_div_i(S * n_new, BM), 1);
-    hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPagedFill, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
+    if (!WIN) {
+        if (g.compact) grid = dim3(ceil_div_i(D, BN) * 2, ceil_div_i(S * n_new, BM), 1);
+        hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPagedFill, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
+        return launch_status();
+    }
+    g.fill_window = window; g.fill_sink = n_sink;
+    if (g.compact) grid = dim3(ceil_div_i(D, BN) * 2, ceil_div_i(live_tokens_bound(S, window, n_sink) * n_new, BM), 1);
+    hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPagedFillLive, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
     return launch_status();
+}
+
+int launch_fill_paged_bf16(uint16_t* const* page_table, const int* new_idx, const int* lengths, const uint16_t* wk,
+                           const uint16_t* wv, int B, int S, int D, int n_new, hipStream_t st) {
+    return fill_paged_bf16<false>(page_table, new_idx, lengths, wk, wv, B, S, D, n_new, 0, 0, st);
+}
+
+int launch_fill_paged_bf16_window(uint16_t* const* page_table, const int* new_idx, const int* lengths, const uint16_t* wk,
+                                  const uint16_t* wv, int B, int S, int D, int n_new, int window, int n_sink, hipStream_t st) {
+    return fill_paged_bf16<true>(page_table, new_idx, lengths, wk, wv, B, S, D, n_new, window, n_sink, st);
 }
 
 // C[M, N] = A[M, K] . Bt[N, K]^T

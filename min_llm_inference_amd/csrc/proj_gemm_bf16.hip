@@ -53,8 +53,11 @@ union Frag8 {
 // MT = 32-row sub-tiles per wave (rows per workgroup = 64 * MT), KB = k extent of a staged tile (32 or 64)
 // FP8 = the pages hold OCP e4m3 bytes (MLI_ELEM_FP8): A rows are widened to bf16 on their way into LDS (exact), K / V rows
 // leave as fp8 (round to nearest even, saturating); the weights are bf16 and everything between is the bf16 kernel
-template <int MODE, int MT = 1, int KB = 32, bool FP8 = false>
+// MODE_ = kPagedFillLive: kPagedFill over the live tokens (the windowed prefill), as in gemm_f32_mfma_kernel
+template <int MODE_, int MT = 1, int KB = 32, bool FP8 = false>
 __global__ __launch_bounds__(kHThreads) void gemm_bf16_mfma_kernel(GemmArgs g) {
+    constexpr bool WIN = MODE_ == kPagedFillLive;   // the windowed prefill's fill: kPagedFill over the live tokens
+    constexpr int MODE = WIN ? kPagedFill : MODE_;
     constexpr int HM = 64 * MT;              // shadows the namespace-level 64
     constexpr int HK = KB;
     constexpr int kLdaBytes = HK * 2 + 16;   // 80 / 144: ds_read_b128 fragment reads are conflict-free
@@ -82,9 +85,11 @@ __global__ __launch_bounds__(kHThreads) void gemm_bf16_mfma_kernel(GemmArgs g) {
     const int tid = threadIdx.x;
     int fill_total = 0;
     if (g.compact) {
-        fill_total = build_fill_index<kHThreads, kLatest>(g, fill_index[0]);
+        fill_total = build_fill_index<kHThreads, kLatest, WIN>(g, fill_index[0]);
         if (m0 >= fill_total) return;  // workgroup-uniform: every lane leaves together
     } else if (MODE == kPagedFill && m0 >= g.lengths[g.new_batch_idx[z]]) {
+        return;
+    } else if (MODE == kPagedFill && WIN && fill_tile_dead(g, m0, HM, z)) {
         return;
     }
     const bool embed = kFillMode && g.emb_table != nullptr;
@@ -93,10 +98,11 @@ __global__ __launch_bounds__(kHThreads) void gemm_bf16_mfma_kernel(GemmArgs g) {
         if (g.compact) {
             if (m0 + tid < fill_total) {
                 int zz, ss;
-                fill_index_lookup(fill_index[0], kLatest ? g.B : g.n_new, m0 + tid, zz, ss);
+                if (WIN) fill_index_lookup_live(g, fill_index[0], m0 + tid, zz, ss);
+                else fill_index_lookup(fill_index[0], kLatest ? g.B : g.n_new, m0 + tid, zz, ss);
                 r = kLatest ? resolve_row<MODE, true, FP8>(g, zz, 0, out_id) : resolve_row<MODE, true, FP8>(g, ss, zz, out_id);
             }
-        } else {
+        } else if (!WIN || !fill_token_dead(g, m0 + tid, z)) {
             r = resolve_row<MODE, true, FP8>(g, m0 + tid, z, out_id);
         }
         a_ptr[tid] = r.a;
@@ -671,11 +677,13 @@ int launch_latest_paged_bf16_native(uint16_t* const* page_table, const int* leng
     return launch_status();
 }
 
-int launch_fill_paged_bf16_embed(const float* emb_table, const float* wpe, const int* tokens,
-                                 uint16_t* const* page_table, const int* new_idx, const int* lengths, const uint16_t* wk,
-                                 const uint16_t* wv, int B, int S, int D, int n_new, hipStream_t st) {
+// FP8: fp8 pages (D % 16 == 0); WIN: the windowed prefill's fill (1 <= window, 0 <= n_sink, n_sink + window < S)
+template <bool FP8, bool WIN>
+static int fill_paged_16bit_embed(const float* emb_table, const float* wpe, const int* tokens, void* const* page_table,
+                                  const int* new_idx, const int* lengths, const uint16_t* wk, const uint16_t* wv, int B, int S,
+                                  int D, int n_new, int window, int n_sink, hipStream_t st) {
     if (n_new == 0) return 0;
-    if (n_new < 0 || B <= 0 || S % kPage != 0 || D % 8 != 0) return MLI_ERR_BAD_ARG;
+    if (n_new < 0 || B <= 0 || S % kPage != 0 || D % (FP8 ? 16 : 8) != 0) return MLI_ERR_BAD_ARG;
     GemmArgs g{};
     g.emb_table = emb_table; g.wpe = wpe; g.inp = tokens;
     g.w[0] = reinterpret_cast<const float*>(wk); g.w[1] = reinterpret_cast<const float*>(wv); g.n_out = 2;
@@ -684,10 +692,28 @@ int launch_fill_paged_bf16_embed(const float* emb_table, const float* wpe, const
     g.page_table = reinterpret_cast<float* const*>(page_table); g.lengths = lengths; g.new_batch_idx = new_idx;
     g.B = B; g.S = S;
     g.n_new = n_new; g.compact = fill_compact(n_new);
+    if (WIN) { g.fill_window = window; g.fill_sink = n_sink; }
+    // the flat list: S pairs per row at most, live_tokens_bound under a window
+    const int flat_rows = WIN ? live_tokens_bound(S, window, n_sink) : S;
     dim3 grid(ceil_div_i(D, HN) * 2, ceil_div_i(S, HM), n_new);
-    if (g.compact) grid = dim3(ceil_div_i(D, HN) * 2, ceil_div_i(S * n_new, HM), 1);
-    hipLaunchKernelGGL((gemm_bf16_mfma_kernel<kPagedFill>), grid, dim3(kHThreads), 0, st, g);
+    if (g.compact) grid = dim3(ceil_div_i(D, HN) * 2, ceil_div_i(flat_rows * n_new, HM), 1);
+    hipLaunchKernelGGL((gemm_bf16_mfma_kernel<WIN ? kPagedFillLive : kPagedFill, 1, 32, FP8>), grid, dim3(kHThreads), 0, st, g);
     return launch_status();
+}
+
+int launch_fill_paged_bf16_embed(const float* emb_table, const float* wpe, const int* tokens,
+                                 uint16_t* const* page_table, const int* new_idx, const int* lengths, const uint16_t* wk,
+                                 const uint16_t* wv, int B, int S, int D, int n_new, hipStream_t st) {
+    return fill_paged_16bit_embed<false, false>(emb_table, wpe, tokens, reinterpret_cast<void* const*>(page_table), new_idx,
+                                                lengths, wk, wv, B, S, D, n_new, 0, 0, st);
+}
+
+int launch_fill_paged_bf16_window_embed(const float* emb_table, const float* wpe, const int* tokens,
+                                        uint16_t* const* page_table, const int* new_idx, const int* lengths,
+                                        const uint16_t* wk, const uint16_t* wv, int B, int S, int D, int n_new, int window,
+                                        int n_sink, hipStream_t st) {
+    return fill_paged_16bit_embed<false, true>(emb_table, wpe, tokens, reinterpret_cast<void* const*>(page_table), new_idx,
+                                               lengths, wk, wv, B, S, D, n_new, window, n_sink, st);
 }
 
 // ---- fp8 (OCP e4m3) pages, bf16 weights: MLI_ELEM_FP8 of the lean entry points --------------------------------------
@@ -720,20 +746,16 @@ int launch_latest_paged_fp8(uint8_t* const* page_table, const int* lengths, cons
 int launch_fill_paged_fp8_embed(const float* emb_table, const float* wpe, const int* tokens, uint8_t* const* page_table,
                                 const int* new_idx, const int* lengths, const uint16_t* wk, const uint16_t* wv, int B, int S,
                                 int D, int n_new, hipStream_t st) {
-    if (n_new == 0) return 0;
-    if (n_new < 0 || B <= 0 || S % kPage != 0 || D % 16 != 0) return MLI_ERR_BAD_ARG;
-    GemmArgs g{};
-    g.emb_table = emb_table; g.wpe = wpe; g.inp = tokens;
-    g.w[0] = reinterpret_cast<const float*>(wk); g.w[1] = reinterpret_cast<const float*>(wv); g.n_out = 2;
-    g.out_id[0] = 0; g.out_id[1] = 2;
-    g.M = S; g.N = D; g.K = D;
-    g.page_table = reinterpret_cast<float* const*>(page_table); g.lengths = lengths; g.new_batch_idx = new_idx;
-    g.B = B; g.S = S;
-    g.n_new = n_new; g.compact = fill_compact(n_new);
-    dim3 grid(ceil_div_i(D, HN) * 2, ceil_div_i(S, HM), n_new);
-    if (g.compact) grid = dim3(ceil_div_i(D, HN) * 2, ceil_div_i(S * n_new, HM), 1);
-    hipLaunchKernelGGL((gemm_bf16_mfma_kernel<kPagedFill, 1, 32, true>), grid, dim3(kHThreads), 0, st, g);
-    return launch_status();
+    return fill_paged_16bit_embed<true, false>(emb_table, wpe, tokens, reinterpret_cast<void* const*>(page_table), new_idx,
+                                               lengths, wk, wv, B, S, D, n_new, 0, 0, st);
+}
+
+int launch_fill_paged_fp8_window_embed(const float* emb_table, const float* wpe, const int* tokens,
+                                       uint8_t* const* page_table, const int* new_idx, const int* lengths, const uint16_t* wk,
+                                       const uint16_t* wv, int B, int S, int D, int n_new, int window, int n_sink,
+                                       hipStream_t st) {
+    return fill_paged_16bit_embed<true, true>(emb_table, wpe, tokens, reinterpret_cast<void* const*>(page_table), new_idx,
+                                              lengths, wk, wv, B, S, D, n_new, window, n_sink, st);
 }
 
 int launch_fill_paged_bf16_native(uint16_t* const* page_table, const int* new_idx, const int* lengths,

@@ -8,7 +8,7 @@ import math
 
 import numpy as np
 
-from ._lib import EngineConfig, EngineStats, MliError, ShardStats, load_library
+from ._lib import EngineConfig, EnginePageStats, EngineStats, MliError, ShardStats, load_library
 
 CONTIGUOUS, PAGED, PAGED_GEMM, PAGED_BF16 = 0, 1, 2, 3  # PAGED_BF16: extension, bf16 pages and weights
 PAGED_FP8 = 4  # extension, opt-in: fp8 (OCP e4m3) pages, bf16 weights
@@ -38,7 +38,8 @@ def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
 
 class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
-                 n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None):
+                 n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None,
+                 release_pages=False):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -52,6 +53,8 @@ class Engine:
             self.set_window(window)
         if sinks is not None:
             self.set_sinks(sinks)
+        if release_pages:
+            self.set_page_release(True)
 
     def _check(self, rc):
         if rc != 0:
@@ -70,6 +73,18 @@ class Engine:
         """Attention sinks (mli_engine_set_sinks): beside the window every row keeps its first `n_sink` tokens attended.
         Before the first step or run, paged kinds; without a window below n_sequence it changes nothing."""
         self._check(self._lib.mli_engine_set_sinks(self._h, int(n_sink)))
+
+    def set_page_release(self, enabled=True):
+        """Early page release (mli_engine_set_page_release): beside a window, rows return the pages below it to the pool
+        while they decode, and new rows take and prefill their live pages only.  Before the first step or run, paged
+        kinds; without a window below n_sequence it changes nothing."""
+        self._check(self._lib.mli_engine_set_page_release(self._h, int(bool(enabled))))
+
+    def page_stats(self):
+        """mli_engine_get_page_stats: pool_pages, in_use, peak_in_use, released_early, preemptions (paged kinds)."""
+        st = EnginePageStats()
+        self._check(self._lib.mli_engine_get_page_stats(self._h, ctypes.byref(st)))
+        return st
 
     def use_private_stream(self):
         self._check(self._lib.mli_engine_use_private_stream(self._h))

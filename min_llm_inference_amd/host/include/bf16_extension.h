@@ -53,6 +53,8 @@ public:
     void set_window(int window) { window_ = window; }
     // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
     void set_sinks(int n_sink) { n_sink_ = n_sink; }
+    // prefill of the live tokens only, for rows whose dead pages are returned early (PagedAttentionLayer::set_page_release)
+    void set_page_release(bool enabled) { page_release_ = enabled; }
 
 private:
     TensorBf16 wk_, wq_, wv_;
@@ -61,6 +63,7 @@ private:
     int n_heads_ = 1;
     int window_ = 0;
     int n_sink_ = 0;
+    bool page_release_ = false;
 };
 
 class PagedAttentionBf16InferenceModel : public NonCopyableNonClonable {
@@ -75,6 +78,7 @@ public:
     void set_n_heads(int n_heads) { attention_layer_.set_n_heads(n_heads); }
     void set_window(int window) { attention_layer_.set_window(window); }
     void set_sinks(int n_sink) { attention_layer_.set_sinks(n_sink); }
+    void set_page_release(bool enabled) { attention_layer_.set_page_release(enabled); }
 
 private:
     PagedAttentionBf16Layer attention_layer_;

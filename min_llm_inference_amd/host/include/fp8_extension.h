@@ -28,6 +28,8 @@ public:
     void set_window(int window) { window_ = window; }
     // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
     void set_sinks(int n_sink) { n_sink_ = n_sink; }
+    // prefill of the live tokens only, for rows whose dead pages are returned early (PagedAttentionLayer::set_page_release)
+    void set_page_release(bool enabled) { page_release_ = enabled; }
 
 private:
     TensorBf16 wk_, wq_, wv_;
@@ -35,6 +37,7 @@ private:
     size_t n_sequence_;
     int window_ = 0;
     int n_sink_ = 0;
+    bool page_release_ = false;
 };
 
 class PagedAttentionFp8InferenceModel : public NonCopyableNonClonable {
@@ -49,6 +52,7 @@ public:
     void set_sampling(const SlotSampling* sampling);
     void set_window(int window) { attention_layer_.set_window(window); }
     void set_sinks(int n_sink) { attention_layer_.set_sinks(n_sink); }
+    void set_page_release(bool enabled) { attention_layer_.set_page_release(enabled); }
 
 private:
     PagedAttentionFp8Layer attention_layer_;

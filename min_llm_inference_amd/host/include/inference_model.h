@@ -39,6 +39,7 @@ public:
     void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
     void set_window(int window) { paged_attention_layer_.set_window(window); }                        // EXTENSION
     void set_sinks(int n_sink) { paged_attention_layer_.set_sinks(n_sink); }                          // EXTENSION
+    void set_page_release(bool enabled) { paged_attention_layer_.set_page_release(enabled); }         // EXTENSION
 
 private:
     PagedAttentionLayer paged_attention_layer_;
@@ -62,6 +63,7 @@ public:
     void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
     void set_window(int window) { paged_attention_layer_.set_window(window); }                        // EXTENSION
     void set_sinks(int n_sink) { paged_attention_layer_.set_sinks(n_sink); }                          // EXTENSION
+    void set_page_release(bool enabled) { paged_attention_layer_.set_page_release(enabled); }         // EXTENSION
 
 private:
     PagedAttentionCublasLayer paged_attention_layer_;

@@ -71,6 +71,11 @@ void paged_attention_lean_layer(TensorFloatPoint& page_table, const TensorInt& l
 void launch_paged_prefill(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,
                           TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
                           const TensorFloat& wk, const TensorFloat& wv, int n_new_items);
+// ... of the live tokens of rows that decode under (window, n_sink) and return their dead pages early
+// (mli_paged_prefill_window; no effective window: launch_paged_prefill)
+void launch_paged_prefill_window(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,
+                                 TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
+                                 const TensorFloat& wk, const TensorFloat& wv, int n_new_items, int window, int n_sink);
 
 // "cuBLAS" variants: same results, produced by the same gather-GEMM-scatter MFMA kernel.  latest_emb and
 // temp_placeholder were scratch for the three cublasSgemm calls and are accepted but not used.

@@ -44,6 +44,9 @@ public:
     void set_window(int window) { window_ = window; }
     // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
     void set_sinks(int n_sink) { n_sink_ = n_sink; }
+    // EXTENSION: the rows' pages below the window are returned early (PagedAttentionsManager::set_page_release): prefill
+    // covers a row's live tokens only and follows no table entry of a dead page (mli_paged_prefill_window)
+    void set_page_release(bool enabled) { page_release_ = enabled; }
 
 private:
     TensorFloat wk_, wq_, wv_;
@@ -52,6 +55,7 @@ private:
     int n_heads_ = 1;
     int window_ = 0;
     int n_sink_ = 0;
+    bool page_release_ = false;
 };
 
 class PagedAttentionCublasLayer : public NonCopyableNonClonable {
@@ -70,6 +74,9 @@ public:
     void set_window(int window) { window_ = window; }
     // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
     void set_sinks(int n_sink) { n_sink_ = n_sink; }
+    // EXTENSION: the rows' pages below the window are returned early (PagedAttentionsManager::set_page_release): prefill
+    // covers a row's live tokens only and follows no table entry of a dead page (mli_paged_prefill_window)
+    void set_page_release(bool enabled) { page_release_ = enabled; }
 
 private:
     TensorFloat wk_, wq_, wv_;
@@ -78,6 +85,7 @@ private:
     int n_heads_ = 1;
     int window_ = 0;
     int n_sink_ = 0;
+    bool page_release_ = false;
     TensorFloat latest_emb_;        // kept for signature parity with the reference; unused by the MFMA path
     TensorFloat temp_placeholder_;
 };

@@ -18,13 +18,20 @@ public:
     int free_blocks_size() const;
     std::list<float*> pop_free_blocks(int size);  // throws std::runtime_error when fewer are free
     void return_free_blocks(std::list<float*>&&);
+    // extension: occupancy (pages out of the pool now, and the most there ever were)
+    int pool_pages() const { return n_blocks_; }
+    int pages_in_use() const { return n_blocks_ - free_blocks_size(); }
+    int peak_pages_in_use() const { return peak_in_use_; }
 
 private:
     TensorFloat block_memory_;
     std::list<float*> free_blocks_;
+    int n_blocks_;
+    int peak_in_use_ = 0;
 };
 
 using BatchIdMemoryBlocksPair = std::pair<int, std::list<float*>>;
+struct PagedAdmission;
 
 class PagedAttentionsManager {
 public:
@@ -44,7 +51,39 @@ public:
     void set_length_reset_quirk(bool enabled) { length_reset_quirk_ = enabled; }
     bool length_reset_quirk() const { return length_reset_quirk_; }
 
+    // EXTENSION: early page release for rows that decode under a sliding window of `window` tokens with n_sink attention
+    // sinks (csrc/page_live.hpp): a page no scan of the row reads any more -- index ceil(n_sink / 16) <= i < max(0, n -
+    // window) / 16 at the row's host token count n -- goes back to the pool while the row decodes, and a new or re-admitted
+    // row takes its live pages only, at their true table indices.  window 0 (the default), window >= n_sequence and n_sink +
+    // window >= n_sequence leave no row such a page and switch release off: every row holds pages 0 .. top as before.
+    // Set before the first admission.  Not with the length-reset quirk (it moves device lengths backwards).
+    void set_page_release(int window, int n_sink);
+    bool page_release() const { return release_window_ > 0; }
+    int release_window() const { return release_window_; }
+    int release_sinks() const { return release_sink_; }
+    long long pages_released_early() const { return released_early_; }
+    long long preemptions() const { return preemptions_; }   // counted with or without release
+
 private:
+    // Release on: what the row list's "page index = position in the list" no longer tells.  Kept by the three scheduler
+    // functions below (friends), which are the only code that moves pages between the pool and a row.
+    struct RowPages {
+        int next_page = 0;     // the row holds pages up to here (exclusive), the released ones excepted
+        int first_window = 0;  // the first window page not yet released: pages [ceil(n_sink / 16), first_window) are gone
+    };
+    friend void allocate_memory_block(MemoryBlockManager&, PagedAttentionsManager&, BatchIdMemoryBlocksPair&);
+    friend void allocate_or_free_memory_blocks_if_needed(PagedAttentionsManager&, MemoryBlockManager&, ProcessingStorage&,
+                                                         ItemStorage&, const std::vector<int>&, int, bool*);
+    friend PagedAdmission admit_new_items(int*, int*, int*, int, int, ItemStorage&, ProcessingStorage&,
+                                          MemoryBlockManager&, PagedAttentionsManager&, int);
+    void count_preemption() { ++preemptions_; }
+    RowPages& row_pages(int batch_id) { return row_pages_[static_cast<size_t>(batch_id)]; }
+    float* block_at(int batch_id, int i_block) const { return page_table_host.data()[static_cast<size_t>(batch_id) * width_ + i_block]; }
+    // a new row with `blocks` at the table indices `indices` (ascending), every other entry below indices.back() null
+    void add_row_at(int batch_id, std::list<float*>&& blocks, const std::vector<int>& indices);
+    // returns the row's pages dead at n_tokens to the pool, nulls their entries; the number returned
+    int release_dead_pages(MemoryBlockManager& pool, BatchIdMemoryBlocksPair& row, int n_tokens);
+
     TensorFloatPoint page_table_host;
     TensorFloatPoint page_table_device;
     std::list<BatchIdMemoryBlocksPair> used_blocks_;  // rows in admission order; the tail is preempted first
@@ -52,6 +91,9 @@ private:
     bool needs_sync_;
     bool length_reset_quirk_;
     std::vector<long long> dirty_;                    // flat indices of entries changed since the last flush
+    int release_window_ = 0, release_sink_ = 0;       // 0 = no early release
+    long long released_early_ = 0, preemptions_ = 0;
+    std::vector<RowPages> row_pages_;                 // [max_batches], meaningful for rows in used_blocks_ with release on
 };
 
 // Gives the row one more page (and records it in the host page table).

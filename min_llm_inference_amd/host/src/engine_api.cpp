@@ -78,6 +78,18 @@ struct mli_engine {
     int n_heads = 1;            // mli_engine_set_heads
     int window = 0;             // mli_engine_set_window (0: none)
     int n_sink = 0;             // mli_engine_set_sinks (0: none; counts beside a window only)
+    bool release_pages = false; // mli_engine_set_page_release: takes effect at the first step or run, beside an effective window
+
+    // at the first step or run: the manager and the model's prefill follow the switch together, or not at all
+    void apply_page_release() {
+        if (!pages) return;
+        pages->set_page_release(release_pages ? window : 0, n_sink);
+        const bool on = pages->page_release();
+        if (paged_model) paged_model->set_page_release(on);
+        if (gemm_model) gemm_model->set_page_release(on);
+        if (bf16_model) bf16_model->set_page_release(on);
+        if (fp8_model) fp8_model->set_page_release(on);
+    }
 
     // EXTENSION: sampled decoding (mli_engine_add_item_sampled).  The parameters live here, keyed by item
     // id, so a preempted item keeps its stream; the decoder head reads them from per-slot device arrays, filled when an
@@ -276,6 +288,7 @@ struct mli_engine {
 
     void start() {
         if (pages) pages->set_length_reset_quirk(cfg.reference_length_reset_quirk != 0);
+        apply_page_release();
         get_global_throughput_counter().reset();
         get_global_throughput_counter().start_record();
         std::vector<int> all(cfg.n_batch);
@@ -293,6 +306,7 @@ struct mli_engine {
         if (!paged() || 2 * cfg.n_forward_rounds > PAGE_BLOCK_SIZE)
             throw std::runtime_error("the pipelined loop serves the paged kinds with n_forward_rounds <= PAGE_BLOCK_SIZE / 2");
         pages->set_length_reset_quirk(cfg.reference_length_reset_quirk != 0);
+        apply_page_release();
         get_global_throughput_counter().reset();
         choose_head();
         started = true;
@@ -474,6 +488,33 @@ int mli_engine_set_sinks(mli_engine* e, int n_sink) {
             if (e->fp8_model) e->fp8_model->set_sinks(n_sink);
             e->n_sink = n_sink;
         }
+    })
+}
+
+// Release rides on the window as the sinks do: the switch is kept and read at the first step or run, so it combines with
+// set_window / set_sinks / set_heads in any order, and without an effective window nothing changes.
+int mli_engine_set_page_release(mli_engine* e, int enabled) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (e->cfg.kind == MLI_ENGINE_CONTIGUOUS)
+            throw std::runtime_error("mli_engine_set_page_release: early page release serves the paged engines");
+        if (e->started) throw std::runtime_error("mli_engine_set_page_release after the engine has started");
+        if (e->cfg.reference_length_reset_quirk)
+            throw std::runtime_error("mli_engine_set_page_release: not with reference_length_reset_quirk (it moves device "
+                                     "lengths backwards; release rests on lengths that only grow)");
+        e->release_pages = enabled != 0;
+    })
+}
+
+int mli_engine_get_page_stats(mli_engine* e, mli_engine_page_stats* out) {
+    MLI_GUARD({
+        if (!e || !out) throw std::runtime_error("null argument");
+        if (!e->pool || !e->pages) throw std::runtime_error("mli_engine_get_page_stats: the contiguous engine has no page pool");
+        out->pool_pages = e->pool->pool_pages();
+        out->in_use = e->pool->pages_in_use();
+        out->peak_in_use = e->pool->peak_pages_in_use();
+        out->released_early = e->pages->pages_released_early();
+        out->preemptions = e->pages->preemptions();
     })
 }
 

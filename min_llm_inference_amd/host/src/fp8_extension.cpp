@@ -26,6 +26,14 @@ void PagedAttentionFp8Layer::prefill(const TensorFloat& emb_table, const TensorF
                                      TensorFloatPoint& page_table, const TensorInt& lengths,
                                      const TensorInt& new_item_indices, int n_new_items) {
     if (n_new_items == 0) return;
+    if (page_release_) {   // the live tokens only; no table entry of a dead page is followed
+        HIP_CHECK(mli_paged_prefill_window(emb_table.data(), pos_emb.data(), inp.data(),
+                                           reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
+                                           new_item_indices.data(), wk_.data(), wv_.data(), (int)inp.shape()[0],
+                                           (int)inp.shape()[1], (int)emb_table.shape()[1], n_new_items,
+                                           window_ > 0 ? window_ : 0, n_sink_, MLI_ELEM_FP8, mli::runtime::compute_stream()));
+        return;
+    }
     HIP_CHECK(mli_paged_prefill(emb_table.data(), pos_emb.data(), inp.data(),
                                 reinterpret_cast<void* const*>(page_table.data()), lengths.data(), new_item_indices.data(),
                                 wk_.data(), wv_.data(), (int)inp.shape()[0], (int)inp.shape()[1],

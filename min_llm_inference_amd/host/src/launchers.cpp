@@ -257,6 +257,16 @@ void launch_paged_prefill(const TensorFloat& emb_table, const TensorFloat& wpe, 
                                 (int)inp.shape()[1], (int)emb_table.shape()[1], n_new_items, /*elem_bf16=*/0, stream()));
 }
 
+void launch_paged_prefill_window(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,
+                                 TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
+                                 const TensorFloat& wk, const TensorFloat& wv, int n_new_items, int window, int n_sink) {
+    if (n_new_items == 0) return;
+    HIP_CHECK(mli_paged_prefill_window(emb_table.data(), wpe.data(), inp.data(), reinterpret_cast<void* const*>(pages(page_table)),
+                                       lengths.data(), new_item_indices.data(), wk.data(), wv.data(), (int)inp.shape()[0],
+                                       (int)inp.shape()[1], (int)emb_table.shape()[1], n_new_items, window > 0 ? window : 0,
+                                       n_sink, MLI_ELEM_F32, stream()));
+}
+
 void launch_prefill(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,
                     TensorFloat& inp_embedding, const TensorInt& lengths, const TensorInt& new_item_indices,
                     const TensorFloat& wk, const TensorFloat& wv, TensorFloat& kt_cache, TensorFloat& v_cache,

@@ -60,13 +60,21 @@ void PagedAttentionLayer::forward(TensorFloatPoint& page_table, const TensorInt&
 void PagedAttentionLayer::prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
                                   TensorFloatPoint& page_table, const TensorInt& lengths,
                                   const TensorInt& new_item_indices, int n_new_items) {
-    launch_paged_prefill(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_, wv_, n_new_items);
+    if (page_release_)
+        launch_paged_prefill_window(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_, wv_, n_new_items,
+                                    window_, n_sink_);
+    else
+        launch_paged_prefill(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_, wv_, n_new_items);
 }
 
 void PagedAttentionCublasLayer::prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
                                         TensorFloatPoint& page_table, const TensorInt& lengths,
                                         const TensorInt& new_item_indices, int n_new_items) {
-    launch_paged_prefill(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_, wv_, n_new_items);
+    if (page_release_)
+        launch_paged_prefill_window(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_, wv_, n_new_items,
+                                    window_, n_sink_);
+    else
+        launch_paged_prefill(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_, wv_, n_new_items);
 }
 
 PagedAttentionCublasLayer::PagedAttentionCublasLayer(TensorFloat&& wk, TensorFloat&& wq, TensorFloat&& wv,

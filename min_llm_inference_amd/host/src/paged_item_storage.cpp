@@ -5,8 +5,17 @@
 #include <iterator>
 #include <stdexcept>
 
+#include "../../csrc/page_live.hpp"   // the rule the windowed prefill compiles too; reached without an include path
 #include "constants.h"
 #include "utils.h"
+
+static_assert(mli::kLivePage == PAGE_BLOCK_SIZE, "page_live.hpp counts in pages of PAGE_BLOCK_SIZE tokens");
+
+// tests/cpp/page_release_test.cpp builds this file with one deliberate fault (-DMLI_PAGE_RELEASE_MUTANT=1 .. 6) to show
+// that it notices; the product never defines it.
+#ifndef MLI_PAGE_RELEASE_MUTANT
+#define MLI_PAGE_RELEASE_MUTANT 0
+#endif
 
 namespace {
 bool g_length_reset_quirk = false;  // only the DEFAULT a newly built PagedAttentionsManager starts with
@@ -17,7 +26,8 @@ bool reference_length_reset_quirk() { return g_length_reset_quirk; }
 
 // ---- MemoryBlockManager -------------------------------------------------------------------------------
 MemoryBlockManager::MemoryBlockManager(int n_blocks, size_t each_block_size)
-    : block_memory_(std::vector<size_t>{static_cast<size_t>(n_blocks) * each_block_size}, DeviceType::DEVICE) {
+    : block_memory_(std::vector<size_t>{static_cast<size_t>(n_blocks) * each_block_size}, DeviceType::DEVICE),
+      n_blocks_(n_blocks) {
     float* base = block_memory_.data();
     for (int i = 0; i < n_blocks; ++i) free_blocks_.push_back(base + static_cast<size_t>(i) * each_block_size);
 }
@@ -29,6 +39,7 @@ std::list<float*> MemoryBlockManager::pop_free_blocks(int size) {
     std::list<float*> taken;
     auto last = std::next(free_blocks_.begin(), size);
     taken.splice(taken.end(), free_blocks_, free_blocks_.begin(), last);
+    peak_in_use_ = std::max(peak_in_use_, pages_in_use());
     return taken;
 }
 
@@ -40,7 +51,8 @@ void MemoryBlockManager::return_free_blocks(std::list<float*>&& blocks) {
 PagedAttentionsManager::PagedAttentionsManager(size_t max_batches, size_t n_sequence, size_t /*emb_dim*/)
     : page_table_host(std::vector<size_t>{max_batches, n_sequence / PAGE_BLOCK_SIZE}, DeviceType::HOST),
       page_table_device(std::vector<size_t>{max_batches, n_sequence / PAGE_BLOCK_SIZE}, DeviceType::DEVICE),
-      width_(n_sequence / PAGE_BLOCK_SIZE), needs_sync_(false), length_reset_quirk_(g_length_reset_quirk) {
+      width_(n_sequence / PAGE_BLOCK_SIZE), needs_sync_(false), length_reset_quirk_(g_length_reset_quirk),
+      row_pages_(max_batches) {
     assert(n_sequence % PAGE_BLOCK_SIZE == 0);
     // every entry starts null on both sides: a kernel that meets a row without pages skips it instead of
     // dereferencing whatever the allocation held
@@ -83,10 +95,63 @@ void PagedAttentionsManager::add_batch_block_pair(BatchIdMemoryBlocksPair&& row)
     needs_sync_ = true;
 }
 
+void PagedAttentionsManager::set_page_release(int window, int n_sink) {
+    if (!used_blocks_.empty()) throw std::runtime_error("set_page_release: rows are in flight");
+    const long long S = static_cast<long long>(width_) * PAGE_BLOCK_SIZE;
+    const bool on = window > 0 && window < S && n_sink >= 0 && static_cast<long long>(n_sink) + window < S;
+    if (on && length_reset_quirk_) throw std::runtime_error("set_page_release: not with the reference's length-reset quirk");
+    release_window_ = on ? window : 0;
+    release_sink_ = on ? n_sink : 0;
+}
+
+void PagedAttentionsManager::add_row_at(int batch_id, std::list<float*>&& blocks, const std::vector<int>& indices) {
+    assert(blocks.size() == indices.size() && !indices.empty());
+    // entries between the pages stay null on both sides: the last occupant of the slot may have left pointers there
+    // that by now name another row's pages (the kernels never follow them; a stale pointer should still not sit there)
+    size_t k = 0;
+    auto block = blocks.begin();
+    for (int i = 0; i <= indices.back(); ++i) {
+        if (indices[k] == i) {
+            set_block_pos(batch_id, i, *block++);
+            ++k;
+        } else if (block_at(batch_id, i) != nullptr) {
+            set_block_pos(batch_id, i, nullptr);
+        }
+    }
+    RowPages& state = row_pages(batch_id);
+    state.next_page = indices.back() + 1;
+    state.first_window = mli::live_sink_pages(release_sink_);
+    used_blocks_.push_back(std::make_pair(batch_id, std::move(blocks)));
+}
+
+int PagedAttentionsManager::release_dead_pages(MemoryBlockManager& pool, BatchIdMemoryBlocksPair& row, int n_tokens) {
+    RowPages& state = row_pages(row.first);
+    const int ps = MLI_PAGE_RELEASE_MUTANT == 2 ? 0 : mli::live_sink_pages(release_sink_);
+    const int p0 = std::min(mli::live_window_page(n_tokens + (MLI_PAGE_RELEASE_MUTANT == 1), release_window_) + (MLI_PAGE_RELEASE_MUTANT == 3), state.next_page);
+    int n = 0;
+    std::list<float*> freed;
+    for (int i = std::max(MLI_PAGE_RELEASE_MUTANT == 2 ? 0 : state.first_window, ps); i < p0; ++i) {
+        float* block = block_at(row.first, i);
+        if (block == nullptr) continue;   // not taken at admission
+        auto held = std::find(row.second.begin(), row.second.end(), block);
+        assert(held != row.second.end());
+        if (MLI_PAGE_RELEASE_MUTANT == 6) freed.push_back(block);   // (returned, and still held: returned again when the row leaves)
+        else freed.splice(freed.end(), row.second, held);
+        set_block_pos(row.first, i, nullptr);
+        ++n;
+    }
+    state.first_window = std::max(state.first_window, p0);
+    pool.return_free_blocks(std::move(freed));
+    released_early_ += n;
+    return n;
+}
+
 void allocate_memory_block(MemoryBlockManager& pool, PagedAttentionsManager& pages, BatchIdMemoryBlocksPair& row) {
     float* block = pool.pop_free_blocks(1).front();
     row.second.push_front(block);
-    pages.set_block_pos(row.first, static_cast<int>(row.second.size()) - 1, block);
+    // the list's length is the next page index only while nothing has been released from it
+    const int at = pages.page_release() ? pages.row_pages(row.first).next_page++ : static_cast<int>(row.second.size()) - 1;
+    pages.set_block_pos(row.first, at, block);
 }
 
 void allocate_or_free_memory_blocks_if_needed(PagedAttentionsManager& pages, MemoryBlockManager& pool,
@@ -116,6 +181,14 @@ void allocate_or_free_memory_blocks_if_needed(PagedAttentionsManager& pages, Mem
         }
     }
 
+    // 1b. early release (PagedAttentionsManager::set_page_release): every row returns the pages dead at its HOST token
+    //     count.  That count is a lower bound of the device length every forward not yet completed sees (equal in the
+    //     sequential loop, up to n_forward_rounds behind in the pipelined one), and a page dead at n is dead at every
+    //     n' >= n.  Before growth and preemption, which may take these pages in the same pass.
+    if (pages.page_release())
+        for (BatchIdMemoryBlocksPair& row : rows)
+            pages.release_dead_pages(pool, row, static_cast<int>(processing_storage.get_token(row.first).second.size()));
+
     // 2. rows whose next n_forward_rounds tokens no longer fit get one more page; when the pool is dry
     //    the most recently admitted row (list tail) is pushed back to the head of the queue
     for (auto it = rows.begin(); it != rows.end();) {
@@ -127,7 +200,8 @@ void allocate_or_free_memory_blocks_if_needed(PagedAttentionsManager& pages, Mem
         // its tests only ever run n_forward_rounds == 1.
         const size_t row_capacity = static_cast<size_t>(pages.max_blocks_per_row()) * PAGE_BLOCK_SIZE;
         const size_t needed = std::min(n_tokens + n_forward_rounds, row_capacity);
-        if (needed <= it->second.size() * PAGE_BLOCK_SIZE) {
+        const size_t covered = pages.page_release() ? static_cast<size_t>(pages.row_pages(it->first).next_page) : it->second.size();
+        if (needed <= covered * PAGE_BLOCK_SIZE) {
             ++it;
             continue;
         }
@@ -141,11 +215,13 @@ void allocate_or_free_memory_blocks_if_needed(PagedAttentionsManager& pages, Mem
             processing_storage.move_to_new(it->first, item_storage);
             pool.return_free_blocks(std::move(it->second));
             it = rows.erase(it);
+            pages.count_preemption();
         } else {
             BatchIdMemoryBlocksPair victim(std::move(rows.back()));
             rows.pop_back();
             processing_storage.move_to_new(victim.first, item_storage);
             pool.return_free_blocks(std::move(victim.second));
+            pages.count_preemption();
         }
     }
 }
@@ -173,7 +249,13 @@ PagedAdmission admit_new_items(int* inp, int* lengths, int* new_idx, int max_bat
         // (The reference uploads whenever any slot is free; kept under the quirk switch.)
         if (lengths[slot] != 0 || quirk) result.lengths_changed = true;
         const int width = pages.max_blocks_per_row();
-        const bool can_admit = pool.free_blocks_size() >= DEFAULT_INIT_NUM_BLOCKS && item_storage.new_count() > 0 &&
+        // release on: exactly the item's live pages for its tokens + n_forward_rounds positions (the minimum of
+        // DEFAULT_INIT_NUM_BLOCKS pages would defeat the per-row bound)
+        const bool release = pages.page_release();
+        const int W = pages.release_window(), K = pages.release_sinks();
+        const bool can_admit = release ? item_storage.new_count() > 0 &&
+                                             pool.free_blocks_size() >= mli::live_pages_covering(item_storage.head_length(), n_forward_rounds, W, K, width)
+                                       : pool.free_blocks_size() >= DEFAULT_INIT_NUM_BLOCKS && item_storage.new_count() > 0 &&
                                pool.free_blocks_size() >= std::min(width, ceil_div(item_storage.head_length() + n_forward_rounds, PAGE_BLOCK_SIZE));
         if (!can_admit) {
             lengths[slot] = 0;
@@ -186,8 +268,18 @@ PagedAdmission admit_new_items(int* inp, int* lengths, int* new_idx, int max_bat
         result.lengths_changed = true;
         std::copy(item.second.begin(), item.second.end(), inp + static_cast<size_t>(slot) * n_sequence);
         new_idx[result.slots.size()] = slot;
-        const int n_pages = std::min(width, std::max(ceil_div(n_tokens + n_forward_rounds, PAGE_BLOCK_SIZE), DEFAULT_INIT_NUM_BLOCKS));
         processing_storage.put(slot, std::move(item));
+        if (release) {
+            const int ahead = MLI_PAGE_RELEASE_MUTANT == 5 ? 0 : n_forward_rounds;
+            const int top = std::min(width, ceil_div(n_tokens + ahead, PAGE_BLOCK_SIZE));
+            std::vector<int> indices;
+            for (int i = 0; i < top; ++i)
+                if (!mli::page_dead(i, n_tokens, W, K)) indices.push_back(MLI_PAGE_RELEASE_MUTANT == 4 ? static_cast<int>(indices.size()) : i);
+            pages.add_row_at(slot, pool.pop_free_blocks(static_cast<int>(indices.size())), indices);
+            result.slots.push_back(slot);
+            continue;
+        }
+        const int n_pages = std::min(width, std::max(ceil_div(n_tokens + n_forward_rounds, PAGE_BLOCK_SIZE), DEFAULT_INIT_NUM_BLOCKS));
         pages.add_batch_block_pair(std::make_pair(slot, pool.pop_free_blocks(n_pages)));
         result.slots.push_back(slot);
     }

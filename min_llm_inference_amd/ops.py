@@ -330,9 +330,20 @@ def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_outpu
                n_sequence, wk.shape[0], extra, n_heads, _elem_of(wk, elem), q_output.device)
 
 
-def paged_prefill(emb_table, wpe, inp, page_table, lengths, new_item_indices, wk, wv, n_new_items, elem=None):
-    """Encoder + prefill fill in one launch (mli_paged_prefill); page element type = elem, default from the weights."""
+def paged_prefill(emb_table, wpe, inp, page_table, lengths, new_item_indices, wk, wv, n_new_items, elem=None, window=None,
+                  sinks=None):
+    """Encoder + prefill fill in one launch (mli_paged_prefill); page element type = elem, default from the weights.
+    window given (sinks beside it): the prefill of the rows' live tokens (mli_paged_prefill_window) -- pages between the
+    sink pages and the window's first page are neither looked up nor written."""
     B, S = inp.shape
+    if sinks is not None and window is None:
+        raise ValueError("sinks exist beside a window: pass window= as well")
+    if window is not None:
+        _check(load_library().mli_paged_prefill_window(_p(emb_table), _p(wpe), _p(inp), _p(page_table), _p(lengths),
+                                                       _p(new_item_indices), _p(wk), _p(wv), B, S, emb_table.shape[1],
+                                                       n_new_items, window, sinks or 0, _elem_of(wk, elem), _stream()),
+               "mli_paged_prefill_window")
+        return
     _check(load_library().mli_paged_prefill(_p(emb_table), _p(wpe), _p(inp), _p(page_table), _p(lengths),
                                             _p(new_item_indices), _p(wk), _p(wv), B, S, emb_table.shape[1], n_new_items,
                                             _elem_of(wk, elem), _stream()), "mli_paged_prefill")
