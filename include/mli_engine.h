@@ -129,6 +129,21 @@ int mli_engine_configure(mli_engine* engine, int lean_layers, int step_graphs);
  * nothing.  Loops, step graphs, preemption, sampling and n_forward_rounds work as with one head. */
 int mli_engine_set_heads(mli_engine* engine, int n_heads);
 
+/* EXTENSION: grouped-query attention (mli_kernels.h: mli_paged_attention_lean_gqa).  n_kv_heads K/V heads serve the
+ * engine's n_heads query heads: query head h attends K/V head h / (n_heads / n_kv_heads), which owns columns
+ * [(h / g) * head_dim, (h / g + 1) * head_dim) of K and V.  Only the first n_kv_heads * head_dim output columns of the
+ * engine's wk / wv matter; pages, pool, projection, prefill and the heads do not change.  Before the first step or run.
+ * n_kv_heads must divide the engine's CURRENT n_heads (set the heads first); n_kv_heads == n_heads is accepted by every
+ * engine kind and changes nothing (on an engine that holds a grouping it takes the grouping away: every head has its own
+ * K/V head again, and nothing stays stored).  Anything else needs MLI_ENGINE_PAGED, MLI_ENGINE_PAGED_GEMM or
+ * MLI_ENGINE_PAGED_BF16 with lean layers (mli_engine_configure(e, 0, ...) afterwards is refused likewise) and is STORED:
+ * a later mli_engine_set_heads keeps the stored n_kv_heads, and is refused for a value n_kv_heads does not divide (for
+ * n_heads == n_kv_heads every head has its own K/V head until the heads change again).  -1 with a message that names
+ * n_kv_heads for n_kv_heads < 1, a non-divisor, another kind, lean_layers = 0 or a call after the first step.  Composes
+ * in any order with window, sinks, page release, sampling, n_forward_rounds, step graphs and both loops: none of them
+ * looks at K / V columns. */
+int mli_engine_set_kv_heads(mli_engine* engine, int n_kv_heads);
+
 /* EXTENSION: sliding-window attention (mli_kernels.h: mli_paged_attention_lean_window).  Every row attends its newest
  * `window` tokens only.  The window changes which slots the scan reads and nothing else: admission, page growth,
  * preemption, re-prefill, n_forward_rounds (the window follows the device-side length), step graphs, sampling and the

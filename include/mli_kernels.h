@@ -278,6 +278,31 @@ int mli_paged_attention_lean_sinks(void* const* page_table, const int* lengths, 
                                    int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int window,
                                    int n_sink, int elem, void* workspace, size_t workspace_bytes, void* stream);
 
+/* EXTENSION: GROUPED-QUERY ATTENTION for the multi-head scan.  n_kv_heads = Hkv K/V heads serve n_heads = H query heads,
+ * 1 <= Hkv <= H, H % Hkv == 0, g = H / Hkv (any integer; Hkv = 1 is multi-query attention), hd = emb_dim / H.  Query head h
+ * owns columns [h * hd, (h + 1) * hd) of q_output and attention_result, as with mli_decode_scan_paged_heads, and attends
+ * K/V head h / g, which owns columns [(h / g) * hd, (h / g + 1) * hd) of the K and the V segment of every page slot; the
+ * columns >= Hkv * hd of those segments are never read (they may hold anything).  Scores are scaled by 1 / sqrtf(hd).  The
+ * result is that of the _sinks call with H heads on pages whose K / V column block h is a copy of block h / g, bit for bit.
+ * Page layout, fill, projection and q_output do not depend on Hkv: wk / wv keep their [emb_dim, emb_dim] shape and only
+ * their first Hkv * hd output columns matter.  window <= 0 or >= n_sequence: no window; n_sink = 0: no sinks; the attended
+ * slots, the zero row for L == 0 and the never-read gap are mli_decode_scan_paged_sinks's.
+ * Hand-off, before anything else, same kernels and same bits: n_kv_heads == n_heads IS the _sinks call (n_heads = 1
+ * included).  Otherwise one scan launch with the grid, item size, mli_tune keys and workspace
+ * (mli_attention_heads_workspace_bytes(n_batch, n_sequence, emb_dim, n_heads)) of H heads; the K / V bytes read fall by g.
+ * elem = MLI_ELEM_F32 or MLI_ELEM_BF16.  MLI_ERR_BAD_ARG, decided before anything is launched: another elem, Hkv < 1,
+ * Hkv > H, H % Hkv != 0, n_sink < 0, and every shape the _heads / _window entry points refuse.  MLI_ERR_WORKSPACE: a shape
+ * of several items per row without the workspace, as for _heads. */
+int mli_decode_scan_paged_gqa(const float* q_output, const void* const* page_table, const int* lengths,
+                              float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads,
+                              int window, int n_sink, int elem, void* workspace, size_t workspace_bytes, void* stream);
+
+/* mli_paged_attention_lean_sinks with grouped K/V heads: fill (n_new_items rows) -> latest -> the scan above. */
+int mli_paged_attention_lean_gqa(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                 const int* new_batch_idx, float* q_output, float* attention_result, int n_batch,
+                                 int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
+                                 int n_sink, int elem, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */

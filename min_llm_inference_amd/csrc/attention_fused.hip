@@ -161,8 +161,8 @@ extern "C" int mli_decode_scan_paged(const float* q_output, const void* const* p
     if (elem_bf16 < MLI_ELEM_F32 || elem_bf16 > MLI_ELEM_FP8) return MLI_ERR_BAD_ARG;
     if (elem_bf16 == MLI_ELEM_FP8 && !(phases & 4)) return MLI_ERR_BAD_ARG;   // the fp8 extension has the lean form only
     if (phases == 7)   // the whole lean job
-        return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, 1, 0,
-                                     0, elem_bf16, workspace, workspace_bytes, st);
+        return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, 1, 1,
+                                     0, 0, elem_bf16, workspace, workspace_bytes, st);
     const mli::WsBody body = mli::ws_body(workspace, workspace_bytes);
     // not applicable: shape not covered by the single-pass kernel (emb_dim too wide) or no workspace
     return mli::fused_status(mli::launch_fused_decode_elem(elem_bf16, q_output, page_table, lengths, qkt_output, attention_result,

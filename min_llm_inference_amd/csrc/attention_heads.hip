@@ -78,8 +78,8 @@ int mli_decode_scan_paged_heads(const float* q_output, const void* const* page_t
                                 void* workspace, size_t workspace_bytes, void* stream) {
     if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) return MLI_ERR_BAD_ARG;
     if (n_heads != 1 && mli::heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem) < 0) return MLI_ERR_BAD_ARG;
-    return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads, 0,
-                                 0, elem, workspace, workspace_bytes, mli::as_stream(stream));
+    return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
+                                 n_heads, 0, 0, elem, workspace, workspace_bytes, mli::as_stream(stream));
 }
 
 // n_heads == 1 is mli_paged_attention_lean; fill and projection do not depend on n_heads
@@ -90,7 +90,7 @@ int mli_paged_attention_lean_heads(void* const* page_table, const int* lengths, 
     if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) return MLI_ERR_BAD_ARG;
     if (n_heads != 1 && mli::heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem) < 0) return MLI_ERR_BAD_ARG;
     return mli::launch_lean_attention(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
-                                      n_batch, n_sequence, emb_dim, n_new_items, n_heads, 0, 0, workspace, workspace_bytes,
+                                      n_batch, n_sequence, emb_dim, n_new_items, n_heads, n_heads, 0, 0, workspace, workspace_bytes,
                                       mli::as_stream(stream));
 }
 

@@ -109,7 +109,7 @@ int mli_decode_scan_paged_window(const float* q_output, const void* const* page_
     }
     if (!mli::window_shape_supported(n_batch, n_sequence, emb_dim, n_heads, elem)) return MLI_ERR_BAD_ARG;
     return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
-                                 window, 0, elem, workspace, workspace_bytes, mli::as_stream(stream));
+                                 n_heads, window, 0, elem, workspace, workspace_bytes, mli::as_stream(stream));
 }
 
 // fill and projection do not depend on the window
@@ -128,7 +128,8 @@ int mli_paged_attention_lean_window(void* const* page_table, const int* lengths,
     }
     if (!mli::window_shape_supported(n_batch, n_sequence, emb_dim, n_heads, elem)) return MLI_ERR_BAD_ARG;
     return mli::launch_lean_attention(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
-                                      n_batch, n_sequence, emb_dim, n_new_items, n_heads, window, 0, workspace, workspace_bytes,
+                                      n_batch, n_sequence, emb_dim, n_new_items, n_heads, n_heads, window, 0, workspace,
+                                      workspace_bytes,
                                       mli::as_stream(stream));
 }
 

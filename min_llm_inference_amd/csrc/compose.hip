@@ -91,8 +91,13 @@ static int launch_fill_and_latest(int elem, void* const* page_table, const int* 
 }
 
 int launch_lean_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
-                     int n_heads, int window, int n_sink, int elem, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                     int n_heads, int n_kv_heads, int window, int n_sink, int elem, void* workspace, size_t workspace_bytes,
+                     hipStream_t st) {
     const WsBody body = ws_body(workspace, workspace_bytes);
+    // grouped-query attention (attention_gqa.hip) only where the K/V heads are fewer: everything else is the path below
+    if (n_kv_heads != n_heads)
+        return launch_gqa_scan(q, page_table, lengths, out, B, S, D, n_heads, n_kv_heads, window, n_sink, elem, body.ptr,
+                               body.bytes, st);
     const ScanKind kind = lean_scan_kind(S, window, n_sink);
     if (kind == kScanSinks)
         return launch_sink_scan(q, page_table, lengths, out, B, S, D, n_heads, window, n_sink, elem, body.ptr, body.bytes, st);
@@ -106,12 +111,12 @@ int launch_lean_scan(const float* q, const void* const* page_table, const int* l
 
 int launch_lean_attention(int elem, void* const* page_table, const int* lengths, const void* wk, const void* wq,
                           const void* wv, const int* new_batch_idx, float* q_output, float* out, int B, int S, int D,
-                          int n_new_items, int n_heads, int window, int n_sink, void* workspace, size_t workspace_bytes,
-                          hipStream_t st) {
+                          int n_new_items, int n_heads, int n_kv_heads, int window, int n_sink, void* workspace,
+                          size_t workspace_bytes, hipStream_t st) {
     const int rc = launch_fill_and_latest(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, B, S, D, n_new_items, st);
     if (rc) return rc;
-    return launch_lean_scan(q_output, reinterpret_cast<const void* const*>(page_table), lengths, out, B, S, D, n_heads, window,
-                            n_sink, elem, workspace, workspace_bytes, st);
+    return launch_lean_scan(q_output, reinterpret_cast<const void* const*>(page_table), lengths, out, B, S, D, n_heads,
+                            n_kv_heads, window, n_sink, elem, workspace, workspace_bytes, st);
 }
 }  // namespace mli
 
@@ -127,7 +132,7 @@ int mli_paged_attention_lean(void* const* page_table, const int* lengths, const 
                              size_t workspace_bytes, void* stream) {
     if (elem_bf16 < MLI_ELEM_F32 || elem_bf16 > MLI_ELEM_FP8) return MLI_ERR_BAD_ARG;
     return mli::launch_lean_attention(elem_bf16, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
-                                      n_batch, n_sequence, emb_dim, n_new_items, 1, 0, 0, workspace, workspace_bytes,
+                                      n_batch, n_sequence, emb_dim, n_new_items, 1, 1, 0, 0, workspace, workspace_bytes,
                                       mli::as_stream(stream));
 }
 

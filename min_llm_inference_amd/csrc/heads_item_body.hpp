@@ -13,6 +13,7 @@
 #pragma once
 
 #include "scan_item_body.hpp"
+#include "scan_plan.hpp"
 
 namespace mli {
 
@@ -54,11 +55,15 @@ __device__ __forceinline__ void heads_xor_step(float (&v)[NJ][16]) {
 // switch: the row is taken from its first live page p0 on, and that page's slots below the window are masked.
 // SINK = true (EXTENSION, attention_sinks.hip; with WIN): fused_scan_item's sink switch -- the first n_sink tokens are attended
 // too, on the virtual row of sink pages + window pages; the mask is per slot of the lane's 16.
-template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false, bool SINK = false>
+// GQA = true (EXTENSION, attention_gqa.hip): grouped-query attention, gq = n_heads / n_kv_heads query heads per K/V head.  Only
+// the unit a lane LOADS changes (gqa_kv_unit, scan_plan.hpp): the lanes of query head h read the K and V columns of K/V head
+// h / gq.  q, the per-lane state, the all-reduce inside a group, the merges and H are those of n_heads heads.
+template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false, bool SINK = false, bool GQA = false>
 __device__ __forceinline__ void heads_scan_item(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ out, float2* ml, float* partial, int S, int D, int lg, int H, int ct, int nchunk_max, int direct,
-    unsigned* arrivals, int b, int c, bool first_grid_row, unsigned char* smem_raw, int window = 0, int n_sink = 0) {
+    unsigned* arrivals, int b, int c, bool first_grid_row, unsigned char* smem_raw, int window = 0, int n_sink = 0,
+    int gq = 1) {
     static_assert(!SINK || WIN, "sinks exist beside a window only");
     constexpr int EPL = E::EPL;
     constexpr int kRowF = NJ * kWave * EPL;   // floats one wave parks
@@ -84,7 +89,9 @@ __device__ __forceinline__ void heads_scan_item(
         const int u = lane + j * kWave;
         const bool live = u < Du;   // dead lanes come in whole groups (Du = H * G): they score zeros nobody reads
         // lanes beyond the row get an offset outside the page block: the buffer range check returns zeros for them
-        voff[j] = live ? (unsigned)u * 16u : 0x40000000u;
+        // (the old statement stays verbatim in the else branch, as for SINK below)
+        if constexpr (GQA) voff[j] = live ? (unsigned)gqa_kv_unit(u, lg, gq) * 16u : 0x40000000u;
+        else voff[j] = live ? (unsigned)u * 16u : 0x40000000u;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) qr[j][e] = live ? q[(int64_t)b * D + u * EPL + e] : 0.f;
     }

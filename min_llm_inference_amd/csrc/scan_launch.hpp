@@ -32,15 +32,20 @@ int launch_window_scan(const float* q, const void* const* page_table, const int*
                        int H, int window, int elem, void* ws, size_t ws_bytes, hipStream_t st);     // attention_window.hip
 int launch_sink_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
                      int H, int window, int n_sink, int elem, void* ws, size_t ws_bytes, hipStream_t st);   // attention_sinks.hip
-// compose.hip: the lean scan for (n_heads, window, n_sink) -- window 0 or >= n_sequence: none; n_sink 0, or n_sink + window >=
-// n_sequence: no sinks, or no gap they could bridge -- over the caller's WHOLE workspace; returns a C ABI status.
+// attention_gqa.hip: n_kv_heads < n_heads (gqa_shape_supported), plain, windowed or with sinks by lean_scan_kind
+int launch_gqa_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D, int H,
+                    int Hkv, int window, int n_sink, int elem, void* ws, size_t ws_bytes, hipStream_t st);
+// compose.hip: the lean scan for (n_heads, n_kv_heads, window, n_sink) -- n_kv_heads == n_heads: no grouping, the scans
+// above; window 0 or >= n_sequence: none; n_sink 0, or n_sink + window >= n_sequence: no sinks, or no gap they could bridge
+// -- over the caller's WHOLE workspace; returns a C ABI status.
 // launch_lean_attention: launch_fill_and_latest, then that scan over q_output.
 int launch_lean_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
-                     int n_heads, int window, int n_sink, int elem, void* workspace, size_t workspace_bytes, hipStream_t st);
+                     int n_heads, int n_kv_heads, int window, int n_sink, int elem, void* workspace, size_t workspace_bytes,
+                     hipStream_t st);
 int launch_lean_attention(int elem, void* const* page_table, const int* lengths, const void* wk, const void* wq,
                           const void* wv, const int* new_batch_idx, float* q_output, float* out, int B, int S, int D,
-                          int n_new_items, int n_heads, int window, int n_sink, void* workspace, size_t workspace_bytes,
-                          hipStream_t st);
+                          int n_new_items, int n_heads, int n_kv_heads, int window, int n_sink, void* workspace,
+                          size_t workspace_bytes, hipStream_t st);
 
 // launch_fused_decode_elem's protocol as a C ABI status: "not applicable" is a bad argument
 inline int fused_status(int r) { return r == 1 ? 0 : r == 0 ? MLI_ERR_BAD_ARG : r < 0 ? r : r - 1; }

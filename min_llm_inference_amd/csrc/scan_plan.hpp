@@ -1,8 +1,8 @@
 // The launch plan of the chunked paged scans -- the single-head scan (attention_fused.hip), the multi-head scan
-// (attention_heads.hip), their sliding-window forms (attention_window.hip) and those with sinks (attention_sinks.hip):
-// every rule that decides how such a scan is launched, once.  Plain C++ over int / size_t / bool, no HIP types and no
-// global state (tests/cpp/scan_plan_test.cpp compiles it alone); the mli_tune values the rules depend on come in as a
-// ScanTune.
+// (attention_heads.hip), their sliding-window forms (attention_window.hip), those with sinks (attention_sinks.hip) and the
+// grouped-query forms (attention_gqa.hip): every rule that decides how such a scan is launched, once.  Plain C++ over int /
+// size_t / bool, no HIP types and no global state (tests/cpp/scan_plan_test.cpp compiles it alone); the mli_tune values the
+// rules depend on come in as a ScanTune.
 #pragma once
 
 #include <cstddef>
@@ -126,8 +126,10 @@ struct ScanPlan {
     bool nt;             // non-temporal K/V loads
 };
 
-// S = n_sequence; span = S, window_span(S, window) or sink_span(S, window, n_sink); esize = bytes per page element
-inline ScanPlan plan_chunked_scan(const ScanTune& t, int B, int S, int span, int D, int H, int esize) {
+// S = n_sequence; span = S, window_span(S, window) or sink_span(S, window, n_sink); esize = bytes per page element.
+// D_read = the columns of a K / V segment the scan reads: D, or with grouped-query attention n_kv_heads * head_dim --
+// the working set the cache policy is judged by.  Everything else follows D: the output and the partial rows are D wide.
+inline ScanPlan plan_chunked_scan(const ScanTune& t, int B, int S, int span, int D, int D_read, int H, int esize) {
     ScanPlan p;
     p.ct = scan_item_tokens(t, B, span, H);
     p.nchunk = plan_ceil_div(span, p.ct);
@@ -137,8 +139,12 @@ inline ScanPlan plan_chunked_scan(const ScanTune& t, int B, int S, int span, int
     p.grid_y = p.direct ? 1 : p.nchunk + 1;
     p.stats_bytes = scan_stats_bytes(B, S, H);
     p.body_bytes = p.stats_bytes + (size_t)B * p.nchunk * D * sizeof(float);
-    p.nt = nt_loads_rule(t.nt_loads, B, span, D, esize);
+    p.nt = nt_loads_rule(t.nt_loads, B, span, D_read, esize);
     return p;
+}
+// every K / V column read: the scans without grouped-query attention
+inline ScanPlan plan_chunked_scan(const ScanTune& t, int B, int S, int span, int D, int H, int esize) {
+    return plan_chunked_scan(t, B, S, span, D, D, H, esize);
 }
 
 // The single-head kernel variant.  epl = elements per 16-byte lane load: 4 (fp32), 8 (bf16), 16 (fp8).
@@ -213,5 +219,19 @@ inline int window_shape_supported(int n_batch, int n_sequence, int emb_dim, int 
     return n_heads == 1 ? window_plain_shape_ok(n_batch, n_sequence, emb_dim, elem)
                         : heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem) >= 0;
 }
+
+// ---- grouped-query attention (attention_gqa.hip) ------------------------------------------------------------------------------
+// n_kv_heads K/V heads serve n_heads query heads, g = n_heads / n_kv_heads (any integer) consecutive query heads each: query
+// head h attends K/V head h / g, which owns columns [(h / g) * hd, (h / g + 1) * hd) of the K and V segments.  The shapes
+// are the multi-head scan's, with or without a window.
+inline int gqa_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads, int elem) {
+    if (n_heads <= 1 || !window_shape_supported(n_batch, n_sequence, emb_dim, n_heads, elem)) return 0;
+    return n_kv_heads >= 1 && n_kv_heads <= n_heads && n_heads % n_kv_heads == 0;
+}
+// The lane map.  A lane's 16-byte unit u lies in query head u >> lg (heads_item_body.hpp: a head is a group of G = 1 << lg
+// lanes); the unit it LOADS from a K or V segment is the same position inside K/V head (u >> lg) / g:
+//   kvu = (u / G / g) * G + u % G,   0 <= kvu < n_kv_heads * G = Dkv / EPL;   g = 1: kvu = u.
+// constexpr, so that the kernel and a host program (tests/cpp/gqa_map_test.cpp) compile this text.
+constexpr int gqa_kv_unit(int u, int lg, int g) { return (((u >> lg) / g) << lg) + (u & ((1 << lg) - 1)); }
 
 }  // namespace mli

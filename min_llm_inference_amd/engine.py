@@ -39,7 +39,7 @@ def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
 class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
                  n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None,
-                 release_pages=False):
+                 release_pages=False, n_kv_heads=None):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -49,6 +49,8 @@ class Engine:
         self._check(self._lib.mli_engine_create(ctypes.byref(self.cfg), *[k[1] for k in keep], ctypes.byref(self._h)))
         if n_heads != 1:
             self.set_heads(n_heads)
+        if n_kv_heads is not None:
+            self.set_kv_heads(n_kv_heads)
         if window is not None:
             self.set_window(window)
         if sinks is not None:
@@ -63,6 +65,12 @@ class Engine:
     def set_heads(self, n_heads):
         """Multi-head attention (mli_engine_set_heads): before the first step or run, fp32 / bf16 paged kinds."""
         self._check(self._lib.mli_engine_set_heads(self._h, int(n_heads)))
+
+    def set_kv_heads(self, n_kv_heads):
+        """Grouped-query attention (mli_engine_set_kv_heads): `n_kv_heads` K/V heads, a divisor of the engine's n_heads,
+        serve the query heads; only the first n_kv_heads * emb_dim / n_heads output columns of wk / wv matter.  Before the
+        first step or run, fp32 / bf16 paged kinds; n_kv_heads == n_heads changes nothing."""
+        self._check(self._lib.mli_engine_set_kv_heads(self._h, int(n_kv_heads)))
 
     def set_window(self, window):
         """Sliding-window attention (mli_engine_set_window): every row attends its newest `window` tokens.  Before the

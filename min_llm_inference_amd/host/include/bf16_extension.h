@@ -49,6 +49,8 @@ public:
                  int n_new_items);
     // attention heads of the lean forward (default 1: one softmax over emb_dim)
     void set_n_heads(int n_heads) { n_heads_ = n_heads; }
+    // EXTENSION: grouped-query attention of the lean forward: K/V heads serving the n_heads query heads (0 = as many)
+    void set_n_kv_heads(int n_kv_heads) { n_kv_heads_ = n_kv_heads; }
     // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
     void set_window(int window) { window_ = window; }
     // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
@@ -61,6 +63,7 @@ private:
     TensorFloat q_output_;
     TensorFloat qkt_output_;
     int n_heads_ = 1;
+    int n_kv_heads_ = 0;
     int window_ = 0;
     int n_sink_ = 0;
     bool page_release_ = false;
@@ -76,6 +79,7 @@ public:
     // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling)
     void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }
     void set_n_heads(int n_heads) { attention_layer_.set_n_heads(n_heads); }
+    void set_n_kv_heads(int n_kv_heads) { attention_layer_.set_n_kv_heads(n_kv_heads); }
     void set_window(int window) { attention_layer_.set_window(window); }
     void set_sinks(int n_sink) { attention_layer_.set_sinks(n_sink); }
     void set_page_release(bool enabled) { attention_layer_.set_page_release(enabled); }

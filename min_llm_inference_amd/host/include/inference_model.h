@@ -37,6 +37,7 @@ public:
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
     void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
     void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
+    void set_n_kv_heads(int n_kv_heads) { paged_attention_layer_.set_n_kv_heads(n_kv_heads); }        // EXTENSION
     void set_window(int window) { paged_attention_layer_.set_window(window); }                        // EXTENSION
     void set_sinks(int n_sink) { paged_attention_layer_.set_sinks(n_sink); }                          // EXTENSION
     void set_page_release(bool enabled) { paged_attention_layer_.set_page_release(enabled); }         // EXTENSION
@@ -61,6 +62,7 @@ public:
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table, GemmHandle handle);
     void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
     void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
+    void set_n_kv_heads(int n_kv_heads) { paged_attention_layer_.set_n_kv_heads(n_kv_heads); }        // EXTENSION
     void set_window(int window) { paged_attention_layer_.set_window(window); }                        // EXTENSION
     void set_sinks(int n_sink) { paged_attention_layer_.set_sinks(n_sink); }                          // EXTENSION
     void set_page_release(bool enabled) { paged_attention_layer_.set_page_release(enabled); }         // EXTENSION

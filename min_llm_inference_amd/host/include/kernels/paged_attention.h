@@ -59,12 +59,21 @@ void paged_attention_lean_sinks(TensorFloatPoint& page_table, const TensorInt& l
                                 TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence,
                                 int n_heads, int window, int n_sink);
 
-// What the four functions above share, and what the fp32 layers call: n_heads heads, window <= 0 or >= n_sequence = none,
-// n_sink sinks beside a window; qkt_output (may be null) serves one head without a window as in paged_attention_lean.
+// EXTENSION: paged_attention_lean_sinks with grouped-query attention: n_kv_heads K/V heads (a divisor of n_heads) serve the
+// n_heads query heads, head h attending K/V head h / (n_heads / n_kv_heads); window <= 0 or >= n_sequence = none, n_sink 0 =
+// no sinks.  wk / wv keep their [emb_dim, emb_dim] shape: their first n_kv_heads * emb_dim / n_heads output columns matter.
+void paged_attention_lean_gqa(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                              const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                              TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence, int n_heads,
+                              int n_kv_heads, int window, int n_sink);
+
+// What the five functions above share, and what the fp32 layers call: n_heads heads, window <= 0 or >= n_sequence = none,
+// n_sink sinks beside a window, n_kv_heads K/V heads (0: as many as n_heads); qkt_output (may be null) serves one head without a
+// window as in paged_attention_lean.
 void paged_attention_lean_layer(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
                                 const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
                                 TensorFloat& q_output, TensorFloat* qkt_output, TensorFloat& attention_result,
-                                int n_new_items, int n_sequence, int n_heads, int window, int n_sink);
+                                int n_new_items, int n_sequence, int n_heads, int window, int n_sink, int n_kv_heads = 0);
 
 // EXTENSION: launch_paged_attention_encoder_kernel + launch_fill_new_k_v_cache_paged_attention in one
 // launch -- the embedding lookup is the fill GEMM's prologue; pages bit-identical to the two-launch form.

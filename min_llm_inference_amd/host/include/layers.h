@@ -40,6 +40,8 @@ public:
 
     // EXTENSION: attention heads of the lean forward (default 1 = the reference's single softmax over emb_dim)
     void set_n_heads(int n_heads) { n_heads_ = n_heads; }
+    // EXTENSION: grouped-query attention of the lean forward: K/V heads serving the n_heads query heads (0 = as many)
+    void set_n_kv_heads(int n_kv_heads) { n_kv_heads_ = n_kv_heads; }
     // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
     void set_window(int window) { window_ = window; }
     // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
@@ -53,6 +55,7 @@ private:
     TensorFloat q_output_;
     TensorFloat qkt_output_;
     int n_heads_ = 1;
+    int n_kv_heads_ = 0;
     int window_ = 0;
     int n_sink_ = 0;
     bool page_release_ = false;
@@ -70,6 +73,8 @@ public:
 
     // EXTENSION: attention heads of the lean forward (default 1 = the reference's single softmax over emb_dim)
     void set_n_heads(int n_heads) { n_heads_ = n_heads; }
+    // EXTENSION: grouped-query attention of the lean forward: K/V heads serving the n_heads query heads (0 = as many)
+    void set_n_kv_heads(int n_kv_heads) { n_kv_heads_ = n_kv_heads; }
     // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
     void set_window(int window) { window_ = window; }
     // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
@@ -83,6 +88,7 @@ private:
     TensorFloat q_output_;
     TensorFloat qkt_output_;
     int n_heads_ = 1;
+    int n_kv_heads_ = 0;
     int window_ = 0;
     int n_sink_ = 0;
     bool page_release_ = false;

@@ -45,11 +45,13 @@ bool lean_layers();
 // lean_scan_kind (scan_plan.hpp) -- window <= 0 or >= n_sequence: none; n_sink counts beside a window only (attention
 // sinks: the first n_sink tokens stay attended).  One head without a window returns the entry point's status
 // (MLI_ERR_BAD_ARG where the rows are too wide for the single-pass kernel: the caller may take its materialising
-// composition); every other form throws on failure.
+// composition); every other form throws on failure.  n_kv_heads (EXTENSION, grouped-query attention): 0 or n_heads = every
+// query head has its own K/V head, the calls above; anything else is mli_paged_attention_lean_gqa.
 bool lean_paged_wanted(int n_heads, int window, int n_sequence);
 int lean_paged_attention(int elem, int n_heads, int window, int n_sink, void* const* page_table, const int* lengths,
                          const void* wk, const void* wq, const void* wv, const int* new_batch_idx, float* q_output,
-                         float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_new_items);
+                         float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_new_items,
+                         int n_kv_heads = 0);
 
 // Which loop start_paged_attention_*_inference_engine runs (default false): the pipelined loop
 // (pipelined_engine.h: the host one step behind the GPU, same tokens per item) wherever it applies -- up to

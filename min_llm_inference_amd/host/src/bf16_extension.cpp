@@ -81,7 +81,8 @@ void PagedAttentionBf16Layer::forward(TensorFloatPoint& page_table, const Tensor
                                                           reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
                                                           wk_.data(), wq_.data(), wv_.data(), new_batch_idx.data(),
                                                           q_output_.data(), attention_result.data(),
-                                                          (int)page_table.shape()[0], n_sequence, D, n_new_items);
+                                                          (int)page_table.shape()[0], n_sequence, D, n_new_items,
+                                                          n_kv_heads_);
         if (rc != MLI_ERR_BAD_ARG || D <= 4096) {  // rows wider than the single-pass kernel covers: fall through
             HIP_CHECK(rc);
             return;

@@ -76,6 +76,7 @@ struct mli_engine {
     bool lean_layers = g_default_lean_layers.load();   // this engine's composition and replay switches (runtime.h)
     bool step_graphs = g_default_step_graphs.load();
     int n_heads = 1;            // mli_engine_set_heads
+    int n_kv_heads = 0;         // mli_engine_set_kv_heads (0: as many as n_heads)
     int window = 0;             // mli_engine_set_window (0: none)
     int n_sink = 0;             // mli_engine_set_sinks (0: none; counts beside a window only)
     bool release_pages = false; // mli_engine_set_page_release: takes effect at the first step or run, beside an effective window
@@ -402,6 +403,9 @@ int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
         if (e->started) throw std::runtime_error("mli_engine_configure after the engine has started");
         if (e->n_heads > 1 && lean_layers == 0)   // refused before anything is changed
             throw std::runtime_error("multi-head attention (mli_engine_set_heads) has the lean compositions only");
+        if (e->n_kv_heads != 0 && lean_layers == 0)
+            throw std::runtime_error("grouped-query attention (mli_engine_set_kv_heads: n_kv_heads < n_heads) has the lean "
+                                     "compositions only");
         if (e->window > 0 && e->window < e->cfg.n_sequence && lean_layers == 0)
             throw std::runtime_error("sliding-window attention (mli_engine_set_window) has the lean compositions only");
         if (lean_layers >= 0) e->lean_layers = lean_layers != 0;
@@ -429,10 +433,44 @@ int mli_engine_set_heads(mli_engine* e, int n_heads) {
             if (e->window > 0 && e->window < e->cfg.n_sequence &&
                 !mli::window_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, elem))
                 throw std::runtime_error("mli_engine_set_heads: the windowed scan (mli_engine_set_window) does not take this shape");
+            if (e->n_kv_heads != 0 && n_heads % e->n_kv_heads != 0)
+                throw std::runtime_error("mli_engine_set_heads: the stored n_kv_heads (mli_engine_set_kv_heads) does not divide "
+                                         "n_heads");
             if (e->paged_model) e->paged_model->set_n_heads(n_heads);
             if (e->gemm_model) e->gemm_model->set_n_heads(n_heads);
             if (e->bf16_model) e->bf16_model->set_n_heads(n_heads);
             e->n_heads = n_heads;
+        }
+    })
+}
+
+// What is stored is a grouping: n_kv_heads < n_heads.  n_kv_heads == n_heads stores "as many as n_heads" (0), the state of an
+// engine the call was never made on.  The shapes are the multi-head scan's, validated by set_heads / set_window.
+int mli_engine_set_kv_heads(mli_engine* e, int n_kv_heads) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (n_kv_heads < 1) throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads must be >= 1");
+        if (n_kv_heads > e->n_heads || e->n_heads % n_kv_heads != 0)
+            throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads must divide the engine's n_heads (mli_engine_set_heads)");
+        const int then = n_kv_heads == e->n_heads ? 0 : n_kv_heads;
+        if (then != e->n_kv_heads) {
+            if (e->started) throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads cannot change after the engine has started");
+            if (then != 0) {
+                // (n_heads > 1 here, so set_heads has accepted the kind, the lean layers and the shape; checked again all the same)
+                const int kind = e->cfg.kind;
+                if (kind != MLI_ENGINE_PAGED && kind != MLI_ENGINE_PAGED_GEMM && kind != MLI_ENGINE_PAGED_BF16)
+                    throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads < n_heads serves the fp32 and bf16 paged engines");
+                if (!e->lean_layers)
+                    throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads < n_heads has the lean compositions only");
+                const int elem = kind == MLI_ENGINE_PAGED_BF16 ? MLI_ELEM_BF16 : MLI_ELEM_F32;
+                if (!mli::gqa_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, e->n_heads, n_kv_heads, elem))
+                    throw std::runtime_error("mli_engine_set_kv_heads: the scan does not take this (n_batch, n_sequence, emb_dim, "
+                                             "n_heads, n_kv_heads)");
+            }
+            if (e->paged_model) e->paged_model->set_n_kv_heads(then);
+            if (e->gemm_model) e->gemm_model->set_n_kv_heads(then);
+            if (e->bf16_model) e->bf16_model->set_n_kv_heads(then);
+            e->n_kv_heads = then;
         }
     })
 }

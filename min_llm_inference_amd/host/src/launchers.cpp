@@ -289,8 +289,14 @@ bool mli::runtime::lean_paged_wanted(int n_heads, int window, int n_sequence) {
 int mli::runtime::lean_paged_attention(int elem, int n_heads, int window, int n_sink, void* const* page_table,
                                        const int* lengths, const void* wk, const void* wq, const void* wv,
                                        const int* new_batch_idx, float* q_output, float* attention_result, int B, int S, int D,
-                                       int n_new_items) {
+                                       int n_new_items, int n_kv_heads) {
     const Scratch ws = attention_scratch(B, S, D, n_heads > 1 ? n_heads : 1);
+    if (n_kv_heads != 0 && n_kv_heads != n_heads) {
+        HIP_CHECK(mli_paged_attention_lean_gqa(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B, S,
+                                               D, n_new_items, n_heads, n_kv_heads, window, n_sink, elem, ws.ptr, ws.bytes,
+                                               stream()));
+        return 0;
+    }
     const mli::ScanKind kind = mli::lean_scan_kind(S, window, n_sink);
     if (kind == mli::kScanSinks) {
         HIP_CHECK(mli_paged_attention_lean_sinks(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B,
@@ -317,11 +323,12 @@ int mli::runtime::lean_paged_attention(int elem, int n_heads, int window, int n_
 void paged_attention_lean_layer(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
                                 const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
                                 TensorFloat& q_output, TensorFloat* qkt_output, TensorFloat& attention_result,
-                                int n_new_items, int n_sequence, int n_heads, int window, int n_sink) {
+                                int n_new_items, int n_sequence, int n_heads, int window, int n_sink, int n_kv_heads) {
     const int B = (int)page_table.shape()[0], D = (int)wk.shape()[0];
     const int rc = mli::runtime::lean_paged_attention(MLI_ELEM_F32, n_heads, window, n_sink, reinterpret_cast<void* const*>(pages(page_table)),
                                                       lengths.data(), wk.data(), wq.data(), wv.data(), new_batch_idx.data(),
-                                                      q_output.data(), attention_result.data(), B, n_sequence, D, n_new_items);
+                                                      q_output.data(), attention_result.data(), B, n_sequence, D, n_new_items,
+                                                      n_kv_heads);
     if (rc == MLI_ERR_BAD_ARG && qkt_output != nullptr && D > 2048 && D % 4 == 0) {
         paged_attention(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, *qkt_output, attention_result,
                         n_new_items, n_sequence);
@@ -363,6 +370,16 @@ void paged_attention_lean_sinks(TensorFloatPoint& page_table, const TensorInt& l
     if (n_sink < 0 || window < 1 || n_heads < 1) HIP_CHECK(MLI_ERR_BAD_ARG);   // as mli_paged_attention_lean_sinks
     paged_attention_lean_layer(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, nullptr, attention_result,
                                n_new_items, n_sequence, n_heads, window, n_sink);
+}
+
+void paged_attention_lean_gqa(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,
+                              const TensorFloat& wq, const TensorFloat& wv, const TensorInt& new_batch_idx,
+                              TensorFloat& q_output, TensorFloat& attention_result, int n_new_items, int n_sequence, int n_heads,
+                              int n_kv_heads, int window, int n_sink) {
+    // as mli_paged_attention_lean_gqa; the layers' "as many as n_heads" is 0
+    if (n_sink < 0 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > n_heads || n_heads % n_kv_heads != 0) HIP_CHECK(MLI_ERR_BAD_ARG);
+    paged_attention_lean_layer(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, nullptr, attention_result,
+                               n_new_items, n_sequence, n_heads, window, n_sink, n_kv_heads);
 }
 
 void paged_attention_with_cublas(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorFloat& wk,

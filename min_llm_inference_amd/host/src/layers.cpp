@@ -51,7 +51,7 @@ void PagedAttentionLayer::forward(TensorFloatPoint& page_table, const TensorInt&
     const int n_sequence = static_cast<int>(qkt_output_.shape()[1]);
     if (mli::runtime::lean_paged_wanted(n_heads_, window_, n_sequence))
         paged_attention_lean_layer(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, &qkt_output_,
-                                   attention_result, n_new_items, n_sequence, n_heads_, window_, n_sink_);
+                                   attention_result, n_new_items, n_sequence, n_heads_, window_, n_sink_, n_kv_heads_);
     else
         paged_attention(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, qkt_output_, attention_result,
                         n_new_items, n_sequence);
@@ -91,7 +91,7 @@ void PagedAttentionCublasLayer::forward(TensorFloatPoint& page_table, const Tens
     const int n_sequence = static_cast<int>(qkt_output_.shape()[1]);
     if (mli::runtime::lean_paged_wanted(n_heads_, window_, n_sequence))
         paged_attention_lean_layer(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, &qkt_output_,
-                                   attention_result, n_new_items, n_sequence, n_heads_, window_, n_sink_);
+                                   attention_result, n_new_items, n_sequence, n_heads_, window_, n_sink_, n_kv_heads_);
     else
         paged_attention_with_cublas(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, qkt_output_,
                                     attention_result, latest_emb_, temp_placeholder_, n_new_items, n_sequence, handle);

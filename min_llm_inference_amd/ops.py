@@ -309,14 +309,29 @@ def decode_scan_paged_sinks(q_output, page_table, lengths, attention_result, n_h
                (n_heads, window, sinks), n_heads, elem, q_output.device)
 
 
+def decode_scan_paged_gqa(q_output, page_table, lengths, attention_result, n_heads, n_kv_heads, window, sinks, elem, n_sequence):
+    """The multi-head scan with grouped-query attention (mli_decode_scan_paged_gqa): query head h attends K/V head
+    h // (n_heads // n_kv_heads), whose columns are [that * D / n_heads, ...) of the K and V segments; the columns beyond
+    n_kv_heads * D / n_heads are never read.  window <= 0 (or None): no window; sinks 0 (or None): none.  n_kv_heads ==
+    n_heads is decode_scan_paged_sinks."""
+    B, D = q_output.shape
+    _lean_call("mli_decode_scan_paged_gqa", (q_output, page_table, lengths, attention_result), B, n_sequence, D,
+               (n_heads, n_kv_heads, window or 0, sinks or 0), n_heads, elem, q_output.device)
+
+
 def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_new_items,
-                         n_sequence, elem=None, n_heads=1, window=None, sinks=None):
+                         n_sequence, elem=None, n_heads=1, window=None, sinks=None, n_kv_heads=None):
     """What the attention layers run: the paged composition without materialising scores / probabilities
     (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads != 1: the
     multi-head form (mli_paged_attention_lean_heads); window given: the sliding-window form
     (mli_paged_attention_lean_window); sinks given as well: the first `sinks` tokens of every row stay attended
-    (mli_paged_attention_lean_sinks)."""
-    if sinks is not None:
+    (mli_paged_attention_lean_sinks); n_kv_heads given: grouped-query attention with that many K/V heads
+    (mli_paged_attention_lean_gqa; wk / wv keep their [D, D] shape, their first n_kv_heads * D / n_heads columns matter)."""
+    if n_kv_heads is not None:
+        if sinks is not None and window is None:
+            raise ValueError("sinks exist beside a window: pass window= as well")
+        name, extra = "mli_paged_attention_lean_gqa", (n_new_items, n_heads, n_kv_heads, window or 0, sinks or 0)
+    elif sinks is not None:
         if window is None:
             raise ValueError("sinks exist beside a window: pass window= as well")
         name, extra = "mli_paged_attention_lean_sinks", (n_new_items, n_heads, window, sinks)
