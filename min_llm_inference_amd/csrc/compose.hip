@@ -61,6 +61,15 @@ int launch_fill_paged_fp8_embed(const float*, const float*, const int*, uint8_t*
                                 const uint16_t*, const uint16_t*, int, int, int, int, hipStream_t);
 int launch_softmax_v_paged_bf16(const float*, const uint16_t* const*, const int*, float*, int, int, int, void*, size_t,
                                 hipStream_t);
+// the lean scan's two kernel families behind launch_lean_scan, over the workspace body, each instantiated in one file per page
+// element type: one head under a window, with or without sinks (attention_window.hpp: B, S, D, kind, window, n_sink), and
+// several heads, grouped or not (attention_heads.hpp: B, S, D, n_heads, n_kv_heads, lg, kind, window, n_sink)
+template <class E>
+int launch_window_decode(const float*, const void* const*, const int*, float*, int, int, int, ScanKind, int, int, void*, size_t,
+                         hipStream_t);
+template <class E>
+int launch_heads_scan(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, ScanKind, int, int,
+                      void*, size_t, hipStream_t);
 
 // What every lean paged composition starts with, by page element type (MLI_ELEM_*; bf16 weights for bf16 and fp8 pages):
 // fill the n_new_items new rows, then project every non-empty row's last token (k, v appended, q to q_output)
@@ -90,20 +99,40 @@ static int launch_fill_and_latest(int elem, void* const* page_table, const int* 
     return rc;
 }
 
+// The lean scans' one argument check: which scan (n_heads, n_kv_heads, window, n_sink) is (lean_scan_kind), or
+// MLI_ERR_BAD_ARG where the head counts are no grouping or that scan does not take the shape.  One head without a window is
+// the plain single-head scan, which judges its shape itself ("not applicable", below): only the element type is held here.
+static int lean_scan_args(int B, int S, int D, int n_heads, int n_kv_heads, int window, int n_sink, int elem) {
+    if (n_heads < 1 || n_kv_heads < 1 || n_kv_heads > n_heads || n_heads % n_kv_heads != 0) return MLI_ERR_BAD_ARG;
+    const ScanKind kind = lean_scan_kind(S, window, n_sink);
+    const bool ok = n_kv_heads != n_heads ? gqa_shape_supported(B, S, D, n_heads, n_kv_heads, elem)
+                    : kind != kScanPlain  ? window_shape_supported(B, S, D, n_heads, elem)
+                    : n_heads > 1         ? heads_lanes_log2(B, S, D, n_heads, elem) >= 0
+                                          : elem >= MLI_ELEM_F32 && elem <= MLI_ELEM_FP8;
+    return ok ? (int)kind : MLI_ERR_BAD_ARG;
+}
+
 int launch_lean_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
                      int n_heads, int n_kv_heads, int window, int n_sink, int elem, void* workspace, size_t workspace_bytes,
                      hipStream_t st) {
+    const int kind = lean_scan_args(B, S, D, n_heads, n_kv_heads, window, n_sink, elem);
+    if (kind < 0) return kind;
     const WsBody body = ws_body(workspace, workspace_bytes);
-    // grouped-query attention (attention_gqa.hip) only where the K/V heads are fewer: everything else is the path below
-    if (n_kv_heads != n_heads)
-        return launch_gqa_scan(q, page_table, lengths, out, B, S, D, n_heads, n_kv_heads, window, n_sink, elem, body.ptr,
-                               body.bytes, st);
-    const ScanKind kind = lean_scan_kind(S, window, n_sink);
-    if (kind == kScanSinks)
-        return launch_sink_scan(q, page_table, lengths, out, B, S, D, n_heads, window, n_sink, elem, body.ptr, body.bytes, st);
-    if (kind == kScanWindow)
-        return launch_window_scan(q, page_table, lengths, out, B, S, D, n_heads, window, elem, body.ptr, body.bytes, st);
-    if (n_heads > 1) return launch_heads_decode(q, page_table, lengths, out, B, S, D, n_heads, elem, body.ptr, body.bytes, st);
+    if (n_heads > 1) {
+        const int lg = heads_lanes_log2(B, S, D, n_heads, elem);
+        const auto go = [&](auto e) {
+            return launch_heads_scan<decltype(e)>(q, page_table, lengths, out, B, S, D, n_heads, n_kv_heads, lg, (ScanKind)kind,
+                                                  window, n_sink, body.ptr, body.bytes, st);
+        };
+        return elem == MLI_ELEM_BF16 ? go(ElemBF16{}) : go(ElemF32{});
+    }
+    if (kind != kScanPlain) {
+        const auto go = [&](auto e) {
+            return launch_window_decode<decltype(e)>(q, page_table, lengths, out, B, S, D, (ScanKind)kind, window, n_sink,
+                                                     body.ptr, body.bytes, st);
+        };
+        return elem == MLI_ELEM_FP8 ? go(ElemFP8{}) : elem == MLI_ELEM_BF16 ? go(ElemBF16{}) : go(ElemF32{});
+    }
     // not applicable (rows too wide for the single-pass kernel, or no workspace) is a bad argument: the host layers then
     // take the materialising composition
     return fused_status(launch_fused_decode_elem(elem, q, page_table, lengths, nullptr, out, B, S, D, body.ptr, body.bytes, st, 7));
@@ -117,6 +146,24 @@ int launch_lean_attention(int elem, void* const* page_table, const int* lengths,
     if (rc) return rc;
     return launch_lean_scan(q_output, reinterpret_cast<const void* const*>(page_table), lengths, out, B, S, D, n_heads,
                             n_kv_heads, window, n_sink, elem, workspace, workspace_bytes, st);
+}
+
+// The fronts of the lean entry points with heads, a window, sinks or grouped K/V heads, one per pair (scan form, fill-first
+// form): the pair's own argument rules, then lean_scan_args -- negative is MLI_ERR_BAD_ARG, before anything is launched.
+// _heads: fp32 and bf16 pages only, one head included
+static int heads_front(int B, int S, int D, int n_heads, int elem) {
+    if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) return MLI_ERR_BAD_ARG;
+    return lean_scan_args(B, S, D, n_heads, n_heads, 0, 0, elem);
+}
+// _window (n_sink 0) and _sinks: a window below one is refused; one head takes fp8 pages
+static int sinks_front(int B, int S, int D, int n_heads, int window, int n_sink, int elem) {
+    if (n_sink < 0 || window < 1) return MLI_ERR_BAD_ARG;
+    return lean_scan_args(B, S, D, n_heads, n_heads, window, n_sink, elem);
+}
+// _gqa: fp32 and bf16 pages only, one head included; a window below one is no window
+static int gqa_front(int B, int S, int D, int n_heads, int n_kv_heads, int window, int n_sink, int elem) {
+    if ((elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) || n_sink < 0 || S < 1) return MLI_ERR_BAD_ARG;
+    return lean_scan_args(B, S, D, n_heads, n_kv_heads, window, n_sink, elem);
 }
 }  // namespace mli
 
@@ -134,6 +181,95 @@ int mli_paged_attention_lean(void* const* page_table, const int* lengths, const 
     return mli::launch_lean_attention(elem_bf16, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
                                       n_batch, n_sequence, emb_dim, n_new_items, 1, 1, 0, 0, workspace, workspace_bytes,
                                       mli::as_stream(stream));
+}
+
+// ---- the lean forms with heads, a window, sinks or grouped K/V heads: a front (above), then the scan, or fill + latest + scan.
+// Fill and projection depend on none of n_heads, n_kv_heads, window and n_sink: the pages stay emb_dim wide.  One head
+// without a window is mli_decode_scan_paged (phases 7) / mli_paged_attention_lean, n_kv_heads == n_heads the call without
+// grouping, n_sink 0 the call without sinks: the same kernels, the same bits, whichever entry point is asked.
+size_t mli_attention_heads_workspace_bytes(int n_batch, int n_sequence, int dim, int n_heads) {
+    if (n_heads == 1) return mli_attention_workspace_bytes(n_batch, n_sequence, dim);
+    // either page element type: the layout does not depend on it
+    if (mli::heads_lanes_log2(n_batch, n_sequence, dim, n_heads, MLI_ELEM_F32) < 0 &&
+        mli::heads_lanes_log2(n_batch, n_sequence, dim, n_heads, MLI_ELEM_BF16) < 0)
+        return 0;
+    const size_t nchunk = (size_t)mli::ceil_div_i(n_sequence, 64);
+    const size_t heads = mli::kArrivalRegionBytes + mli::scan_stats_bytes(n_batch, n_sequence, n_heads) +
+                         (nchunk <= 1 ? 0 : (size_t)n_batch * nchunk * (size_t)dim * sizeof(float));
+    const size_t plain = mli_attention_workspace_bytes(n_batch, n_sequence, dim);
+    return heads > plain ? heads : plain;
+}
+
+int mli_decode_scan_paged_heads(const float* q_output, const void* const* page_table, const int* lengths,
+                                float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int elem,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    if (mli::heads_front(n_batch, n_sequence, emb_dim, n_heads, elem) < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
+                                 n_heads, 0, 0, elem, workspace, workspace_bytes, mli::as_stream(stream));
+}
+
+int mli_paged_attention_lean_heads(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                   const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                   int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int elem,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (mli::heads_front(n_batch, n_sequence, emb_dim, n_heads, elem) < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_lean_attention(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
+                                      n_batch, n_sequence, emb_dim, n_new_items, n_heads, n_heads, 0, 0, workspace,
+                                      workspace_bytes, mli::as_stream(stream));
+}
+
+int mli_decode_scan_paged_window(const float* q_output, const void* const* page_table, const int* lengths,
+                                 float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int window,
+                                 int elem, void* workspace, size_t workspace_bytes, void* stream) {
+    if (mli::sinks_front(n_batch, n_sequence, emb_dim, n_heads, window, 0, elem) < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
+                                 n_heads, window, 0, elem, workspace, workspace_bytes, mli::as_stream(stream));
+}
+
+int mli_paged_attention_lean_window(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                    const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                    int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int window,
+                                    int elem, void* workspace, size_t workspace_bytes, void* stream) {
+    if (mli::sinks_front(n_batch, n_sequence, emb_dim, n_heads, window, 0, elem) < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_lean_attention(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
+                                      n_batch, n_sequence, emb_dim, n_new_items, n_heads, n_heads, window, 0, workspace,
+                                      workspace_bytes, mli::as_stream(stream));
+}
+
+int mli_decode_scan_paged_sinks(const float* q_output, const void* const* page_table, const int* lengths,
+                                float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int window,
+                                int n_sink, int elem, void* workspace, size_t workspace_bytes, void* stream) {
+    if (mli::sinks_front(n_batch, n_sequence, emb_dim, n_heads, window, n_sink, elem) < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
+                                 n_heads, window, n_sink, elem, workspace, workspace_bytes, mli::as_stream(stream));
+}
+
+int mli_paged_attention_lean_sinks(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                   const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                   int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int window,
+                                   int n_sink, int elem, void* workspace, size_t workspace_bytes, void* stream) {
+    if (mli::sinks_front(n_batch, n_sequence, emb_dim, n_heads, window, n_sink, elem) < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_lean_attention(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
+                                      n_batch, n_sequence, emb_dim, n_new_items, n_heads, n_heads, window, n_sink, workspace,
+                                      workspace_bytes, mli::as_stream(stream));
+}
+
+int mli_decode_scan_paged_gqa(const float* q_output, const void* const* page_table, const int* lengths,
+                              float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads,
+                              int window, int n_sink, int elem, void* workspace, size_t workspace_bytes, void* stream) {
+    if (mli::gqa_front(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, elem) < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_lean_scan(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
+                                 n_kv_heads, window, n_sink, elem, workspace, workspace_bytes, mli::as_stream(stream));
+}
+
+int mli_paged_attention_lean_gqa(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                 const int* new_batch_idx, float* q_output, float* attention_result, int n_batch,
+                                 int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
+                                 int n_sink, int elem, void* workspace, size_t workspace_bytes, void* stream) {
+    if (mli::gqa_front(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, elem) < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_lean_attention(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_batch,
+                                      n_sequence, emb_dim, n_new_items, n_heads, n_kv_heads, window, n_sink, workspace,
+                                      workspace_bytes, mli::as_stream(stream));
 }
 
 int mli_get_latest_k_q_v_paged_lean(void* const* page_table, const int* lengths, const void* wk, const void* wq,

@@ -51,11 +51,11 @@ __device__ __forceinline__ void heads_xor_step(float (&v)[NJ][16]) {
 // ml: [B][nchunk_max][H] (max, sum) per item and head; partial: [B][nchunk_max][D] un-normalised partial rows.
 // TBR = rows per load batch, PD = batches in flight (of four register buffers).
 // smem_raw: ct / 16 page pointers | max(4 waves x (NJ * 64 * EPL floats + NJ * 64 float2), nchunk_max * H float2)
-// WIN = true (EXTENSION, attention_window.hip): the row attends its newest `window` tokens -- fused_scan_item's window
+// WIN = true (EXTENSION, attention_heads.hpp): the row attends its newest `window` tokens -- fused_scan_item's window
 // switch: the row is taken from its first live page p0 on, and that page's slots below the window are masked.
-// SINK = true (EXTENSION, attention_sinks.hip; with WIN): fused_scan_item's sink switch -- the first n_sink tokens are attended
+// SINK = true (EXTENSION, attention_heads.hpp; with WIN): fused_scan_item's sink switch -- the first n_sink tokens are attended
 // too, on the virtual row of sink pages + window pages; the mask is per slot of the lane's 16.
-// GQA = true (EXTENSION, attention_gqa.hip): grouped-query attention, gq = n_heads / n_kv_heads query heads per K/V head.  Only
+// GQA = true (EXTENSION, attention_heads.hpp): grouped-query attention, gq = n_heads / n_kv_heads query heads per K/V head.  Only
 // the unit a lane LOADS changes (gqa_kv_unit, scan_plan.hpp): the lanes of query head h read the K and V columns of K/V head
 // h / gq.  q, the per-lane state, the all-reduce inside a group, the merges and H are those of n_heads heads.
 template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false, bool SINK = false, bool GQA = false>

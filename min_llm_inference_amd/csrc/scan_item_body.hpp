@@ -114,8 +114,8 @@ __device__ __forceinline__ void row_publish_merge(float m, float l, float2* ml_r
     }
 }
 
-// Is slot t of a page attended?  nt: the page's slots inside the row; nlo (WIN, attention_window.hip): its slots below the
-// row's window; nk (SINK, attention_sinks.hip): its slots among the row's sink tokens, attended whatever the window.
+// Is slot t of a page attended?  nt: the page's slots inside the row; nlo (WIN, attention_window.hpp): its slots below the
+// row's window; nk (SINK, attention_window.hpp): its slots among the row's sink tokens, attended whatever the window.
 template <bool WIN, bool SINK = false>
 __device__ __forceinline__ bool slot_live(int t, int nt, int nlo, int nk = 0) {
     if constexpr (SINK) return t < nt && (t < nk || t >= nlo);
@@ -130,12 +130,12 @@ __device__ __forceinline__ int sink_page(int v, int ps, int skip) { return v < p
 // b, c: the item (row, grid row); first_grid_row: this workgroup is the one that writes the zero result of an empty row.
 // RPI = token slots per load instruction (scan_common.hpp; 1 except for narrow fp8 rows): a batch is TBR instructions =
 //   TBR * RPI slots
-// WIN = true (EXTENSION, attention_window.hip; lean form only): the row attends its newest `window` tokens, slots
+// WIN = true (EXTENSION, attention_window.hpp; lean form only): the row attends its newest `window` tokens, slots
 //   [lo, L) with lo = max(0, L - window).  Its first live page is p0 = lo / 16; everything below is done on the row as it
 //   looks from token 16 * p0 on (relative length L - 16 * p0 <= window + 15; page pointers from page_table[b][p0 + ...], an
 //   entry below p0 is never read), and in the row's first live page the slots t < lo - 16 * p0 are masked exactly as the
 //   slots >= nt of its last one are.  WIN = false ignores `window`.
-// SINK = true (EXTENSION, attention_sinks.hip; with WIN): the row attends its first n_sink tokens as well, slots s < L with
+// SINK = true (EXTENSION, attention_window.hpp; with WIN): the row attends its first n_sink tokens as well, slots s < L with
 //   s < n_sink or s >= lo.  Its ps = ceil(n_sink / 16) sink pages stay, skip = max(0, p0 - ps) pages between them and page p0
 //   are dropped, and everything below is done on the virtual row of L - 16 * skip tokens whose page v is physical page
 //   sink_page(v): items are cut over the virtual row (one may straddle the joint), page pointers are staged through that

@@ -22,22 +22,15 @@ int launch_stream_decode(const float* q, const void* const* page_table, const in
                          void* ws, size_t ws_bytes, hipStream_t st);
 template <class E>
 bool stream_decode_applies(int B, int S, int D);
-// The launchers below take the workspace BODY (ws_body) and a shape their entry points have accepted.
-// attention_fused.hip: 1 = ran, 0 = not applicable (rows too wide, or no workspace), else an error (+1 if positive)
+// attention_fused.hip, over the workspace BODY (ws_body) and an element type its caller has accepted: 1 = ran, 0 = not
+// applicable (rows too wide, or no workspace), else an error (+1 if positive)
 int launch_fused_decode_elem(int elem, const float* q, const void* const* page_table, const int* lengths, float* qkt,
                              float* out, int B, int S, int D, void* ws, size_t ws_bytes, hipStream_t st, int phases);
-int launch_heads_decode(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
-                        int H, int elem, void* ws, size_t ws_bytes, hipStream_t st);                // attention_heads.hip
-int launch_window_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
-                       int H, int window, int elem, void* ws, size_t ws_bytes, hipStream_t st);     // attention_window.hip
-int launch_sink_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
-                     int H, int window, int n_sink, int elem, void* ws, size_t ws_bytes, hipStream_t st);   // attention_sinks.hip
-// attention_gqa.hip: n_kv_heads < n_heads (gqa_shape_supported), plain, windowed or with sinks by lean_scan_kind
-int launch_gqa_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D, int H,
-                    int Hkv, int window, int n_sink, int elem, void* ws, size_t ws_bytes, hipStream_t st);
-// compose.hip: the lean scan for (n_heads, n_kv_heads, window, n_sink) -- n_kv_heads == n_heads: no grouping, the scans
-// above; window 0 or >= n_sequence: none; n_sink 0, or n_sink + window >= n_sequence: no sinks, or no gap they could bridge
-// -- over the caller's WHOLE workspace; returns a C ABI status.
+// compose.hip: the lean scan for (n_heads, n_kv_heads, window, n_sink) -- n_kv_heads == n_heads: no grouping; window <= 0
+// or >= n_sequence: none; n_sink 0, or n_sink + window >= n_sequence: no sinks, or no gap they could bridge -- over the
+// caller's WHOLE workspace; returns a C ABI status.  It holds the one check of head counts and shape (MLI_ERR_BAD_ARG before
+// any launch) and picks the kernel family: the plain single-head scan above, the single-head scan under a window
+// (attention_window.hpp) or the multi-head scan (attention_heads.hpp).
 // launch_lean_attention: launch_fill_and_latest, then that scan over q_output.
 int launch_lean_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S, int D,
                      int n_heads, int n_kv_heads, int window, int n_sink, int elem, void* workspace, size_t workspace_bytes,

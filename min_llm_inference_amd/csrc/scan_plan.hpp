@@ -1,6 +1,6 @@
-// The launch plan of the chunked paged scans -- the single-head scan (attention_fused.hip), the multi-head scan
-// (attention_heads.hip), their sliding-window forms (attention_window.hip), those with sinks (attention_sinks.hip) and the
-// grouped-query forms (attention_gqa.hip): every rule that decides how such a scan is launched, once.  Plain C++ over int /
+// The launch plan of the chunked paged scans -- the single-head scan (attention_fused.hip), its forms under a sliding
+// window, with or without sinks (attention_window.hpp), and the multi-head scan, plain, windowed, with sinks and with
+// grouped-query attention (attention_heads.hpp): every rule that decides how such a scan is launched, once.  Plain C++ over int /
 // size_t / bool, no HIP types and no global state (tests/cpp/scan_plan_test.cpp compiles it alone); the mli_tune values the
 // rules depend on come in as a ScanTune.
 #pragma once
@@ -220,7 +220,7 @@ inline int window_shape_supported(int n_batch, int n_sequence, int emb_dim, int 
                         : heads_lanes_log2(n_batch, n_sequence, emb_dim, n_heads, elem) >= 0;
 }
 
-// ---- grouped-query attention (attention_gqa.hip) ------------------------------------------------------------------------------
+// ---- grouped-query attention (attention_heads.hpp, GQA) -----------------------------------------------------------------------
 // n_kv_heads K/V heads serve n_heads query heads, g = n_heads / n_kv_heads (any integer) consecutive query heads each: query
 // head h attends K/V head h / g, which owns columns [(h / g) * hd, (h / g + 1) * hd) of the K and V segments.  The shapes
 // are the multi-head scan's, with or without a window.

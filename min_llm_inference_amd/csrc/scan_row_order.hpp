@@ -12,9 +12,9 @@ namespace mli {
 // the row of rank r by page count (descending; equal counts in row order).  Every workgroup derives the same ranking from
 // the lengths -- a histogram over the page counts, then the j-th row of its bucket by a block-wide count --: ~2 us of
 // prologue per workgroup, no pre-pass, deterministic.  All kFuThreads threads call it; n_batch <= kMaxOrderedRows.
-// WIN = true (attention_window.hip): the rows are ranked by the pages their window leaves live, ceil(L / 16) - lo / 16 with
+// WIN = true (the windowed scans): the rows are ranked by the pages their window leaves live, ceil(L / 16) - lo / 16 with
 // lo = max(0, L - window); S / 16 may then exceed kMaxOrderedPages as long as the window's span does not.
-// SINK = true (attention_sinks.hip; with WIN): ... by the pages of the virtual row, ceil(L / 16) - max(0, lo / 16 - ceil(n_sink / 16)).
+// SINK = true (with WIN): ... by the pages of the virtual row, ceil(L / 16) - max(0, lo / 16 - ceil(n_sink / 16)).
 template <bool WIN = false, bool SINK = false>
 __device__ __forceinline__ int longest_first_row(const int* __restrict__ lengths, int n_batch, int S, int rank, int window = 0,
                                                  int n_sink = 0) {
