@@ -103,6 +103,29 @@ int mli_engine_stream(mli_engine* engine, void** stream);
 /* Finished item `index` (0 <= index < stats.finished), in completion order: id and tokens (prompt + generated). */
 int mli_engine_get_finished(mli_engine* engine, int index, int* id, int* tokens, int capacity, int* n_tokens);
 
+/* EXTENSION: per-token log-probabilities and top-n alternatives (mli_kernels.h: mli_sample_tokens_logprobs, DESIGN.md
+ * 3.6c).  For every token it generates, the engine records the natural-log probability of that token under the RAW model
+ * distribution at its position -- independent of the item's temperature, top_k, top_p and seed, so greedy and sampled
+ * items report on one scale -- and the n_top (0 .. 8) candidates of largest logit with theirs, ordered by (logit
+ * descending, index ascending).  Before the first step or run; all five kinds.  -1 with a message for a null engine, a
+ * started engine, an engine created with reference_length_reset_quirk, n_top outside 0 .. 8, or an engine an id was already
+ * queued on twice.  An engine the call was never made on behaves exactly as before.
+ * What it changes: the engine decodes with the sampled head family (materialised logits) even when every item is greedy
+ * -- plain mli_engine_add_item items decode with temperature 0, as in any sampled engine --, the token streams are those
+ * of the same engine without logprobs, and item ids must be unique from then on (mli_engine_add_item and
+ * mli_engine_add_item_sampled refuse a duplicate).  The figures cross to the host with the tokens, at the same
+ * synchronisation point of either loop, and are kept per item id where the token is appended: a token dropped in flight by
+ * a preemption takes its figures with it, a re-admitted item keeps those of the tokens it had generated; n_forward_rounds
+ * and step graphs need nothing more. */
+int mli_engine_set_logprobs(mli_engine* engine, int n_top);
+
+/* The figures of finished item `index` (the index of mli_engine_get_finished): entry i belongs to token n_prompt + i of
+ * that item's tokens, and *n_generated == n_tokens - *n_prompt always.  Up to `capacity` entries of token_logprobs and up
+ * to `top_capacity` entries of top_ids / top_logprobs ([n_generated, n_top] row-major) are written; any of the three may
+ * be NULL.  -1 on an engine without logprobs. */
+int mli_engine_get_finished_logprobs(mli_engine* engine, int index, int* n_prompt, float* token_logprobs, int capacity,
+                                     int* n_generated, int* top_ids, float* top_logprobs, int top_capacity);
+
 /* The DEFAULT of engines created afterwards (every engine keeps its own value, see mli_engine_configure; two engines in one
  * process never change each other's composition): 1 (default) = the models' layers run the lean compositions (prefill with the encoder as the fill GEMM's
  * prologue, attention without materialised scores / probabilities, decoder head with the argmax as the logits GEMM's

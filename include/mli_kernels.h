@@ -424,6 +424,47 @@ int mli_paged_decoder_sampled(const float* batch_result, const float* emb_table,
                               const float* temperature, const int* top_k, const float* top_p, const int64_t* seed,
                               void* scratch, size_t scratch_bytes, void* stream);
 
+/* EXTENSION: per-token log-probabilities and top-n alternatives from the sampled heads.  The token is the
+ * one the plain entry point emits on the same inputs (bit-identical, greedy rows included); beside it the head reports,
+ * for a row with logits x[0..V) whose candidates are the finite x (as in the draw),
+ *   logprob(v) = (x_v - m) - log(sum over candidates of exp(x_u - m)),   m = the largest candidate.
+ * These are natural-log probabilities of the RAW model distribution: they do not depend on the row's temperature, top_k,
+ * top_p or seed, so greedy and sampled rows report on one scale (the common "raw logprobs" convention; the distribution
+ * a sampled token was actually drawn from is the tempered, truncated one).
+ *   token_logprob [n_batch * n_decoder_results]         logprob of the emitted token
+ *   top_ids       [n_batch * n_decoder_results, n_top]  the n_top candidates of largest logit, ordered by (logit
+ *   top_logprobs  [n_batch * n_decoder_results, n_top]  descending, index ascending), and their logprobs
+ * all strided like decoder_result: row b reports at b * n_decoder_results + i_decoder (mli_sample_tokens_logprobs: at b).
+ * n_top in 0 .. MLI_MAX_TOP_LOGPROBS; the selection compares fp32 values and does no arithmetic.  With fewer than n_top
+ * candidates the remaining entries are id -1, logprob -inf.  An emitted token that is among the alternatives has the same
+ * bits in both places.  A row that emits no token (an empty row, or no finite logit: token -1) reports -inf, ids -1 and
+ * logprobs -inf.  An emitted token whose own logit is -inf reports -inf, one whose logit is +inf or NaN reports NaN (the
+ * greedy pick takes a +inf); nothing faults on any device value.  The figures depend on the row's logits and n_vocab only
+ * (fixed summation order, expf / logf) and are run-to-run deterministic.
+ * MLI_ERR_BAD_ARG, checked before anything else and before any launch: n_top < 0, n_top > MLI_MAX_TOP_LOGPROBS, a null
+ * token_logprob, null top_ids / top_logprobs with n_top > 0.  Otherwise every refusal and the scratch contract
+ * (mli_sample_scratch_bytes / mli_decoder_sampled_scratch_bytes) of the plain entry points.  The contiguous form takes
+ * n_decoder_results / i_decoder for the three outputs and decoder_result alike. */
+#define MLI_MAX_TOP_LOGPROBS 8
+int mli_sample_tokens_logprobs(const float* logits, const float* temperature, const int* top_k, const float* top_p,
+                               const int64_t* seed, const int* lengths, int* tokens,
+                               float* token_logprob, int* top_ids, float* top_logprobs,
+                               int n_batch, int n_vocab, int n_top, void* scratch, size_t scratch_bytes, void* stream);
+int mli_decoder_sampled_logprobs(const float* batch_result, const float* emb_table, const float* wpe_table,
+                                 float* inp_embedding, int* lengths, int* decoder_result,
+                                 int n_batch, int n_vocab, int n_sequence, int emb_dim,
+                                 int n_decoder_results, int i_decoder,
+                                 const float* temperature, const int* top_k, const float* top_p, const int64_t* seed,
+                                 float* token_logprob, int* top_ids, float* top_logprobs, int n_top,
+                                 void* scratch, size_t scratch_bytes, void* stream);
+int mli_paged_decoder_sampled_logprobs(const float* batch_result, const float* emb_table, const float* wpe_table,
+                                       void* const* page_table, int* lengths, int* decoder_result,
+                                       int n_batch, int n_vocab, int n_sequence, int emb_dim,
+                                       int n_decoder_results, int i_decoder, int elem,
+                                       const float* temperature, const int* top_k, const float* top_p, const int64_t* seed,
+                                       float* token_logprob, int* top_ids, float* top_logprobs, int n_top,
+                                       void* scratch, size_t scratch_bytes, void* stream);
+
 /* PREFILL of the newly inserted rows in ONE launch: the encoder as the fill GEMM's prologue.  The A
  * tile rows are computed on the fly as emb_table[inp[b, s]] + wpe[s] -- nothing is read back from the input-embedding
  * segment -- multiplied by [Wk | Wv], and the workgroups of the first column tile also write those rows to segment 0

@@ -53,7 +53,8 @@ int mli_shard_group_size(const mli_shard_group* group);
 
 /* Queue one item on rank (id mod n_ranks) -- the global queue dealt round-robin, so every rank's scheduler sees the
  * same kind of load. */
-/* Greedy decoding only: the group has no sampled entry (mli_engine_add_item_sampled is per engine). */
+/* Greedy decoding only: the group has no sampled entry (mli_engine_add_item_sampled is per engine).  Its engines run
+ * without log-probabilities (mli_engine_set_logprobs is per engine too, and is not offered through the group). */
 int mli_shard_group_add_item(mli_shard_group* group, int id, const int* tokens, int n_tokens);
 
 /* Run every rank to completion in lock step: iteration = every rank's mli_engine_step, then its all-gather; the group

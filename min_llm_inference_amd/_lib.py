@@ -84,6 +84,9 @@ SIGNATURES = {
     "mli_decoder_sampled_scratch_bytes": [_I, _I],
     "mli_decoder_sampled": [_P] * 6 + [_I] * 4 + [_P] * 4 + [_P, _Z, _P],
     "mli_paged_decoder_sampled": [_P] * 6 + [_I] * 7 + [_P] * 4 + [_P, _Z, _P],
+    "mli_sample_tokens_logprobs": [_P] * 10 + [_I] * 3 + [_P, _Z, _P],
+    "mli_decoder_sampled_logprobs": [_P] * 6 + [_I] * 6 + [_P] * 7 + [_I] + [_P, _Z, _P],
+    "mli_paged_decoder_sampled_logprobs": [_P] * 6 + [_I] * 7 + [_P] * 7 + [_I] + [_P, _Z, _P],
     "mli_paged_prefill": [_P] * 8 + [_I] * 5 + [_P],
     "mli_paged_prefill_window": [_P] * 8 + [_I] * 7 + [_P],
     "mli_prefill": [_P] * 10 + [_I] * 5 + [_P],
@@ -138,6 +141,8 @@ ENGINE_SIGNATURES = {
     "mli_engine_get_stats": [_P, ctypes.POINTER(EngineStats)],
     "mli_engine_decoder_result": [_P, _PP, _IP],
     "mli_engine_get_finished": [_P, _I, _IP, _P, _I, _IP],
+    "mli_engine_set_logprobs": [_P, _I],
+    "mli_engine_get_finished_logprobs": [_P, _I, _IP, _P, _I, _IP, _P, _P, _I],
     "mli_engine_configure": [_P, _I, _I],
     "mli_engine_set_heads": [_P, _I],
     "mli_engine_set_window": [_P, _I],

@@ -15,6 +15,15 @@
 // order-preserving uint32 key of the float, 15 probes per pass (a 16-ary search: <= 8 passes for 32 bits).  A probe's
 // weight -- 1 for the top-k count, exp(x / T - max / T) for the top-p mass -- is summed per thread in stride order and
 // reduced by a fixed butterfly and a fixed cross-wave order: no atomics, the result depends on the row's data and V only.
+//
+// Log-probabilities (the LOGPROBS instantiations): after the pick the same workgroup reports, for the RAW
+// distribution of the row (no temperature, top-k or top-p: greedy and sampled rows on one scale),
+//   logprob(v) = (x_v - m) - log(sum over candidates of exp(x_u - m)),  m = the largest candidate
+// of the emitted token and of the n_top <= 8 candidates of largest logit, ordered by (logit descending, index ascending).
+// The alternatives are selected in one pass -- every thread keeps the 8 best of its own candidates in registers -- and
+// n_top rounds of block_argmax over the heads of those lists: comparisons only, no marks in the row, no scratch.  expf /
+// logf, the sum per thread in stride order and block_sum's fixed order: the figures depend on the row's data and V only.
+// Without the switch the kernels are the ones they were.
 #include <cfloat>
 
 #include "embed_store.hpp"
@@ -152,28 +161,107 @@ __device__ __forceinline__ uint32_t search_threshold(const float* x, int V, uint
     return lo;
 }
 
-// The token of one row (every thread returns it).  x = the row's logits in global memory; stage = dynamic LDS of
-// min(V, kStageMax) floats when V <= kStageMax.
-__device__ __forceinline__ int sample_row(const float* __restrict__ xg, int V, float T, int K, float P, uint64_t seed, int L,
-                          float* stage, SampleShared& sh) {
-    if (!(T > 0.f)) {  // greedy: the scores as they are, the order and the -FLT_MAX floor of decoder_argmax_kernel
-        float mv = -FLT_MAX;
-        int mi = -1;
-        for (int v = threadIdx.x; v < V; v += kThreads) {
-            const float xv = xg[v];
-            if (xv > mv) {
-                mv = xv;
-                mi = v;
-            }
+// Where the LOGPROBS kernels report (the arrays of mli_sample_tokens_logprobs); nothing without the switch
+template <bool LOGPROBS>
+struct LogprobOut {};
+template <>
+struct LogprobOut<true> {
+    float* token_logprob;  // [rows]
+    int* top_ids;          // [rows, n_top]
+    float* top_logprobs;   // [rows, n_top]
+    int n_top;
+};
+
+// a row that emits no token: -inf, ids -1, logprobs -inf
+__device__ __forceinline__ void no_token_logprobs(const LogprobOut<true>& o, int64_t slot) {
+    if (threadIdx.x == 0) o.token_logprob[slot] = -INFINITY;
+    for (int k = threadIdx.x; k < o.n_top; k += kThreads) {
+        o.top_ids[slot * o.n_top + k] = -1;
+        o.top_logprobs[slot * o.n_top + k] = -INFINITY;
+    }
+}
+
+// The figures of one row after its pick.  x = the row (staged or global), tok = the emitted token (every thread has it).
+__device__ __forceinline__ void row_logprobs(const float* x, int V, int tok, const LogprobOut<true>& o, int64_t slot,
+                                             SampleShared& sh) {
+    if (tok < 0) {  // no candidate
+        no_token_logprobs(o, slot);
+        return;
+    }
+    // One pass: every thread keeps the kTop best of its own candidates, sorted by (value descending, index ascending) --
+    // it meets them by ascending index, so an equal value goes behind.  Static indices only: the lists live in registers.
+    constexpr int kTop = MLI_MAX_TOP_LOGPROBS;
+    float tv[kTop];
+    int ti[kTop];
+#pragma unroll
+    for (int j = 0; j < kTop; ++j) {
+        tv[j] = -INFINITY;
+        ti[j] = -1;
+    }
+    for (int v = threadIdx.x; v < V; v += kThreads) {
+        const float xv = x[v];
+        if (!finite_bits(xv) || !(xv > tv[kTop - 1])) continue;
+        tv[kTop - 1] = xv;
+        ti[kTop - 1] = v;
+#pragma unroll
+        for (int j = kTop - 1; j > 0; --j) {
+            const bool up = tv[j] > tv[j - 1];
+            const float fv = tv[j];
+            const int fi = ti[j];
+            tv[j] = up ? tv[j - 1] : fv;
+            ti[j] = up ? ti[j - 1] : fi;
+            tv[j - 1] = up ? fv : tv[j - 1];
+            ti[j - 1] = up ? fi : ti[j - 1];
         }
-        return block_argmax(mv, mi, sh);
     }
-    const float* x = xg;
-    if (V <= kStageMax) {
-        for (int v = threadIdx.x; v < V; v += kThreads) stage[v] = xg[v];
-        __syncthreads();
-        x = stage;
+    // Then n_top rounds over the lists' heads: the next alternative overall is the head of some thread's list, and the
+    // thread that owns the winner moves on to its next (no thread gives more than n_top <= kTop).
+    float m = 0.f, log_s = 0.f;
+    int n_found = 0;
+    const int rounds = max(o.n_top, 1);  // the first round finds m, needed without alternatives too
+    for (int k = 0; k < rounds; ++k) {
+        const int bi = block_argmax(tv[0], ti[0], sh);
+        if (bi < 0) break;  // fewer candidates than n_top (the same in every thread)
+        const float pv = x[bi];
+        if (ti[0] == bi) {
+#pragma unroll
+            for (int j = 0; j + 1 < kTop; ++j) {
+                tv[j] = tv[j + 1];
+                ti[j] = ti[j + 1];
+            }
+            tv[kTop - 1] = -INFINITY;
+            ti[kTop - 1] = -1;
+        }
+        if (k == 0) {
+            m = pv;
+            float s[1] = {0.f};
+            for (int v = threadIdx.x; v < V; v += kThreads) {
+                const float xv = x[v];
+                if (finite_bits(xv)) s[0] += expf(__fsub_rn(xv, m));
+            }
+            block_sum(s, sh);
+            log_s = logf(s[0]);
+        }
+        if (k < o.n_top && threadIdx.x == 0) {
+            o.top_ids[slot * o.n_top + k] = bi;
+            o.top_logprobs[slot * o.n_top + k] = __fsub_rn(__fsub_rn(pv, m), log_s);
+        }
+        n_found = k + 1;
     }
+    for (int k = n_found + threadIdx.x; k < o.n_top; k += kThreads) {
+        o.top_ids[slot * o.n_top + k] = -1;
+        o.top_logprobs[slot * o.n_top + k] = -INFINITY;
+    }
+    if (threadIdx.x == 0) {
+        const float xt = x[tok];
+        // a candidate (then n_found >= 1), or a token the greedy head took for its +inf; -inf and NaN are never taken
+        o.token_logprob[slot] = finite_bits(xt) && n_found > 0 ? __fsub_rn(__fsub_rn(xt, m), log_s)
+                                                                : (xt == -INFINITY ? -INFINITY : NAN);
+    }
+}
+
+// The drawn token of one row with T > 0 (every thread returns it).  x = the row's logits, staged or global.
+__device__ __forceinline__ int draw_row(const float* x, int V, float T, int K, float P, uint64_t seed, int L, SampleShared& sh) {
     // candidates: count and key range
     float n_cand[1] = {0.f};  // exact: V < 2^24
     uint32_t kmax = 0u, kmin = 0xffffffffu;
@@ -230,45 +318,81 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ xg, int V, f
     return block_argmax(mv, mi, sh);
 }
 
+// The token of one row (every thread returns it).  xg = the row's logits in global memory; stage = dynamic LDS of
+// min(V, kStageMax) floats when V <= kStageMax.  LOGPROBS: the row's figures are reported too (slot = its place in the
+// output arrays), and a greedy row is staged as well -- its token comes from the same values in the same order.
+template <bool LOGPROBS>
+__device__ __forceinline__ int sample_row(const float* __restrict__ xg, int V, float T, int K, float P, uint64_t seed, int L,
+                                          float* stage, SampleShared& sh, const LogprobOut<LOGPROBS>& out, int64_t slot) {
+    const bool greedy = !(T > 0.f);
+    const float* x = xg;
+    if ((LOGPROBS || !greedy) && V <= kStageMax) {
+        for (int v = threadIdx.x; v < V; v += kThreads) stage[v] = xg[v];
+        __syncthreads();
+        x = stage;
+    }
+    int tok;
+    if (greedy) {  // the scores as they are, the order and the -FLT_MAX floor of decoder_argmax_kernel
+        float mv = -FLT_MAX;
+        int mi = -1;
+        for (int v = threadIdx.x; v < V; v += kThreads) {
+            const float xv = x[v];
+            if (xv > mv) {
+                mv = xv;
+                mi = v;
+            }
+        }
+        tok = block_argmax(mv, mi, sh);
+    } else {
+        tok = draw_row(x, V, T, K, P, seed, L, sh);
+    }
+    if constexpr (LOGPROBS) row_logprobs(x, V, tok, out, slot, sh);
+    return tok;
+}
+
+template <bool LOGPROBS>
 __global__ __launch_bounds__(kThreads) void sample_tokens_kernel(
     const float* __restrict__ logits, const float* __restrict__ temperature, const int* __restrict__ top_k,
     const float* __restrict__ top_p, const int64_t* __restrict__ seed, const int* __restrict__ lengths,
-    int* __restrict__ tokens, int V) {
+    int* __restrict__ tokens, int V, const LogprobOut<LOGPROBS> out) {
     extern __shared__ float stage[];
     __shared__ SampleShared sh;
     const int b = blockIdx.x;
     const int L = lengths[b];
     if (L == 0) {  // empty slot
         if (threadIdx.x == 0) tokens[b] = MLI_EMPTY_ROW_TOKEN_ID;
+        if constexpr (LOGPROBS) no_token_logprobs(out, b);
         return;
     }
-    const int tok = sample_row(logits + (int64_t)b * V, V, temperature[b], top_k[b], top_p[b], (uint64_t)seed[b], L,
-                               stage, sh);
+    const int tok = sample_row<LOGPROBS>(logits + (int64_t)b * V, V, temperature[b], top_k[b], top_p[b], (uint64_t)seed[b],
+                                         L, stage, sh, out, b);
     if (threadIdx.x == 0) tokens[b] = tok;
 }
 
 // the token pick, then what decoder_finalize_kernel does with it: result, length update, next input embedding
-template <bool PAGED, int ELEM>
+template <bool PAGED, int ELEM, bool LOGPROBS>
 __global__ __launch_bounds__(kThreads) void decoder_sample_kernel(
     const float* __restrict__ emb_score, const float* __restrict__ temperature, const int* __restrict__ top_k,
     const float* __restrict__ top_p, const int64_t* __restrict__ seed, int* __restrict__ decoder_result,
     int* __restrict__ lengths, float* __restrict__ inp_embedding, float* const* __restrict__ page_table,
     const float* __restrict__ wpe_table, const float* __restrict__ emb_table, int V, int S, int D,
-    int n_decoder_results, int i_decoder) {
+    int n_decoder_results, int i_decoder, const LogprobOut<LOGPROBS> out) {
     extern __shared__ float stage[];
     __shared__ SampleShared sh;
     const int b = blockIdx.x;
     const int L = lengths[b];
+    const int64_t slot = (int64_t)b * n_decoder_results + i_decoder;  // strided like decoder_result
     if (L == 0) {  // empty slot
-        if (threadIdx.x == 0) decoder_result[(int64_t)b * n_decoder_results + i_decoder] = MLI_EMPTY_ROW_TOKEN_ID;
+        if (threadIdx.x == 0) decoder_result[slot] = MLI_EMPTY_ROW_TOKEN_ID;
+        if constexpr (LOGPROBS) no_token_logprobs(out, slot);
         return;
     }
     // every thread has read L: sample_row's reductions pass barriers before thread 0 writes the new length
-    const int tok = sample_row(emb_score + (int64_t)b * V, V, temperature[b], top_k[b], top_p[b], (uint64_t)seed[b], L,
-                               stage, sh);
+    const int tok = sample_row<LOGPROBS>(emb_score + (int64_t)b * V, V, temperature[b], top_k[b], top_p[b],
+                                         (uint64_t)seed[b], L, stage, sh, out, slot);
     const bool done = (L + 1 >= S) || tok == MLI_EOF_TOKEN_ID;
     if (threadIdx.x == 0) {
-        decoder_result[(int64_t)b * n_decoder_results + i_decoder] = tok;
+        decoder_result[slot] = tok;
         lengths[b] = done ? 0 : L + 1;
     }
     if (done || tok < 0) return;  // finished rows get no next embedding
@@ -296,14 +420,35 @@ size_t mli_sample_scratch_bytes(int n_batch, int n_vocab) {
     return 0;  // the draw keeps everything in registers and LDS
 }
 
+// the refusals of the _logprobs entries, before any device pointer is looked at
+static bool logprob_args_ok(const float* token_logprob, const int* top_ids, const float* top_logprobs, int n_top) {
+    return n_top >= 0 && n_top <= MLI_MAX_TOP_LOGPROBS && token_logprob != nullptr &&
+           (n_top == 0 || (top_ids != nullptr && top_logprobs != nullptr));
+}
+
 int mli_sample_tokens(const float* logits, const float* temperature, const int* top_k, const float* top_p,
                       const int64_t* seed, const int* lengths, int* tokens, int n_batch, int n_vocab, void* scratch,
                       size_t scratch_bytes, void* stream) {
     (void)scratch;
     (void)scratch_bytes;
     if (n_batch <= 0 || n_vocab <= 0) return MLI_ERR_BAD_ARG;
-    hipLaunchKernelGGL(mli::sample_tokens_kernel, dim3(n_batch), dim3(mli::kThreads), mli::stage_bytes(n_vocab),
-                       mli::as_stream(stream), logits, temperature, top_k, top_p, seed, lengths, tokens, n_vocab);
+    hipLaunchKernelGGL(mli::sample_tokens_kernel<false>, dim3(n_batch), dim3(mli::kThreads), mli::stage_bytes(n_vocab),
+                       mli::as_stream(stream), logits, temperature, top_k, top_p, seed, lengths, tokens, n_vocab,
+                       mli::LogprobOut<false>{});
+    return mli::launch_status();
+}
+
+int mli_sample_tokens_logprobs(const float* logits, const float* temperature, const int* top_k, const float* top_p,
+                               const int64_t* seed, const int* lengths, int* tokens, float* token_logprob, int* top_ids,
+                               float* top_logprobs, int n_batch, int n_vocab, int n_top, void* scratch,
+                               size_t scratch_bytes, void* stream) {
+    (void)scratch;
+    (void)scratch_bytes;
+    if (!logprob_args_ok(token_logprob, top_ids, top_logprobs, n_top)) return MLI_ERR_BAD_ARG;
+    if (n_batch <= 0 || n_vocab <= 0) return MLI_ERR_BAD_ARG;
+    hipLaunchKernelGGL(mli::sample_tokens_kernel<true>, dim3(n_batch), dim3(mli::kThreads), mli::stage_bytes(n_vocab),
+                       mli::as_stream(stream), logits, temperature, top_k, top_p, seed, lengths, tokens, n_vocab,
+                       mli::LogprobOut<true>{token_logprob, top_ids, top_logprobs, n_top});
     return mli::launch_status();
 }
 
@@ -312,12 +457,15 @@ size_t mli_decoder_sampled_scratch_bytes(int n_batch, int n_vocab) {
     return (size_t)n_batch * n_vocab * sizeof(float) + mli_sample_scratch_bytes(n_batch, n_vocab);
 }
 
+}  // extern "C"
+
 // layout: 0 = contiguous (inp_embedding), 1 = paged fp32, 2 = paged bf16, 3 = paged fp8
+template <bool LOGPROBS>
 static int decoder_sampled(int layout, const float* batch_result, const float* emb_table, const float* wpe_table,
                            float* inp_embedding, float* const* page_table, int* lengths, int* decoder_result,
                            int n_batch, int n_vocab, int n_sequence, int emb_dim, int n_decoder_results, int i_decoder,
                            const float* temperature, const int* top_k, const float* top_p, const int64_t* seed,
-                           void* scratch, size_t scratch_bytes, void* stream) {
+                           void* scratch, size_t scratch_bytes, void* stream, const mli::LogprobOut<LOGPROBS>& out) {
     if (emb_dim % (layout == 3 ? 16 : layout == 2 ? 8 : 4) != 0 || n_batch <= 0 || n_vocab <= 0 || n_decoder_results <= 0 ||
         i_decoder < 0 || i_decoder >= n_decoder_results || (layout != 0 && n_sequence % mli::kPage != 0))
         return MLI_ERR_BAD_ARG;
@@ -329,9 +477,9 @@ static int decoder_sampled(int layout, const float* batch_result, const float* e
     const dim3 grid(n_batch), block(mli::kThreads);
     const size_t lds = mli::stage_bytes(n_vocab);
 #define MLI_SAMPLE_HEAD(PAGED, ELEM)                                                                                       \
-    hipLaunchKernelGGL((mli::decoder_sample_kernel<PAGED, ELEM>), grid, block, lds, st, emb_score, temperature, top_k,     \
-                       top_p, seed, decoder_result, lengths, inp_embedding, page_table, wpe_table, emb_table, n_vocab,     \
-                       n_sequence, emb_dim, n_decoder_results, i_decoder)
+    hipLaunchKernelGGL((mli::decoder_sample_kernel<PAGED, ELEM, LOGPROBS>), grid, block, lds, st, emb_score, temperature,  \
+                       top_k, top_p, seed, decoder_result, lengths, inp_embedding, page_table, wpe_table, emb_table,       \
+                       n_vocab, n_sequence, emb_dim, n_decoder_results, i_decoder, out)
     if (layout == 0) MLI_SAMPLE_HEAD(false, MLI_ELEM_F32);
     else if (layout == 1) MLI_SAMPLE_HEAD(true, MLI_ELEM_F32);
     else if (layout == 2) MLI_SAMPLE_HEAD(true, MLI_ELEM_BF16);
@@ -340,13 +488,15 @@ static int decoder_sampled(int layout, const float* batch_result, const float* e
     return mli::launch_status();
 }
 
+extern "C" {
+
 int mli_decoder_sampled(const float* batch_result, const float* emb_table, const float* wpe_table, float* inp_embedding,
                         int* lengths, int* decoder_result, int n_batch, int n_vocab, int n_sequence, int emb_dim,
                         const float* temperature, const int* top_k, const float* top_p, const int64_t* seed,
                         void* scratch, size_t scratch_bytes, void* stream) {
-    return decoder_sampled(0, batch_result, emb_table, wpe_table, inp_embedding, nullptr, lengths, decoder_result, n_batch,
-                           n_vocab, n_sequence, emb_dim, 1, 0, temperature, top_k, top_p, seed, scratch, scratch_bytes,
-                           stream);
+    return decoder_sampled<false>(0, batch_result, emb_table, wpe_table, inp_embedding, nullptr, lengths, decoder_result,
+                                  n_batch, n_vocab, n_sequence, emb_dim, 1, 0, temperature, top_k, top_p, seed, scratch,
+                                  scratch_bytes, stream, {});
 }
 
 int mli_paged_decoder_sampled(const float* batch_result, const float* emb_table, const float* wpe_table,
@@ -355,9 +505,36 @@ int mli_paged_decoder_sampled(const float* batch_result, const float* emb_table,
                               const float* temperature, const int* top_k, const float* top_p, const int64_t* seed,
                               void* scratch, size_t scratch_bytes, void* stream) {
     if (elem < MLI_ELEM_F32 || elem > MLI_ELEM_FP8) return MLI_ERR_BAD_ARG;
-    return decoder_sampled(1 + elem, batch_result, emb_table, wpe_table, nullptr, reinterpret_cast<float* const*>(page_table),
-                           lengths, decoder_result, n_batch, n_vocab, n_sequence, emb_dim, n_decoder_results, i_decoder,
-                           temperature, top_k, top_p, seed, scratch, scratch_bytes, stream);
+    return decoder_sampled<false>(1 + elem, batch_result, emb_table, wpe_table, nullptr,
+                                  reinterpret_cast<float* const*>(page_table), lengths, decoder_result, n_batch, n_vocab,
+                                  n_sequence, emb_dim, n_decoder_results, i_decoder, temperature, top_k, top_p, seed, scratch,
+                                  scratch_bytes, stream, {});
+}
+
+int mli_decoder_sampled_logprobs(const float* batch_result, const float* emb_table, const float* wpe_table,
+                                 float* inp_embedding, int* lengths, int* decoder_result, int n_batch, int n_vocab,
+                                 int n_sequence, int emb_dim, int n_decoder_results, int i_decoder,
+                                 const float* temperature, const int* top_k, const float* top_p, const int64_t* seed,
+                                 float* token_logprob, int* top_ids, float* top_logprobs, int n_top, void* scratch,
+                                 size_t scratch_bytes, void* stream) {
+    if (!logprob_args_ok(token_logprob, top_ids, top_logprobs, n_top)) return MLI_ERR_BAD_ARG;
+    return decoder_sampled<true>(0, batch_result, emb_table, wpe_table, inp_embedding, nullptr, lengths, decoder_result,
+                                 n_batch, n_vocab, n_sequence, emb_dim, n_decoder_results, i_decoder, temperature, top_k,
+                                 top_p, seed, scratch, scratch_bytes, stream, {token_logprob, top_ids, top_logprobs, n_top});
+}
+
+int mli_paged_decoder_sampled_logprobs(const float* batch_result, const float* emb_table, const float* wpe_table,
+                                       void* const* page_table, int* lengths, int* decoder_result, int n_batch,
+                                       int n_vocab, int n_sequence, int emb_dim, int n_decoder_results, int i_decoder,
+                                       int elem, const float* temperature, const int* top_k, const float* top_p,
+                                       const int64_t* seed, float* token_logprob, int* top_ids, float* top_logprobs,
+                                       int n_top, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!logprob_args_ok(token_logprob, top_ids, top_logprobs, n_top)) return MLI_ERR_BAD_ARG;
+    if (elem < MLI_ELEM_F32 || elem > MLI_ELEM_FP8) return MLI_ERR_BAD_ARG;
+    return decoder_sampled<true>(1 + elem, batch_result, emb_table, wpe_table, nullptr,
+                                 reinterpret_cast<float* const*>(page_table), lengths, decoder_result, n_batch, n_vocab,
+                                 n_sequence, emb_dim, n_decoder_results, i_decoder, temperature, top_k, top_p, seed, scratch,
+                                 scratch_bytes, stream, {token_logprob, top_ids, top_logprobs, n_top});
 }
 
 }  // extern "C"

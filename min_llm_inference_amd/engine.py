@@ -39,7 +39,7 @@ def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
 class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
                  n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None,
-                 release_pages=False, n_kv_heads=None):
+                 release_pages=False, n_kv_heads=None, logprobs=None):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -57,6 +57,8 @@ class Engine:
             self.set_sinks(sinks)
         if release_pages:
             self.set_page_release(True)
+        if logprobs is not None:
+            self.set_logprobs(logprobs)
 
     def _check(self, rc):
         if rc != 0:
@@ -87,6 +89,32 @@ class Engine:
         while they decode, and new rows take and prefill their live pages only.  Before the first step or run, paged
         kinds; without a window below n_sequence it changes nothing."""
         self._check(self._lib.mli_engine_set_page_release(self._h, int(bool(enabled))))
+
+    def set_logprobs(self, n_top=0):
+        """Per-token log-probabilities (mli_engine_set_logprobs): the engine records, for every generated
+        token, its natural-log probability under the raw model distribution and the `n_top` (0 .. 8) most probable
+        alternatives.  Before the first step or run, every kind; item ids must be unique from then on."""
+        self._check(self._lib.mli_engine_set_logprobs(self._h, int(n_top)))
+        self._n_top = int(n_top)
+
+    def finished_logprobs(self):
+        """{id: (n_prompt, logprobs [n], top_ids [n, n_top], top_logprobs [n, n_top])} of the finished items: entry i
+        belongs to token n_prompt + i of finished()'s tokens (mli_engine_get_finished_logprobs)."""
+        out = {}
+        n_top = getattr(self, "_n_top", 0)
+        cap = self.cfg.n_sequence + 16
+        lp = np.empty(cap, np.float32)
+        ids = np.empty(cap * max(n_top, 1), np.int32)
+        tops = np.empty(cap * max(n_top, 1), np.float32)
+        for i, (item_id, _) in enumerate(self.finished()):
+            n_prompt, n = ctypes.c_int(), ctypes.c_int()
+            self._check(self._lib.mli_engine_get_finished_logprobs(
+                self._h, i, ctypes.byref(n_prompt), lp.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(n),
+                ids.ctypes.data_as(ctypes.c_void_p), tops.ctypes.data_as(ctypes.c_void_p), cap * n_top))
+            k = n.value
+            out[item_id] = (n_prompt.value, lp[:k].copy(), ids[:k * n_top].reshape(k, n_top).copy(),
+                            tops[:k * n_top].reshape(k, n_top).copy())
+        return out
 
     def page_stats(self):
         """mli_engine_get_page_stats: pool_pages, in_use, peak_in_use, released_early, preemptions (paged kinds)."""

@@ -78,6 +78,9 @@ public:
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
     // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling)
     void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }
+    // EXTENSION: the sampled head reports log-probabilities into buffers this model owns (DecoderLayer::set_logprobs)
+    void set_logprobs(int n_top) { logprobs_.allocate(n_batch_, (size_t)n_forward_rounds_, n_top); }
+    const DecoderLogprobs& logprobs() const { return logprobs_; }
     void set_n_heads(int n_heads) { attention_layer_.set_n_heads(n_heads); }
     void set_n_kv_heads(int n_kv_heads) { attention_layer_.set_n_kv_heads(n_kv_heads); }
     void set_window(int window) { attention_layer_.set_window(window); }
@@ -91,6 +94,7 @@ private:
     TensorFloat emb_score_;
     int n_forward_rounds_;
     const SlotSampling* sampling_ = nullptr;
+    DecoderLogprobs logprobs_;
 };
 
 void start_paged_attention_bf16_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table,

@@ -50,6 +50,9 @@ public:
     // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling); allocates the
     // logits buffer the sampled head needs
     void set_sampling(const SlotSampling* sampling);
+    // EXTENSION: the sampled head reports log-probabilities into buffers this model owns (DecoderLayer::set_logprobs)
+    void set_logprobs(int n_top) { logprobs_.allocate(n_batch_, (size_t)n_forward_rounds_, n_top); }
+    const DecoderLogprobs& logprobs() const { return logprobs_; }
     void set_window(int window) { attention_layer_.set_window(window); }
     void set_sinks(int n_sink) { attention_layer_.set_sinks(n_sink); }
     void set_page_release(bool enabled) { attention_layer_.set_page_release(enabled); }
@@ -62,6 +65,7 @@ private:
     int n_forward_rounds_;
     const SlotSampling* sampling_ = nullptr;
     std::unique_ptr<TensorFloat> emb_score_;  // [n_batch, n_vocab], allocated when sampling is set
+    DecoderLogprobs logprobs_;
 };
 
 void start_paged_attention_fp8_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table,

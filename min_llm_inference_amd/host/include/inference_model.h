@@ -16,6 +16,9 @@ public:
                  const TensorFloat& pos_emb_table);
     // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling)
     void set_sampling(const SlotSampling* sampling) { decoder_layer_.set_sampling(sampling); }
+    // EXTENSION: the sampled head reports log-probabilities into buffers the decoder layer owns (DecoderLayer::set_logprobs)
+    void set_logprobs(int n_top) { decoder_layer_.set_logprobs(1, n_top); }
+    const DecoderLogprobs& logprobs() const { return decoder_layer_.logprobs(); }
 
 private:
     SelfAttentionLayer attention_layer_;
@@ -36,6 +39,8 @@ public:
                  TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
     void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
+    void set_logprobs(int n_top) { paged_decoder_layer_.set_logprobs(n_forward_rounds_, n_top); }     // EXTENSION
+    const DecoderLogprobs& logprobs() const { return paged_decoder_layer_.logprobs(); }
     void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
     void set_n_kv_heads(int n_kv_heads) { paged_attention_layer_.set_n_kv_heads(n_kv_heads); }        // EXTENSION
     void set_window(int window) { paged_attention_layer_.set_window(window); }                        // EXTENSION
@@ -61,6 +66,8 @@ public:
                  TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
                  const TensorFloat& pos_emb_table, TensorFloatPoint& page_table, GemmHandle handle);
     void set_sampling(const SlotSampling* sampling) { paged_decoder_layer_.set_sampling(sampling); }  // EXTENSION
+    void set_logprobs(int n_top) { paged_decoder_layer_.set_logprobs(n_forward_rounds_, n_top); }     // EXTENSION
+    const DecoderLogprobs& logprobs() const { return paged_decoder_layer_.logprobs(); }
     void set_n_heads(int n_heads) { paged_attention_layer_.set_n_heads(n_heads); }                    // EXTENSION
     void set_n_kv_heads(int n_kv_heads) { paged_attention_layer_.set_n_kv_heads(n_kv_heads); }        // EXTENSION
     void set_window(int window) { paged_attention_layer_.set_window(window); }                        // EXTENSION

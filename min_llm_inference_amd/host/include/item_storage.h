@@ -63,11 +63,21 @@ private:
 
 void append_token_to_id_string_pair(IdTokensPair& id_string_pair, int to_add);
 
+// EXTENSION: figures that travel with decoder_result (the engines' per-token log-probabilities).  fetch() is
+// called where decoder_result crosses to the host -- the blocking copy of the sequential loop (in_flight = false), or
+// queued behind the pipelined loop's stream-ordered copy, before its marker (in_flight = true) -- and token() where a
+// token of that result has just been appended to its item: a token that is dropped takes its figures with it.
+struct ResultFigures {
+    virtual ~ResultFigures() = default;
+    virtual void fetch(bool in_flight) = 0;
+    virtual void token(const IdTokensPair& item, int slot, int round) = 0;  // item: the token already appended
+};
+
 // D2H copy of the decoder output, append tokens, detect finished rows (EOF or n_sequence tokens).
 // Returns the slots that can take a new item (finished or empty), in slot order.
 std::vector<int> process_decoder_result(const TensorInt& decoder_result_device, TensorInt& decoder_result_host,
                                         ItemStorage& item_storage, ProcessingStorage& processing_storage,
-                                        int n_sequence);
+                                        int n_sequence, ResultFigures* figures = nullptr);
 
 // Contiguous engine: fill the given slots from the queue (length 0 when the queue runs dry), upload.
 // Returns the number of newly inserted items.

@@ -7,7 +7,7 @@
 #include "tensor.hpp"
 #include "utils.h"
 
-struct SlotSampling;  // kernels/decoder.h
+#include "kernels/decoder.h"  // SlotSampling, DecoderLogprobs
 
 class SelfAttentionLayer : public NonCopyableNonClonable {
 public:
@@ -119,10 +119,15 @@ public:
 
     // EXTENSION: from now on forward() runs the sampled head with these per-slot parameters (nullptr: the greedy head)
     void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }
+    // EXTENSION: the sampled head also reports log-probabilities into buffers this layer owns from now on:
+    // [n_batch, n_rounds(, n_top)], n_top in 0 .. 8.  Takes effect where the sampled head runs (set_sampling).
+    void set_logprobs(int n_rounds, int n_top) { logprobs_.allocate(emb_score_.shape()[0], (size_t)n_rounds, n_top); }
+    const DecoderLogprobs& logprobs() const { return logprobs_; }
 
 private:
     TensorFloat emb_score_;  // [n_batch, n_vocab]
     const SlotSampling* sampling_ = nullptr;
+    DecoderLogprobs logprobs_;
 };
 
 class PagedDecoderLayer : public NonCopyableNonClonable {
@@ -132,10 +137,13 @@ public:
                  TensorFloatPoint& page_table, TensorInt& lengths, TensorInt& decoder_result, int i_decoder_round);
 
     void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }  // EXTENSION, as DecoderLayer's
+    void set_logprobs(int n_rounds, int n_top) { logprobs_.allocate(emb_score_.shape()[0], (size_t)n_rounds, n_top); }
+    const DecoderLogprobs& logprobs() const { return logprobs_; }
 
 private:
     TensorFloat emb_score_;
     const SlotSampling* sampling_ = nullptr;
+    DecoderLogprobs logprobs_;
 };
 
 class PagedCublasDecoderLayer : public NonCopyableNonClonable {
@@ -146,8 +154,11 @@ public:
                  GemmHandle& handle);
 
     void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }  // EXTENSION, as DecoderLayer's
+    void set_logprobs(int n_rounds, int n_top) { logprobs_.allocate(emb_score_.shape()[0], (size_t)n_rounds, n_top); }
+    const DecoderLogprobs& logprobs() const { return logprobs_; }
 
 private:
     TensorFloat emb_score_;
     const SlotSampling* sampling_ = nullptr;
+    DecoderLogprobs logprobs_;
 };

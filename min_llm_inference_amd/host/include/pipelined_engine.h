@@ -36,7 +36,7 @@ long long run_paged_engine_pipelined(ItemStorage& item_storage, ProcessingStorag
                                      MemoryBlockManager& memory_block_manager,
                                      PagedAttentionsManager& paged_attention_manager, size_t n_batch_size,
                                      size_t n_sequence, const PagedForward& forward, int n_forward_rounds = 1,
-                                     const PagedAdmitHook& on_admit = {});
+                                     const PagedAdmitHook& on_admit = {}, ResultFigures* figures = nullptr);
 
 void start_paged_attention_inference_engine_pipelined(const TensorFloat& emb_table, const TensorFloat& pos_table,
                                                       ItemStorage& item_storage, ProcessingStorage& processing_storage,

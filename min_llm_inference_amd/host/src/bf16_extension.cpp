@@ -134,7 +134,7 @@ void PagedAttentionBf16InferenceModel::forward(const TensorInt& inp, TensorInt& 
         }
         if (sampling_) {
             launch_paged_attention_decoder_sampled(attention_result_, emb_table, emb_score_, pos_emb_table, page_table,
-                                                   lengths, decoder_result, round, MLI_ELEM_BF16, *sampling_);
+                                                   lengths, decoder_result, round, MLI_ELEM_BF16, *sampling_, &logprobs_);
         } else if (mli::runtime::lean_layers()) {
             HIP_CHECK(mli_paged_decoder_fused(attention_result_.data(), emb_table.data(), pos_emb_table.data(),
                                               reinterpret_cast<void* const*>(page_table.data()), lengths.data(),

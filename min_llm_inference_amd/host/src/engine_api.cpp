@@ -11,6 +11,7 @@
 #include <numeric>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "bf16_extension.h"
@@ -119,11 +120,76 @@ struct mli_engine {
         return it == sampling.end() ? Sampling{} : it->second;
     }
 
+    // EXTENSION: per-token log-probabilities (mli_engine_set_logprobs).  The decoder layer owns the device
+    // buffers; the figures cross to the host with decoder_result and are appended, keyed by item id, where the token is
+    // appended to the item -- so a token dropped by a preemption takes its figures with it and a re-admitted item keeps
+    // those of the tokens it already generated.
+    struct Logprobs : ResultFigures {
+        struct Record {
+            int n_prompt = 0;
+            std::vector<float> token_logprob, top_logprobs;
+            std::vector<int> top_ids;
+        };
+        int n_top, n_rounds, width;
+        TensorFloat token_device, top_device, token_host, top_host;  // shallow copies of the layer's / pinned mirrors
+        TensorInt ids_device, ids_host;
+        std::unordered_map<int, Record> records;
+
+        explicit Logprobs(const DecoderLogprobs& d)
+            : n_top(d.n_top), n_rounds(d.n_rounds), width(d.n_top > 0 ? d.n_top : 1), token_device(*d.token_logprob),
+              top_device(*d.top_logprobs), token_host(d.token_logprob->shape(), DeviceType::HOST, TensorDataType::SYNC_ALLOCATE),
+              top_host(d.top_logprobs->shape(), DeviceType::HOST, TensorDataType::SYNC_ALLOCATE), ids_device(*d.top_ids),
+              ids_host(d.top_ids->shape(), DeviceType::HOST, TensorDataType::SYNC_ALLOCATE) {}
+
+        void fetch(bool in_flight) override {
+            if (in_flight) {
+                token_host.copy_range_from_async(token_device, 0, token_host.get_total_size());
+                if (n_top > 0) {
+                    ids_host.copy_range_from_async(ids_device, 0, ids_host.get_total_size());
+                    top_host.copy_range_from_async(top_device, 0, top_host.get_total_size());
+                }
+                return;
+            }
+            token_host.copy_from(token_device);
+            if (n_top > 0) {
+                ids_host.copy_from(ids_device);
+                top_host.copy_from(top_device);
+            }
+        }
+
+        void token(const IdTokensPair& item, int slot, int round) override {
+            auto it = records.find(item.first);
+            if (it == records.end()) {
+                it = records.emplace(item.first, Record{}).first;
+                it->second.n_prompt = (int)item.second.size() - 1;  // its first generated token has just been appended
+            }
+            Record& r = it->second;
+            const size_t at = (size_t)slot * n_rounds + round;
+            r.token_logprob.push_back(token_host.data()[at]);
+            if (n_top > 0) {
+                r.top_ids.insert(r.top_ids.end(), ids_host.data() + at * width, ids_host.data() + (at + 1) * width);
+                r.top_logprobs.insert(r.top_logprobs.end(), top_host.data() + at * width, top_host.data() + (at + 1) * width);
+            }
+        }
+    };
+    int logprobs_n_top = -1;              // mli_engine_set_logprobs: -1 = never called
+    std::unique_ptr<Logprobs> logprobs;   // from the first step or run of an engine with logprobs
+    std::unordered_set<int> item_ids;     // every id queued so far
+    bool duplicate_ids = false;
+
+    void note_item_id(int id) {
+        if (!item_ids.insert(id).second) {
+            if (logprobs_n_top >= 0) throw std::invalid_argument("an engine with logprobs keys them by item id: duplicate id " + std::to_string(id));
+            duplicate_ids = true;
+        }
+    }
+
     void choose_head() {
         if (head >= 0) return;
         head = 0;
         for (const auto& kv : sampling)
             if (kv.second.temperature > 0.f) head = 1;
+        if (logprobs_n_top >= 0) head = 1;  // the figures come from materialised logits, for greedy items too
         if (!head) return;
         const size_t B = cfg.n_batch;
         slots_device = std::make_unique<SlotArrays>(B, DeviceType::DEVICE);
@@ -137,6 +203,16 @@ struct mli_engine {
         if (gemm_model) gemm_model->set_sampling(&slot_sampling);
         if (bf16_model) bf16_model->set_sampling(&slot_sampling);
         if (fp8_model) fp8_model->set_sampling(&slot_sampling);
+        if (logprobs_n_top < 0) return;
+        const DecoderLogprobs* buffers = nullptr;
+#define MLI_SET_LOGPROBS(model) if (model) { model->set_logprobs(logprobs_n_top); buffers = &model->logprobs(); }
+        MLI_SET_LOGPROBS(naive_model)
+        MLI_SET_LOGPROBS(paged_model)
+        MLI_SET_LOGPROBS(gemm_model)
+        MLI_SET_LOGPROBS(bf16_model)
+        MLI_SET_LOGPROBS(fp8_model)
+#undef MLI_SET_LOGPROBS
+        logprobs = std::make_unique<Logprobs>(*buffers);
     }
 
     void set_slot_host(int b, const Sampling& s) {
@@ -326,7 +402,7 @@ struct mli_engine {
                 else
                     gemm_model->forward(inp, lengths, new_idx, result, n_new, emb_table, pos_table,
                                         pages->get_page_table_device(), handle);
-            }, cfg.n_forward_rounds, [&](const std::vector<int>& slots) { scatter_admitted(slots); });
+            }, cfg.n_forward_rounds, [&](const std::vector<int>& slots) { scatter_admitted(slots); }, logprobs.get());
     }
 
     double t_forward = 0, t_result = 0, t_pages = 0, t_insert = 0;  // host seconds per phase (MLI_ENGINE_TIMING=1)
@@ -355,7 +431,8 @@ struct mli_engine {
                                 pos_table, pages->get_page_table_device(), handle);
         const double t1 = now();
         std::vector<int> free_slots =
-            process_decoder_result(result_device, result_host, item_storage, processing_storage, cfg.n_sequence);
+            process_decoder_result(result_device, result_host, item_storage, processing_storage, cfg.n_sequence,
+                                   logprobs.get());
         const double t2 = now();
         if (paged())
             allocate_or_free_memory_blocks_if_needed(*pages, *pool, processing_storage, item_storage, free_slots,
@@ -587,7 +664,10 @@ void mli_engine_destroy(mli_engine* e) {
 
 int mli_engine_add_item(mli_engine* e, int id, const int* tokens, int n_tokens) {
     if (!e || !tokens || n_tokens <= 0 || n_tokens + 1 > e->cfg.n_sequence) { g_last_error = "bad item"; return -1; }
-    MLI_GUARD(e->item_storage.add_new_item(std::make_pair(id, std::vector<int>(tokens, tokens + n_tokens))))
+    MLI_GUARD({
+        e->note_item_id(id);
+        e->item_storage.add_new_item(std::make_pair(id, std::vector<int>(tokens, tokens + n_tokens)));
+    })
 }
 
 int mli_engine_add_item_sampled(mli_engine* e, int id, const int* tokens, int n_tokens, float temperature, int top_k,
@@ -605,6 +685,7 @@ int mli_engine_add_item_sampled(mli_engine* e, int id, const int* tokens, int n_
         if (e->head == 0 && temperature > 0.f)
             throw std::runtime_error("this engine chose the greedy head at its first step: a sampled item (temperature "
                                      "> 0) must be queued before the first step or run");
+        e->note_item_id(id);
         e->item_storage.add_new_item(std::make_pair(id, std::vector<int>(tokens, tokens + n_tokens)));
         mli_engine::Sampling params;
         params.temperature = temperature;
@@ -612,6 +693,42 @@ int mli_engine_add_item_sampled(mli_engine* e, int id, const int* tokens, int n_
         params.top_p = top_p;
         params.seed = seed;
         e->sampling[id] = params;
+    })
+}
+
+int mli_engine_set_logprobs(mli_engine* e, int n_top) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (n_top < 0 || n_top > MLI_MAX_TOP_LOGPROBS)
+            throw std::invalid_argument("mli_engine_set_logprobs: n_top must lie in 0 .. " + std::to_string(MLI_MAX_TOP_LOGPROBS));
+        if (e->started) throw std::runtime_error("mli_engine_set_logprobs after the engine has started");
+        if (e->cfg.reference_length_reset_quirk)
+            throw std::invalid_argument("mli_engine_set_logprobs: not with reference_length_reset_quirk (the sampled head, "
+                                        "which reports the figures, and the quirk exclude each other)");
+        if (e->duplicate_ids)
+            throw std::invalid_argument("mli_engine_set_logprobs: the figures are keyed by item id, and an id was queued twice");
+        e->logprobs_n_top = n_top;
+    })
+}
+
+int mli_engine_get_finished_logprobs(mli_engine* e, int index, int* n_prompt, float* token_logprobs, int capacity,
+                                     int* n_generated, int* top_ids, float* top_logprobs, int top_capacity) {
+    MLI_GUARD({
+        if (!e || !n_prompt || !n_generated) throw std::runtime_error("null argument");
+        if (e->logprobs_n_top < 0) throw std::runtime_error("mli_engine_get_finished_logprobs: an engine without logprobs "
+                                                            "(mli_engine_set_logprobs)");
+        const auto& items = e->item_storage.get_finished_items();
+        if (index < 0 || index >= (int)items.size()) throw std::out_of_range("finished item index");
+        const int id = std::next(items.begin(), index)->first;
+        if (!e->logprobs || !e->logprobs->records.count(id)) throw std::runtime_error("no figures for item " + std::to_string(id));
+        const auto& r = e->logprobs->records.at(id);
+        *n_prompt = r.n_prompt;
+        *n_generated = (int)r.token_logprob.size();
+        if (token_logprobs && capacity > 0)
+            std::memcpy(token_logprobs, r.token_logprob.data(), sizeof(float) * std::min<size_t>(capacity, r.token_logprob.size()));
+        const size_t n = top_capacity > 0 ? std::min<size_t>(top_capacity, r.top_ids.size()) : 0;
+        if (top_ids && n) std::memcpy(top_ids, r.top_ids.data(), sizeof(int) * n);
+        if (top_logprobs && n) std::memcpy(top_logprobs, r.top_logprobs.data(), sizeof(float) * n);
     })
 }
 

@@ -57,7 +57,7 @@ void PagedAttentionFp8InferenceModel::forward(const TensorInt& inp, TensorInt& l
         attention_layer_.forward(page_table, lengths, new_item_indices, attention_result_, 0);
         if (sampling_) {
             launch_paged_attention_decoder_sampled(attention_result_, emb_table, *emb_score_, pos_emb_table, page_table,
-                                                   lengths, decoder_result, round, MLI_ELEM_FP8, *sampling_);
+                                                   lengths, decoder_result, round, MLI_ELEM_FP8, *sampling_, &logprobs_);
             continue;
         }
         HIP_CHECK(mli_paged_decoder_fused(attention_result_.data(), emb_table.data(), pos_emb_table.data(),

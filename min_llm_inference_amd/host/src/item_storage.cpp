@@ -85,10 +85,11 @@ void upload_changed_rows(TensorInt& inp_device, TensorInt& inp_host, const std::
 // ---- per-iteration host steps -------------------------------------------------------------------------
 std::vector<int> process_decoder_result(const TensorInt& decoder_result_device, TensorInt& decoder_result_host,
                                         ItemStorage& item_storage, ProcessingStorage& processing_storage,
-                                        int n_sequence) {
+                                        int n_sequence, ResultFigures* figures) {
     const int n_batch = static_cast<int>(decoder_result_host.shape()[0]);
     const int n_rounds = decoder_result_host.shape().size() == 2 ? static_cast<int>(decoder_result_host.shape()[1]) : 1;
     decoder_result_host.copy_from(decoder_result_device);  // the device -> host sync point of the iteration
+    if (figures) figures->fetch(/*in_flight=*/false);
     const int* tokens = decoder_result_host.data();
 
     std::vector<int> free_slots;
@@ -103,6 +104,7 @@ std::vector<int> process_decoder_result(const TensorInt& decoder_result_device, 
             }
             IdTokensPair& item = processing_storage.get_token(b);
             append_token_to_id_string_pair(item, tok);
+            if (figures) figures->token(item, b, r);
             ++appended;
             row_done = tok == EOF_TOKEN_ID || static_cast<int>(item.second.size()) >= n_sequence;
         }

@@ -456,7 +456,16 @@ void launch_paged_attention_decoder_fused(const TensorFloat& batch_result, const
 // EXTENSION: the sampled head; emb_score [n_batch, n_vocab] is the scratch that receives the logits
 void launch_decoder_sampled(const TensorFloat& batch_result, const TensorFloat& emb_table, TensorFloat& emb_score,
                             const TensorFloat& wpe_table, TensorFloat& inp_embedding, TensorInt& lengths,
-                            TensorInt& decoder_result, const SlotSampling& s) {
+                            TensorInt& decoder_result, const SlotSampling& s, const DecoderLogprobs* lp) {
+    if (lp && lp->on()) {
+        HIP_CHECK(mli_decoder_sampled_logprobs(
+            batch_result.data(), emb_table.data(), wpe_table.data(), inp_embedding.data(), lengths.data(),
+            decoder_result.data(), (int)batch_result.shape()[0], (int)emb_table.shape()[0], (int)wpe_table.shape()[0],
+            (int)batch_result.shape()[1], /*n_decoder_results=*/1, /*i_decoder=*/0, s.temperature, s.top_k, s.top_p, s.seed,
+            lp->token_logprob->data(), lp->top_ids->data(), lp->top_logprobs->data(), lp->n_top, emb_score.data(),
+            emb_score.get_total_size() * sizeof(float), stream()));
+        return;
+    }
     HIP_CHECK(mli_decoder_sampled(batch_result.data(), emb_table.data(), wpe_table.data(), inp_embedding.data(),
                                   lengths.data(), decoder_result.data(), (int)batch_result.shape()[0],
                                   (int)emb_table.shape()[0], (int)wpe_table.shape()[0], (int)batch_result.shape()[1],
@@ -467,8 +476,18 @@ void launch_decoder_sampled(const TensorFloat& batch_result, const TensorFloat& 
 void launch_paged_attention_decoder_sampled(const TensorFloat& batch_result, const TensorFloat& emb_table,
                                             TensorFloat& emb_score, const TensorFloat& wpe_table,
                                             TensorFloatPoint& page_table, TensorInt& lengths, TensorInt& decoder_result,
-                                            int i_decoder, int elem, const SlotSampling& s) {
+                                            int i_decoder, int elem, const SlotSampling& s, const DecoderLogprobs* lp) {
     const int n_results = decoder_result.shape().size() == 2 ? (int)decoder_result.shape()[1] : 1;
+    if (lp && lp->on()) {
+        if (lp->n_rounds != n_results) throw std::runtime_error("decoder logprobs: buffers sized for another number of rounds");
+        HIP_CHECK(mli_paged_decoder_sampled_logprobs(
+            batch_result.data(), emb_table.data(), wpe_table.data(), reinterpret_cast<void* const*>(pages(page_table)),
+            lengths.data(), decoder_result.data(), (int)batch_result.shape()[0], (int)emb_table.shape()[0],
+            (int)wpe_table.shape()[0], (int)batch_result.shape()[1], n_results, i_decoder, elem, s.temperature, s.top_k,
+            s.top_p, s.seed, lp->token_logprob->data(), lp->top_ids->data(), lp->top_logprobs->data(), lp->n_top,
+            emb_score.data(), emb_score.get_total_size() * sizeof(float), stream()));
+        return;
+    }
     HIP_CHECK(mli_paged_decoder_sampled(batch_result.data(), emb_table.data(), wpe_table.data(),
                                         reinterpret_cast<void* const*>(pages(page_table)), lengths.data(),
                                         decoder_result.data(), (int)batch_result.shape()[0], (int)emb_table.shape()[0],

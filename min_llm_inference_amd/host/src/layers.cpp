@@ -122,7 +122,7 @@ void DecoderLayer::forward(const TensorFloat& batch_result, const TensorFloat& e
                            TensorInt& decoder_result) {
     if (sampling_)
         launch_decoder_sampled(batch_result, emb_table, emb_score_, wpe_table, inp_embedding, lengths, decoder_result,
-                               *sampling_);
+                               *sampling_, &logprobs_);
     else if (mli::runtime::lean_layers())
         launch_decoder_fused(batch_result, emb_table, emb_score_, wpe_table, inp_embedding, lengths, decoder_result);
     else
@@ -137,7 +137,7 @@ void PagedDecoderLayer::forward(const TensorFloat& batch_result, const TensorFlo
                                 TensorInt& decoder_result, int i_decoder_round) {
     if (sampling_)
         launch_paged_attention_decoder_sampled(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
-                                               decoder_result, i_decoder_round, MLI_ELEM_F32, *sampling_);
+                                               decoder_result, i_decoder_round, MLI_ELEM_F32, *sampling_, &logprobs_);
     else if (mli::runtime::lean_layers())
         launch_paged_attention_decoder_fused(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
                                              decoder_result, i_decoder_round);
@@ -155,7 +155,7 @@ void PagedCublasDecoderLayer::forward(const TensorFloat& batch_result, const Ten
                                       GemmHandle& handle) {
     if (sampling_)
         launch_paged_attention_decoder_sampled(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
-                                               decoder_result, i_decoder_round, MLI_ELEM_F32, *sampling_);
+                                               decoder_result, i_decoder_round, MLI_ELEM_F32, *sampling_, &logprobs_);
     else if (mli::runtime::lean_layers())
         launch_paged_attention_decoder_fused(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
                                              decoder_result, i_decoder_round);

@@ -29,7 +29,7 @@ struct MarkerHandle {
 long long run_paged_engine_pipelined(ItemStorage& item_storage, ProcessingStorage& processing_storage,
                                      MemoryBlockManager& pool, PagedAttentionsManager& pages, size_t n_batch_size,
                                      size_t n_sequence, const PagedForward& forward, int n_forward_rounds,
-                                     const PagedAdmitHook& on_admit) {
+                                     const PagedAdmitHook& on_admit, ResultFigures* figures) {
     // Every in-flight row has up to R tokens in flight and is about to produce R more, so the page bookkeeping is asked
     // for tokens + 2 R positions; its rule "a row needs at most one more page per pass" holds while 2 R <= PAGE_BLOCK_SIZE.
     const int R = n_forward_rounds;
@@ -116,6 +116,7 @@ long long run_paged_engine_pipelined(ItemStorage& item_storage, ProcessingStorag
                     const int tok = tokens[static_cast<size_t>(b) * R + r];
                     if (tok == EMPTY_ROW_TOKEN_ID) throw std::runtime_error("pipelined engine: in-flight row reported empty");
                     append_token_to_id_string_pair(item, tok);
+                    if (figures) figures->token(item, b, r);
                     ++appended;
                     if (tok == EOF_TOKEN_ID || static_cast<int>(item.second.size()) >= S) {
                         processing_storage.move_to_finished(b, item_storage);
@@ -154,6 +155,7 @@ long long run_paged_engine_pipelined(ItemStorage& item_storage, ProcessingStorag
     while (true) {
         // A. result(step) starts travelling as soon as forward(step) is done
         result_host.copy_range_from_async(result_device, 0, n_batch_size * n_rounds);
+        if (figures) figures->fetch(/*in_flight=*/true);  // the same sync point: one marker covers both
         mli::mem::record_marker(marker.m);
 
         // B. pages for forward(step + 1): every in-flight row has up to R tokens in flight (one per round of

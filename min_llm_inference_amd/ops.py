@@ -430,6 +430,28 @@ def sample_tokens(logits, temperature, top_k, top_p, seed, lengths, tokens=None)
     return tokens
 
 
+def sample_tokens_logprobs(logits, temperature, top_k, top_p, seed, lengths, n_top=0, tokens=None):
+    """EXTENSION: sample_tokens plus, per row, the natural-log probability of the emitted token under the raw distribution of
+    the row's finite logits and the n_top (0 .. 8) candidates of largest logit with theirs (mli_sample_tokens_logprobs;
+    DESIGN 3.6c).  Returns (tokens [B] int32, token_logprob [B] float32, top_ids [B, n_top] int32, top_logprobs [B, n_top]
+    float32)."""
+    lib = load_library()
+    B, V = logits.shape
+    n_top = int(n_top)
+    if tokens is None:
+        tokens = torch.empty(B, dtype=torch.int32, device=logits.device)
+    token_logprob = torch.empty(B, dtype=torch.float32, device=logits.device)
+    top_ids = torch.empty((B, max(n_top, 0)), dtype=torch.int32, device=logits.device)
+    top_logprobs = torch.empty((B, max(n_top, 0)), dtype=torch.float32, device=logits.device)
+    need = int(lib.mli_sample_scratch_bytes(B, V))
+    sc = torch.empty(max(need, 16), dtype=torch.uint8, device=logits.device) if need else None
+    _check(lib.mli_sample_tokens_logprobs(_p(logits), *_sampling_args(temperature, top_k, top_p, seed), _p(lengths), _p(tokens),
+                                          _p(token_logprob), _p(top_ids) if n_top > 0 else None,
+                                          _p(top_logprobs) if n_top > 0 else None, B, V, n_top, _p(sc), need, _stream()),
+           "mli_sample_tokens_logprobs")
+    return tokens, token_logprob, top_ids, top_logprobs
+
+
 def _sampled_scratch(n_batch, n_vocab, device):
     need = int(load_library().mli_decoder_sampled_scratch_bytes(n_batch, n_vocab))
     return torch.empty(max(need, 16), dtype=torch.uint8, device=device), need
@@ -458,6 +480,45 @@ def paged_decoder_sampled(batch_result, emb_table, wpe_table, page_table, length
                                                     wpe_table.shape[0], D, n_res, i_decoder, int(elem),
                                                     *_sampling_args(temperature, top_k, top_p, seed), _p(sc), need,
                                                     _stream()), "mli_paged_decoder_sampled")
+
+
+def _logprob_outputs(decoder_result, n_top):
+    """token_logprob, top_ids, top_logprobs shaped and strided like decoder_result ([B] or [B, n_results])"""
+    shape, dev = tuple(decoder_result.shape), decoder_result.device
+    return (torch.empty(shape, dtype=torch.float32, device=dev), torch.empty(shape + (n_top,), dtype=torch.int32, device=dev),
+            torch.empty(shape + (n_top,), dtype=torch.float32, device=dev))
+
+
+def decoder_sampled_logprobs(batch_result, emb_table, wpe_table, inp_embedding, lengths, decoder_result, i_decoder,
+                             temperature, top_k, top_p, seed, n_top=0):
+    """EXTENSION: decoder_sampled plus the log-probabilities of sample_tokens_logprobs (mli_decoder_sampled_logprobs);
+    decoder_result [B] or [B, n_results], written at column i_decoder.  Returns (token_logprob, top_ids, top_logprobs),
+    shaped like decoder_result (+ [n_top])."""
+    B, D = batch_result.shape
+    n_res = decoder_result.shape[1] if decoder_result.dim() == 2 else 1
+    lp, ids, tops = _logprob_outputs(decoder_result, int(n_top))
+    sc, need = _sampled_scratch(B, emb_table.shape[0], batch_result.device)
+    _check(load_library().mli_decoder_sampled_logprobs(
+        _p(batch_result), _p(emb_table), _p(wpe_table), _p(inp_embedding), _p(lengths), _p(decoder_result), B,
+        emb_table.shape[0], wpe_table.shape[0], D, n_res, i_decoder, *_sampling_args(temperature, top_k, top_p, seed),
+        _p(lp), _p(ids) if n_top else None, _p(tops) if n_top else None, int(n_top), _p(sc), need, _stream()),
+        "mli_decoder_sampled_logprobs")
+    return lp, ids, tops
+
+
+def paged_decoder_sampled_logprobs(batch_result, emb_table, wpe_table, page_table, lengths, decoder_result, i_decoder, elem,
+                                   temperature, top_k, top_p, seed, n_top=0):
+    """EXTENSION: paged_decoder_sampled plus the log-probabilities (mli_paged_decoder_sampled_logprobs)."""
+    B, D = batch_result.shape
+    n_res = decoder_result.shape[1] if decoder_result.dim() == 2 else 1
+    lp, ids, tops = _logprob_outputs(decoder_result, int(n_top))
+    sc, need = _sampled_scratch(B, emb_table.shape[0], batch_result.device)
+    _check(load_library().mli_paged_decoder_sampled_logprobs(
+        _p(batch_result), _p(emb_table), _p(wpe_table), _p(page_table), _p(lengths), _p(decoder_result), B,
+        emb_table.shape[0], wpe_table.shape[0], D, n_res, i_decoder, int(elem),
+        *_sampling_args(temperature, top_k, top_p, seed), _p(lp), _p(ids) if n_top else None,
+        _p(tops) if n_top else None, int(n_top), _p(sc), need, _stream()), "mli_paged_decoder_sampled_logprobs")
+    return lp, ids, tops
 
 
 def stream_wait_stream(waiter, signaller):
