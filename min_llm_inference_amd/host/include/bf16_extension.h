@@ -37,64 +37,28 @@ void launch_paged_attention_decoder_multi_rounds_bf16(const TensorFloat& batch_r
                                                       TensorFloatPoint& page_table, TensorInt& lengths,
                                                       TensorInt& decoder_result, int i_decoder);
 
-class PagedAttentionBf16Layer : public NonCopyableNonClonable {
+class PagedAttentionBf16Layer : public PagedAttentionLayerCore<TensorBf16> {
 public:
     PagedAttentionBf16Layer(TensorBf16&& wk, TensorBf16&& wq, TensorBf16&& wv, size_t n_batch, size_t emb_dim,
                             size_t n_sequence);
     void forward(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_batch_idx,
                  TensorFloat& attention_result, int n_new_items);
-    // encoder + K/V prefill of the new rows in one launch (mli_paged_prefill, elem_bf16 = 1)
-    void prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
-                 TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
-                 int n_new_items);
-    // attention heads of the lean forward (default 1: one softmax over emb_dim)
-    void set_n_heads(int n_heads) { n_heads_ = n_heads; }
-    // EXTENSION: grouped-query attention of the lean forward: K/V heads serving the n_heads query heads (0 = as many)
-    void set_n_kv_heads(int n_kv_heads) { n_kv_heads_ = n_kv_heads; }
-    // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
-    void set_window(int window) { window_ = window; }
-    // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
-    void set_sinks(int n_sink) { n_sink_ = n_sink; }
-    // prefill of the live tokens only, for rows whose dead pages are returned early (PagedAttentionLayer::set_page_release)
-    void set_page_release(bool enabled) { page_release_ = enabled; }
 
 private:
-    TensorBf16 wk_, wq_, wv_;
-    TensorFloat q_output_;
     TensorFloat qkt_output_;
-    int n_heads_ = 1;
-    int n_kv_heads_ = 0;
-    int window_ = 0;
-    int n_sink_ = 0;
-    bool page_release_ = false;
 };
 
-class PagedAttentionBf16InferenceModel : public NonCopyableNonClonable {
+class PagedAttentionBf16InferenceModel : public PagedInferenceModel {
 public:
     PagedAttentionBf16InferenceModel(PagedAttentionBf16Layer&&, size_t n_batch, size_t n_sequence, size_t emb_dim,
                                      size_t n_vocab, int n_forward_rounds);
-    void forward(const TensorInt& inp, TensorInt& lengths, const TensorInt& new_item_indices,
-                 TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
-                 const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
-    // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling)
-    void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }
-    // EXTENSION: the sampled head reports log-probabilities into buffers this model owns (DecoderLayer::set_logprobs)
-    void set_logprobs(int n_top) { logprobs_.allocate(n_batch_, (size_t)n_forward_rounds_, n_top); }
-    const DecoderLogprobs& logprobs() const { return logprobs_; }
-    void set_n_heads(int n_heads) { attention_layer_.set_n_heads(n_heads); }
-    void set_n_kv_heads(int n_kv_heads) { attention_layer_.set_n_kv_heads(n_kv_heads); }
-    void set_window(int window) { attention_layer_.set_window(window); }
-    void set_sinks(int n_sink) { attention_layer_.set_sinks(n_sink); }
-    void set_page_release(bool enabled) { attention_layer_.set_page_release(enabled); }
+    void forward_paged(const PagedStep& s, int n_new_items) override;
+    PagedAttentionOptions& options() override { return attention_layer_.options(); }
 
 private:
+    DecoderHead& decoder_head() override { return decoder_head_; }
     PagedAttentionBf16Layer attention_layer_;
-    size_t n_batch_, n_sequence_, emb_dim_;
-    TensorFloat attention_result_;
-    TensorFloat emb_score_;
-    int n_forward_rounds_;
-    const SlotSampling* sampling_ = nullptr;
-    DecoderLogprobs logprobs_;
+    DecoderHead decoder_head_;  // its emb_score is lent to the lean head as scratch
 };
 
 void start_paged_attention_bf16_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table,

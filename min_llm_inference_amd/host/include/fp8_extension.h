@@ -7,65 +7,37 @@
 // elem = MLI_ELEM_FP8): there is no scores-materialising form to fall back to.
 #pragma once
 
-#include <memory>
-
 #include "bf16_extension.h"
 
 // floats to ask MemoryBlockManager for so that one block holds 16 x 3 x emb_dim fp8 elements
 inline size_t fp8_page_block_floats(size_t emb_dim) { return 16 * 3 * emb_dim / 4; }
 
-class PagedAttentionFp8Layer : public NonCopyableNonClonable {
+class PagedAttentionFp8Layer : public PagedAttentionLayerCore<TensorBf16> {
 public:
     PagedAttentionFp8Layer(TensorBf16&& wk, TensorBf16&& wq, TensorBf16&& wv, size_t n_batch, size_t emb_dim,
                            size_t n_sequence);
     void forward(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_batch_idx,
                  TensorFloat& attention_result, int n_new_items);
-    // encoder + K/V prefill of the new rows in one launch (mli_paged_prefill, elem = MLI_ELEM_FP8)
-    void prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
-                 TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
-                 int n_new_items);
-    // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
-    void set_window(int window) { window_ = window; }
-    // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
-    void set_sinks(int n_sink) { n_sink_ = n_sink; }
-    // prefill of the live tokens only, for rows whose dead pages are returned early (PagedAttentionLayer::set_page_release)
-    void set_page_release(bool enabled) { page_release_ = enabled; }
 
-private:
-    TensorBf16 wk_, wq_, wv_;
-    TensorFloat q_output_;
-    size_t n_sequence_;
-    int window_ = 0;
-    int n_sink_ = 0;
-    bool page_release_ = false;
+private:  // the fp8 scan has one head: of the option setters the layer has set_window, set_sinks and set_page_release
+    using PagedAttentionOptionSetters::set_n_heads;
+    using PagedAttentionOptionSetters::set_n_kv_heads;
 };
 
-class PagedAttentionFp8InferenceModel : public NonCopyableNonClonable {
+class PagedAttentionFp8InferenceModel : public PagedInferenceModel {
 public:
     PagedAttentionFp8InferenceModel(PagedAttentionFp8Layer&&, size_t n_batch, size_t n_sequence, size_t emb_dim,
                                     size_t n_vocab, int n_forward_rounds);
-    void forward(const TensorInt& inp, TensorInt& lengths, const TensorInt& new_item_indices,
-                 TensorInt& decoder_result, int n_new_items, const TensorFloat& emb_table,
-                 const TensorFloat& pos_emb_table, TensorFloatPoint& page_table);
-    // EXTENSION: the decoder head draws with these per-slot parameters (DecoderLayer::set_sampling); allocates the
-    // logits buffer the sampled head needs
-    void set_sampling(const SlotSampling* sampling);
-    // EXTENSION: the sampled head reports log-probabilities into buffers this model owns (DecoderLayer::set_logprobs)
-    void set_logprobs(int n_top) { logprobs_.allocate(n_batch_, (size_t)n_forward_rounds_, n_top); }
-    const DecoderLogprobs& logprobs() const { return logprobs_; }
-    void set_window(int window) { attention_layer_.set_window(window); }
-    void set_sinks(int n_sink) { attention_layer_.set_sinks(n_sink); }
-    void set_page_release(bool enabled) { attention_layer_.set_page_release(enabled); }
+    void forward_paged(const PagedStep& s, int n_new_items) override;
+    PagedAttentionOptions& options() override { return attention_layer_.options(); }
 
 private:
+    using PagedAttentionOptionSetters::set_n_heads;  // as the layer
+    using PagedAttentionOptionSetters::set_n_kv_heads;
+    DecoderHead& decoder_head() override { return decoder_head_; }
     PagedAttentionFp8Layer attention_layer_;
-    size_t n_batch_, n_sequence_, emb_dim_, n_vocab_;
-    TensorFloat attention_result_;
-    TensorFloat decoder_scratch_;
-    int n_forward_rounds_;
-    const SlotSampling* sampling_ = nullptr;
-    std::unique_ptr<TensorFloat> emb_score_;  // [n_batch, n_vocab], allocated when sampling is set
-    DecoderLogprobs logprobs_;
+    // lean only: the scratch of mli_decoder_scratch_bytes, and the logits buffer once sampling is set
+    DecoderHead decoder_head_;
 };
 
 void start_paged_attention_fp8_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table,

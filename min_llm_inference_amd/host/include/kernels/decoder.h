@@ -27,7 +27,7 @@ void launch_decoder_fused(const TensorFloat& batch_result, const TensorFloat& em
 void launch_paged_attention_decoder_fused(const TensorFloat& batch_result, const TensorFloat& emb_table,
                                           TensorFloat& emb_score, const TensorFloat& wpe_table,
                                           TensorFloatPoint& page_table, TensorInt& lengths, TensorInt& decoder_result,
-                                          int i_decoder);
+                                          int i_decoder, int elem = 0);  // elem = MLI_ELEM_* of the pages (0: fp32)
 
 // EXTENSION: the sampled decoder head (mli_decoder_sampled / mli_paged_decoder_sampled).  Per-slot device
 // arrays [n_batch] of the draw's parameters; a slot with temperature 0 decodes greedily.  emb_score receives the logits.

@@ -3,6 +3,9 @@
 // on the inference path.  FeedForward (used by no model in the reference) is out of scope.
 #pragma once
 
+#include <cstdint>
+#include <memory>
+
 #include "kernels/paged_attention.h"
 #include "tensor.hpp"
 #include "utils.h"
@@ -27,71 +30,93 @@ private:
     TensorFloat qkt_output_;  // [n_batch, n_sequence]
 };
 
-class PagedAttentionLayer : public NonCopyableNonClonable {
+// EXTENSION: the options of the paged attention layers' lean forward, one struct for the four layers and the four models.
+// A new per-layer option is a field here, its setter below, one validation in the engine setter (engine_api.cpp) and its
+// use where the layer launches (layers.cpp).
+struct PagedAttentionOptions {
+    int n_heads = 1;            // attention heads (1 = the reference's single softmax over emb_dim)
+    int n_kv_heads = 0;         // grouped-query attention: K/V heads serving the n_heads query heads (0 = as many)
+    int window = 0;             // sliding window: a row attends its newest `window` tokens (0 or >= n_sequence: all)
+    int n_sink = 0;             // attention sinks: beside a window a row keeps its first n_sink tokens attended (0: none)
+    // the rows' pages below the window are returned early (PagedAttentionsManager::set_page_release): prefill covers a
+    // row's live tokens only and follows no table entry of a dead page (mli_paged_prefill_window)
+    bool page_release = false;
+};
+
+// The setters of the option set, defined once for every class that has them: a layer owns the struct, a model hands out
+// its layer's.  A class whose scan has one head only (fp8 pages) takes set_n_heads / set_n_kv_heads out of its interface.
+class PagedAttentionOptionSetters {
+public:
+    void set_n_heads(int n_heads) { options().n_heads = n_heads; }
+    void set_n_kv_heads(int n_kv_heads) { options().n_kv_heads = n_kv_heads; }
+    void set_window(int window) { options().window = window; }
+    void set_sinks(int n_sink) { options().n_sink = n_sink; }
+    void set_page_release(bool enabled) { options().page_release = enabled; }
+    virtual PagedAttentionOptions& options() = 0;
+
+protected:
+    ~PagedAttentionOptionSetters() = default;
+};
+
+// What the paged attention layers of every page element type share: weights, the q scratch, the option set, the fused
+// prefill and the lean scan.  Weights = TensorFloat (fp32 pages) or Tensor<uint16_t> (bf16 weights: bf16 and fp8 pages).
+template <class Weights>
+class PagedAttentionLayerCore : public NonCopyableNonClonable, public PagedAttentionOptionSetters {
+public:
+    // extension: encoder + K/V prefill of the new rows in one launch (the model then calls forward with n_new_items = 0);
+    // n_new_items == 0 launches nothing
+    void prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
+                 TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
+                 int n_new_items);
+    PagedAttentionOptions& options() override { return options_; }
+    int elem() const { return elem_; }  // MLI_ELEM_* of the pages
+
+protected:
+    PagedAttentionLayerCore(int elem, Weights&& wk, Weights&& wq, Weights&& wv, size_t n_batch, size_t emb_dim,
+                            size_t n_sequence);
+    // runtime::lean_paged_attention over this layer's pages and options; its status comes back because what a layer does
+    // with rows too wide for the single-pass kernel differs by element type
+    int lean_scan(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_batch_idx,
+                  TensorFloat& attention_result, int n_new_items, int n_heads, int n_kv_heads);
+
+    int elem_;
+    Weights wk_, wq_, wv_;
+    TensorFloat q_output_;
+    size_t n_sequence_;
+    PagedAttentionOptions options_;
+};
+extern template class PagedAttentionLayerCore<TensorFloat>;
+extern template class PagedAttentionLayerCore<Tensor<uint16_t>>;
+
+// PagedAttentionLayer and PagedAttentionCublasLayer are one layer but for the materialising composition they run with the
+// lean layers off (and for rows too wide for the lean scan).
+class PagedAttentionFloatLayer : public PagedAttentionLayerCore<TensorFloat> {
+protected:
+    PagedAttentionFloatLayer(TensorFloat&& wk, TensorFloat&& wq, TensorFloat&& wv, size_t n_batch, size_t emb_dim,
+                             size_t n_sequence);
+    // true: the lean composition ran.  false: the caller runs its materialising composition into qkt_output_ -- the lean
+    // layers are off, or the scan refused one head without a window with MLI_ERR_BAD_ARG for emb_dim > 2048, % 4 == 0
+    bool forward_lean(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_batch_idx,
+                      TensorFloat& attention_result, int n_new_items);
+    TensorFloat qkt_output_;
+};
+
+class PagedAttentionLayer : public PagedAttentionFloatLayer {
 public:
     PagedAttentionLayer(TensorFloat&& wk, TensorFloat&& wq, TensorFloat&& wv, size_t n_batch, size_t emb_dim,
                         size_t n_sequence);
     void forward(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_batch_idx,
                  TensorFloat& attention_result, int n_new_items);
-    // extension: encoder + K/V prefill of the new rows in one launch (the model then calls forward with n_new_items = 0)
-    void prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
-                 TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
-                 int n_new_items);
-
-    // EXTENSION: attention heads of the lean forward (default 1 = the reference's single softmax over emb_dim)
-    void set_n_heads(int n_heads) { n_heads_ = n_heads; }
-    // EXTENSION: grouped-query attention of the lean forward: K/V heads serving the n_heads query heads (0 = as many)
-    void set_n_kv_heads(int n_kv_heads) { n_kv_heads_ = n_kv_heads; }
-    // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
-    void set_window(int window) { window_ = window; }
-    // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
-    void set_sinks(int n_sink) { n_sink_ = n_sink; }
-    // EXTENSION: the rows' pages below the window are returned early (PagedAttentionsManager::set_page_release): prefill
-    // covers a row's live tokens only and follows no table entry of a dead page (mli_paged_prefill_window)
-    void set_page_release(bool enabled) { page_release_ = enabled; }
-
-private:
-    TensorFloat wk_, wq_, wv_;
-    TensorFloat q_output_;
-    TensorFloat qkt_output_;
-    int n_heads_ = 1;
-    int n_kv_heads_ = 0;
-    int window_ = 0;
-    int n_sink_ = 0;
-    bool page_release_ = false;
 };
 
-class PagedAttentionCublasLayer : public NonCopyableNonClonable {
+class PagedAttentionCublasLayer : public PagedAttentionFloatLayer {
 public:
     PagedAttentionCublasLayer(TensorFloat&& wk, TensorFloat&& wq, TensorFloat&& wv, size_t n_batch, size_t emb_dim,
                               size_t n_sequence);
     void forward(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_batch_idx,
                  TensorFloat& attention_result, int n_new_items, GemmHandle& handle);
-    void prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
-                 TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
-                 int n_new_items);  // extension, as PagedAttentionLayer::prefill
-
-    // EXTENSION: attention heads of the lean forward (default 1 = the reference's single softmax over emb_dim)
-    void set_n_heads(int n_heads) { n_heads_ = n_heads; }
-    // EXTENSION: grouped-query attention of the lean forward: K/V heads serving the n_heads query heads (0 = as many)
-    void set_n_kv_heads(int n_kv_heads) { n_kv_heads_ = n_kv_heads; }
-    // EXTENSION: sliding window of the lean forward: a row attends its newest `window` tokens (0 or >= n_sequence: all)
-    void set_window(int window) { window_ = window; }
-    // EXTENSION: attention sinks of the lean forward: beside a window a row keeps its first n_sink tokens attended (0: none)
-    void set_sinks(int n_sink) { n_sink_ = n_sink; }
-    // EXTENSION: the rows' pages below the window are returned early (PagedAttentionsManager::set_page_release): prefill
-    // covers a row's live tokens only and follows no table entry of a dead page (mli_paged_prefill_window)
-    void set_page_release(bool enabled) { page_release_ = enabled; }
 
 private:
-    TensorFloat wk_, wq_, wv_;
-    TensorFloat q_output_;
-    TensorFloat qkt_output_;
-    int n_heads_ = 1;
-    int n_kv_heads_ = 0;
-    int window_ = 0;
-    int n_sink_ = 0;
-    bool page_release_ = false;
     TensorFloat latest_emb_;        // kept for signature parity with the reference; unused by the MFMA path
     TensorFloat temp_placeholder_;
 };
@@ -111,54 +136,53 @@ public:
                  int n_new_items);
 };
 
-class DecoderLayer : public NonCopyableNonClonable {
+// What the three decoder layers and the bf16 / fp8 models hold of a decoder head: the logits buffer, the sampling
+// parameters, the log-probability buffers, and the one choice between the sampled, the lean and the materialising head.
+class DecoderHead : public NonCopyableNonClonable {
 public:
-    DecoderLayer(size_t n_batch, size_t n_vocab);
-    void forward(const TensorFloat& batch_result, const TensorFloat& emb_table, const TensorFloat& wpe_table,
-                 TensorFloat& inp_embedding, TensorInt& lengths, TensorInt& decoder_result);
+    // lean_only (fp8 pages, which have no materialising head): the lean head's scratch (mli_decoder_scratch_bytes) is
+    // all that is allocated, and emb_score [n_batch, n_vocab] follows when set_sampling asks for the sampled head
+    DecoderHead(size_t n_batch, size_t n_vocab, bool lean_only = false);
 
     // EXTENSION: from now on forward() runs the sampled head with these per-slot parameters (nullptr: the greedy head)
-    void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }
-    // EXTENSION: the sampled head also reports log-probabilities into buffers this layer owns from now on:
+    void set_sampling(const SlotSampling* sampling);
+    // EXTENSION: the sampled head also reports log-probabilities into buffers this head owns from now on:
     // [n_batch, n_rounds(, n_top)], n_top in 0 .. 8.  Takes effect where the sampled head runs (set_sampling).
-    void set_logprobs(int n_rounds, int n_top) { logprobs_.allocate(emb_score_.shape()[0], (size_t)n_rounds, n_top); }
+    void set_logprobs(int n_rounds, int n_top) { logprobs_.allocate(n_batch_, (size_t)n_rounds, n_top); }
     const DecoderLogprobs& logprobs() const { return logprobs_; }
 
-private:
-    TensorFloat emb_score_;  // [n_batch, n_vocab]
+    // The head of one round over pages of elem = MLI_ELEM_*: sampled (with or without log-probabilities) if set_sampling
+    // gave parameters, else the lean fused head, else -- lean layers off -- the element type's materialising head.
+    void forward_paged(int elem, const TensorFloat& batch_result, const TensorFloat& emb_table,
+                       const TensorFloat& wpe_table, TensorFloatPoint& page_table, TensorInt& lengths,
+                       TensorInt& decoder_result, int i_decoder_round);
+
+protected:
+    size_t n_batch_, n_vocab_;
+    std::unique_ptr<TensorFloat> emb_score_;     // [n_batch, n_vocab]; lent to the lean head as scratch
+    std::unique_ptr<TensorFloat> lean_scratch_;  // a lean_only head's scratch instead
     const SlotSampling* sampling_ = nullptr;
     DecoderLogprobs logprobs_;
 };
 
-class PagedDecoderLayer : public NonCopyableNonClonable {
+class DecoderLayer : public DecoderHead {
 public:
-    PagedDecoderLayer(size_t n_batch, size_t n_vocab);
+    DecoderLayer(size_t n_batch, size_t n_vocab) : DecoderHead(n_batch, n_vocab) {}
+    void forward(const TensorFloat& batch_result, const TensorFloat& emb_table, const TensorFloat& wpe_table,
+                 TensorFloat& inp_embedding, TensorInt& lengths, TensorInt& decoder_result);
+};
+
+class PagedDecoderLayer : public DecoderHead {
+public:
+    PagedDecoderLayer(size_t n_batch, size_t n_vocab) : DecoderHead(n_batch, n_vocab) {}
     void forward(const TensorFloat& batch_result, const TensorFloat& emb_table, const TensorFloat& wpe_table,
                  TensorFloatPoint& page_table, TensorInt& lengths, TensorInt& decoder_result, int i_decoder_round);
-
-    void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }  // EXTENSION, as DecoderLayer's
-    void set_logprobs(int n_rounds, int n_top) { logprobs_.allocate(emb_score_.shape()[0], (size_t)n_rounds, n_top); }
-    const DecoderLogprobs& logprobs() const { return logprobs_; }
-
-private:
-    TensorFloat emb_score_;
-    const SlotSampling* sampling_ = nullptr;
-    DecoderLogprobs logprobs_;
 };
 
-class PagedCublasDecoderLayer : public NonCopyableNonClonable {
+class PagedCublasDecoderLayer : public DecoderHead {
 public:
-    PagedCublasDecoderLayer(size_t n_batch, size_t n_vocab);
+    PagedCublasDecoderLayer(size_t n_batch, size_t n_vocab) : DecoderHead(n_batch, n_vocab) {}
     void forward(const TensorFloat& batch_result, const TensorFloat& emb_table, const TensorFloat& wpe_table,
                  TensorFloatPoint& page_table, TensorInt& lengths, TensorInt& decoder_result, int i_decoder_round,
                  GemmHandle& handle);
-
-    void set_sampling(const SlotSampling* sampling) { sampling_ = sampling; }  // EXTENSION, as DecoderLayer's
-    void set_logprobs(int n_rounds, int n_top) { logprobs_.allocate(emb_score_.shape()[0], (size_t)n_rounds, n_top); }
-    const DecoderLogprobs& logprobs() const { return logprobs_; }
-
-private:
-    TensorFloat emb_score_;
-    const SlotSampling* sampling_ = nullptr;
-    DecoderLogprobs logprobs_;
 };

@@ -38,6 +38,12 @@ long long run_paged_engine_pipelined(ItemStorage& item_storage, ProcessingStorag
                                      size_t n_sequence, const PagedForward& forward, int n_forward_rounds = 1,
                                      const PagedAdmitHook& on_admit = {}, ResultFigures* figures = nullptr);
 
+// the loop over any paged model; the four functions below are this one under their models' names
+void start_paged_engine_pipelined(const TensorFloat& emb_table, const TensorFloat& pos_table, ItemStorage& item_storage,
+                                  ProcessingStorage& processing_storage, MemoryBlockManager& memory_block_manager,
+                                  PagedAttentionsManager& paged_attention_manager, PagedInferenceModel& inference_model,
+                                  size_t n_batch_size, size_t n_sequence, int n_forward_rounds = 1);
+
 void start_paged_attention_inference_engine_pipelined(const TensorFloat& emb_table, const TensorFloat& pos_table,
                                                       ItemStorage& item_storage, ProcessingStorage& processing_storage,
                                                       MemoryBlockManager& memory_block_manager,

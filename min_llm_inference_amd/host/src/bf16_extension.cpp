@@ -67,84 +67,38 @@ void launch_paged_attention_decoder_multi_rounds_bf16(const TensorFloat& batch_r
 
 PagedAttentionBf16Layer::PagedAttentionBf16Layer(TensorBf16&& wk, TensorBf16&& wq, TensorBf16&& wv, size_t n_batch,
                                                  size_t emb_dim, size_t n_sequence)
-    : wk_(std::move(wk)), wq_(std::move(wq)), wv_(std::move(wv)),
-      q_output_(std::vector<size_t>{n_batch, emb_dim}, DeviceType::DEVICE),
+    : PagedAttentionLayerCore(MLI_ELEM_BF16, std::move(wk), std::move(wq), std::move(wv), n_batch, emb_dim, n_sequence),
       qkt_output_(std::vector<size_t>{n_batch, n_sequence}, DeviceType::DEVICE) {}
 
 void PagedAttentionBf16Layer::forward(TensorFloatPoint& page_table, const TensorInt& lengths,
                                       const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                       int n_new_items) {
-    const int n_sequence = static_cast<int>(qkt_output_.shape()[1]);
-    if (mli::runtime::lean_paged_wanted(n_heads_, window_, n_sequence)) {
-        const int D = (int)wk_.shape()[0];
-        const int rc = mli::runtime::lean_paged_attention(MLI_ELEM_BF16, n_heads_, window_, n_sink_,
-                                                          reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
-                                                          wk_.data(), wq_.data(), wv_.data(), new_batch_idx.data(),
-                                                          q_output_.data(), attention_result.data(),
-                                                          (int)page_table.shape()[0], n_sequence, D, n_new_items,
-                                                          n_kv_heads_);
-        if (rc != MLI_ERR_BAD_ARG || D <= 4096) {  // rows wider than the single-pass kernel covers: fall through
+    if (mli::runtime::lean_paged_wanted(options_.n_heads, options_.window, (int)n_sequence_)) {
+        const int rc = lean_scan(page_table, lengths, new_batch_idx, attention_result, n_new_items, options_.n_heads,
+                                 options_.n_kv_heads);
+        if (rc != MLI_ERR_BAD_ARG || wk_.shape()[0] <= 4096) {  // rows wider than the single-pass kernel covers: fall through
             HIP_CHECK(rc);
             return;
         }
     }
     paged_attention_bf16(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, qkt_output_, attention_result,
-                         n_new_items, n_sequence);
-}
-
-void PagedAttentionBf16Layer::prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
-                                      TensorFloatPoint& page_table, const TensorInt& lengths,
-                                      const TensorInt& new_item_indices, int n_new_items) {
-    if (n_new_items == 0) return;
-    if (page_release_) {   // the live tokens only; no table entry of a dead page is followed
-        HIP_CHECK(mli_paged_prefill_window(emb_table.data(), pos_emb.data(), inp.data(),
-                                           reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
-                                           new_item_indices.data(), wk_.data(), wv_.data(), (int)inp.shape()[0],
-                                           (int)inp.shape()[1], (int)emb_table.shape()[1], n_new_items,
-                                           window_ > 0 ? window_ : 0, n_sink_, MLI_ELEM_BF16, mli::runtime::compute_stream()));
-        return;
-    }
-    HIP_CHECK(mli_paged_prefill(emb_table.data(), pos_emb.data(), inp.data(),
-                                reinterpret_cast<void* const*>(page_table.data()), lengths.data(), new_item_indices.data(),
-                                wk_.data(), wv_.data(), (int)inp.shape()[0], (int)inp.shape()[1],
-                                (int)emb_table.shape()[1], n_new_items, /*elem_bf16=*/1, mli::runtime::compute_stream()));
+                         n_new_items, (int)n_sequence_);
 }
 
 PagedAttentionBf16InferenceModel::PagedAttentionBf16InferenceModel(PagedAttentionBf16Layer&& attention_layer,
                                                                    size_t n_batch, size_t n_sequence, size_t emb_dim,
                                                                    size_t n_vocab, int n_forward_rounds)
-    : attention_layer_(std::move(attention_layer)), n_batch_(n_batch), n_sequence_(n_sequence), emb_dim_(emb_dim),
-      attention_result_(std::vector<size_t>{n_batch, emb_dim}, DeviceType::DEVICE),
-      emb_score_(std::vector<size_t>{n_batch, n_vocab}, DeviceType::DEVICE), n_forward_rounds_(n_forward_rounds) {}
+    : PagedInferenceModel(n_batch, n_sequence, emb_dim, n_forward_rounds), attention_layer_(std::move(attention_layer)),
+      decoder_head_(n_batch, n_vocab) {}
 
-void PagedAttentionBf16InferenceModel::forward(const TensorInt& inp, TensorInt& lengths,
-                                               const TensorInt& new_item_indices, TensorInt& decoder_result,
-                                               int n_new_items, const TensorFloat& emb_table,
-                                               const TensorFloat& pos_emb_table, TensorFloatPoint& page_table) {
-    for (int round = 0; round < n_forward_rounds_; ++round) {
-        const int fresh = round == 0 ? n_new_items : 0;  // later rounds only decode
-        if (mli::runtime::lean_layers()) {
-            attention_layer_.prefill(emb_table, pos_emb_table, inp, page_table, lengths, new_item_indices, fresh);
-            attention_layer_.forward(page_table, lengths, new_item_indices, attention_result_, 0);
-        } else {
-            launch_paged_attention_encoder_kernel_bf16(emb_table.data(), pos_emb_table.data(), inp.data(),
-                                                       page_table.data(), lengths.data(), new_item_indices.data(),
+// no StepGraph, whatever runtime::set_step_graphs says: graph replay is built and tested for the fp32 and GEMM models only
+void PagedAttentionBf16InferenceModel::forward_paged(const PagedStep& s, int n_new_items) {
+    run_rounds(
+        s, n_new_items, mli::runtime::lean_layers(), attention_layer_, decoder_head_,
+        [&](int fresh) {
+            launch_paged_attention_encoder_kernel_bf16(s.emb_table.data(), s.pos_emb_table.data(), s.inp.data(),
+                                                       s.page_table.data(), s.lengths.data(), s.new_item_indices.data(),
                                                        (int)n_batch_, (int)n_sequence_, (int)emb_dim_, fresh);
-            attention_layer_.forward(page_table, lengths, new_item_indices, attention_result_, fresh);
-        }
-        if (sampling_) {
-            launch_paged_attention_decoder_sampled(attention_result_, emb_table, emb_score_, pos_emb_table, page_table,
-                                                   lengths, decoder_result, round, MLI_ELEM_BF16, *sampling_, &logprobs_);
-        } else if (mli::runtime::lean_layers()) {
-            HIP_CHECK(mli_paged_decoder_fused(attention_result_.data(), emb_table.data(), pos_emb_table.data(),
-                                              reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
-                                              decoder_result.data(), (int)n_batch_, (int)emb_table.shape()[0],
-                                              (int)n_sequence_, (int)emb_dim_, n_forward_rounds_, round, /*elem_bf16=*/1,
-                                              emb_score_.data(), emb_score_.get_total_size() * sizeof(float),
-                                              mli::runtime::compute_stream()));
-        } else {
-            launch_paged_attention_decoder_multi_rounds_bf16(attention_result_, emb_table, emb_score_, pos_emb_table,
-                                                             page_table, lengths, decoder_result, round);
-        }
-    }
+        },
+        [&](int fresh) { attention_layer_.forward(s.page_table, s.lengths, s.new_item_indices, attention_result_, fresh); });
 }

@@ -50,11 +50,8 @@ struct mli_engine {
     TensorFloat emb_table, pos_table;
     ItemStorage item_storage;
     ProcessingStorage processing_storage;
-    std::unique_ptr<InferenceModel> naive_model;
-    std::unique_ptr<PagedAttentionInferenceModel> paged_model;
-    std::unique_ptr<PagedAttentionCublasInferenceModel> gemm_model;
-    std::unique_ptr<PagedAttentionBf16InferenceModel> bf16_model;
-    std::unique_ptr<PagedAttentionFp8InferenceModel> fp8_model;
+    std::unique_ptr<InferenceModel> naive_model;  // the contiguous kind's model, or
+    std::unique_ptr<PagedInferenceModel> paged;   // the model of one of the four paged kinds
     std::unique_ptr<MemoryBlockManager> pool;
     std::unique_ptr<PagedAttentionsManager> pages;
     TensorInt inp_device, inp_host, lengths_device, lengths_host, new_idx_device, new_idx_host;
@@ -62,35 +59,41 @@ struct mli_engine {
     bool started = false;
     int n_new_items = 0;
     long long iterations = 0;
-    GemmHandle handle;
     ThroughputCounter counter;  // this engine's own (the reference has one per process)
     int pipelined = -1;         // mli_engine_set_pipelined: 1 / 0 = run() uses the pipelined / the sequential loop,
                                 // -1 (default) = pipelined wherever it applies (see use_pipelined())
     // the pipelined loop serves the paged kinds with up to PAGE_BLOCK_SIZE / 2 rounds, without the reference's quirk,
     // and only an engine that is run to completion from the start (mli_engine_step drives the sequential loop)
     bool pipelined_applies() const {
-        return cfg.kind != MLI_ENGINE_CONTIGUOUS && 2 * cfg.n_forward_rounds <= PAGE_BLOCK_SIZE &&
+        return paged_kind() && 2 * cfg.n_forward_rounds <= PAGE_BLOCK_SIZE &&
                !cfg.reference_length_reset_quirk && !started;
     }
     bool use_pipelined() const { return pipelined == 1 || (pipelined == -1 && pipelined_applies()); }
     void* stream = nullptr;     // private compute stream (mli_engine_use_private_stream), else the thread's
     bool lean_layers = g_default_lean_layers.load();   // this engine's composition and replay switches (runtime.h)
     bool step_graphs = g_default_step_graphs.load();
-    int n_heads = 1;            // mli_engine_set_heads
-    int n_kv_heads = 0;         // mli_engine_set_kv_heads (0: as many as n_heads)
-    int window = 0;             // mli_engine_set_window (0: none)
-    int n_sink = 0;             // mli_engine_set_sinks (0: none; counts beside a window only)
+    // What mli_engine_set_heads / _kv_heads / _window / _sinks have accepted is kept in one place, the paged model's own
+    // option set (layers.h): n_heads, n_kv_heads (0: as many as n_heads), window (0: none), n_sink (counts beside a window
+    // only).  Every one of those setters refuses the contiguous kind, which therefore reads the defaults.
+    PagedAttentionOptions no_options;
+    PagedAttentionOptions& options() { return paged ? paged->options() : no_options; }
     bool release_pages = false; // mli_engine_set_page_release: takes effect at the first step or run, beside an effective window
+
+    bool paged_kind() const { return cfg.kind != MLI_ENGINE_CONTIGUOUS; }   // mli_engine_create admits the five kinds only
+    bool heads_kind() const { return paged_kind() && cfg.kind != MLI_ENGINE_PAGED_FP8; }  // the fp8 scan has one head
+    int elem() const {   // MLI_ELEM_* of the kind's pages
+        return cfg.kind == MLI_ENGINE_PAGED_FP8 ? MLI_ELEM_FP8 : cfg.kind == MLI_ENGINE_PAGED_BF16 ? MLI_ELEM_BF16 : MLI_ELEM_F32;
+    }
+    DecoderHeadSetters& model_head() {
+        if (paged) return *paged;
+        return *naive_model;
+    }
 
     // at the first step or run: the manager and the model's prefill follow the switch together, or not at all
     void apply_page_release() {
-        if (!pages) return;
-        pages->set_page_release(release_pages ? window : 0, n_sink);
-        const bool on = pages->page_release();
-        if (paged_model) paged_model->set_page_release(on);
-        if (gemm_model) gemm_model->set_page_release(on);
-        if (bf16_model) bf16_model->set_page_release(on);
-        if (fp8_model) fp8_model->set_page_release(on);
+        if (!paged) return;
+        pages->set_page_release(release_pages ? options().window : 0, options().n_sink);
+        paged->set_page_release(pages->page_release());
     }
 
     // EXTENSION: sampled decoding (mli_engine_add_item_sampled).  The parameters live here, keyed by item
@@ -198,21 +201,10 @@ struct mli_engine {
         upload_slots();
         slot_sampling = {slots_device->temperature.data(), slots_device->top_k.data(), slots_device->top_p.data(),
                          slots_device->seed.data()};
-        if (naive_model) naive_model->set_sampling(&slot_sampling);
-        if (paged_model) paged_model->set_sampling(&slot_sampling);
-        if (gemm_model) gemm_model->set_sampling(&slot_sampling);
-        if (bf16_model) bf16_model->set_sampling(&slot_sampling);
-        if (fp8_model) fp8_model->set_sampling(&slot_sampling);
+        model_head().set_sampling(&slot_sampling);
         if (logprobs_n_top < 0) return;
-        const DecoderLogprobs* buffers = nullptr;
-#define MLI_SET_LOGPROBS(model) if (model) { model->set_logprobs(logprobs_n_top); buffers = &model->logprobs(); }
-        MLI_SET_LOGPROBS(naive_model)
-        MLI_SET_LOGPROBS(paged_model)
-        MLI_SET_LOGPROBS(gemm_model)
-        MLI_SET_LOGPROBS(bf16_model)
-        MLI_SET_LOGPROBS(fp8_model)
-#undef MLI_SET_LOGPROBS
-        logprobs = std::make_unique<Logprobs>(*buffers);
+        model_head().set_logprobs(logprobs_n_top);
+        logprobs = std::make_unique<Logprobs>(model_head().logprobs());
     }
 
     void set_slot_host(int b, const Sampling& s) {
@@ -298,42 +290,35 @@ struct mli_engine {
           new_idx_device({(size_t)c.n_batch}, DeviceType::DEVICE), new_idx_host({(size_t)c.n_batch}, DeviceType::HOST),
           result_device(result_shape(c), DeviceType::DEVICE), result_host(result_shape(c), DeviceType::HOST) {
         const size_t B = c.n_batch, S = c.n_sequence, D = c.emb_dim, V = c.n_vocab;
-        if (c.kind == MLI_ENGINE_PAGED_BF16) {
-            pool = std::make_unique<MemoryBlockManager>(c.n_blocks, bf16_page_block_floats(D));
+        const int R = c.n_forward_rounds;
+        if (paged_kind()) {   // a block holds 16 x 3 x emb_dim elements of the kind's page element type
+            pool = std::make_unique<MemoryBlockManager>(c.n_blocks, elem() == MLI_ELEM_FP8    ? fp8_page_block_floats(D)
+                                                                    : elem() == MLI_ELEM_BF16 ? bf16_page_block_floats(D)
+                                                                                              : (size_t)PAGE_BLOCK_SIZE * 3 * D);
             pages = std::make_unique<PagedAttentionsManager>(B, S, D);
-            bf16_model = std::make_unique<PagedAttentionBf16InferenceModel>(
-                PagedAttentionBf16Layer(make_device_bf16(wk, {D, D}), make_device_bf16(wq, {D, D}),
-                                        make_device_bf16(wv, {D, D}), B, D, S),
-                B, S, D, V, c.n_forward_rounds);
-            init_loop_tensors(B, S);
-            return;
         }
-        if (c.kind == MLI_ENGINE_PAGED_FP8) {
-            pool = std::make_unique<MemoryBlockManager>(c.n_blocks, fp8_page_block_floats(D));
-            pages = std::make_unique<PagedAttentionsManager>(B, S, D);
-            fp8_model = std::make_unique<PagedAttentionFp8InferenceModel>(
-                PagedAttentionFp8Layer(make_device_bf16(wk, {D, D}), make_device_bf16(wq, {D, D}),
-                                       make_device_bf16(wv, {D, D}), B, D, S),
-                B, S, D, V, c.n_forward_rounds);
-            init_loop_tensors(B, S);
-            return;
-        }
-        TensorFloat dk = upload(wk, {D, D}), dq = upload(wq, {D, D}), dv = upload(wv, {D, D});
-        if (c.kind == MLI_ENGINE_CONTIGUOUS) {
-            naive_model = std::make_unique<InferenceModel>(
-                SelfAttentionLayer(std::move(dk), std::move(dq), std::move(dv), B, D, S), EncoderLayer(),
-                DecoderLayer(B, V), B, S, D);
-        } else {
-            pool = std::make_unique<MemoryBlockManager>(c.n_blocks, (size_t)PAGE_BLOCK_SIZE * 3 * D);
-            pages = std::make_unique<PagedAttentionsManager>(B, S, D);
-            if (c.kind == MLI_ENGINE_PAGED)
-                paged_model = std::make_unique<PagedAttentionInferenceModel>(
-                    PagedAttentionLayer(std::move(dk), std::move(dq), std::move(dv), B, D, S), PagedEncoderLayer(),
-                    PagedDecoderLayer(B, V), B, S, D, c.n_forward_rounds);
+        if (elem() != MLI_ELEM_F32) {   // bf16 weights
+            TensorBf16 dk = make_device_bf16(wk, {D, D}), dq = make_device_bf16(wq, {D, D}), dv = make_device_bf16(wv, {D, D});
+            if (c.kind == MLI_ENGINE_PAGED_BF16)
+                paged = std::make_unique<PagedAttentionBf16InferenceModel>(
+                    PagedAttentionBf16Layer(std::move(dk), std::move(dq), std::move(dv), B, D, S), B, S, D, V, R);
             else
-                gemm_model = std::make_unique<PagedAttentionCublasInferenceModel>(
-                    PagedAttentionCublasLayer(std::move(dk), std::move(dq), std::move(dv), B, D, S),
-                    PagedEncoderLayer(), PagedCublasDecoderLayer(B, V), B, S, D, c.n_forward_rounds);
+                paged = std::make_unique<PagedAttentionFp8InferenceModel>(
+                    PagedAttentionFp8Layer(std::move(dk), std::move(dq), std::move(dv), B, D, S), B, S, D, V, R);
+        } else {
+            TensorFloat dk = upload(wk, {D, D}), dq = upload(wq, {D, D}), dv = upload(wv, {D, D});
+            if (c.kind == MLI_ENGINE_CONTIGUOUS)
+                naive_model = std::make_unique<InferenceModel>(
+                    SelfAttentionLayer(std::move(dk), std::move(dq), std::move(dv), B, D, S), EncoderLayer(),
+                    DecoderLayer(B, V), B, S, D);
+            else if (c.kind == MLI_ENGINE_PAGED)
+                paged = std::make_unique<PagedAttentionInferenceModel>(
+                    PagedAttentionLayer(std::move(dk), std::move(dq), std::move(dv), B, D, S), PagedEncoderLayer(),
+                    PagedDecoderLayer(B, V), B, S, D, R);
+            else
+                paged = std::make_unique<PagedAttentionCublasInferenceModel>(
+                    PagedAttentionCublasLayer(std::move(dk), std::move(dq), std::move(dv), B, D, S), PagedEncoderLayer(),
+                    PagedCublasDecoderLayer(B, V), B, S, D, R);
         }
         init_loop_tensors(B, S);
     }
@@ -350,10 +335,16 @@ struct mli_engine {
         return {(size_t)c.n_batch, (size_t)c.n_forward_rounds};
     }
 
-    bool paged() const { return cfg.kind != MLI_ENGINE_CONTIGUOUS; }
+    // one forward of whichever model the engine has
+    void forward(const TensorInt& inp, TensorInt& lengths, const TensorInt& new_idx, TensorInt& result, int n_new) {
+        if (paged)
+            paged->forward(inp, lengths, new_idx, result, n_new, emb_table, pos_table, pages->get_page_table_device());
+        else
+            naive_model->forward(inp, lengths, new_idx, result, n_new, emb_table, pos_table);
+    }
 
     void insert(const std::vector<int>& free_slots) {
-        if (paged()) {
+        if (paged_kind()) {
             n_new_items = (int)insert_new_items(inp_device, inp_host, lengths_device, lengths_host, new_idx_device,
                                                 new_idx_host, item_storage, processing_storage, *pool, *pages,
                                                 cfg.n_forward_rounds).size();
@@ -380,7 +371,7 @@ struct mli_engine {
 
     void run_pipelined() {
         if (started) throw std::runtime_error("pipelined run on an engine that has already been stepped");
-        if (!paged() || 2 * cfg.n_forward_rounds > PAGE_BLOCK_SIZE)
+        if (!paged_kind() || 2 * cfg.n_forward_rounds > PAGE_BLOCK_SIZE)
             throw std::runtime_error("the pipelined loop serves the paged kinds with n_forward_rounds <= PAGE_BLOCK_SIZE / 2");
         pages->set_length_reset_quirk(cfg.reference_length_reset_quirk != 0);
         apply_page_release();
@@ -390,18 +381,7 @@ struct mli_engine {
         iterations = run_paged_engine_pipelined(
             item_storage, processing_storage, *pool, *pages, cfg.n_batch, cfg.n_sequence,
             [&](const TensorInt& inp, TensorInt& lengths, const TensorInt& new_idx, TensorInt& result, int n_new) {
-                if (cfg.kind == MLI_ENGINE_PAGED)
-                    paged_model->forward(inp, lengths, new_idx, result, n_new, emb_table, pos_table,
-                                         pages->get_page_table_device());
-                else if (cfg.kind == MLI_ENGINE_PAGED_BF16)
-                    bf16_model->forward(inp, lengths, new_idx, result, n_new, emb_table, pos_table,
-                                        pages->get_page_table_device());
-                else if (cfg.kind == MLI_ENGINE_PAGED_FP8)
-                    fp8_model->forward(inp, lengths, new_idx, result, n_new, emb_table, pos_table,
-                                       pages->get_page_table_device());
-                else
-                    gemm_model->forward(inp, lengths, new_idx, result, n_new, emb_table, pos_table,
-                                        pages->get_page_table_device(), handle);
+                forward(inp, lengths, new_idx, result, n_new);
             }, cfg.n_forward_rounds, [&](const std::vector<int>& slots) { scatter_admitted(slots); }, logprobs.get());
     }
 
@@ -414,33 +394,19 @@ struct mli_engine {
         if (!started) start();
         if (done()) return;
         const double t0 = now();
-        if (cfg.kind == MLI_ENGINE_CONTIGUOUS)
-            naive_model->forward(inp_device, lengths_device, new_idx_device, result_device, n_new_items, emb_table,
-                                 pos_table);
-        else if (cfg.kind == MLI_ENGINE_PAGED)
-            paged_model->forward(inp_device, lengths_device, new_idx_device, result_device, n_new_items, emb_table,
-                                 pos_table, pages->get_page_table_device());
-        else if (cfg.kind == MLI_ENGINE_PAGED_BF16)
-            bf16_model->forward(inp_device, lengths_device, new_idx_device, result_device, n_new_items, emb_table,
-                                pos_table, pages->get_page_table_device());
-        else if (cfg.kind == MLI_ENGINE_PAGED_FP8)
-            fp8_model->forward(inp_device, lengths_device, new_idx_device, result_device, n_new_items, emb_table,
-                               pos_table, pages->get_page_table_device());
-        else
-            gemm_model->forward(inp_device, lengths_device, new_idx_device, result_device, n_new_items, emb_table,
-                                pos_table, pages->get_page_table_device(), handle);
+        forward(inp_device, lengths_device, new_idx_device, result_device, n_new_items);
         const double t1 = now();
         std::vector<int> free_slots =
             process_decoder_result(result_device, result_host, item_storage, processing_storage, cfg.n_sequence,
                                    logprobs.get());
         const double t2 = now();
-        if (paged())
+        if (paged_kind())
             allocate_or_free_memory_blocks_if_needed(*pages, *pool, processing_storage, item_storage, free_slots,
                                                      cfg.n_forward_rounds);
         const double t3 = now();
         insert(free_slots);
         refresh_slots_sequential();
-        if (paged() && processing_storage.size() == 0 && item_storage.new_count() > 0)
+        if (paged_kind() && processing_storage.size() == 0 && item_storage.new_count() > 0)
             throw std::runtime_error("paged engine: the page pool is too small for the next queued item");
         const double t4 = now();
         t_forward += t1 - t0; t_result += t2 - t1; t_pages += t3 - t2; t_insert += t4 - t3;
@@ -478,12 +444,13 @@ void mli_engine_set_step_graphs(int enabled) { g_default_step_graphs.store(enabl
 int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
     MLI_GUARD({
         if (e->started) throw std::runtime_error("mli_engine_configure after the engine has started");
-        if (e->n_heads > 1 && lean_layers == 0)   // refused before anything is changed
+        PagedAttentionOptions& o = e->options();
+        if (o.n_heads > 1 && lean_layers == 0)   // refused before anything is changed
             throw std::runtime_error("multi-head attention (mli_engine_set_heads) has the lean compositions only");
-        if (e->n_kv_heads != 0 && lean_layers == 0)
+        if (o.n_kv_heads != 0 && lean_layers == 0)
             throw std::runtime_error("grouped-query attention (mli_engine_set_kv_heads: n_kv_heads < n_heads) has the lean "
                                      "compositions only");
-        if (e->window > 0 && e->window < e->cfg.n_sequence && lean_layers == 0)
+        if (o.window > 0 && o.window < e->cfg.n_sequence && lean_layers == 0)
             throw std::runtime_error("sliding-window attention (mli_engine_set_window) has the lean compositions only");
         if (lean_layers >= 0) e->lean_layers = lean_layers != 0;
         if (step_graphs >= 0) e->step_graphs = step_graphs != 0;
@@ -495,28 +462,25 @@ int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
 int mli_engine_set_heads(mli_engine* e, int n_heads) {
     MLI_GUARD({
         if (!e) throw std::runtime_error("null argument");
+        PagedAttentionOptions& o = e->options();
         if (n_heads < 1) throw std::runtime_error("mli_engine_set_heads: n_heads must be >= 1");
-        if (n_heads != e->n_heads) {
+        if (n_heads != o.n_heads) {
             if (e->started) throw std::runtime_error("mli_engine_set_heads after the engine has started");
-            const int kind = e->cfg.kind;
-            if (kind != MLI_ENGINE_PAGED && kind != MLI_ENGINE_PAGED_GEMM && kind != MLI_ENGINE_PAGED_BF16)
+            if (!e->heads_kind())
                 throw std::runtime_error("mli_engine_set_heads: multi-head attention serves the fp32 and bf16 paged engines");
             if (n_heads > 1 && !e->lean_layers)
                 throw std::runtime_error("mli_engine_set_heads: multi-head attention has the lean compositions only");
-            const int elem = kind == MLI_ENGINE_PAGED_BF16 ? MLI_ELEM_BF16 : MLI_ELEM_F32;
+            const int elem = e->elem();
             if (n_heads > 1 && !mli::heads_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, elem))
                 throw std::runtime_error("mli_engine_set_heads: unsupported (emb_dim, n_heads): head_dim must be 32, 64, 128 or "
                                          "256 and emb_dim at most 512 (fp32) / 1024 (bf16)");
-            if (e->window > 0 && e->window < e->cfg.n_sequence &&
+            if (o.window > 0 && o.window < e->cfg.n_sequence &&
                 !mli::window_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, elem))
                 throw std::runtime_error("mli_engine_set_heads: the windowed scan (mli_engine_set_window) does not take this shape");
-            if (e->n_kv_heads != 0 && n_heads % e->n_kv_heads != 0)
+            if (o.n_kv_heads != 0 && n_heads % o.n_kv_heads != 0)
                 throw std::runtime_error("mli_engine_set_heads: the stored n_kv_heads (mli_engine_set_kv_heads) does not divide "
                                          "n_heads");
-            if (e->paged_model) e->paged_model->set_n_heads(n_heads);
-            if (e->gemm_model) e->gemm_model->set_n_heads(n_heads);
-            if (e->bf16_model) e->bf16_model->set_n_heads(n_heads);
-            e->n_heads = n_heads;
+            o.n_heads = n_heads;
         }
     })
 }
@@ -526,28 +490,24 @@ int mli_engine_set_heads(mli_engine* e, int n_heads) {
 int mli_engine_set_kv_heads(mli_engine* e, int n_kv_heads) {
     MLI_GUARD({
         if (!e) throw std::runtime_error("null argument");
+        PagedAttentionOptions& o = e->options();
         if (n_kv_heads < 1) throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads must be >= 1");
-        if (n_kv_heads > e->n_heads || e->n_heads % n_kv_heads != 0)
+        if (n_kv_heads > o.n_heads || o.n_heads % n_kv_heads != 0)
             throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads must divide the engine's n_heads (mli_engine_set_heads)");
-        const int then = n_kv_heads == e->n_heads ? 0 : n_kv_heads;
-        if (then != e->n_kv_heads) {
+        const int then = n_kv_heads == o.n_heads ? 0 : n_kv_heads;
+        if (then != o.n_kv_heads) {
             if (e->started) throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads cannot change after the engine has started");
             if (then != 0) {
                 // (n_heads > 1 here, so set_heads has accepted the kind, the lean layers and the shape; checked again all the same)
-                const int kind = e->cfg.kind;
-                if (kind != MLI_ENGINE_PAGED && kind != MLI_ENGINE_PAGED_GEMM && kind != MLI_ENGINE_PAGED_BF16)
+                if (!e->heads_kind())
                     throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads < n_heads serves the fp32 and bf16 paged engines");
                 if (!e->lean_layers)
                     throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads < n_heads has the lean compositions only");
-                const int elem = kind == MLI_ENGINE_PAGED_BF16 ? MLI_ELEM_BF16 : MLI_ELEM_F32;
-                if (!mli::gqa_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, e->n_heads, n_kv_heads, elem))
+                if (!mli::gqa_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, o.n_heads, n_kv_heads, e->elem()))
                     throw std::runtime_error("mli_engine_set_kv_heads: the scan does not take this (n_batch, n_sequence, emb_dim, "
                                              "n_heads, n_kv_heads)");
             }
-            if (e->paged_model) e->paged_model->set_n_kv_heads(then);
-            if (e->gemm_model) e->gemm_model->set_n_kv_heads(then);
-            if (e->bf16_model) e->bf16_model->set_n_kv_heads(then);
-            e->n_kv_heads = then;
+            o.n_kv_heads = then;
         }
     })
 }
@@ -555,30 +515,24 @@ int mli_engine_set_kv_heads(mli_engine* e, int n_kv_heads) {
 int mli_engine_set_window(mli_engine* e, int window) {
     MLI_GUARD({
         if (!e) throw std::runtime_error("null argument");
+        PagedAttentionOptions& o = e->options();
         if (window < 1) throw std::runtime_error("mli_engine_set_window: window must be >= 1");
         // what counts is the window the scan would see: n_sequence or more is none, accepted everywhere, changing nothing
         const int S = e->cfg.n_sequence;
-        const int now = e->window > 0 && e->window < S ? e->window : S;
+        const int now = o.window > 0 && o.window < S ? o.window : S;
         const int then = window < S ? window : S;
         if (then != now) {
-            const int kind = e->cfg.kind;
-            if (kind != MLI_ENGINE_PAGED && kind != MLI_ENGINE_PAGED_GEMM && kind != MLI_ENGINE_PAGED_BF16 &&
-                kind != MLI_ENGINE_PAGED_FP8)
+            if (!e->paged_kind())
                 throw std::runtime_error("mli_engine_set_window: sliding-window attention serves the paged engines");
             if (e->started) throw std::runtime_error("mli_engine_set_window after the engine has started");
             if (then < S) {
                 if (!e->lean_layers)
                     throw std::runtime_error("mli_engine_set_window: sliding-window attention has the lean compositions only");
-                const int elem = kind == MLI_ENGINE_PAGED_FP8 ? MLI_ELEM_FP8 : kind == MLI_ENGINE_PAGED_BF16 ? MLI_ELEM_BF16 : MLI_ELEM_F32;
-                if (!mli::window_shape_supported(e->cfg.n_batch, S, e->cfg.emb_dim, e->n_heads, elem))
+                if (!mli::window_shape_supported(e->cfg.n_batch, S, e->cfg.emb_dim, o.n_heads, e->elem()))
                     throw std::runtime_error("mli_engine_set_window: the windowed scan does not take this (n_batch, n_sequence, "
                                              "emb_dim, n_heads)");
             }
-            if (e->paged_model) e->paged_model->set_window(then);
-            if (e->gemm_model) e->gemm_model->set_window(then);
-            if (e->bf16_model) e->bf16_model->set_window(then);
-            if (e->fp8_model) e->fp8_model->set_window(then);
-            e->window = then;
+            o.window = then;
         }
     })
 }
@@ -588,20 +542,15 @@ int mli_engine_set_window(mli_engine* e, int window) {
 int mli_engine_set_sinks(mli_engine* e, int n_sink) {
     MLI_GUARD({
         if (!e) throw std::runtime_error("null argument");
+        PagedAttentionOptions& o = e->options();
         if (n_sink < 0) throw std::runtime_error("mli_engine_set_sinks: n_sink must be >= 0");
-        const int kind = e->cfg.kind;
-        if (kind != MLI_ENGINE_PAGED && kind != MLI_ENGINE_PAGED_GEMM && kind != MLI_ENGINE_PAGED_BF16 &&
-            kind != MLI_ENGINE_PAGED_FP8)
+        if (!e->paged_kind())
             throw std::runtime_error("mli_engine_set_sinks: attention sinks serve the paged engines");
-        if (n_sink != e->n_sink) {
+        if (n_sink != o.n_sink) {
             if (e->started) throw std::runtime_error("mli_engine_set_sinks after the engine has started");
             if (!e->lean_layers)
                 throw std::runtime_error("mli_engine_set_sinks: attention sinks have the lean compositions only");
-            if (e->paged_model) e->paged_model->set_sinks(n_sink);
-            if (e->gemm_model) e->gemm_model->set_sinks(n_sink);
-            if (e->bf16_model) e->bf16_model->set_sinks(n_sink);
-            if (e->fp8_model) e->fp8_model->set_sinks(n_sink);
-            e->n_sink = n_sink;
+            o.n_sink = n_sink;
         }
     })
 }
@@ -611,7 +560,7 @@ int mli_engine_set_sinks(mli_engine* e, int n_sink) {
 int mli_engine_set_page_release(mli_engine* e, int enabled) {
     MLI_GUARD({
         if (!e) throw std::runtime_error("null argument");
-        if (e->cfg.kind == MLI_ENGINE_CONTIGUOUS)
+        if (!e->paged_kind())
             throw std::runtime_error("mli_engine_set_page_release: early page release serves the paged engines");
         if (e->started) throw std::runtime_error("mli_engine_set_page_release after the engine has started");
         if (e->cfg.reference_length_reset_quirk)

@@ -40,11 +40,22 @@ void throw_if_stuck(ItemStorage& item_storage, ProcessingStorage& processing_sto
         throw std::runtime_error("paged engine: the page pool is too small for the next queued item");
 }
 
-// Shared body of the two paged engines; `forward` hides the model type (and its GemmHandle).
-template <typename Forward>
-void run_paged_engine(ItemStorage& item_storage, ProcessingStorage& processing_storage,
-                      MemoryBlockManager& memory_block_manager, PagedAttentionsManager& paged_attention_manager,
-                      size_t n_batch_size, size_t n_sequence, int n_forward_rounds, Forward&& forward) {
+// the pipelined loop is the default wherever it applies (runtime.h: set_sequential_engine_loop)
+bool pipelined_loop_applies(const PagedAttentionsManager& pages, int n_forward_rounds) {
+    return !mli::runtime::sequential_engine_loop() && 2 * n_forward_rounds <= PAGE_BLOCK_SIZE && !pages.length_reset_quirk();
+}
+
+}  // namespace
+
+void start_paged_engine(const TensorFloat& emb_table, const TensorFloat& pos_table, ItemStorage& item_storage,
+                        ProcessingStorage& processing_storage, MemoryBlockManager& memory_block_manager,
+                        PagedAttentionsManager& paged_attention_manager, PagedInferenceModel& inference_model,
+                        size_t n_batch_size, size_t n_sequence, int n_forward_rounds) {
+    if (pipelined_loop_applies(paged_attention_manager, n_forward_rounds)) {
+        start_paged_engine_pipelined(emb_table, pos_table, item_storage, processing_storage, memory_block_manager,
+                                     paged_attention_manager, inference_model, n_batch_size, n_sequence, n_forward_rounds);
+        return;
+    }
     LoopTensors t(n_batch_size, n_sequence, {n_batch_size, static_cast<size_t>(n_forward_rounds)});
     // Every slot starts empty on both sides.  The reference's first insert writes and uploads every slot; here an
     // insert uploads only what changed, so the mirrors (pinned memory) and the device tensors (hipMalloc) must not
@@ -66,7 +77,9 @@ void run_paged_engine(ItemStorage& item_storage, ProcessingStorage& processing_s
     while (!is_done(item_storage, processing_storage)) {
         {
             Range r("forward");
-            forward(t, static_cast<int>(new_item_indices.size()));
+            inference_model.forward(t.inp_device, t.lengths_device, t.new_items_indices_device, t.decoder_result_device,
+                                    static_cast<int>(new_item_indices.size()), emb_table, pos_table,
+                                    paged_attention_manager.get_page_table_device());
         }
         std::vector<int> finished_indices;
         {
@@ -92,14 +105,6 @@ void run_paged_engine(ItemStorage& item_storage, ProcessingStorage& processing_s
     get_global_throughput_counter().print_throughput();
 }
 
-
-// the pipelined loop is the default wherever it applies (runtime.h: set_sequential_engine_loop)
-bool pipelined_loop_applies(const PagedAttentionsManager& pages, int n_forward_rounds) {
-    return !mli::runtime::sequential_engine_loop() && 2 * n_forward_rounds <= PAGE_BLOCK_SIZE && !pages.length_reset_quirk();
-}
-
-}  // namespace
-
 void start_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table, ItemStorage& item_storage,
                             ProcessingStorage& processing_storage, InferenceModel& inference_model,
                             size_t n_batch_size, size_t n_sequence) {
@@ -120,85 +125,36 @@ void start_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos
     }
 }
 
-void start_paged_attention_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table,
-                                            ItemStorage& item_storage, ProcessingStorage& processing_storage,
-                                            MemoryBlockManager& memory_block_manager,
-                                            PagedAttentionsManager& paged_attention_manager,
-                                            PagedAttentionInferenceModel& inference_model, size_t n_batch_size,
-                                            size_t n_sequence, int n_forward_rounds) {
-    if (pipelined_loop_applies(paged_attention_manager, n_forward_rounds)) {
-        start_paged_attention_inference_engine_pipelined(emb_table, pos_table, item_storage, processing_storage,
-                                                         memory_block_manager, paged_attention_manager, inference_model,
-                                                         n_batch_size, n_sequence, n_forward_rounds);
-        return;
-    }
-    run_paged_engine(item_storage, processing_storage, memory_block_manager, paged_attention_manager, n_batch_size,
-                     n_sequence, n_forward_rounds, [&](LoopTensors& t, int n_new_items) {
-                         inference_model.forward(t.inp_device, t.lengths_device, t.new_items_indices_device,
-                                                 t.decoder_result_device, n_new_items, emb_table, pos_table,
-                                                 paged_attention_manager.get_page_table_device());
-                     });
+// The reference's two paged engines and their bf16 / fp8 extensions (no reference counterpart) are start_paged_engine under
+// the reference's names.  (It creates / destroys a cublasHandle_t in the "cublas" one; nothing to create for MFMA.)
+void start_paged_attention_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table, ItemStorage& item_storage,
+        ProcessingStorage& processing_storage, MemoryBlockManager& memory_block_manager,
+        PagedAttentionsManager& paged_attention_manager, PagedAttentionInferenceModel& inference_model, size_t n_batch_size,
+        size_t n_sequence, int n_forward_rounds) {
+    start_paged_engine(emb_table, pos_table, item_storage, processing_storage, memory_block_manager, paged_attention_manager,
+                       inference_model, n_batch_size, n_sequence, n_forward_rounds);
 }
 
-void start_paged_attention_cublas_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table,
-                                                   ItemStorage& item_storage, ProcessingStorage& processing_storage,
-                                                   MemoryBlockManager& memory_block_manager,
-                                                   PagedAttentionsManager& paged_attention_manager,
-                                                   PagedAttentionCublasInferenceModel& inference_model,
-                                                   size_t n_batch_size, size_t n_sequence, int n_forward_rounds) {
-    if (pipelined_loop_applies(paged_attention_manager, n_forward_rounds)) {
-        start_paged_attention_cublas_inference_engine_pipelined(emb_table, pos_table, item_storage, processing_storage,
-                                                                memory_block_manager, paged_attention_manager,
-                                                                inference_model, n_batch_size, n_sequence, n_forward_rounds);
-        return;
-    }
-    GemmHandle handle;  // the reference creates / destroys a cublasHandle_t here; nothing to create for MFMA
-    run_paged_engine(item_storage, processing_storage, memory_block_manager, paged_attention_manager, n_batch_size,
-                     n_sequence, n_forward_rounds, [&](LoopTensors& t, int n_new_items) {
-                         inference_model.forward(t.inp_device, t.lengths_device, t.new_items_indices_device,
-                                                 t.decoder_result_device, n_new_items, emb_table, pos_table,
-                                                 paged_attention_manager.get_page_table_device(), handle);
-                     });
+void start_paged_attention_cublas_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table, ItemStorage& item_storage,
+        ProcessingStorage& processing_storage, MemoryBlockManager& memory_block_manager,
+        PagedAttentionsManager& paged_attention_manager, PagedAttentionCublasInferenceModel& inference_model, size_t n_batch_size,
+        size_t n_sequence, int n_forward_rounds) {
+    start_paged_engine(emb_table, pos_table, item_storage, processing_storage, memory_block_manager, paged_attention_manager,
+                       inference_model, n_batch_size, n_sequence, n_forward_rounds);
 }
 
-// EXTENSION (no reference counterpart): the same loop over bf16 pages and weights.
-void start_paged_attention_bf16_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table,
-                                                 ItemStorage& item_storage, ProcessingStorage& processing_storage,
-                                                 MemoryBlockManager& memory_block_manager,
-                                                 PagedAttentionsManager& paged_attention_manager,
-                                                 PagedAttentionBf16InferenceModel& inference_model,
-                                                 size_t n_batch_size, size_t n_sequence, int n_forward_rounds) {
-    if (pipelined_loop_applies(paged_attention_manager, n_forward_rounds)) {
-        start_paged_attention_bf16_inference_engine_pipelined(emb_table, pos_table, item_storage, processing_storage,
-                                                              memory_block_manager, paged_attention_manager,
-                                                              inference_model, n_batch_size, n_sequence, n_forward_rounds);
-        return;
-    }
-    run_paged_engine(item_storage, processing_storage, memory_block_manager, paged_attention_manager, n_batch_size,
-                     n_sequence, n_forward_rounds, [&](LoopTensors& t, int n_new_items) {
-                         inference_model.forward(t.inp_device, t.lengths_device, t.new_items_indices_device,
-                                                 t.decoder_result_device, n_new_items, emb_table, pos_table,
-                                                 paged_attention_manager.get_page_table_device());
-                     });
+void start_paged_attention_bf16_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table, ItemStorage& item_storage,
+        ProcessingStorage& processing_storage, MemoryBlockManager& memory_block_manager,
+        PagedAttentionsManager& paged_attention_manager, PagedAttentionBf16InferenceModel& inference_model, size_t n_batch_size,
+        size_t n_sequence, int n_forward_rounds) {
+    start_paged_engine(emb_table, pos_table, item_storage, processing_storage, memory_block_manager, paged_attention_manager,
+                       inference_model, n_batch_size, n_sequence, n_forward_rounds);
 }
 
-// EXTENSION, opt-in (no reference counterpart): the same loop over fp8 (OCP e4m3) pages and bf16 weights.
-void start_paged_attention_fp8_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table,
-                                                ItemStorage& item_storage, ProcessingStorage& processing_storage,
-                                                MemoryBlockManager& memory_block_manager,
-                                                PagedAttentionsManager& paged_attention_manager,
-                                                PagedAttentionFp8InferenceModel& inference_model, size_t n_batch_size,
-                                                size_t n_sequence, int n_forward_rounds) {
-    if (pipelined_loop_applies(paged_attention_manager, n_forward_rounds)) {
-        start_paged_attention_fp8_inference_engine_pipelined(emb_table, pos_table, item_storage, processing_storage,
-                                                             memory_block_manager, paged_attention_manager,
-                                                             inference_model, n_batch_size, n_sequence, n_forward_rounds);
-        return;
-    }
-    run_paged_engine(item_storage, processing_storage, memory_block_manager, paged_attention_manager, n_batch_size,
-                     n_sequence, n_forward_rounds, [&](LoopTensors& t, int n_new_items) {
-                         inference_model.forward(t.inp_device, t.lengths_device, t.new_items_indices_device,
-                                                 t.decoder_result_device, n_new_items, emb_table, pos_table,
-                                                 paged_attention_manager.get_page_table_device());
-                     });
+void start_paged_attention_fp8_inference_engine(const TensorFloat& emb_table, const TensorFloat& pos_table, ItemStorage& item_storage,
+        ProcessingStorage& processing_storage, MemoryBlockManager& memory_block_manager,
+        PagedAttentionsManager& paged_attention_manager, PagedAttentionFp8InferenceModel& inference_model, size_t n_batch_size,
+        size_t n_sequence, int n_forward_rounds) {
+    start_paged_engine(emb_table, pos_table, item_storage, processing_storage, memory_block_manager, paged_attention_manager,
+                       inference_model, n_batch_size, n_sequence, n_forward_rounds);
 }

@@ -248,23 +248,34 @@ void paged_attention(TensorFloatPoint& page_table, const TensorInt& lengths, con
                                   B, n_sequence, D, n_new_items, ws.ptr, ws.bytes, stream()));
 }
 
+void launch_paged_prefill_elem(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,
+                               TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
+                               const void* wk, const void* wv, int n_new_items, int elem, bool live_only, int window,
+                               int n_sink) {
+    if (n_new_items == 0) return;
+    void* const* table = reinterpret_cast<void* const*>(pages(page_table));
+    const int B = (int)inp.shape()[0], S = (int)inp.shape()[1], D = (int)emb_table.shape()[1];
+    if (live_only)   // the live tokens only; no table entry of a dead page is followed
+        HIP_CHECK(mli_paged_prefill_window(emb_table.data(), wpe.data(), inp.data(), table, lengths.data(),
+                                           new_item_indices.data(), wk, wv, B, S, D, n_new_items, window > 0 ? window : 0,
+                                           n_sink, elem, stream()));
+    else
+        HIP_CHECK(mli_paged_prefill(emb_table.data(), wpe.data(), inp.data(), table, lengths.data(),
+                                    new_item_indices.data(), wk, wv, B, S, D, n_new_items, elem, stream()));
+}
+
 void launch_paged_prefill(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,
                           TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
                           const TensorFloat& wk, const TensorFloat& wv, int n_new_items) {
-    if (n_new_items == 0) return;
-    HIP_CHECK(mli_paged_prefill(emb_table.data(), wpe.data(), inp.data(), reinterpret_cast<void* const*>(pages(page_table)),
-                                lengths.data(), new_item_indices.data(), wk.data(), wv.data(), (int)inp.shape()[0],
-                                (int)inp.shape()[1], (int)emb_table.shape()[1], n_new_items, /*elem_bf16=*/0, stream()));
+    launch_paged_prefill_elem(emb_table, wpe, inp, page_table, lengths, new_item_indices, wk.data(), wv.data(), n_new_items,
+                              MLI_ELEM_F32, false, 0, 0);
 }
 
 void launch_paged_prefill_window(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,
                                  TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
                                  const TensorFloat& wk, const TensorFloat& wv, int n_new_items, int window, int n_sink) {
-    if (n_new_items == 0) return;
-    HIP_CHECK(mli_paged_prefill_window(emb_table.data(), wpe.data(), inp.data(), reinterpret_cast<void* const*>(pages(page_table)),
-                                       lengths.data(), new_item_indices.data(), wk.data(), wv.data(), (int)inp.shape()[0],
-                                       (int)inp.shape()[1], (int)emb_table.shape()[1], n_new_items, window > 0 ? window : 0,
-                                       n_sink, MLI_ELEM_F32, stream()));
+    launch_paged_prefill_elem(emb_table, wpe, inp, page_table, lengths, new_item_indices, wk.data(), wv.data(), n_new_items,
+                              MLI_ELEM_F32, true, window, n_sink);
 }
 
 void launch_prefill(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,
@@ -443,14 +454,13 @@ void launch_decoder_fused(const TensorFloat& batch_result, const TensorFloat& em
 void launch_paged_attention_decoder_fused(const TensorFloat& batch_result, const TensorFloat& emb_table,
                                           TensorFloat& emb_score, const TensorFloat& wpe_table,
                                           TensorFloatPoint& page_table, TensorInt& lengths, TensorInt& decoder_result,
-                                          int i_decoder) {
+                                          int i_decoder, int elem) {
     const int n_results = decoder_result.shape().size() == 2 ? (int)decoder_result.shape()[1] : 1;
     HIP_CHECK(mli_paged_decoder_fused(batch_result.data(), emb_table.data(), wpe_table.data(),
                                       reinterpret_cast<void* const*>(pages(page_table)), lengths.data(),
                                       decoder_result.data(), (int)batch_result.shape()[0], (int)emb_table.shape()[0],
                                       (int)wpe_table.shape()[0], (int)batch_result.shape()[1], n_results, i_decoder,
-                                      /*elem_bf16=*/0, emb_score.data(), emb_score.get_total_size() * sizeof(float),
-                                      stream()));
+                                      elem, emb_score.data(), emb_score.get_total_size() * sizeof(float), stream()));
 }
 
 // EXTENSION: the sampled head; emb_score [n_batch, n_vocab] is the scratch that receives the logits

@@ -2,6 +2,7 @@
 
 #include <utility>
 
+#include "bf16_extension.h"  // launch_paged_attention_decoder_multi_rounds_bf16
 #include "kernels/decoder.h"
 #include "kernels/encoder.h"
 #include "kernels/paged_attention.h"
@@ -40,61 +41,75 @@ void SelfAttentionLayer::prefill(const TensorFloat& emb_table, const TensorFloat
                    n_new_items);
 }
 
+template <class Weights>
+PagedAttentionLayerCore<Weights>::PagedAttentionLayerCore(int elem, Weights&& wk, Weights&& wq, Weights&& wv,
+                                                          size_t n_batch, size_t emb_dim, size_t n_sequence)
+    : elem_(elem), wk_(std::move(wk)), wq_(std::move(wq)), wv_(std::move(wv)),
+      q_output_(device_tensor({n_batch, emb_dim})), n_sequence_(n_sequence) {}
+
+template <class Weights>
+void PagedAttentionLayerCore<Weights>::prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb,
+                                               const TensorInt& inp, TensorFloatPoint& page_table,
+                                               const TensorInt& lengths, const TensorInt& new_item_indices,
+                                               int n_new_items) {
+    launch_paged_prefill_elem(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_.data(), wv_.data(),
+                              n_new_items, elem_, options_.page_release, options_.window, options_.n_sink);
+}
+
+template <class Weights>
+int PagedAttentionLayerCore<Weights>::lean_scan(TensorFloatPoint& page_table, const TensorInt& lengths,
+                                                const TensorInt& new_batch_idx, TensorFloat& attention_result,
+                                                int n_new_items, int n_heads, int n_kv_heads) {
+    return mli::runtime::lean_paged_attention(elem_, n_heads, options_.window, options_.n_sink,
+                                              reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
+                                              wk_.data(), wq_.data(), wv_.data(), new_batch_idx.data(), q_output_.data(),
+                                              attention_result.data(), (int)page_table.shape()[0], (int)n_sequence_,
+                                              (int)wk_.shape()[0], n_new_items, n_kv_heads);
+}
+
+template class PagedAttentionLayerCore<TensorFloat>;
+template class PagedAttentionLayerCore<Tensor<uint16_t>>;
+
+PagedAttentionFloatLayer::PagedAttentionFloatLayer(TensorFloat&& wk, TensorFloat&& wq, TensorFloat&& wv, size_t n_batch,
+                                                   size_t emb_dim, size_t n_sequence)
+    : PagedAttentionLayerCore(MLI_ELEM_F32, std::move(wk), std::move(wq), std::move(wv), n_batch, emb_dim, n_sequence),
+      qkt_output_(device_tensor({n_batch, n_sequence})) {}
+
+bool PagedAttentionFloatLayer::forward_lean(TensorFloatPoint& page_table, const TensorInt& lengths,
+                                            const TensorInt& new_batch_idx, TensorFloat& attention_result,
+                                            int n_new_items) {
+    if (!mli::runtime::lean_paged_wanted(options_.n_heads, options_.window, (int)n_sequence_)) return false;
+    const int rc = lean_scan(page_table, lengths, new_batch_idx, attention_result, n_new_items, options_.n_heads,
+                             options_.n_kv_heads);
+    const int D = (int)wk_.shape()[0];
+    if (rc == MLI_ERR_BAD_ARG && D > 2048 && D % 4 == 0) return false;  // rows wider than the single-pass kernel covers
+    HIP_CHECK(rc);
+    return true;
+}
+
 PagedAttentionLayer::PagedAttentionLayer(TensorFloat&& wk, TensorFloat&& wq, TensorFloat&& wv, size_t n_batch,
                                          size_t emb_dim, size_t n_sequence)
-    : wk_(std::move(wk)), wq_(std::move(wq)), wv_(std::move(wv)),
-      q_output_(device_tensor({n_batch, emb_dim})),
-      qkt_output_(device_tensor({n_batch, n_sequence})) {}
+    : PagedAttentionFloatLayer(std::move(wk), std::move(wq), std::move(wv), n_batch, emb_dim, n_sequence) {}
 
 void PagedAttentionLayer::forward(TensorFloatPoint& page_table, const TensorInt& lengths,
                                   const TensorInt& new_batch_idx, TensorFloat& attention_result, int n_new_items) {
-    const int n_sequence = static_cast<int>(qkt_output_.shape()[1]);
-    if (mli::runtime::lean_paged_wanted(n_heads_, window_, n_sequence))
-        paged_attention_lean_layer(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, &qkt_output_,
-                                   attention_result, n_new_items, n_sequence, n_heads_, window_, n_sink_, n_kv_heads_);
-    else
+    if (!forward_lean(page_table, lengths, new_batch_idx, attention_result, n_new_items))
         paged_attention(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, qkt_output_, attention_result,
-                        n_new_items, n_sequence);
-}
-
-void PagedAttentionLayer::prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
-                                  TensorFloatPoint& page_table, const TensorInt& lengths,
-                                  const TensorInt& new_item_indices, int n_new_items) {
-    if (page_release_)
-        launch_paged_prefill_window(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_, wv_, n_new_items,
-                                    window_, n_sink_);
-    else
-        launch_paged_prefill(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_, wv_, n_new_items);
-}
-
-void PagedAttentionCublasLayer::prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
-                                        TensorFloatPoint& page_table, const TensorInt& lengths,
-                                        const TensorInt& new_item_indices, int n_new_items) {
-    if (page_release_)
-        launch_paged_prefill_window(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_, wv_, n_new_items,
-                                    window_, n_sink_);
-    else
-        launch_paged_prefill(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_, wv_, n_new_items);
+                        n_new_items, (int)n_sequence_);
 }
 
 PagedAttentionCublasLayer::PagedAttentionCublasLayer(TensorFloat&& wk, TensorFloat&& wq, TensorFloat&& wv,
                                                      size_t n_batch, size_t emb_dim, size_t n_sequence)
-    : wk_(std::move(wk)), wq_(std::move(wq)), wv_(std::move(wv)),
-      q_output_(device_tensor({n_batch, emb_dim})),
-      qkt_output_(device_tensor({n_batch, n_sequence})),
+    : PagedAttentionFloatLayer(std::move(wk), std::move(wq), std::move(wv), n_batch, emb_dim, n_sequence),
       latest_emb_(device_tensor({n_batch, emb_dim})),
       temp_placeholder_(device_tensor({n_batch, emb_dim})) {}
 
 void PagedAttentionCublasLayer::forward(TensorFloatPoint& page_table, const TensorInt& lengths,
                                         const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                         int n_new_items, GemmHandle& handle) {
-    const int n_sequence = static_cast<int>(qkt_output_.shape()[1]);
-    if (mli::runtime::lean_paged_wanted(n_heads_, window_, n_sequence))
-        paged_attention_lean_layer(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, &qkt_output_,
-                                   attention_result, n_new_items, n_sequence, n_heads_, window_, n_sink_, n_kv_heads_);
-    else
+    if (!forward_lean(page_table, lengths, new_batch_idx, attention_result, n_new_items))
         paged_attention_with_cublas(page_table, lengths, wk_, wq_, wv_, new_batch_idx, q_output_, qkt_output_,
-                                    attention_result, latest_emb_, temp_placeholder_, n_new_items, n_sequence, handle);
+                                    attention_result, latest_emb_, temp_placeholder_, n_new_items, (int)n_sequence_, handle);
 }
 
 void EncoderLayer::forward(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
@@ -115,51 +130,57 @@ void PagedEncoderLayer::forward(const TensorFloat& emb_table, const TensorFloat&
                                           n_new_items);
 }
 
-DecoderLayer::DecoderLayer(size_t n_batch, size_t n_vocab) : emb_score_(device_tensor({n_batch, n_vocab})) {}
+DecoderHead::DecoderHead(size_t n_batch, size_t n_vocab, bool lean_only) : n_batch_(n_batch), n_vocab_(n_vocab) {
+    if (lean_only)
+        lean_scratch_ = std::make_unique<TensorFloat>(device_tensor({(mli_decoder_scratch_bytes((int)n_batch, (int)n_vocab) + 3) / 4}));
+    else
+        emb_score_ = std::make_unique<TensorFloat>(device_tensor({n_batch, n_vocab}));
+}
+
+void DecoderHead::set_sampling(const SlotSampling* sampling) {
+    if (sampling && !emb_score_) emb_score_ = std::make_unique<TensorFloat>(device_tensor({n_batch_, n_vocab_}));
+    sampling_ = sampling;
+}
+
+void DecoderHead::forward_paged(int elem, const TensorFloat& batch_result, const TensorFloat& emb_table,
+                                const TensorFloat& wpe_table, TensorFloatPoint& page_table, TensorInt& lengths,
+                                TensorInt& decoder_result, int i_decoder_round) {
+    if (sampling_)
+        launch_paged_attention_decoder_sampled(batch_result, emb_table, *emb_score_, wpe_table, page_table, lengths,
+                                               decoder_result, i_decoder_round, elem, *sampling_, &logprobs_);
+    else if (lean_scratch_ || mli::runtime::lean_layers())  // a lean_only head does not read the switch
+        launch_paged_attention_decoder_fused(batch_result, emb_table, lean_scratch_ ? *lean_scratch_ : *emb_score_,
+                                             wpe_table, page_table, lengths, decoder_result, i_decoder_round, elem);
+    else if (elem == MLI_ELEM_BF16)
+        launch_paged_attention_decoder_multi_rounds_bf16(batch_result, emb_table, *emb_score_, wpe_table, page_table,
+                                                         lengths, decoder_result, i_decoder_round);
+    else
+        launch_paged_attention_decoder_multi_rounds(batch_result, emb_table, *emb_score_, wpe_table, page_table, lengths,
+                                                    decoder_result, i_decoder_round);
+}
 
 void DecoderLayer::forward(const TensorFloat& batch_result, const TensorFloat& emb_table,
                            const TensorFloat& wpe_table, TensorFloat& inp_embedding, TensorInt& lengths,
                            TensorInt& decoder_result) {
     if (sampling_)
-        launch_decoder_sampled(batch_result, emb_table, emb_score_, wpe_table, inp_embedding, lengths, decoder_result,
+        launch_decoder_sampled(batch_result, emb_table, *emb_score_, wpe_table, inp_embedding, lengths, decoder_result,
                                *sampling_, &logprobs_);
     else if (mli::runtime::lean_layers())
-        launch_decoder_fused(batch_result, emb_table, emb_score_, wpe_table, inp_embedding, lengths, decoder_result);
+        launch_decoder_fused(batch_result, emb_table, *emb_score_, wpe_table, inp_embedding, lengths, decoder_result);
     else
-        launch_decoder(batch_result, emb_table, emb_score_, wpe_table, inp_embedding, lengths, decoder_result);
+        launch_decoder(batch_result, emb_table, *emb_score_, wpe_table, inp_embedding, lengths, decoder_result);
 }
-
-PagedDecoderLayer::PagedDecoderLayer(size_t n_batch, size_t n_vocab)
-    : emb_score_(device_tensor({n_batch, n_vocab})) {}
 
 void PagedDecoderLayer::forward(const TensorFloat& batch_result, const TensorFloat& emb_table,
                                 const TensorFloat& wpe_table, TensorFloatPoint& page_table, TensorInt& lengths,
                                 TensorInt& decoder_result, int i_decoder_round) {
-    if (sampling_)
-        launch_paged_attention_decoder_sampled(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
-                                               decoder_result, i_decoder_round, MLI_ELEM_F32, *sampling_, &logprobs_);
-    else if (mli::runtime::lean_layers())
-        launch_paged_attention_decoder_fused(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
-                                             decoder_result, i_decoder_round);
-    else
-        launch_paged_attention_decoder_multi_rounds(batch_result, emb_table, emb_score_, wpe_table, page_table,
-                                                    lengths, decoder_result, i_decoder_round);
+    forward_paged(MLI_ELEM_F32, batch_result, emb_table, wpe_table, page_table, lengths, decoder_result, i_decoder_round);
 }
 
-PagedCublasDecoderLayer::PagedCublasDecoderLayer(size_t n_batch, size_t n_vocab)
-    : emb_score_(device_tensor({n_batch, n_vocab})) {}
-
+// the "cuBLAS" materialising head is the plain one (launch_paged_attention_cublas_decoder_multi_rounds, launchers.cpp)
 void PagedCublasDecoderLayer::forward(const TensorFloat& batch_result, const TensorFloat& emb_table,
                                       const TensorFloat& wpe_table, TensorFloatPoint& page_table,
                                       TensorInt& lengths, TensorInt& decoder_result, int i_decoder_round,
-                                      GemmHandle& handle) {
-    if (sampling_)
-        launch_paged_attention_decoder_sampled(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
-                                               decoder_result, i_decoder_round, MLI_ELEM_F32, *sampling_, &logprobs_);
-    else if (mli::runtime::lean_layers())
-        launch_paged_attention_decoder_fused(batch_result, emb_table, emb_score_, wpe_table, page_table, lengths,
-                                             decoder_result, i_decoder_round);
-    else
-        launch_paged_attention_cublas_decoder_multi_rounds(batch_result, emb_table, emb_score_, wpe_table, page_table,
-                                                           lengths, decoder_result, i_decoder_round, handle);
+                                      GemmHandle& /*handle*/) {
+    forward_paged(MLI_ELEM_F32, batch_result, emb_table, wpe_table, page_table, lengths, decoder_result, i_decoder_round);
 }

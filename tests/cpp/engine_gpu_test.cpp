@@ -13,6 +13,7 @@
 #include "constants.h"
 #include "inference_model.h"
 #include "inferencer.h"
+#include "mli_engine.h"
 #include "pipelined_engine.h"
 #include "runtime.h"
 #include "throughput_counter.h"
@@ -39,6 +40,192 @@ static std::map<int, std::vector<int>> collect(const ItemStorage& s) {
     for (const auto& it : s.get_finished_items()) out[it.first] = it.second;
     return out;
 }
+
+// ---- the C++ surface beyond the reference's: fp8 pages, the option setters on the models, early page
+// release -- on a small shape, 4 heads on 2 K/V heads under window 12 with 4 sinks (what tests/test_gqa_engine_gpu.py runs
+// through the C ABI, which the other tests audit against float64).  Own generator, own items: nothing here reaches the
+// checksum below.
+namespace small {
+
+const size_t B = 8, S = 64, D = 128, V = 1100;
+const int H = 4, HKV = 2, W = 12, K = 4, N_ITEMS = 20, WORST_CASE_BLOCKS = B * S / PAGE_BLOCK_SIZE;
+using Tokens = std::map<int, std::vector<int>>;
+
+struct Case {
+    std::vector<float> emb, pos, wk, wq, wv;   // host values: the C ABI takes these, the C++ models their uploads
+    std::vector<IdTokensPair> items;
+    Case() {
+        std::mt19937 gen(1812);
+        auto fill = [&](std::vector<float>& v, size_t n, float scale) {
+            std::uniform_real_distribution<float> u(-scale, scale);
+            v.resize(n);
+            for (float& x : v) x = u(gen);
+        };
+        fill(emb, V * D, 1.0f), fill(pos, S * D, 0.5f);
+        fill(wk, D * D, 0.18f), fill(wq, D * D, 0.18f), fill(wv, D * D, 0.18f);
+        for (int i = 0; i < N_ITEMS; ++i) {
+            std::vector<int> toks(1 + gen() % 40);
+            for (int& t : toks) t = gen() % EOF_TOKEN_ID;
+            items.emplace_back(i, toks);
+        }
+    }
+};
+
+TensorFloat device(const std::vector<float>& values, std::vector<size_t> shape) {
+    TensorFloat host(shape, DeviceType::HOST), dev(shape, DeviceType::DEVICE);
+    std::memcpy(host.data(), values.data(), values.size() * sizeof(float));
+    dev.copy_from(host);
+    return dev;
+}
+
+template <class Model>
+void set_options(Model& model) {
+    model.set_n_heads(H);
+    model.set_n_kv_heads(HKV);
+    model.set_window(W);
+    model.set_sinks(K);
+}
+
+// one run of `model` through start (under the sequential loop) or start_pipelined; failures counts unfinished items and
+// damaged prompts
+template <class Model, class Start>
+Tokens run(const Case& c, Model&& model, Start start, Start start_pipelined, bool pipelined, size_t block_floats, int n_blocks,
+           bool release, int& failures) {
+    ItemStorage storage;
+    ProcessingStorage processing;
+    for (const auto& it : c.items) storage.add_new_item(IdTokensPair(it));
+    MemoryBlockManager pool(n_blocks, block_floats);
+    PagedAttentionsManager pages(B, S, D);
+    if (release) {
+        pages.set_page_release(W, K);
+        model.set_page_release(true);
+    }
+    TensorFloat emb = device(c.emb, {V, D}), pos = device(c.pos, {S, D});
+    mli::runtime::set_sequential_engine_loop(!pipelined);
+    (pipelined ? start_pipelined : start)(emb, pos, storage, processing, pool, pages, model, B, S, 1);
+    mli::runtime::set_sequential_engine_loop(false);
+    Tokens out = collect(storage);
+    failures += storage.finish_count() != N_ITEMS;
+    for (const auto& kv : out) {
+        const std::vector<int>& prompt = c.items[kv.first].second;
+        failures += kv.second.size() <= prompt.size() || !std::equal(prompt.begin(), prompt.end(), kv.second.begin());
+    }
+    return out;
+}
+
+PagedAttentionInferenceModel fp32_model(const Case& c) {
+    return PagedAttentionInferenceModel(PagedAttentionLayer(device(c.wk, {D, D}), device(c.wq, {D, D}), device(c.wv, {D, D}), B, D, S),
+                                        PagedEncoderLayer(), PagedDecoderLayer(B, V), B, S, D, 1);
+}
+PagedAttentionCublasInferenceModel gemm_model(const Case& c) {
+    return PagedAttentionCublasInferenceModel(
+        PagedAttentionCublasLayer(device(c.wk, {D, D}), device(c.wq, {D, D}), device(c.wv, {D, D}), B, D, S), PagedEncoderLayer(),
+        PagedCublasDecoderLayer(B, V), B, S, D, 1);
+}
+PagedAttentionBf16InferenceModel bf16_model(const Case& c) {
+    return PagedAttentionBf16InferenceModel(
+        PagedAttentionBf16Layer(make_device_bf16(c.wk.data(), {D, D}), make_device_bf16(c.wq.data(), {D, D}),
+                                make_device_bf16(c.wv.data(), {D, D}), B, D, S), B, S, D, V, 1);
+}
+PagedAttentionFp8InferenceModel fp8_model(const Case& c) {
+    return PagedAttentionFp8InferenceModel(
+        PagedAttentionFp8Layer(make_device_bf16(c.wk.data(), {D, D}), make_device_bf16(c.wq.data(), {D, D}),
+                               make_device_bf16(c.wv.data(), {D, D}), B, D, S), B, S, D, V, 1);
+}
+
+// the same model, items and options through the engine C ABI
+Tokens run_c_engine(const Case& c, int kind, int& failures) {
+    mli_engine_config cfg{};
+    cfg.kind = kind, cfg.n_batch = B, cfg.n_sequence = S, cfg.emb_dim = D, cfg.n_vocab = V;
+    cfg.n_blocks = WORST_CASE_BLOCKS, cfg.n_forward_rounds = 1;
+    mli_engine* e = nullptr;
+    int rc = mli_engine_create(&cfg, c.emb.data(), c.pos.data(), c.wk.data(), c.wq.data(), c.wv.data(), &e);
+    if (rc == 0) rc = mli_engine_set_heads(e, H) | mli_engine_set_kv_heads(e, HKV) | mli_engine_set_window(e, W) | mli_engine_set_sinks(e, K);
+    for (const auto& it : c.items)
+        if (rc == 0) rc = mli_engine_add_item(e, it.first, it.second.data(), (int)it.second.size());
+    mli_engine_stats stats{};
+    if (rc == 0) rc = mli_engine_run(e, &stats);
+    Tokens out;
+    for (int i = 0; rc == 0 && i < stats.finished; ++i) {
+        int id = 0, n = 0;
+        std::vector<int> toks(S);
+        rc = mli_engine_get_finished(e, i, &id, toks.data(), (int)toks.size(), &n);
+        toks.resize(n);
+        out[id] = toks;
+    }
+    if (rc != 0) std::printf("engine C ABI, kind %d: %s\n", kind, mli_engine_last_error());
+    failures += rc != 0 || stats.finished != N_ITEMS;
+    mli_engine_destroy(e);
+    return out;
+}
+
+int differing(const Tokens& a, const Tokens& b) {
+    int n = a.size() != b.size();
+    for (const auto& kv : a) n += !b.count(kv.first) || b.at(kv.first) != kv.second;
+    return n;
+}
+
+int run_all() {
+    const Case c;
+    int failures = 0;
+    const size_t f32_block = PAGE_BLOCK_SIZE * 3 * D;
+    // 8. fp8 pages through C++: both loops finish every item with its prompt intact and give the same tokens
+    {
+        const Tokens seq = run(c, fp8_model(c), start_paged_attention_fp8_inference_engine,
+                               start_paged_attention_fp8_inference_engine_pipelined, false, fp8_page_block_floats(D),
+                               WORST_CASE_BLOCKS, false, failures);
+        const Tokens pipe = run(c, fp8_model(c), start_paged_attention_fp8_inference_engine,
+                                start_paged_attention_fp8_inference_engine_pipelined, true, fp8_page_block_floats(D),
+                                WORST_CASE_BLOCKS, false, failures);
+        std::printf("fp8 paged engine: items that differ between the loops: %d\n", differing(seq, pipe));
+        failures += differing(seq, pipe) != 0;
+    }
+    // 9. the option setters on the fp32 and the GEMM model: the two models and the two loops agree, the setters reach the
+    //    scan (some item differs from the model nothing was set on), and the engine C ABI decodes the same
+    Tokens with_options;
+    {
+        auto fp32 = [&](bool pipelined, bool options, bool release, int n_blocks) {
+            PagedAttentionInferenceModel model = fp32_model(c);
+            if (options) set_options(model);
+            return run(c, model, start_paged_attention_inference_engine, start_paged_attention_inference_engine_pipelined,
+                       pipelined, f32_block, n_blocks, release, failures);
+        };
+        auto gemm = [&](bool pipelined, bool release, int n_blocks) {
+            PagedAttentionCublasInferenceModel model = gemm_model(c);
+            set_options(model);
+            return run(c, model, start_paged_attention_cublas_inference_engine,
+                       start_paged_attention_cublas_inference_engine_pipelined, pipelined, f32_block, n_blocks, release, failures);
+        };
+        with_options = fp32(false, true, false, WORST_CASE_BLOCKS);
+        const int loops = differing(with_options, fp32(true, true, false, WORST_CASE_BLOCKS));
+        const int models = differing(with_options, gemm(false, false, WORST_CASE_BLOCKS)) +
+                           differing(with_options, gemm(true, false, WORST_CASE_BLOCKS));
+        const int plain = differing(with_options, fp32(false, false, false, WORST_CASE_BLOCKS));
+        const int abi = differing(with_options, run_c_engine(c, MLI_ENGINE_PAGED, failures));
+        std::printf("fp32 / GEMM models with heads, K/V heads, window, sinks: differ between loops %d, between models %d, from "
+                    "the engine C ABI %d; items the options changed: %d\n", loops, models, abi, plain);
+        failures += loops != 0 || models != 0 || abi != 0 || plain == 0;
+        // 10. early page release on a pool half the worst case: the same tokens
+        const int released = differing(with_options, fp32(false, true, true, WORST_CASE_BLOCKS / 2)) +
+                             differing(with_options, gemm(true, true, WORST_CASE_BLOCKS / 2));
+        std::printf("... with page release on half the pool: items that differ: %d\n", released);
+        failures += released != 0;
+    }
+    // 11. the same setters on the bf16 model against the bf16 engine of the C ABI
+    {
+        PagedAttentionBf16InferenceModel model = bf16_model(c);
+        set_options(model);
+        const Tokens cpp = run(c, model, start_paged_attention_bf16_inference_engine,
+                               start_paged_attention_bf16_inference_engine_pipelined, true, bf16_page_block_floats(D),
+                               WORST_CASE_BLOCKS, false, failures);
+        const int abi = differing(cpp, run_c_engine(c, MLI_ENGINE_PAGED_BF16, failures));
+        std::printf("bf16 model with the same options: items that differ from the engine C ABI: %d\n", abi);
+        failures += abi != 0;
+    }
+    return failures;
+}
+
+}  // namespace small
 
 int main() {
     const size_t B = 96, S = 160, D = 256, V = 1100;
@@ -200,6 +387,7 @@ int main() {
                     threw ? "reported as too small" : "NOT reported");
         failures += !threw;
     }
+    failures += small::run_all();
     int mismatched = 0;
     for (const auto& kv : naive)
         if (paged[kv.first] != kv.second || gemm[kv.first] != kv.second || pipelined[kv.first] != kv.second ||
