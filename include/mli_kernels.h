@@ -605,6 +605,39 @@ int mli_f32_to_fp8(const float* src, uint8_t* dst, size_t n, void* stream);
  *                      rounding order of the fp32 accumulation) */
 int mli_tune(const char* key, int value);
 
+/* Launch counters: which branch of a launcher the calling thread's calls took.  PER THREAD, like the knobs above: an engine
+ * runs in its caller's thread, so the caller reads what its own engine launched, and nothing another thread runs is seen.
+ * Host side only: a counter is incremented where the launcher enqueues the kernel (one increment per launch); no kernel reads
+ * or writes them and no kernel differs for them.  A launch enqueued while its stream is being captured into a graph counts
+ * ONCE, at capture; replays of the graph do not count.  A launcher that answers "not applicable" or refuses its arguments
+ * before enqueueing counts nothing -- a silent hand-back to another kernel shows as that kernel's count.
+ * mli_launch_count stores the count of `family` since the thread's last reset (0 at thread start) in *count; MLI_ERR_BAD_ARG
+ * for a null or unknown name or a null count, which is left untouched.  mli_launch_counts_reset zeroes every family.
+ * Kernel families (a launch of one of these kernels counts in exactly one; other kernels are not counted):
+ *   "gemm_f32_panel"         fp32 GEMM, latency-shaped 32x32 kernel ("gemm_panel")
+ *   "gemm_f32_rows64"        fp32 GEMM, 64-row tiles, one wave loads and multiplies
+ *   "gemm_f32_rows64_split"  fp32 GEMM, 64-row tiles, loader waves + MFMA waves ("gemm_split")
+ *   "gemm_f32_rows128"       fp32 GEMM, 128-row tiles ("gemm_tall_tiles")
+ *   "gemm_bf16_widened"      bf16 pages through the fp32 MFMA kernel ("bf16_native_mfma" 0), projection and fill
+ *   "gemm_bf16_rows64"       bf16 / fp8 decode projection, 64-row tiles, 32 k per stage
+ *   "gemm_bf16_deep"         ... 64-row tiles, 128 k per stage (emb_dim 256 .. 1024)
+ *   "gemm_bf16_rows128"      ... 128-row tiles ("gemm_tall_tiles")
+ *   "gemm_bf16_dma"          ... the LDS-DMA loader-wave / MFMA-wave kernel ("gemm_bf16_split")
+ *   "gemm_bf16_fill"         the prefill fill of bf16 / fp8 pages (native MFMA)
+ *   "scan_equal_shares"      the equal-page-shares scan ("scan_stream")
+ *   "scan_chunked"           the single-head chunked scan, lean or materialising, every grid form
+ *   "scan_heads_window"      the scans with several heads, a window, sinks or grouped K/V heads
+ * Forms, counted beside the launch's kernel family:
+ *   "latest_compact"         a decode projection over the compacted list of non-empty rows ("latest_compact"; the panel and
+ *                            the LDS-DMA kernel have no such list)
+ *   "fill_flat" / "fill_per_row"   a prefill fill over the flat (new row, token) list / one tile grid per new row ("fill_compact")
+ *   "prefill_fused" / "prefill_two_launch"   mli_prefill, mli_paged_prefill[_window] with new rows: the encoder as the fill's
+ *                            prologue / encoder + fill ("prefill_fused")
+ *   "scan_rows_ordered" / "scan_rows_grid_order"   a "scan_chunked" launch with one workgroup per row: rows handed out longest
+ *                            first / in grid order ("scan_row_order") */
+int mli_launch_count(const char* family, unsigned long long* count);
+int mli_launch_counts_reset(void);
+
 /* The resident slice of "scan_resident_mib", restated for tests and tools.  mli_scan_resident_threshold: the threshold
  * (0 .. 65536) of a launch whose rows hold total_pages pages in all (elem: MLI_ELEM_*; MLI_ERR_BAD_ARG for another tag, a
  * negative page count or emb_dim <= 0).  mli_scan_resident_keeps: 1 if that launch loads the page at page_ptr with the

@@ -103,6 +103,8 @@ SIGNATURES = {
     "mli_paged_decoder_multi_rounds": [_P] * 7 + [_I] * 6 + [_P],
     "mli_clone_inp_embedding_k_v_cache": [_P] * 5 + [_I] * 3 + [_P],
     "mli_tune": [ctypes.c_char_p, _I],
+    "mli_launch_count": [ctypes.c_char_p, ctypes.POINTER(ctypes.c_ulonglong)],
+    "mli_launch_counts_reset": [],
     "mli_scan_resident_threshold": [ctypes.c_longlong, _I, _I, _I],
     "mli_scan_resident_keeps": [_P, _I],
     "mli_stream_copy": [_P, _P, _Z, _P],

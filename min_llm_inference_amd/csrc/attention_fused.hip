@@ -114,6 +114,8 @@ static int launch_fused_decode(const float* q, const void* const* page_table, co
         });
     };
     if (phases & 1) {
+        count_launch(kLfScanChunked);
+        if (p.direct) count_launch(p.direct == 2 ? kLfScanRowsOrdered : kLfScanRowsGridOrder);
         if (kFp8 || lean) launch(std::false_type{});
         else if constexpr (!kFp8) launch(std::true_type{});
     }

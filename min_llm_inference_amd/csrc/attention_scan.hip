@@ -12,6 +12,7 @@
 #include <string>
 
 #include "device_common.hpp"
+#include "launch_count.hpp"
 #include "scan_plan.hpp"
 
 namespace mli {
@@ -725,6 +726,18 @@ int mli_tune(const char* key, int value) {
     } else {
         return MLI_ERR_BAD_ARG;
     }
+    return 0;
+}
+
+int mli_launch_count(const char* family, unsigned long long* count) {
+    const int f = mli::launch_family_of(family);
+    if (f < 0 || count == nullptr) return MLI_ERR_BAD_ARG;
+    *count = mli::g_launch_counts[f];
+    return 0;
+}
+
+int mli_launch_counts_reset(void) {
+    for (int f = 0; f < mli::kLaunchFamilies; ++f) mli::g_launch_counts[f] = 0;
     return 0;
 }
 

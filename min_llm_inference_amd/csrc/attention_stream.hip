@@ -600,6 +600,7 @@ int launch_stream_decode(const float* q, const void* const* page_table, const in
                         (size_t)maxseg * kStWaves * sizeof(float2) + (size_t)maxseg * sizeof(int) + (8 + 3 * (size_t)maxseg + 1) * sizeof(int);
     if ((size_t)ml_per_row * sizeof(float2) > (size_t)maxseg * D * sizeof(float) || smem > 80 * 1024) return 0;
     const bool nt = nt_loads_for(B, S, D, E::kBytes);
+    count_launch(kLfScanEqualShares);   // past every "not applicable": one of the launches below runs
 #define MLI_ST_LAUNCH(NJ, NT, TBR, MAXSEG, ...)                                                                         \
     do {                                                                                                                 \
         auto kern = fused_decode_stream_kernel<E, NJ, NT, TBR, MAXSEG, ##__VA_ARGS__>;                                   \

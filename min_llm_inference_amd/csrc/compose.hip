@@ -349,6 +349,8 @@ int mli_paged_prefill(const float* emb_table, const float* wpe, const int* inp, 
     if (emb_table == nullptr || wpe == nullptr || inp == nullptr) return MLI_ERR_BAD_ARG;
     hipStream_t st = mli::as_stream(stream);
     if (elem_bf16 < MLI_ELEM_F32 || elem_bf16 > MLI_ELEM_FP8) return MLI_ERR_BAD_ARG;
+    if (n_new_items > 0)
+        mli::count_launch(elem_bf16 == MLI_ELEM_FP8 || mli::prefill_fuses(emb_dim) ? mli::kLfPrefillFused : mli::kLfPrefillTwoLaunch);
     if (elem_bf16 == MLI_ELEM_FP8)
         return mli::launch_fill_paged_fp8_embed(emb_table, wpe, inp, reinterpret_cast<uint8_t* const*>(page_table),
                                                 new_item_indices, lengths, static_cast<const mli_bf16*>(wk),
@@ -394,6 +396,8 @@ int mli_paged_prefill_window(const float* emb_table, const float* wpe, const int
     hipStream_t st = mli::as_stream(stream);
     if (elem < MLI_ELEM_F32 || elem > MLI_ELEM_FP8) return MLI_ERR_BAD_ARG;
     const mli_bf16 *k16 = static_cast<const mli_bf16*>(wk), *v16 = static_cast<const mli_bf16*>(wv);
+    if (n_new_items > 0)
+        mli::count_launch(elem == MLI_ELEM_FP8 || mli::prefill_fuses(emb_dim) ? mli::kLfPrefillFused : mli::kLfPrefillTwoLaunch);
     if (elem == MLI_ELEM_FP8)
         return mli::launch_fill_paged_fp8_window_embed(emb_table, wpe, inp, reinterpret_cast<uint8_t* const*>(page_table),
                                                        new_item_indices, lengths, k16, v16, n_batch, n_sequence, emb_dim,

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "device_common.hpp"
+#include "launch_count.hpp"
 #include "page_live.hpp"
 
 namespace mli {

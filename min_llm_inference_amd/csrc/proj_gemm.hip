@@ -428,6 +428,14 @@ int gemm_panel_tiles_n(int N);
 template <int MODE, bool BT>
 int launch_gemm_panel(const GemmArgs& g, int rows, hipStream_t st);
 
+// the launch counters beside the kernel's family: the row list a projection or a fill of the tiled kernels runs over
+template <int MODE>
+static void count_gemm_form(const GemmArgs& g) {
+    constexpr bool kFill = MODE == kNaiveFill || MODE == kPagedFill || MODE == kPagedFillLive;
+    if (kFill) count_launch(g.compact ? kLfFillFlat : kLfFillPerRow);
+    else if ((MODE == kPagedLatest || MODE == kNaiveLatest) && g.compact) count_launch(kLfLatestCompact);
+}
+
 // rows = live extent of the M dimension (per z-slice)
 template <int MODE, bool BT>
 static int launch_gemm(const GemmArgs& g, int rows, int z, bool vec4, hipStream_t st) {
@@ -437,11 +445,13 @@ static int launch_gemm(const GemmArgs& g, int rows, int z, bool vec4, hipStream_
         if (z == 1 && gemm_panel_wanted(rows, g.N * g.n_out, g.K, vec4)) return launch_gemm_panel<MODE, BT>(g, rows, st);
     }
     const int tiles_x = ceil_div_i(g.N, BN) * g.n_out;
+    count_gemm_form<MODE>(g);
     // 128-row tiles when they still fill the chip (>= 2 workgroups per CU) -- decode projection / logits of a large
     // batch; the prefill fill keeps 64-row tiles (a new row's prompt rarely fills 128 rows)
     constexpr bool kTallOk = MODE == kPagedLatest || MODE == kNaiveLatest || MODE == kPlain;
     if (kTallOk && vec4 && gemm_use_tall_tiles((int64_t)tiles_x * ceil_div_i(rows, 128) * z)) {
         dim3 grid(tiles_x, ceil_div_i(rows, 128), z);
+        count_launch(kLfGemmF32Rows128);
         hipLaunchKernelGGL((gemm_f32_mfma_kernel<MODE, BT, true, false, 2>), grid, dim3(kGemmThreads), 0, st, g);
         return launch_status();
     }
@@ -452,9 +462,11 @@ static int launch_gemm(const GemmArgs& g, int rows, int z, bool vec4, hipStream_
     // rows 61 -> 52 us, prefill of 128 / 256 / 512 / 4096 prompt tokens 60 -> 49 / 63 -> 52 / 96 -> 86 / 593 -> 588 us,
     // config 4 logits (K = 512) 21.4 -> 19.5 us: never slower
     if (vec4 && g_gemm_split && g.K >= 256) {
+        count_launch(kLfGemmF32Rows64Split);
         hipLaunchKernelGGL((gemm_f32_mfma_kernel<MODE, BT, true, false, 1, true>), grid, dim3(2 * kGemmThreads), 0, st, g);
         return launch_status();
     }
+    count_launch(kLfGemmF32Rows64);
     if (vec4) hipLaunchKernelGGL((gemm_f32_mfma_kernel<MODE, BT, true>), grid, dim3(kGemmThreads), 0, st, g);
     else hipLaunchKernelGGL((gemm_f32_mfma_kernel<MODE, BT, false>), grid, dim3(kGemmThreads), 0, st, g);
     return launch_status();
@@ -574,6 +586,8 @@ int launch_latest_paged_bf16(uint16_t* const* page_table, const int* lengths, co
     g.B = B; g.S = S;
     g.compact = latest_compact(B, D);
     dim3 grid(ceil_div_i(D, BN) * 3, ceil_div_i(B, BM), 1);
+    count_launch(kLfGemmBf16Widened);
+    count_gemm_form<kPagedLatest>(g);
     hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPagedLatest, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
     return launch_status();
 }
@@ -598,6 +612,8 @@ static int fill_paged_bf16(uint16_t* const* page_table, const int* new_idx, cons
     g.B = B; g.S = S;
     g.n_new = n_new; g.compact = fill_compact(n_new);
     dim3 grid(ceil_div_i(D, BN) * 2, ceil_div_i(S, BM), n_new);
+    count_launch(kLfGemmBf16Widened);
+    count_gemm_form<kPagedFill>(g);
     if (!WIN) {
         if (g.compact) grid = dim3(ceil_div_i(D, BN) * 2, ceil_div_i(S * n_new, BM), 1);
         hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPagedFill, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
@@ -706,7 +722,9 @@ int mli_prefill(const float* emb_table, const float* wpe, const int* inp, float*
     if (emb_table == nullptr || wpe == nullptr || inp == nullptr) return MLI_ERR_BAD_ARG;
     // wide models: encoder + fill as two launches (see mli_paged_prefill).  The encoder kernel moves float4, so a width
     // that is no multiple of 4 has the prologue form only (its scalar-load instantiation), whatever "prefill_fused" says
-    if (!mli::prefill_fuses(input_dim) && input_dim % 4 == 0) {
+    const bool two_launches = !mli::prefill_fuses(input_dim) && input_dim % 4 == 0;
+    if (n_new_items > 0) mli::count_launch(two_launches ? mli::kLfPrefillTwoLaunch : mli::kLfPrefillFused);
+    if (two_launches) {
         int rc = mli_inference_optimized_encoder(emb_table, wpe, inp, inp_embedding, lengths, new_item_indices, n_batch,
                                                  n_sequence, input_dim, n_new_items, stream);
         if (rc) return rc;

@@ -658,11 +658,14 @@ int launch_latest_paged_bf16_native(uint16_t* const* page_table, const int* leng
         if (const char* dbg = std::getenv("MLI_DMA_DEBUG")) g.n_new = std::atoi(dbg);
 #endif
         const int col_tiles = D / 64, row_tiles = ceil_div_i(B, kDmM);   // 3 weights x D / 192 columns
+        count_launch(kLfGemmBf16Dma);
         hipLaunchKernelGGL((gemm_bf16_dma_kernel<kPagedLatest>), dim3(col_tiles * row_tiles), dim3(kDmThreads), kDmSmem, st,
                            g, col_tiles, row_tiles);
         return launch_status();
     }
+    if (g.compact) count_launch(kLfLatestCompact);
     if (gemm_use_tall_tiles((int64_t)tiles_x * ceil_div_i(B, 128))) {  // as the fp32 kernel: >= 2 workgroups per CU
+        count_launch(kLfGemmBf16Rows128);
         hipLaunchKernelGGL((gemm_bf16_mfma_kernel<kPagedLatest, 2, 64>), dim3(tiles_x, ceil_div_i(B, 128), 1),
                            dim3(kHThreads), 0, st, g);
         return launch_status();
@@ -670,6 +673,7 @@ int launch_latest_paged_bf16_native(uint16_t* const* page_table, const int* leng
     dim3 grid(tiles_x, ceil_div_i(B, HM), 1);
     // Short reductions are latency-bound (config 4: 16 k-steps of 32, each exposing a global-load round trip that
     // one workgroup per SIMD cannot hide): stage 128 k per tile instead -- 4 round trips.
+    count_launch(D >= 256 && D <= 1024 ? kLfGemmBf16Deep : kLfGemmBf16Rows64);
     if (D >= 256 && D <= 1024)
         hipLaunchKernelGGL((gemm_bf16_mfma_kernel<kPagedLatest, 1, 128>), grid, dim3(kHThreads), 0, st, g);
     else
@@ -697,6 +701,8 @@ static int fill_paged_16bit_embed(const float* emb_table, const float* wpe, cons
     const int flat_rows = WIN ? live_tokens_bound(S, window, n_sink) : S;
     dim3 grid(ceil_div_i(D, HN) * 2, ceil_div_i(S, HM), n_new);
     if (g.compact) grid = dim3(ceil_div_i(D, HN) * 2, ceil_div_i(flat_rows * n_new, HM), 1);
+    count_launch(kLfGemmBf16Fill);
+    count_launch(g.compact ? kLfFillFlat : kLfFillPerRow);
     hipLaunchKernelGGL((gemm_bf16_mfma_kernel<WIN ? kPagedFillLive : kPagedFill, 1, 32, FP8>), grid, dim3(kHThreads), 0, st, g);
     return launch_status();
 }
@@ -729,12 +735,15 @@ int launch_latest_paged_fp8(uint8_t* const* page_table, const int* lengths, cons
     g.B = B; g.S = S;
     g.compact = latest_compact(B, D);
     const int tiles_x = ceil_div_i(D, HN) * 3;
+    if (g.compact) count_launch(kLfLatestCompact);
     if (gemm_use_tall_tiles((int64_t)tiles_x * ceil_div_i(B, 128))) {
+        count_launch(kLfGemmBf16Rows128);
         hipLaunchKernelGGL((gemm_bf16_mfma_kernel<kPagedLatest, 2, 64, true>), dim3(tiles_x, ceil_div_i(B, 128), 1),
                            dim3(kHThreads), 0, st, g);
         return launch_status();
     }
     dim3 grid(tiles_x, ceil_div_i(B, HM), 1);
+    count_launch(D >= 256 && D <= 1024 ? kLfGemmBf16Deep : kLfGemmBf16Rows64);
     if (D >= 256 && D <= 1024)
         hipLaunchKernelGGL((gemm_bf16_mfma_kernel<kPagedLatest, 1, 128, true>), grid, dim3(kHThreads), 0, st, g);
     else

@@ -54,6 +54,7 @@ int launch_gemm_panel(const GemmArgs& g, int rows, hipStream_t st) {
         opted_in.fetch_or(bit, std::memory_order_relaxed);
     }
     const dim3 grid(ceil_div_i(g.N, PN) * g.n_out, ceil_div_i(rows, PM), 1);
+    count_launch(kLfGemmF32Panel);
     hipLaunchKernelGGL((gemm_f32_panel_kernel<MODE, BT>), grid, dim3(kPanelThreads), kPanelSmem, st, g);
     return launch_status();
 }

@@ -4,6 +4,7 @@
 
 #include <type_traits>
 
+#include "launch_count.hpp"
 #include "scan_item_body.hpp"
 #include "scan_plan.hpp"
 

@@ -45,6 +45,20 @@ def _check(rc, what):
         raise MliError(f"Hip Failure: {what} returned {rc}")
 
 
+def launch_count(family):
+    """How many launches of the kernel family (or form) `family` the calling thread has enqueued since its last
+    reset_launch_counts(): mli_launch_count of include/mli_kernels.h, which lists the names."""
+    n = ctypes.c_ulonglong(0)
+    name = family.encode() if isinstance(family, str) else family
+    _check(load_library().mli_launch_count(name, ctypes.byref(n)), f"mli_launch_count({family!r})")
+    return int(n.value)
+
+
+def reset_launch_counts():
+    """Zero the calling thread's launch counters (mli_launch_counts_reset)."""
+    _check(load_library().mli_launch_counts_reset(), "mli_launch_counts_reset")
+
+
 def workspace_for(n_batch, n_sequence, dim, device, n_heads=1):
     """Caller-owned scratch for the split-sequence kernels (grown on demand, never inside a timed region).  n_heads > 1:
     sized for the multi-head scan (mli_attention_heads_workspace_bytes), which covers the single-head calls too."""

@@ -48,6 +48,59 @@ def test_abi_version_and_workspace_query(mli):
     assert mli.mli_attention_workspace_bytes(0, 4096, 512) == 0
 
 
+LAUNCH_FAMILIES = ["gemm_f32_panel", "gemm_f32_rows64", "gemm_f32_rows64_split", "gemm_f32_rows128", "gemm_bf16_widened",
+                   "gemm_bf16_rows64", "gemm_bf16_deep", "gemm_bf16_rows128", "gemm_bf16_dma", "gemm_bf16_fill",
+                   "scan_equal_shares", "scan_chunked", "scan_heads_window", "latest_compact", "fill_flat", "fill_per_row",
+                   "prefill_fused", "prefill_two_launch", "scan_rows_ordered", "scan_rows_grid_order"]
+
+
+def test_launch_counters_know_every_documented_family_and_start_at_zero(mli):
+    """Every name the header lists is known, nothing has been launched in this process (no GPU), and the header lists
+    every name this test knows."""
+    text = open(os.path.join(ROOT, "include", "mli_kernels.h")).read()
+    assert mli.mli_launch_counts_reset() == 0
+    for name in LAUNCH_FAMILIES:
+        assert f'"{name}"' in text, f"include/mli_kernels.h does not document {name}"
+        n = ctypes.c_ulonglong(77)
+        assert mli.mli_launch_count(name.encode(), ctypes.byref(n)) == 0, name
+        assert n.value == 0, name
+
+
+def test_launch_counter_refuses_unknown_names_and_null_pointers(mli):
+    n = ctypes.c_ulonglong(77)
+    for bad in (b"", b"gemm", b"gemm_f32_panel ", b"GEMM_F32_PANEL", b"scan_equal_shares\n", b"x" * 300):
+        assert mli.mli_launch_count(bad, ctypes.byref(n)) == -22, bad   # MLI_ERR_BAD_ARG
+        assert n.value == 77                                              # ... and *count is left untouched
+    assert mli.mli_launch_count(None, ctypes.byref(n)) == -22 and n.value == 77
+    assert mli.mli_launch_count(b"gemm_f32_panel", None) == -22
+    assert mli.mli_launch_count(None, None) == -22
+
+
+def test_launch_counters_are_per_thread_and_reset_is_idempotent(mli):
+    """The reset touches the calling thread's counters and can be called any number of times; a fresh thread reads zeros
+    and its reset succeeds too (what moves a counter needs a launch: tests/test_engine_dispatch_gpu.py)."""
+    import threading
+    from min_llm_inference_amd import ops
+    assert mli.mli_launch_counts_reset() == 0 and mli.mli_launch_counts_reset() == 0
+    assert ops.launch_count("scan_chunked") == 0
+    seen = {}
+
+    def other():
+        ops.reset_launch_counts()
+        seen["n"] = [ops.launch_count(name) for name in LAUNCH_FAMILIES]
+
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert seen["n"] == [0] * len(LAUNCH_FAMILIES)
+    try:
+        ops.launch_count("no_such_family")
+    except ops.MliError as e:
+        assert "-22" in str(e)
+    else:
+        raise AssertionError("ops.launch_count must raise on an unknown family")
+
+
 def test_missing_library_is_a_hard_error(monkeypatch, tmp_path):
     from min_llm_inference_amd import _lib
     monkeypatch.setattr(_lib, "_LIB", None)

@@ -52,7 +52,8 @@ def _kind(variant):
 
 
 def _run(kind_name, model, items, shape, n_blocks, rounds=1, pipelined=False, graphs=False, lean=None, n_heads=1, window=None,
-         sinks=None, sampling=None, quirk=False):
+         sinks=None, sampling=None, quirk=False, after=None):
+    """after: called with the engine once it has run, before it is closed (page statistics and the like)"""
     from min_llm_inference_amd import engine as eng
     kind = getattr(eng, kind_name)
     e = eng.Engine(kind, shape["B"], shape["S"], shape["D"], shape["V"], model["emb_table"], model["pos_table"], model["wk"],
@@ -73,6 +74,8 @@ def _run(kind_name, model, items, shape, n_blocks, rounds=1, pipelined=False, gr
             else:
                 e.add_item(item_id, toks)
         st = e.run()
+        if after is not None:
+            after(e)
         return st, e.finished()
     finally:
         e.close()
