@@ -563,7 +563,7 @@ int mli_f32_to_fp8(const float* src, uint8_t* dst, size_t n, void* stream);
  *                      (Rows wider than 64 16-byte lane loads keep their loads non-temporal and touch the lines of a
  *                      kept page with default-policy loads first.)
  *   "scan_stream"      (lean mode) 1 (default) = batches that fill the chip (n_batch * n_sequence >= 2^21, n_batch <= 2048,
- *                      n_sequence >= 256) are scanned in EQUAL PAGE SHARES: the pages of all rows form one sequence
+ *                      n_sequence >= 1024) are scanned in EQUAL PAGE SHARES: the pages of all rows form one sequence
  *                      that 2 x CUs workgroups split evenly, each streaming its share across row boundaries and merging
  *                      per row like "scan_merge" (attention_stream.hip); 0 = always one workgroup per (row, chunk).
  *                      Same result for the same lengths on every launch; against the chunked form the split points of
