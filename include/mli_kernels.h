@@ -132,6 +132,9 @@ int mli_get_latest_k_q_v_paged(float* const* page_table, const int* lengths,
                                int n_batch, int n_sequence, int emb_dim, void* stream);
 
 /* replaces launch_qkt_paged_attention (paged_attention.h:37-39, paged_attention.cu:270-280). */
+/* mli_qkt_paged[_bf16] and mli_qkt stage the row's q in LDS: emb_dim beyond what 64 KiB hold beside the item's page pointers
+ * (16360 with a small batch; mli_qkt: dim <= 15344) is MLI_ERR_BAD_ARG before anything is launched.
+ * mli_decode_scan_contiguous takes emb_dim <= 13052 for the same reason. */
 int mli_qkt_paged(const float* q_output, const float* const* page_table, const int* lengths,
                   float* qkt_output, int n_batch, int n_sequence, int emb_dim, void* stream);
 
@@ -337,7 +340,15 @@ int mli_decode_scan_contiguous(const float* q_output, const float* kt_cache, con
  * (may be NULL) and the scan merges every row's chunks itself, so 5 = 7 = the whole job in ONE launch (6 = nothing;
  * with mli_tune("scan_merge", 0) the merge stays a second, slimmer launch and 5 / 6 time the two apart).  Rows of up to two 16-byte lane loads (fp32 <= 512,
  * bf16 <= 1024) give every wave whole pages; wider rows (fp32 <= 2048, bf16 <= 4096) are split across the four
- * waves of a workgroup.  Returns MLI_ERR_BAD_ARG beyond that: use the separate entry points then. */
+ * waves of a workgroup; MLI_ELEM_FP8 (lean phases only) takes rows of up to two lane loads (<= 2048).  Returns
+ * MLI_ERR_BAD_ARG beyond that, in every phase, before anything is launched: use the separate entry points then.
+ * n_batch is not bounded by the 16384 arrival counters: with more rows the lean form keeps the merge in a second, slimmer
+ * launch (as under mli_tune("scan_merge", 0)), touches no counter and gives the same bits; the multi-head, window, sink
+ * and grouped entry points refuse n_batch > 16384 instead.  n_sequence is bounded by the LDS the merge statistics are staged
+ * in -- 8 bytes per 64 tokens of n_sequence beside the item's page pointers, within the 64 KiB a launch gets less 512 bytes
+ * for the kernels' static part: n_sequence <= 519936 at items of 64 tokens, 519680 at items of 128 (under a window: 8 bytes
+ * per item of the span, the same figures) -- and is MLI_ERR_BAD_ARG beyond that, in every phase and from the window and sink
+ * entry points alike, before anything is launched. */
 int mli_decode_scan_paged(const float* q_output, const void* const* page_table, const int* lengths,
                           float* qkt_output, float* attention_result, int n_batch, int n_sequence, int emb_dim,
                           int elem_bf16, int phases, void* workspace, size_t workspace_bytes, void* stream);
@@ -567,7 +578,16 @@ int mli_f32_to_fp8(const float* src, uint8_t* dst, size_t n, void* stream);
  *                      that 2 x CUs workgroups split evenly, each streaming its share across row boundaries and merging
  *                      per row like "scan_merge" (attention_stream.hip); 0 = always one workgroup per (row, chunk).
  *                      Same result for the same lengths on every launch; against the chunked form the split points of
- *                      a row differ, i.e. the fp32 rounding of the merge (<= 1e-5 on attention_result)
+ *                      a row differ, i.e. the fp32 rounding of the merge (<= 1e-5 on attention_result).
+ *                      The chunked scan runs instead, silently and with the same contract ("scan_chunked" counts, not
+ *                      "scan_equal_shares"), wherever one of these holds: n_batch > 2048; n_sequence < 1024; n_batch *
+ *                      n_sequence below "scan_stream_min_tokens"; rows of more than two 16-byte lane loads; a row's
+ *                      n_sequence / 64 statistics pairs larger than the kernel's q buffer (8 * ceil(n_sequence / 64) >
+ *                      MAXSEG * emb_dim * 4 with MAXSEG = 4, or 2 for bf16 / fp8 rows of 1024 columns: fp32 emb_dim 64
+ *                      stops at n_sequence 8192); or more than 80 KiB of LDS per workgroup, which grows with n_batch and
+ *                      with n_batch * n_sequence / CUs (2048 rows of emb_dim 512 on 256 CUs: n_sequence 14336 is taken
+ *                      with 76.25 KiB, 16384 would need 80.25 KiB).  From 64 KiB on the launcher raises the kernel's
+ *                      dynamic-LDS limit first.
  *   "scan_stream_min_tokens"  the n_batch * n_sequence threshold of "scan_stream" (tests lower it)
  *   "scan_stream_dynamic_pct" / "scan_stream_granule"  the last x per cent (default 4, at most 12; 0 = none) of the page
  *                      sequence are not part of the equal shares but handed out by a ticket counter in granules of that

@@ -104,6 +104,7 @@ static int launch_fused_decode(const float* q, const void* const* page_table, co
     if (!(lean && g_scan_merge && B <= kMaxArrivalRows)) w.arrivals = nullptr;
     const int ml_per_row = ceil_div_i(S, 64);
     const size_t smem = scan_lds_bytes(p.ct, plain_reduction_bytes(v, E::EPL), plain_merge_stat_bytes(S));
+    if (!scan_lds_fits(smem)) return 0;   // rows too long for the statistics' LDS: not applicable, nothing launched
     const auto launch = [&](auto scores) {  // SCORES: the materialising form
         // TBR = rows per load batch: TBR * RPI = 8 token slots for rows of one lane load, 4 for rows of two
         dispatch_scan_variant<E>(v, p.nt, [&](auto NJ, auto DS, auto RPI, auto NT) {

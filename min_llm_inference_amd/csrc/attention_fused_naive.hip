@@ -212,7 +212,7 @@ int launch_fused_decode_naive(const float* q, const float* kt, const float* v, c
     const int nj = (D >> 2) <= kWave ? 1 : 2;
     const size_t smem = sizeof(float4) * kNvWaves * kWave + sizeof(float4) * kNvWaves * kWave * nj + sizeof(float) * kNvChunk +
                         sizeof(float) * (size_t)D;
-    if (smem > 64 * 1024) return 0;
+    if (smem + 16 > 64 * 1024) return 0;   // static and dynamic LDS together: chunk_ml and last_sh are 12 bytes (emb_dim <= 13052)
     const dim3 grid(B, nchunk);
     const bool nt = nt_loads_for(B, S, D, 4);
 #define MLI_NV_LAUNCH(NJ, NT)                                                                                          \

@@ -63,6 +63,7 @@ static int launch_heads_scan_t(const float* q, const void* const* page_table, co
     if (!carve_scan_ws(p, ws, ws_bytes, &w)) return MLI_ERR_WORKSPACE;
     // page pointers of the item | the waves' parked rows and statistics, later the row's (item, head) statistics
     const size_t smem = scan_lds_bytes(p.ct, heads_reduction_bytes(nj, E::EPL), heads_merge_stat_bytes(p.nchunk, H));
+    if (!scan_lds_fits(smem)) return MLI_ERR_BAD_ARG;   // (kMaxMergeStats keeps every accepted shape far inside)
     count_launch(kLfScanHeadsWindow);
     dispatch_scan_variant<E>(ScanVariant{nj, false, 1}, p.nt, [&](auto NJ, auto, auto, auto NT) {
         hipLaunchKernelGGL((heads_decode_scan_kernel<E, NJ(), NT(), WIN, SINK, GQA>), dim3(B, p.grid_y), dim3(kFuThreads), smem,

@@ -535,6 +535,7 @@ int launch_qkt_paged_stats(const float* q, const float* const* page_table, const
     if (S % kPage != 0 || D % 4 != 0 || B <= 0) return MLI_ERR_BAD_ARG;
     const int ct = pick_chunk_tokens(B, S);
     const size_t smem = (size_t)D * 4 + (size_t)(ct / kPage) * 8;
+    if (smem + 64 > 64 * 1024) return MLI_ERR_BAD_ARG;   // q is staged in LDS (static part: 32 bytes): emb_dim up to ~16 K
     dim3 grid(B, ceil_div_i(S, ct));
 #define MLI_QKT_LAUNCH(NT) \
     hipLaunchKernelGGL((qkt_paged_kernel<NT>), grid, dim3(kScanThreads), smem, st, q, page_table, lengths, qkt, S, D, ct, stats)
@@ -552,6 +553,7 @@ int launch_qkt_paged(const float* q, const float* const* page_table, const int* 
 int launch_qkt_naive_stats(const float* q, const float* kt, const int* lengths, float* qkt, int B, int S, int D,
                            SoftmaxStats stats, hipStream_t st) {
     if (S % 4 != 0 || B <= 0) return MLI_ERR_BAD_ARG;
+    if (sizeof(float4) * kScanWaves * kWave + (size_t)D * 4 + 64 > 64 * 1024) return MLI_ERR_BAD_ARG;   // q is staged in LDS: dim <= 15344
     hipLaunchKernelGGL(qkt_naive_kernel, dim3(B, ceil_div_i(S, 256)), dim3(kScanThreads),
                        sizeof(float4) * kScanWaves * kWave + (size_t)D * 4, st, q, kt, lengths, qkt, S, D, stats);
     return launch_status();

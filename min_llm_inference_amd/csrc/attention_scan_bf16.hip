@@ -263,6 +263,7 @@ static int launch_qkt_paged_bf16_stats(const float* q, const uint16_t* const* pa
     if (S % kPage != 0 || D % 8 != 0 || B <= 0) return MLI_ERR_BAD_ARG;
     const int ct = chunk_tokens_for(B, S);
     const size_t smem = (size_t)D * 4 + (size_t)(ct / kPage) * 8;
+    if (smem + 64 > 64 * 1024) return MLI_ERR_BAD_ARG;   // q is staged in LDS (static part: 32 bytes): emb_dim up to ~16 K
     dim3 grid(B, ceil_div_i(S, ct));
     if (nt_loads_for(B, S, D, 2))
         hipLaunchKernelGGL((qkt_paged_bf16_kernel<8, true>), grid, dim3(kBfThreads), smem, st, q, page_table, lengths, qkt, S, D, ct, stats);

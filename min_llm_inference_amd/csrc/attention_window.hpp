@@ -57,6 +57,7 @@ static int launch_window_decode_t(const float* q, const void* const* page_table,
     ScanWs w;
     if (!carve_scan_ws(p, ws, ws_bytes, &w)) return MLI_ERR_WORKSPACE;
     const size_t smem = scan_lds_bytes(p.ct, plain_reduction_bytes(v, E::EPL), window_merge_stat_bytes(p.nchunk));
+    if (!scan_lds_fits(smem)) return MLI_ERR_BAD_ARG;   // a span of more items than the statistics' LDS holds: nothing launched
     count_launch(kLfScanHeadsWindow);
     dispatch_scan_variant<E>(v, p.nt, [&](auto NJ, auto DS, auto RPI, auto NT) {
         hipLaunchKernelGGL((window_decode_scan_kernel<E, NJ(), NT(), (NJ() == 1 ? 8 : 4) / RPI(), DS(), RPI(), SINK>),

@@ -168,6 +168,13 @@ inline ScanVariant plain_scan_variant(int D, int epl) {
 inline size_t scan_lds_bytes(int ct, size_t reduction_bytes, size_t merge_stat_bytes) {
     return (size_t)(ct / kPlanPage) * 8 + (reduction_bytes > merge_stat_bytes ? reduction_bytes : merge_stat_bytes);
 }
+// What a launch gets without raising the kernel's dynamic-LDS limit: 64 KiB for static and dynamic LDS together.  The scan
+// kernels' static part (wave statistics, the row-order histogram, a flag) is 312 bytes at most; 512 are set aside.  A plan
+// beyond it is refused before anything is launched: the merge statistics grow with n_sequence (single head: 8 bytes per 64
+// tokens, i.e. n_sequence 519936 at items of 64; under a window: 8 bytes per item of the span).
+constexpr size_t kLaunchLdsLimit = 64 * 1024;
+constexpr size_t kScanStaticLds = 512;
+inline bool scan_lds_fits(size_t dynamic_bytes) { return dynamic_bytes + kScanStaticLds <= kLaunchLdsLimit; }
 // single head: the waves' partial output rows, or with the D-split two buffers of the 16 partial scores of a page
 inline size_t plain_reduction_bytes(const ScanVariant& v, int epl) {
     return (v.ds ? (size_t)2 * kPlanWaves * 16 : (size_t)kPlanWaves * v.nj * (kPlanWave / v.rpi) * epl) * sizeof(float);
