@@ -126,6 +126,29 @@ int mli_engine_set_logprobs(mli_engine* engine, int n_top);
 int mli_engine_get_finished_logprobs(mli_engine* engine, int index, int* n_prompt, float* token_logprobs, int capacity,
                                      int* n_generated, int* top_ids, float* top_logprobs, int top_capacity);
 
+/* EXTENSION: PROMPT log-probabilities (mli_kernels.h: mli_paged_prompt_logprobs).  Beside the figures of the
+ * tokens it generates, the engine reports for every prompt token but the first the natural-log probability the model gives
+ * it after the tokens before it, and the n_top alternatives at that position -- the figures mli_engine_set_logprobs defines,
+ * for a token that was GIVEN: scoring and perplexity, ranking of continuations, "echo".  The new rows' prompts are scored in
+ * the forward that prefills them, directly behind the prefill and on the same stream, in passes of at most n_batch positions
+ * (a longer prompt continues in the next pass).  An item is scored at its first admission only: a preempted and re-admitted
+ * item keeps its figures and is not scored again, and "prompt" means the tokens it was queued with.  Tokens and
+ * generated-token figures are bit-identical to the same engine without the switch, in both loops, with several rounds, step
+ * graphs and sampling; a forward with new rows waits for its figures to reach the host, every other forward is untouched.
+ * Call before the first step or run and after mli_engine_set_logprobs, which supplies n_top.  -1 with a message for a null
+ * or started engine, an engine without logprobs, MLI_ENGINE_CONTIGUOUS and MLI_ENGINE_PAGED_FP8, an engine with page release
+ * (its prefill skips dead pages, so the prompt's K / V are not all there; mli_engine_set_page_release afterwards is refused
+ * likewise), or a shape the prompt scan does not take (rows of more than two 16-byte lane loads: emb_dim > 512 fp32 / 1024
+ * bf16). */
+int mli_engine_set_prompt_logprobs(mli_engine* engine, int enabled);
+
+/* The prompt figures of finished item `index` (the index of mli_engine_get_finished): entry i belongs to prompt token i + 1,
+ * and *n_scored == n_prompt - 1 always (a one-token prompt has none).  Up to `capacity` entries of token_logprobs and up to
+ * `top_capacity` entries of top_ids / top_logprobs ([n_scored, n_top] row-major) are written; any of the three may be NULL.
+ * -1 on an engine without prompt log-probabilities. */
+int mli_engine_get_finished_prompt_logprobs(mli_engine* engine, int index, float* token_logprobs, int capacity, int* n_scored,
+                                            int* top_ids, float* top_logprobs, int top_capacity);
+
 /* The DEFAULT of engines created afterwards (every engine keeps its own value, see mli_engine_configure; two engines in one
  * process never change each other's composition): 1 (default) = the models' layers run the lean compositions (prefill with the encoder as the fill GEMM's
  * prologue, attention without materialised scores / probabilities, decoder head with the argmax as the logits GEMM's

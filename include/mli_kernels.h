@@ -476,6 +476,59 @@ int mli_paged_decoder_sampled_logprobs(const float* batch_result, const float* e
                                        float* token_logprob, int* top_ids, float* top_logprobs, int n_top,
                                        void* scratch, size_t scratch_bytes, void* stream);
 
+/* EXTENSION: PROMPT log-probabilities.  The decode path computes attention and logits for a row's last
+ * position only; these entry points compute them for the positions of a prompt, from the pages a prefill has written.
+ * SEGMENTS name the positions: segment i is (seg_row[i], seg_first[i], seg_count[i], seg_offset[i]) -- its query j is position
+ * t = seg_first + j of batch row seg_row, 0 <= t < n_sequence, and lives in row seg_offset + j of the dense arrays (q, out,
+ * token_logprob, top_*: n_q or n_positions rows).  The four arrays are device arrays of n_seg ints; n_seg and max_count (>= every
+ * seg_count, <= n_sequence) are host integers, so every grid is known without a read-back.  A row may have several segments (a
+ * prompt longer than one pass continues with seg_first > 0), segments may come in any order; two segments that share an offset
+ * race.  A segment that does not lie inside (n_batch, n_sequence, the dense arrays) is skipped whole, a null page reads as
+ * zeros or gathers nothing: nothing faults on any device value.  A dense row that belongs to no query is never written.
+ *
+ * mli_prompt_scan_paged -- the causal multi-query paged scan: query t attends slot s of its row iff s <= t and (no window, or
+ *   s > t - window, or s < n_sink), one softmax per head over q_h . K_h / sqrtf(head_dim), query head h on K/V head
+ *   h / (n_heads / n_kv_heads): what mli_decode_scan_paged[_heads / _window / _sinks / _gqa] compute for a row of length t + 1
+ *   (fp32 rounding apart).  window <= 0 or >= n_sequence: none; n_sink without a window, or n_sink + window >= n_sequence: none.
+ *   One launch ("scan_prompt"), no workspace: a workgroup streams the pages a block of mli_prompt_scan_tq consecutive queries
+ *   attends once and shares every K / V load among them; no byte of a slot a query does not attend is multiplied, and the
+ *   table entries of the pages between the sinks and a block's window are never read.  Shapes: fp32 / bf16 pages with rows of
+ *   at most two 16-byte lane loads -- one head: MLI_ELEM_F32 to emb_dim 512, MLI_ELEM_BF16 to 1024; several heads and grouped
+ *   K/V heads: what mli_decode_scan_paged_heads / _gqa take; n_batch <= 16384.  MLI_ERR_BAD_ARG before any launch: every
+ *   other shape, MLI_ELEM_FP8, n_seg < 0, window < 0, n_sink < 0, and with n_seg > 0 a null pointer, max_count outside
+ *   1 .. n_sequence or n_q < 1.  n_seg == 0 is a no-op returning 0.
+ * mli_prompt_scan_tq -- the queries per workgroup of the variant (emb_dim, n_heads > 1, elem) runs: 8, 4 or 2 (tests place
+ *   their segment edges by it); MLI_ERR_BAD_ARG for a row the scan does not take.
+ * mli_prompt_project_q -- q[i] = x(row, pos) . Wq for every position of the segments: x from segment 0 of the pages, gathered
+ *   into `gathered` (n_q * emb_dim page elements, 16-byte aligned) and multiplied by one MFMA GEMM launch; fp32 x and Wq on
+ *   fp32 pages, bf16 x and Wq with fp32 accumulation on bf16 pages, q fp32: the decode projection's weights and rounding.
+ * mli_score_tokens_logprobs -- the figures of mli_sample_tokens_logprobs (raw distribution, finite candidates, the same
+ *   summation order, n_top <= MLI_MAX_TOP_LOGPROBS alternatives ordered by (logit, index)) for the token targets[i] it is
+ *   GIVEN.  A target outside [0, n_vocab) reports -inf for the token and the alternatives all the same.  Where the target is
+ *   the token mli_sample_tokens_logprobs emits, token_logprob has the same bits.  n == 0 is a no-op; the refusals are that
+ *   entry point's.
+ * mli_paged_prompt_logprobs -- projection, scan, logits (attention . emb_table^T) and scoring for one list of segments; the
+ *   target of position t of row b is inp[b, t + 1] (inp [n_batch, n_sequence] token ids; -1, hence -inf, at the last position).
+ *   The segments' offsets tile [0, n_positions).  scratch: mli_prompt_logprobs_scratch_bytes (0 for a non-positive argument);
+ *   null or too small is MLI_ERR_WORKSPACE, no byte beyond that size is written.  Refusals: the scan's and the scoring's. */
+int mli_prompt_scan_tq(int emb_dim, int n_heads, int elem);
+int mli_prompt_scan_paged(const float* q, const void* const* page_table, const int* seg_row, const int* seg_first,
+                          const int* seg_count, const int* seg_offset, float* out, int n_seg, int max_count, int n_q,
+                          int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads, int window, int n_sink, int elem,
+                          void* stream);
+int mli_prompt_project_q(const void* const* page_table, const int* seg_row, const int* seg_first, const int* seg_count,
+                         const int* seg_offset, const void* wq, void* gathered, float* q, int n_seg, int max_count, int n_q,
+                         int n_batch, int n_sequence, int emb_dim, int elem, void* stream);
+int mli_score_tokens_logprobs(const float* logits, const int* targets, float* token_logprob, int* top_ids,
+                              float* top_logprobs, int n, int n_vocab, int n_top, void* stream);
+size_t mli_prompt_logprobs_scratch_bytes(int n_positions, int emb_dim, int n_vocab);
+int mli_paged_prompt_logprobs(const void* const* page_table, const int* inp, const void* wq, const float* emb_table,
+                              const int* seg_row, const int* seg_first, const int* seg_count, const int* seg_offset,
+                              float* token_logprob, int* top_ids, float* top_logprobs, int n_seg, int max_count,
+                              int n_positions, int n_batch, int n_sequence, int emb_dim, int n_vocab, int n_heads,
+                              int n_kv_heads, int window, int n_sink, int elem, int n_top, void* scratch, size_t scratch_bytes,
+                              void* stream);
+
 /* PREFILL of the newly inserted rows in ONE launch: the encoder as the fill GEMM's prologue.  The A
  * tile rows are computed on the fly as emb_table[inp[b, s]] + wpe[s] -- nothing is read back from the input-embedding
  * segment -- multiplied by [Wk | Wv], and the workgroups of the first column tile also write those rows to segment 0
@@ -647,6 +700,7 @@ int mli_tune(const char* key, int value);
  *   "scan_equal_shares"      the equal-page-shares scan ("scan_stream")
  *   "scan_chunked"           the single-head chunked scan, lean or materialising, every grid form
  *   "scan_heads_window"      the scans with several heads, a window, sinks or grouped K/V heads
+ *   "scan_prompt"            the causal multi-query scan over prompt positions (mli_prompt_scan_paged)
  * Forms, counted beside the launch's kernel family:
  *   "latest_compact"         a decode projection over the compacted list of non-empty rows ("latest_compact"; the panel and
  *                            the LDS-DMA kernel have no such list)

@@ -87,6 +87,12 @@ SIGNATURES = {
     "mli_sample_tokens_logprobs": [_P] * 10 + [_I] * 3 + [_P, _Z, _P],
     "mli_decoder_sampled_logprobs": [_P] * 6 + [_I] * 6 + [_P] * 7 + [_I] + [_P, _Z, _P],
     "mli_paged_decoder_sampled_logprobs": [_P] * 6 + [_I] * 7 + [_P] * 7 + [_I] + [_P, _Z, _P],
+    "mli_prompt_scan_tq": [_I, _I, _I],
+    "mli_prompt_scan_paged": [_P] * 7 + [_I] * 11 + [_P],
+    "mli_prompt_project_q": [_P] * 8 + [_I] * 7 + [_P],
+    "mli_score_tokens_logprobs": [_P] * 5 + [_I] * 3 + [_P],
+    "mli_prompt_logprobs_scratch_bytes": [_I, _I, _I],
+    "mli_paged_prompt_logprobs": [_P] * 11 + [_I] * 13 + [_P, _Z, _P],
     "mli_paged_prefill": [_P] * 8 + [_I] * 5 + [_P],
     "mli_paged_prefill_window": [_P] * 8 + [_I] * 7 + [_P],
     "mli_prefill": [_P] * 10 + [_I] * 5 + [_P],
@@ -145,6 +151,8 @@ ENGINE_SIGNATURES = {
     "mli_engine_get_finished": [_P, _I, _IP, _P, _I, _IP],
     "mli_engine_set_logprobs": [_P, _I],
     "mli_engine_get_finished_logprobs": [_P, _I, _IP, _P, _I, _IP, _P, _P, _I],
+    "mli_engine_set_prompt_logprobs": [_P, _I],
+    "mli_engine_get_finished_prompt_logprobs": [_P, _I, _P, _I, _IP, _P, _P, _I],
     "mli_engine_configure": [_P, _I, _I],
     "mli_engine_set_heads": [_P, _I],
     "mli_engine_set_window": [_P, _I],
@@ -177,7 +185,7 @@ class ShardStats(ctypes.Structure):
 
 _RESTYPES = {"mli_shard_last_error": ctypes.c_char_p, "mli_shard_group_destroy": None, "mli_shard_group_engine": _P,
              "mli_attention_workspace_bytes": _Z, "mli_attention_heads_workspace_bytes": _Z,
-             "mli_decoder_scratch_bytes": _Z,
+             "mli_decoder_scratch_bytes": _Z, "mli_prompt_logprobs_scratch_bytes": _Z,
              "mli_sample_scratch_bytes": _Z, "mli_decoder_sampled_scratch_bytes": _Z, "mli_engine_last_error": ctypes.c_char_p,
              "mli_engine_destroy": None, "mli_engine_set_lean_layers": None,
              "mli_engine_set_step_graphs": None}

@@ -1,0 +1,7 @@
+// The causal multi-query prompt scan over bf16 pages: attention_prompt.hpp has the kernel, the launcher and the account.
+#include "attention_prompt.hpp"
+
+namespace mli {
+template int launch_prompt_scan<ElemBF16>(const float*, const void* const*, const int*, const int*, const int*, const int*, float*,
+                                          int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
+}

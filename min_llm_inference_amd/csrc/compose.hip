@@ -165,9 +165,99 @@ static int gqa_front(int B, int S, int D, int n_heads, int n_kv_heads, int windo
     if ((elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) || n_sink < 0 || S < 1) return MLI_ERR_BAD_ARG;
     return lean_scan_args(B, S, D, n_heads, n_kv_heads, window, n_sink, elem);
 }
+// ---- prompt log-probabilities (attention_prompt.hpp) ----------------------------------------------------------------------------
+int launch_prompt_project_q(int, const void* const*, const int*, const int*, const int*, const int*, const void*, void*, float*,
+                            int, int, int, int, int, int, hipStream_t);   // proj_gemm.hip
+int launch_prompt_scan_elem(const float*, const void* const*, const int*, const int*, const int*, const int*, float*, int, int,
+                            int, int, int, int, int, int, int, int, int, hipStream_t);   // attention_prompt.hip
+int launch_gemm_nt(const float*, const float*, float*, int, int, int, hipStream_t);
+
+// the token that FOLLOWS every scored position: targets[offset + j] = inp[row, first + j + 1], -1 beyond the sequence
+__global__ __launch_bounds__(256) void prompt_targets_kernel(const int* __restrict__ inp, const int* __restrict__ seg_row,
+                                                             const int* __restrict__ seg_first, const int* __restrict__ seg_count,
+                                                             const int* __restrict__ seg_offset, int* __restrict__ targets,
+                                                             int n_seg, int max_count, int n_q, int B, int S) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_seg * max_count) return;
+    const int seg = i / max_count, j = i % max_count;
+    const int cnt = seg_count[seg];
+    if (j >= cnt) return;
+    const int b = seg_row[seg], first = seg_first[seg], off = seg_offset[seg];
+    if (b < 0 || b >= B || first < 0 || (int64_t)first + cnt > S || off < 0 || (int64_t)off + cnt > n_q) return;
+    const int s = first + j + 1;
+    targets[off + j] = s < S ? inp[(int64_t)b * S + s] : -1;
+}
+
+// scratch of mli_paged_prompt_logprobs: gathered x | q | attention | logits | targets, each region 256-byte aligned
+struct PromptScratch {
+    size_t gathered, q, attn, logits, targets, total;
+};
+static PromptScratch prompt_scratch(int n, int D, int V) {
+    const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    PromptScratch p;
+    const size_t row = up((size_t)n * D * sizeof(float));
+    p.gathered = 0;
+    p.q = row;
+    p.attn = 2 * row;
+    p.logits = 3 * row;
+    p.targets = p.logits + up((size_t)n * V * sizeof(float));
+    p.total = p.targets + up((size_t)n * sizeof(int));
+    return p;
+}
+
 }  // namespace mli
 
 extern "C" {
+
+size_t mli_prompt_logprobs_scratch_bytes(int n_positions, int emb_dim, int n_vocab) {
+    if (n_positions <= 0 || emb_dim <= 0 || n_vocab <= 0) return 0;
+    return mli::prompt_scratch(n_positions, emb_dim, n_vocab).total;
+}
+
+int mli_prompt_project_q(const void* const* page_table, const int* seg_row, const int* seg_first, const int* seg_count,
+                         const int* seg_offset, const void* wq, void* gathered, float* q, int n_seg, int max_count, int n_q,
+                         int n_batch, int n_sequence, int emb_dim, int elem, void* stream) {
+    return mli::launch_prompt_project_q(elem, page_table, seg_row, seg_first, seg_count, seg_offset, wq, gathered, q, n_seg,
+                                        max_count, n_q, n_batch, n_sequence, emb_dim, mli::as_stream(stream));
+}
+
+int mli_paged_prompt_logprobs(const void* const* page_table, const int* inp, const void* wq, const float* emb_table,
+                              const int* seg_row, const int* seg_first, const int* seg_count, const int* seg_offset,
+                              float* token_logprob, int* top_ids, float* top_logprobs, int n_seg, int max_count,
+                              int n_positions, int n_batch, int n_sequence, int emb_dim, int n_vocab, int n_heads,
+                              int n_kv_heads, int window, int n_sink, int elem, int n_top, void* scratch, size_t scratch_bytes,
+                              void* stream) {
+    if (n_top < 0 || n_top > MLI_MAX_TOP_LOGPROBS || token_logprob == nullptr ||
+        (n_top > 0 && (top_ids == nullptr || top_logprobs == nullptr)))
+        return MLI_ERR_BAD_ARG;
+    if (n_seg < 0 || window < 0 || n_sink < 0 || n_vocab <= 0 ||
+        !mli::prompt_scan_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, elem))
+        return MLI_ERR_BAD_ARG;
+    if (n_seg == 0) return 0;
+    if (max_count < 1 || max_count > n_sequence || n_positions < 1 || inp == nullptr || wq == nullptr || emb_table == nullptr)
+        return MLI_ERR_BAD_ARG;
+    const mli::PromptScratch p = mli::prompt_scratch(n_positions, emb_dim, n_vocab);
+    if (scratch == nullptr || scratch_bytes < p.total) return MLI_ERR_WORKSPACE;
+    hipStream_t st = mli::as_stream(stream);
+    char* base = static_cast<char*>(scratch);
+    float* q = reinterpret_cast<float*>(base + p.q);
+    float* attn = reinterpret_cast<float*>(base + p.attn);
+    float* logits = reinterpret_cast<float*>(base + p.logits);
+    int* targets = reinterpret_cast<int*>(base + p.targets);
+    int rc = mli::launch_prompt_project_q(elem, page_table, seg_row, seg_first, seg_count, seg_offset, wq, base + p.gathered, q,
+                                          n_seg, max_count, n_positions, n_batch, n_sequence, emb_dim, st);
+    if (rc) return rc;
+    rc = mli::launch_prompt_scan_elem(q, page_table, seg_row, seg_first, seg_count, seg_offset, attn, n_seg, max_count,
+                                      n_positions, n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, elem, st);
+    if (rc) return rc;
+    rc = mli::launch_gemm_nt(attn, emb_table, logits, n_positions, n_vocab, emb_dim, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mli::prompt_targets_kernel, dim3(mli::ceil_div_i(n_seg * max_count, 256)), dim3(256), 0, st, inp, seg_row,
+                       seg_first, seg_count, seg_offset, targets, n_seg, max_count, n_positions, n_batch, n_sequence);
+    rc = mli::launch_status();
+    if (rc) return rc;
+    return mli_score_tokens_logprobs(logits, targets, token_logprob, top_ids, top_logprobs, n_positions, n_vocab, n_top, stream);
+}
 
 int mli_abi_version(void) { return 4; }
 

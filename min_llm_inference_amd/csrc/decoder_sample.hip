@@ -407,6 +407,26 @@ __global__ __launch_bounds__(kThreads) void decoder_sample_kernel(
     for (int i = threadIdx.x; i < (D >> 2); i += kThreads) store_sum4<ELEM>(dst, i, e[i], p[i]);
 }
 
+// The figures of mli_sample_tokens_logprobs for a token the caller GIVES (prompt log-probabilities): row_logprobs on the
+// row staged as sample_row stages it, so a target that is the token the head emits reports the same bits.  A target outside
+// [0, V) reports -inf for the token and the alternatives all the same.
+__global__ __launch_bounds__(kThreads) void score_tokens_kernel(const float* __restrict__ logits, const int* __restrict__ targets,
+                                                                int V, const LogprobOut<true> out) {
+    extern __shared__ float stage[];
+    __shared__ SampleShared sh;
+    const int b = blockIdx.x;
+    const float* x = logits + (int64_t)b * V;
+    if (V <= kStageMax) {
+        for (int v = threadIdx.x; v < V; v += kThreads) stage[v] = x[v];
+        __syncthreads();
+        x = stage;
+    }
+    const int target = targets[b];
+    const bool known = target >= 0 && target < V;
+    row_logprobs(x, V, known ? target : 0, out, b, sh);
+    if (!known && threadIdx.x == 0) out.token_logprob[b] = -INFINITY;   // (the same thread wrote the stand-in's figure)
+}
+
 size_t stage_bytes(int V) { return V <= kStageMax ? (size_t)V * sizeof(float) : 0; }
 
 }  // namespace
@@ -449,6 +469,17 @@ int mli_sample_tokens_logprobs(const float* logits, const float* temperature, co
     hipLaunchKernelGGL(mli::sample_tokens_kernel<true>, dim3(n_batch), dim3(mli::kThreads), mli::stage_bytes(n_vocab),
                        mli::as_stream(stream), logits, temperature, top_k, top_p, seed, lengths, tokens, n_vocab,
                        mli::LogprobOut<true>{token_logprob, top_ids, top_logprobs, n_top});
+    return mli::launch_status();
+}
+
+int mli_score_tokens_logprobs(const float* logits, const int* targets, float* token_logprob, int* top_ids,
+                              float* top_logprobs, int n, int n_vocab, int n_top, void* stream) {
+    if (!logprob_args_ok(token_logprob, top_ids, top_logprobs, n_top)) return MLI_ERR_BAD_ARG;
+    if (n < 0 || n_vocab <= 0) return MLI_ERR_BAD_ARG;
+    if (n == 0) return 0;
+    if (logits == nullptr || targets == nullptr) return MLI_ERR_BAD_ARG;
+    hipLaunchKernelGGL(mli::score_tokens_kernel, dim3(n), dim3(mli::kThreads), mli::stage_bytes(n_vocab), mli::as_stream(stream),
+                       logits, targets, n_vocab, mli::LogprobOut<true>{token_logprob, top_ids, top_logprobs, n_top});
     return mli::launch_status();
 }
 

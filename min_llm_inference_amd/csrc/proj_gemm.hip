@@ -646,6 +646,66 @@ int launch_gemm_nt(const float* A, const float* Bt, float* C, int M, int N, int 
     return launch_gemm<kPlain, true>(g, M, 1, vec4, st);
 }
 
+// Q for prompt positions (attention_prompt.hpp): q[i] = x(row, pos) . Wq for the positions of a list of segments, i =
+// seg_offset + j for position seg_first + j of row seg_row.  A gather of the x rows (segment 0 of the pages, where the prefill
+// has just written them) into `gathered` ([n_q, D] page elements), then the plain product of this file's template over it: fp32 x
+// and Wq, or (BF16) bf16 x and Wq widened to fp32 while they are staged -- the exact k-ordered fp32 MFMA chain either way.
+// A position outside its row's pages or the q array gathers nothing; its q row is then whatever `gathered` held.
+template <int EB>   // bytes per page element
+__global__ __launch_bounds__(256) void prompt_gather_x_kernel(const void* const* __restrict__ page_table,
+                                                              const int* __restrict__ seg_row, const int* __restrict__ seg_first,
+                                                              const int* __restrict__ seg_count, const int* __restrict__ seg_offset,
+                                                              void* __restrict__ gathered, int n_q, int B, int S, int D) {
+    const int seg = blockIdx.y, j = blockIdx.x;
+    const int cnt = seg_count[seg];
+    if (j >= cnt) return;
+    const int b = seg_row[seg], first = seg_first[seg], off = seg_offset[seg];
+    if (b < 0 || b >= B || first < 0 || (int64_t)first + cnt > S || off < 0 || (int64_t)off + cnt > n_q) return;
+    const int s = first + j;
+    const char* page = static_cast<const char*>(page_table[(int64_t)b * (S / kPage) + s / kPage]);
+    if (page == nullptr) return;
+    const uint2* src = reinterpret_cast<const uint2*>(page + page_row_offset(s, D, kSegInp) * EB);   // D * EB % 8 == 0
+    uint2* dst = reinterpret_cast<uint2*>(static_cast<char*>(gathered) + ((int64_t)off + j) * D * EB);
+    for (int i = threadIdx.x; i < D * EB / 8; i += 256) dst[i] = src[i];
+}
+
+int launch_prompt_project_q(int elem, const void* const* page_table, const int* seg_row, const int* seg_first,
+                            const int* seg_count, const int* seg_offset, const void* wq, void* gathered, float* q, int n_seg,
+                            int max_count, int n_q, int B, int S, int D, hipStream_t st) {
+    if ((elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) || n_seg < 0 || B <= 0 || S <= 0 || S % kPage != 0 || D <= 0 ||
+        D % (elem == MLI_ELEM_BF16 ? 8 : 4) != 0)
+        return MLI_ERR_BAD_ARG;
+    if (n_seg == 0) return 0;
+    if (max_count < 1 || max_count > S || n_q < 1 || n_seg > 65535) return MLI_ERR_BAD_ARG;
+    if (page_table == nullptr || seg_row == nullptr || seg_first == nullptr || seg_count == nullptr || seg_offset == nullptr ||
+        wq == nullptr || gathered == nullptr || q == nullptr || !aligned16(wq) || !aligned16(gathered))
+        return MLI_ERR_BAD_ARG;
+    const bool bf16 = elem == MLI_ELEM_BF16;
+    if (bf16)
+        hipLaunchKernelGGL(prompt_gather_x_kernel<2>, dim3(max_count, n_seg), dim3(256), 0, st, page_table, seg_row, seg_first,
+                           seg_count, seg_offset, gathered, n_q, B, S, D);
+    else
+        hipLaunchKernelGGL(prompt_gather_x_kernel<4>, dim3(max_count, n_seg), dim3(256), 0, st, page_table, seg_row, seg_first,
+                           seg_count, seg_offset, gathered, n_q, B, S, D);
+    int rc = launch_status();
+    if (rc) return rc;
+    GemmArgs g{};
+    g.w[0] = static_cast<const float*>(wq); g.n_out = 1; g.out_id[0] = 1;
+    g.M = n_q; g.N = D; g.K = D;
+    g.a_plain = static_cast<const float*>(gathered); g.c_plain = q;
+    g.lda = bf16 ? D / 2 : D;   // in floats: a bf16 row is D / 2 of them
+    g.ldc = D;
+    const dim3 grid(ceil_div_i(D, BN), ceil_div_i(n_q, BM), 1);
+    if (bf16) {
+        count_launch(kLfGemmBf16Widened);
+        hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPlain, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
+    } else {
+        count_launch(kLfGemmF32Rows64);
+        hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPlain, false, true>), grid, dim3(kGemmThreads), 0, st, g);
+    }
+    return launch_status();
+}
+
 // The same product with the argmax epilogue: nothing of C[M, N] is stored, row_best[m][t] = (max, lowest index of the
 // max) over the columns of tile t.  Tiles per row: gemm_nt_argmax_tiles(N).
 // (the panel kernel's tiles are 32 columns wide, the tiled kernel's 64: n_tiles tells the caller which ran)

@@ -241,4 +241,27 @@ inline int gqa_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_h
 // constexpr, so that the kernel and a host program (tests/cpp/gqa_map_test.cpp) compile this text.
 constexpr int gqa_kv_unit(int u, int lg, int g) { return (((u >> lg) / g) << lg) + (u & ((1 << lg) - 1)); }
 
+// ---- the causal multi-query prompt scan (attention_prompt.hpp) --------------------------------------------------------------
+// What it takes: fp32 and bf16 pages with rows of at most two lane loads -- one head: fp32 to emb_dim 512, bf16 to 1024;
+// several heads, with or without grouped K/V heads: what heads_lanes_log2 / gqa_shape_supported accept.  n_kv_heads ==
+// n_heads: no grouping.  Everything else, fp8 pages included, is refused before any launch.
+inline bool prompt_scan_shape_ok(int B, int S, int D, int H, int Hkv, int elem) {
+    if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) return false;
+    if (H < 1 || Hkv < 1 || Hkv > H) return false;
+    if (H == 1) {
+        if (!window_plain_shape_ok(B, S, D, elem)) return false;
+        const int epl = elem == MLI_ELEM_BF16 ? 8 : 4;
+        return plan_ceil_div(D / epl, kPlanWave) <= 2;
+    }
+    if (Hkv == H) return heads_lanes_log2(B, S, D, H, elem) >= 0;
+    return gqa_shape_supported(B, S, D, H, Hkv, elem) != 0;
+}
+// TQ, the consecutive query positions a workgroup of the prompt scan shares every K / V load among: a compile-time constant
+// per kernel variant (element type, lane loads per row, one head or several), the largest of 8 / 4 / 2 that compiles without
+// scratch (DESIGN 3.6d has the register table).  constexpr: the kernel's template argument and mli_prompt_scan_tq are this text.
+constexpr int prompt_scan_tq(int epl, int nj, bool heads) {
+    if (heads) return (epl == 4 ? 8 : 4) / nj;   // fp32: 8 / 4 for rows of one / two lane loads; bf16: 4 / 2
+    return epl == 8 && nj == 2 ? 4 : 8;
+}
+
 }  // namespace mli

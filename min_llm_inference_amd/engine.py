@@ -39,7 +39,7 @@ def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
 class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
                  n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None,
-                 release_pages=False, n_kv_heads=None, logprobs=None):
+                 release_pages=False, n_kv_heads=None, logprobs=None, prompt_logprobs=False):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -59,6 +59,8 @@ class Engine:
             self.set_page_release(True)
         if logprobs is not None:
             self.set_logprobs(logprobs)
+        if prompt_logprobs:
+            self.set_prompt_logprobs(True)
 
     def _check(self, rc):
         if rc != 0:
@@ -114,6 +116,30 @@ class Engine:
             k = n.value
             out[item_id] = (n_prompt.value, lp[:k].copy(), ids[:k * n_top].reshape(k, n_top).copy(),
                             tops[:k * n_top].reshape(k, n_top).copy())
+        return out
+
+    def set_prompt_logprobs(self, enabled=True):
+        """Prompt log-probabilities (mli_engine_set_prompt_logprobs): the engine also reports, for every prompt
+        token but the first, its log-probability after the tokens before it and the alternatives there.  After
+        set_logprobs (which supplies n_top), before the first step or run; fp32 / bf16 paged kinds, not with page release."""
+        self._check(self._lib.mli_engine_set_prompt_logprobs(self._h, int(bool(enabled))))
+
+    def finished_prompt_logprobs(self):
+        """{id: (logprobs [n], top_ids [n, n_top], top_logprobs [n, n_top])} of the finished items: entry i belongs to prompt
+        token i + 1, n = n_prompt - 1 (mli_engine_get_finished_prompt_logprobs)."""
+        out = {}
+        n_top = getattr(self, "_n_top", 0)
+        cap = self.cfg.n_sequence + 16
+        lp = np.empty(cap, np.float32)
+        ids = np.empty(cap * max(n_top, 1), np.int32)
+        tops = np.empty(cap * max(n_top, 1), np.float32)
+        for i, (item_id, _) in enumerate(self.finished()):
+            n = ctypes.c_int()
+            self._check(self._lib.mli_engine_get_finished_prompt_logprobs(
+                self._h, i, lp.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(n), ids.ctypes.data_as(ctypes.c_void_p),
+                tops.ctypes.data_as(ctypes.c_void_p), cap * n_top))
+            k = n.value
+            out[item_id] = (lp[:k].copy(), ids[:k * n_top].reshape(k, n_top).copy(), tops[:k * n_top].reshape(k, n_top).copy())
         return out
 
     def page_stats(self):

@@ -84,12 +84,16 @@ protected:
         auto rounds = [&] {
             for (int round = 0; round < n_forward_rounds_; ++round) {
                 const int fresh = round == 0 ? n_new_items : 0;  // later rounds only decode
+                // (prompt log-probabilities, layers.h PromptScoring: directly behind the new rows' prefill; a forward with new
+                // rows is never a replayed graph)
                 if (lean) {
                     layer.prefill(s.emb_table, s.pos_emb_table, s.inp, s.page_table, s.lengths, s.new_item_indices, fresh);
+                    if (fresh > 0) layer.score_prompts(s.emb_table, s.inp, s.page_table);
                     attend(0);
                 } else {
                     encode(fresh);
                     attend(fresh);
+                    if (fresh > 0) layer.score_prompts(s.emb_table, s.inp, s.page_table);
                 }
                 head.forward_paged(layer.elem(), attention_result_, s.emb_table, s.pos_emb_table, s.page_table, s.lengths,
                                    s.decoder_result, round);

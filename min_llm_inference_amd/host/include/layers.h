@@ -33,6 +33,16 @@ private:
 // EXTENSION: the options of the paged attention layers' lean forward, one struct for the four layers and the four models.
 // A new per-layer option is a field here, its setter below, one validation in the engine setter (engine_api.cpp) and its
 // use where the layer launches (layers.cpp).
+// EXTENSION: prompt log-probabilities.  What a layer calls right after the prefill of a forward's new rows, on
+// the forward's stream, with its own projection weights and options: the engine's scorer (engine_api.cpp) cuts the new rows'
+// prompts into passes and runs mli_paged_prompt_logprobs on each.  A forward without new rows never calls it.
+struct PagedAttentionOptions;
+struct PromptScoring {
+    virtual ~PromptScoring() = default;
+    virtual void score(int elem, const void* wq, const PagedAttentionOptions& options, void* const* page_table, const int* inp,
+                       const float* emb_table, int n_batch, int n_sequence, int emb_dim, int n_vocab) = 0;
+};
+
 struct PagedAttentionOptions {
     int n_heads = 1;            // attention heads (1 = the reference's single softmax over emb_dim)
     int n_kv_heads = 0;         // grouped-query attention: K/V heads serving the n_heads query heads (0 = as many)
@@ -41,6 +51,7 @@ struct PagedAttentionOptions {
     // the rows' pages below the window are returned early (PagedAttentionsManager::set_page_release): prefill covers a
     // row's live tokens only and follows no table entry of a dead page (mli_paged_prefill_window)
     bool page_release = false;
+    PromptScoring* prompt_logprobs = nullptr;   // prompt log-probabilities: who scores the new rows' prompts (nullptr: nobody)
 };
 
 // The setters of the option set, defined once for every class that has them: a layer owns the struct, a model hands out
@@ -52,6 +63,7 @@ public:
     void set_window(int window) { options().window = window; }
     void set_sinks(int n_sink) { options().n_sink = n_sink; }
     void set_page_release(bool enabled) { options().page_release = enabled; }
+    void set_prompt_logprobs(PromptScoring* scoring) { options().prompt_logprobs = scoring; }
     virtual PagedAttentionOptions& options() = 0;
 
 protected:
@@ -68,6 +80,8 @@ public:
     void prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb, const TensorInt& inp,
                  TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
                  int n_new_items);
+    // extension: the prompt log-probabilities of the rows just prefilled (PromptScoring); nothing without a scorer
+    void score_prompts(const TensorFloat& emb_table, const TensorInt& inp, TensorFloatPoint& page_table);
     PagedAttentionOptions& options() override { return options_; }
     int elem() const { return elem_; }  // MLI_ELEM_* of the pages
 

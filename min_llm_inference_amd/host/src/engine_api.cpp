@@ -23,8 +23,9 @@
 #include "mli_engine.h"
 #include "mli_kernels.h"
 #include "pipelined_engine.h"
+#include "prompt_plan.hpp"  // cut_prompt_passes
 #include "runtime.h"
-#include "scan_plan.hpp"   // heads_shape_supported, window_shape_supported
+#include "scan_plan.hpp"   // heads_shape_supported, window_shape_supported, prompt_scan_shape_ok
 #include "throughput_counter.h"
 
 namespace {
@@ -175,6 +176,104 @@ struct mli_engine {
             }
         }
     };
+    // EXTENSION: prompt log-probabilities (mli_engine_set_prompt_logprobs).  The rows admitted for a forward are
+    // noted here (admitted()); the model's layer calls score() directly behind their prefill, on the forward's stream.  The
+    // prompts are cut into passes of at most n_batch positions (prompt_plan.hpp), each pass is one mli_paged_prompt_logprobs
+    // call, and its figures cross to the host at once with a blocking copy -- a forward with new rows waits for its scoring,
+    // every other forward is untouched -- and are kept per item id.  An id is noted once: a re-admitted item is not scored
+    // again, and "prompt" is the tokens it was queued with.
+    struct PromptLogprobs : PromptScoring {
+        struct Record {
+            std::vector<float> token_logprob, top_logprobs;
+            std::vector<int> top_ids;
+        };
+        int n_top, width, limit;
+        TensorInt seg_device, seg_host, ids_device, ids_host;       // segments: [4][limit]
+        TensorFloat token_device, token_host, top_device, top_host, scratch;
+        size_t scratch_bytes;
+        std::vector<mli::PromptRow> pending;
+        std::unordered_map<int, int> pending_id;                    // batch row -> item id
+        std::unordered_map<int, Record> records;
+
+        static std::vector<size_t> shape(size_t n) { return {n}; }
+        PromptLogprobs(int n_top_, int n_batch, int emb_dim, int n_vocab)
+            : n_top(n_top_), width(n_top_ > 0 ? n_top_ : 1), limit(n_batch),
+              seg_device(shape(4 * (size_t)n_batch), DeviceType::DEVICE, TensorDataType::SYNC_ALLOCATE),
+              seg_host(shape(4 * (size_t)n_batch), DeviceType::HOST, TensorDataType::SYNC_ALLOCATE),
+              ids_device(shape((size_t)n_batch * width), DeviceType::DEVICE, TensorDataType::SYNC_ALLOCATE),
+              ids_host(shape((size_t)n_batch * width), DeviceType::HOST, TensorDataType::SYNC_ALLOCATE),
+              token_device(shape((size_t)n_batch), DeviceType::DEVICE, TensorDataType::SYNC_ALLOCATE),
+              token_host(shape((size_t)n_batch), DeviceType::HOST, TensorDataType::SYNC_ALLOCATE),
+              top_device(shape((size_t)n_batch * width), DeviceType::DEVICE, TensorDataType::SYNC_ALLOCATE),
+              top_host(shape((size_t)n_batch * width), DeviceType::HOST, TensorDataType::SYNC_ALLOCATE),
+              scratch(shape((mli_prompt_logprobs_scratch_bytes(n_batch, emb_dim, n_vocab) + 3) / 4), DeviceType::DEVICE,
+                      TensorDataType::SYNC_ALLOCATE),
+              scratch_bytes(mli_prompt_logprobs_scratch_bytes(n_batch, emb_dim, n_vocab)) {}
+
+        // the item in batch row `row` has just been admitted with n_tokens tokens
+        void admitted(int row, int id, int n_tokens) {
+            if (!records.emplace(id, Record{}).second) return;      // scored at its first admission only
+            pending.push_back(mli::PromptRow{row, n_tokens});
+            pending_id[row] = id;
+        }
+
+        void score(int elem, const void* wq, const PagedAttentionOptions& o, void* const* page_table, const int* inp,
+                   const float* emb_table, int n_batch, int n_sequence, int emb_dim, int n_vocab) override {
+            if (pending.empty()) return;
+            const int n_kv_heads = o.n_kv_heads != 0 ? o.n_kv_heads : o.n_heads;
+            for (const mli::PromptPass& pass : mli::cut_prompt_passes(pending, limit)) {
+                const int n_seg = (int)pass.segments.size();
+                int* seg = seg_host.data();
+                for (int i = 0; i < n_seg; ++i) {
+                    seg[i] = pass.segments[i].row;
+                    seg[limit + i] = pass.segments[i].first;
+                    seg[2 * limit + i] = pass.segments[i].count;
+                    seg[3 * limit + i] = pass.segments[i].offset;
+                }
+                seg_device.copy_from(seg_host);
+                const int* d = seg_device.data();
+                const int rc = mli_paged_prompt_logprobs(
+                    page_table, inp, wq, emb_table, d, d + limit, d + 2 * limit, d + 3 * limit, token_device.data(),
+                    n_top > 0 ? ids_device.data() : nullptr, n_top > 0 ? top_device.data() : nullptr, n_seg, pass.max_count,
+                    pass.n_positions, n_batch, n_sequence, emb_dim, n_vocab, o.n_heads, n_kv_heads, o.window, o.n_sink, elem,
+                    n_top, scratch.data(), scratch_bytes, mli::runtime::compute_stream());
+                if (rc != 0) throw std::runtime_error("mli_paged_prompt_logprobs failed: " + std::to_string(rc));
+                token_host.copy_from(token_device);                  // blocking: the pass has run
+                if (n_top > 0) {
+                    ids_host.copy_from(ids_device);
+                    top_host.copy_from(top_device);
+                }
+                for (const mli::PromptSegment& g : pass.segments) {
+                    Record& r = records.at(pending_id.at(g.row));
+                    r.token_logprob.insert(r.token_logprob.end(), token_host.data() + g.offset, token_host.data() + g.offset + g.count);
+                    if (n_top > 0) {
+                        const size_t a = (size_t)g.offset * width, b = (size_t)(g.offset + g.count) * width;
+                        r.top_ids.insert(r.top_ids.end(), ids_host.data() + a, ids_host.data() + b);
+                        r.top_logprobs.insert(r.top_logprobs.end(), top_host.data() + a, top_host.data() + b);
+                    }
+                }
+            }
+            pending.clear();
+            pending_id.clear();
+        }
+    };
+    bool prompt_logprobs_wanted = false;             // mli_engine_set_prompt_logprobs
+    std::unique_ptr<PromptLogprobs> prompt_logprobs; // from the first step or run of an engine with the switch set
+
+    // the rows admitted for the next forward (both loops): their prompts are scored in that forward
+    void note_admitted(const std::vector<int>& slots) {
+        if (!prompt_logprobs) return;
+        for (int b : slots) {
+            const IdTokensPair& item = processing_storage.get_token(b);
+            prompt_logprobs->admitted(b, item.first, (int)item.second.size());
+        }
+    }
+    bool prompt_shape_ok() {
+        const PagedAttentionOptions& o = options();
+        return mli::prompt_scan_shape_ok(cfg.n_batch, cfg.n_sequence, cfg.emb_dim, o.n_heads,
+                                         o.n_kv_heads != 0 ? o.n_kv_heads : o.n_heads, elem());
+    }
+
     int logprobs_n_top = -1;              // mli_engine_set_logprobs: -1 = never called
     std::unique_ptr<Logprobs> logprobs;   // from the first step or run of an engine with logprobs
     std::unordered_set<int> item_ids;     // every id queued so far
@@ -205,6 +304,13 @@ struct mli_engine {
         if (logprobs_n_top < 0) return;
         model_head().set_logprobs(logprobs_n_top);
         logprobs = std::make_unique<Logprobs>(model_head().logprobs());
+        if (!prompt_logprobs_wanted) return;
+        // (the setters that came after mli_engine_set_prompt_logprobs may have changed what it validated)
+        if (!paged || release_pages || !prompt_shape_ok())
+            throw std::runtime_error("prompt log-probabilities (mli_engine_set_prompt_logprobs): not with page release, and "
+                                     "the prompt scan does not take this (n_batch, n_sequence, emb_dim, n_heads, n_kv_heads)");
+        prompt_logprobs = std::make_unique<PromptLogprobs>(logprobs_n_top, cfg.n_batch, cfg.emb_dim, cfg.n_vocab);
+        paged->set_prompt_logprobs(prompt_logprobs.get());
     }
 
     void set_slot_host(int b, const Sampling& s) {
@@ -345,9 +451,11 @@ struct mli_engine {
 
     void insert(const std::vector<int>& free_slots) {
         if (paged_kind()) {
-            n_new_items = (int)insert_new_items(inp_device, inp_host, lengths_device, lengths_host, new_idx_device,
-                                                new_idx_host, item_storage, processing_storage, *pool, *pages,
-                                                cfg.n_forward_rounds).size();
+            const std::vector<int> slots = insert_new_items(inp_device, inp_host, lengths_device, lengths_host, new_idx_device,
+                                                            new_idx_host, item_storage, processing_storage, *pool, *pages,
+                                                            cfg.n_forward_rounds);
+            n_new_items = (int)slots.size();
+            note_admitted(slots);
         } else {
             n_new_items = insert_new_items(free_slots, inp_device, inp_host, lengths_device, lengths_host,
                                            new_idx_device, new_idx_host, item_storage, processing_storage);
@@ -382,7 +490,10 @@ struct mli_engine {
             item_storage, processing_storage, *pool, *pages, cfg.n_batch, cfg.n_sequence,
             [&](const TensorInt& inp, TensorInt& lengths, const TensorInt& new_idx, TensorInt& result, int n_new) {
                 forward(inp, lengths, new_idx, result, n_new);
-            }, cfg.n_forward_rounds, [&](const std::vector<int>& slots) { scatter_admitted(slots); }, logprobs.get());
+            }, cfg.n_forward_rounds, [&](const std::vector<int>& slots) {
+                scatter_admitted(slots);
+                note_admitted(slots);
+            }, logprobs.get());
     }
 
     double t_forward = 0, t_result = 0, t_pages = 0, t_insert = 0;  // host seconds per phase (MLI_ENGINE_TIMING=1)
@@ -566,6 +677,9 @@ int mli_engine_set_page_release(mli_engine* e, int enabled) {
         if (e->cfg.reference_length_reset_quirk)
             throw std::runtime_error("mli_engine_set_page_release: not with reference_length_reset_quirk (it moves device "
                                      "lengths backwards; release rests on lengths that only grow)");
+        if (enabled && e->prompt_logprobs_wanted)
+            throw std::runtime_error("mli_engine_set_page_release: not with prompt log-probabilities (a prefill that skips dead "
+                                     "pages leaves the prompt's K / V incomplete)");
         e->release_pages = enabled != 0;
     })
 }
@@ -673,6 +787,48 @@ int mli_engine_get_finished_logprobs(mli_engine* e, int index, int* n_prompt, fl
         const auto& r = e->logprobs->records.at(id);
         *n_prompt = r.n_prompt;
         *n_generated = (int)r.token_logprob.size();
+        if (token_logprobs && capacity > 0)
+            std::memcpy(token_logprobs, r.token_logprob.data(), sizeof(float) * std::min<size_t>(capacity, r.token_logprob.size()));
+        const size_t n = top_capacity > 0 ? std::min<size_t>(top_capacity, r.top_ids.size()) : 0;
+        if (top_ids && n) std::memcpy(top_ids, r.top_ids.data(), sizeof(int) * n);
+        if (top_logprobs && n) std::memcpy(top_logprobs, r.top_logprobs.data(), sizeof(float) * n);
+    })
+}
+
+int mli_engine_set_prompt_logprobs(mli_engine* e, int enabled) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (e->started) throw std::runtime_error("mli_engine_set_prompt_logprobs after the engine has started");
+        if (e->logprobs_n_top < 0)
+            throw std::runtime_error("mli_engine_set_prompt_logprobs: an engine without logprobs (mli_engine_set_logprobs comes "
+                                     "first: it supplies n_top)");
+        if (e->cfg.kind == MLI_ENGINE_CONTIGUOUS || e->cfg.kind == MLI_ENGINE_PAGED_FP8)
+            throw std::runtime_error("mli_engine_set_prompt_logprobs: prompt log-probabilities serve the fp32 and bf16 paged "
+                                     "engines");
+        if (e->release_pages)
+            throw std::runtime_error("mli_engine_set_prompt_logprobs: not with page release (mli_engine_set_page_release: its "
+                                     "prefill skips dead pages, so the prompt's K / V are not all there)");
+        if (!e->prompt_shape_ok())
+            throw std::runtime_error("mli_engine_set_prompt_logprobs: the prompt scan does not take this (n_batch, n_sequence, "
+                                     "emb_dim, n_heads, n_kv_heads): rows of at most two 16-byte lane loads");
+        e->prompt_logprobs_wanted = enabled != 0;
+    })
+}
+
+int mli_engine_get_finished_prompt_logprobs(mli_engine* e, int index, float* token_logprobs, int capacity, int* n_scored,
+                                            int* top_ids, float* top_logprobs, int top_capacity) {
+    MLI_GUARD({
+        if (!e || !n_scored) throw std::runtime_error("null argument");
+        if (!e->prompt_logprobs_wanted)
+            throw std::runtime_error("mli_engine_get_finished_prompt_logprobs: an engine without prompt log-probabilities "
+                                     "(mli_engine_set_prompt_logprobs)");
+        const auto& items = e->item_storage.get_finished_items();
+        if (index < 0 || index >= (int)items.size()) throw std::out_of_range("finished item index");
+        const int id = std::next(items.begin(), index)->first;
+        if (!e->prompt_logprobs || !e->prompt_logprobs->records.count(id))
+            throw std::runtime_error("no prompt figures for item " + std::to_string(id));
+        const auto& r = e->prompt_logprobs->records.at(id);
+        *n_scored = (int)r.token_logprob.size();
         if (token_logprobs && capacity > 0)
             std::memcpy(token_logprobs, r.token_logprob.data(), sizeof(float) * std::min<size_t>(capacity, r.token_logprob.size()));
         const size_t n = top_capacity > 0 ? std::min<size_t>(top_capacity, r.top_ids.size()) : 0;

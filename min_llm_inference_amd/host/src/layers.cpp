@@ -57,6 +57,15 @@ void PagedAttentionLayerCore<Weights>::prefill(const TensorFloat& emb_table, con
 }
 
 template <class Weights>
+void PagedAttentionLayerCore<Weights>::score_prompts(const TensorFloat& emb_table, const TensorInt& inp,
+                                                     TensorFloatPoint& page_table) {
+    if (options_.prompt_logprobs == nullptr) return;
+    options_.prompt_logprobs->score(elem_, wq_.data(), options_, reinterpret_cast<void* const*>(page_table.data()), inp.data(),
+                                    emb_table.data(), (int)page_table.shape()[0], (int)n_sequence_, (int)wk_.shape()[0],
+                                    (int)emb_table.shape()[0]);
+}
+
+template <class Weights>
 int PagedAttentionLayerCore<Weights>::lean_scan(TensorFloatPoint& page_table, const TensorInt& lengths,
                                                 const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                                 int n_new_items, int n_heads, int n_kv_heads) {

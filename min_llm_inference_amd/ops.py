@@ -466,6 +466,95 @@ def sample_tokens_logprobs(logits, temperature, top_k, top_p, seed, lengths, n_t
     return tokens, token_logprob, top_ids, top_logprobs
 
 
+def _segments(segments, device):
+    """The four device arrays of a list of segments [(row, first position, count)] with dense offsets in list order, the
+    largest count and the number of positions."""
+    rows = [int(r) for r, _, _ in segments]
+    first = [int(f) for _, f, _ in segments]
+    count = [int(n) for _, _, n in segments]
+    offset = [sum(count[:i]) for i in range(len(count))]
+    arrays = [torch.tensor(a, dtype=torch.int32, device=device) for a in (rows, first, count, offset)]
+    return arrays, max(count, default=0), sum(count)
+
+
+def prompt_scan_tq(emb_dim, n_heads, elem):
+    """The consecutive query positions a workgroup of prompt_scan_paged shares its K / V loads among (mli_prompt_scan_tq)."""
+    tq = int(load_library().mli_prompt_scan_tq(int(emb_dim), int(n_heads), int(elem)))
+    if tq < 0:
+        raise MliError(f"Hip Failure: mli_prompt_scan_tq returned {tq}")
+    return tq
+
+
+def prompt_scan_paged(q, page_table, segments, out, n_batch, n_sequence, elem, n_heads=1, n_kv_heads=None, window=None,
+                      sinks=None, seg_arrays=None):
+    """EXTENSION: the causal multi-query paged scan (mli_prompt_scan_paged).  segments = [(row, first position,
+    count)]: query j of a segment is position first + j of its row and attends the slots s <= its position (inside the window or
+    among the sinks); q and out [n_q, D] hold the queries in list order.  seg_arrays = (rows, first, count, offset, max_count)
+    device arrays replace the list."""
+    n_q, D = q.shape
+    if seg_arrays is None:
+        arrays, max_count, _ = _segments(segments, q.device)
+    else:
+        arrays, max_count = list(seg_arrays[:4]), int(seg_arrays[4])
+    _check(load_library().mli_prompt_scan_paged(_p(q), _p(page_table), *map(_p, arrays), _p(out), int(arrays[0].numel()),
+                                                max_count, n_q, int(n_batch), int(n_sequence), D, int(n_heads),
+                                                int(n_kv_heads or n_heads), int(window or 0), int(sinks or 0), int(elem),
+                                                _stream()), "mli_prompt_scan_paged")
+    return out
+
+
+def prompt_project_q(page_table, segments, wq, n_batch, n_sequence, elem):
+    """q [n_q, D] float32 = x(row, position) . wq for the positions of the segments (mli_prompt_project_q)."""
+    D = wq.shape[0]
+    arrays, max_count, n_q = _segments(segments, wq.device)
+    gathered = torch.empty(max(n_q, 1) * D, dtype=torch.float32, device=wq.device)
+    q = torch.empty((n_q, D), dtype=torch.float32, device=wq.device)
+    _check(load_library().mli_prompt_project_q(_p(page_table), *map(_p, arrays), _p(wq), _p(gathered), _p(q), len(segments),
+                                               max_count, n_q, int(n_batch), int(n_sequence), D, int(elem), _stream()),
+           "mli_prompt_project_q")
+    return q
+
+
+def _score_outputs(n, n_top, device):
+    return (torch.empty(n, dtype=torch.float32, device=device), torch.empty((n, max(n_top, 0)), dtype=torch.int32, device=device),
+            torch.empty((n, max(n_top, 0)), dtype=torch.float32, device=device))
+
+
+def score_tokens_logprobs(logits, targets, n_top=0):
+    """EXTENSION: the figures of sample_tokens_logprobs for the token targets[i] each row is GIVEN (mli_score_tokens_logprobs).
+    Returns (token_logprob [n], top_ids [n, n_top], top_logprobs [n, n_top])."""
+    n, V = logits.shape
+    n_top = int(n_top)
+    if targets.dtype != torch.int32:
+        raise MliError(f"targets must be int32, got {targets.dtype}")
+    token_logprob, top_ids, top_logprobs = _score_outputs(n, n_top, logits.device)
+    _check(load_library().mli_score_tokens_logprobs(_p(logits), _p(targets), _p(token_logprob),
+                                                    _p(top_ids) if n_top > 0 else None,
+                                                    _p(top_logprobs) if n_top > 0 else None, n, V, n_top, _stream()),
+           "mli_score_tokens_logprobs")
+    return token_logprob, top_ids, top_logprobs
+
+
+def paged_prompt_logprobs(page_table, inp, wq, emb_table, segments, n_batch, n_sequence, elem, n_top=0, n_heads=1,
+                          n_kv_heads=None, window=None, sinks=None):
+    """EXTENSION: prompt log-probabilities for the positions of the segments from the pages a prefill has written
+    (mli_paged_prompt_logprobs): projection, causal scan, logits, scoring of inp[row, position + 1].  Returns (token_logprob
+    [n], top_ids [n, n_top], top_logprobs [n, n_top]) in list order."""
+    lib = load_library()
+    D, V = wq.shape[0], emb_table.shape[0]
+    n_top = int(n_top)
+    arrays, max_count, n = _segments(segments, wq.device)
+    token_logprob, top_ids, top_logprobs = _score_outputs(n, n_top, wq.device)
+    need = int(lib.mli_prompt_logprobs_scratch_bytes(n, D, V))
+    sc = torch.empty(max(need, 16), dtype=torch.uint8, device=wq.device)
+    _check(lib.mli_paged_prompt_logprobs(_p(page_table), _p(inp), _p(wq), _p(emb_table), *map(_p, arrays), _p(token_logprob),
+                                         _p(top_ids) if n_top > 0 else None, _p(top_logprobs) if n_top > 0 else None,
+                                         len(segments), max_count, n, int(n_batch), int(n_sequence), D, V, int(n_heads),
+                                         int(n_kv_heads or n_heads), int(window or 0), int(sinks or 0), int(elem), n_top,
+                                         _p(sc), need, _stream()), "mli_paged_prompt_logprobs")
+    return token_logprob, top_ids, top_logprobs
+
+
 def _sampled_scratch(n_batch, n_vocab, device):
     need = int(load_library().mli_decoder_sampled_scratch_bytes(n_batch, n_vocab))
     return torch.empty(max(need, 16), dtype=torch.uint8, device=device), need

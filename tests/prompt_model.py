@@ -1,0 +1,216 @@
+"""The causal multi-query prompt scan and the prompt log-probabilities, for the tests.
+
+The scan.  A segment is (row b, first position p, count n); its query j is position t = p + j of row b and attends slot s of
+that row iff s <= t and (no window, or s > t - W, or s < K).  That is the decode problem of a row of length t + 1: query i of a
+list becomes VIRTUAL ROW i -- its own q, the K and V of its row, length t + 1 -- and the references are the existing ones on the
+virtual rows: gqa_model.model_gqa / oracle_gqa (which are sinks_model's, window_model's and heads_model's on the expanded
+operands; with one head and no window the plain float64 model and the plain oracle).  Errors, tolerance and the comparison per
+score family are heads_model's: f64_model.tolerance of the fp32 oracle's own error, nothing from a kernel.
+
+The figures.  Entry i of an item's prompt log-probabilities belongs to prompt token i + 1: logprobs_model.reference on the
+logits of position i of the float64 forward over the item's tokens (replay_model.Replay with rows 0 .. p - 2), given token
+tokens[i + 1].
+
+MUTANTS are the faults such a kernel and its host actually have, each as a wrong model the comparison must reject.
+
+TEST INFRASTRUCTURE, like heads_model.py: never used by the product."""
+import numpy as np
+
+import gqa_model as gm
+import heads_model as hm
+import logprobs_model as lm
+import replay_model as rm
+
+# (seed, D, H, Hkv, page type): n_sequence 128 throughout -- the smallest shapes that reach every kernel variant (element type x
+# lane loads per row x one head or several): fp32 D 64 (a partly filled lane load), 256, 512 (two lane loads); bf16 D 128, 1024;
+# 4 heads at head_dim 32 and 64; 8 heads on 2 and on 1 K/V heads
+S = 128
+SHAPES = [
+    (701, 64, 1, 1, "f32"), (702, 256, 1, 1, "f32"), (703, 512, 1, 1, "f32"), (704, 128, 1, 1, "bf16"), (705, 1024, 1, 1, "bf16"),
+    (706, 128, 4, 4, "f32"), (707, 256, 4, 4, "bf16"), (708, 256, 8, 2, "f32"), (709, 512, 8, 1, "bf16"), (710, 1024, 8, 2, "bf16"),
+    (711, 512, 4, 4, "f32"),
+]
+# (window, n_sink): plain, a window of several pages, the same with sinks, a window of a single page
+FORMS = ((0, 0), (40, 0), (40, 4), (16, 0))
+FAMILIES = ("flat", "peaked", "offset+", "offset-", "late_peak", "early_peak")
+
+
+def segments_for(tq, n_sequence=S):
+    """Segments [(row, first, count)] for a variant of `tq` queries per workgroup, rows in permuted order: counts 1, tq - 1, tq,
+    tq + 1 and 2 tq + 1; first positions 0, 15, 16, 17; a query at n_sequence - 1; two segments of one row (a continuation with
+    first > 0) -- and the rows each list needs (last scored position + 1 per row)."""
+    segs = [(5, 0, 1), (2, 15, tq - 1), (7, 16, tq), (0, 17, tq + 1), (3, 0, 2 * tq + 1), (6, n_sequence - tq - 1, tq + 1),
+            (1, 0, tq + 3), (4, 33, 1), (1, tq + 3, 2 * tq), (8, 47, 3 * tq)]
+    segs = [s for s in segs if s[2] >= 1]
+    n_rows = max(r for r, _, _ in segs) + 1
+    lengths = np.zeros(n_rows, np.int32)
+    for r, f, n in segs:
+        lengths[r] = max(lengths[r], f + n)
+    assert lengths.max() == n_sequence and (lengths > 0).all()
+    return segs, lengths
+
+
+def queries(segments):
+    """(row, position) of every query, in the dense order of the segments' offsets"""
+    rows = np.concatenate([np.full(n, r, np.int64) for r, _, n in segments])
+    pos = np.concatenate([np.arange(f, f + n, dtype=np.int64) for _, f, n in segments])
+    return rows, pos
+
+
+def query_vectors(q_rows, rows, pos):
+    """One q per query from the row's q: scaled by a factor that differs between the positions of a row, so that two queries
+    swapped, or one computed for its neighbour's position, differ beyond any tolerance."""
+    return (q_rows[rows] * (1.0 + 0.03125 * (pos % 8))[:, None].astype(np.float32)).astype(np.float32)
+
+
+def virtual(kt, v, rows, pos):
+    """The virtual rows' operands: (kt [n_q, D, S], v [n_q, S, D], lengths t + 1)"""
+    return kt[rows], v[rows], (pos + 1).astype(np.int32)
+
+
+def model_prompt(qv, kt, v, rows, pos, H, Hkv, W, K):
+    ktv, vv, Lv = virtual(kt, v, rows, pos)
+    return gm.model_gqa(qv, ktv, vv, Lv, H, Hkv, W, K)
+
+
+def oracle_prompt(oracle, qv, kt, v, rows, pos, H, Hkv, W, K):
+    ktv, vv, Lv = virtual(kt, v, rows, pos)
+    return gm.oracle_gqa(oracle, qv, ktv, vv, Lv, H, Hkv, W, K)
+
+
+def scan_float64(qv, kt, v, rows, pos, H, Hkv, W, K):
+    """The scan stated directly (a mask per query, a softmax per head): the model the virtual rows are checked against."""
+    n, D = qv.shape
+    hd, g = D // H, H // Hkv
+    out = np.zeros((n, D), np.float64)
+    for i in range(n):
+        b, t = int(rows[i]), int(pos[i])
+        s = np.arange(t + 1)
+        m = np.ones(t + 1, bool) if not W else (s > t - W) | (s < K)
+        for h in range(H):
+            qs, ks = hm.head_slice(h, H, D), hm.head_slice(h // g, H, D)
+            x = (qv[i, qs].astype(np.float64) @ kt[b, ks, :t + 1].astype(np.float64)) / np.sqrt(hd)
+            x = np.where(m, x, -np.inf)
+            p = np.exp(x - x.max())
+            out[i, qs] = (p / p.sum()) @ v[b, :t + 1, ks].astype(np.float64)
+    return out
+
+
+# ---- wrong models --------------------------------------------------------------------------------------------------------------
+def _with(qv, kt, v, rows, pos, H, Hkv, W, K, lengths=None, lo_shift=0, hi_shift=0, n_sink=None, group=True, positions=None):
+    """float64 attention of a scan whose query at position t of a row holding `lengths` tokens attends s <= t + hi_shift (inside
+    the row) and (no window, or s > t - W + lo_shift, or s < n_sink), head h on K/V head h // g (group) or h"""
+    n, D = qv.shape
+    hd, g = D // H, H // Hkv
+    pos = pos if positions is None else positions
+    out = np.zeros((n, D), np.float64)
+    for i in range(n):
+        b, t = int(rows[i]), int(pos[i])
+        top = t + hi_shift if lengths is None else min(t + hi_shift, int(lengths[b]) - 1)
+        s = np.arange(top + 1)
+        m = np.ones(top + 1, bool) if not W else (s > t - W + lo_shift) | (s < (K if n_sink is None else n_sink))
+        for h in range(H):
+            qs, ks = hm.head_slice(h, H, D), hm.head_slice(h // g if group else h, H, D)
+            x = np.where(m, (qv[i, qs].astype(np.float64) @ kt[b, ks, :top + 1].astype(np.float64)) / np.sqrt(hd), -np.inf)
+            p = np.exp(x - x.max())
+            out[i, qs] = (p / p.sum()) @ v[b, :top + 1, ks].astype(np.float64)
+    return out
+
+
+def restarted_positions(segments):
+    """positions with the SECOND segment of a row restarted at 0 (a continuation pass that forgets its first position)"""
+    seen, out = set(), []
+    for r, f, n in segments:
+        out.append(np.arange(0, n) if r in seen and f > 0 else np.arange(f, f + n))
+        seen.add(r)
+    return np.concatenate(out).astype(np.int64)
+
+
+SCAN_MUTANTS = {
+    "the query attends slot t + 1": dict(hi_shift=1),
+    "window lower bound one too low": dict(lo_shift=-1),
+    "window lower bound one too high": dict(lo_shift=1),
+    "sinks dropped": dict(n_sink=0),
+    "K/V head h instead of h / g": dict(group=False),
+    "second segment restarted at position 0": dict(positions="restarted"),
+}
+
+
+def scan_mutant(name, segments, lengths, qv, kt, v, rows, pos, H, Hkv, W, K):
+    """(float64 attention of the wrong scan, whether the fault can show in this form at all)"""
+    kw = dict(SCAN_MUTANTS[name])
+    applies = True
+    if "lo_shift" in kw:
+        applies = W > 0
+    if "n_sink" in kw:
+        applies = W > 0 and K > 0
+    if "group" in kw:
+        applies = Hkv < H
+    if kw.get("positions") == "restarted":
+        kw["positions"] = restarted_positions(segments)
+        applies = bool((kw["positions"] != pos).any())
+    return _with(qv, kt, v, rows, pos, H, Hkv, W, K, lengths=lengths, **kw), applies
+
+
+# ---- the prompt figures --------------------------------------------------------------------------------------------------------
+def prompt_replay(model, tokens, n_prompt, spec):
+    """replay_model.Replay over the item's tokens with the logits of the prompt positions 0 .. n_prompt - 2 (position i chooses
+    token i + 1)"""
+    return rm.Replay(model, np.asarray(tokens, np.int32), spec, rows=np.arange(0, max(int(n_prompt) - 1, 0)))
+
+
+def given_reference(logits, given, n_top):
+    """logprobs_model.reference for tokens the rows are GIVEN: a token outside [0, V) reports -inf for the token and the
+    alternatives all the same (logprobs_model.reference reports nothing for a negative token: a head that emitted none)."""
+    logits = np.asarray(logits, np.float32)
+    given = np.asarray(given, np.int64)
+    known = (given >= 0) & (given < logits.shape[1])
+    tok_lp, ids, lps = lm.reference(logits, np.where(known, given, 0), n_top)
+    return np.where(known, tok_lp, -np.inf), ids, lps
+
+
+def compare_given(got, logits, given, n_top):
+    """logprobs_model.compare against given_reference: (error, tolerance, complaints)"""
+    tok_lp, ids, lps = (np.asarray(a) for a in got)
+    w_lp, w_ids, w_lps = given_reference(logits, given, n_top)
+    bad = []
+    err = max(lm.value_error(tok_lp, w_lp), lm.value_error(lps.reshape(w_lps.shape), w_lps) if n_top else 0.0)
+    if n_top and not (ids.reshape(w_ids.shape) == w_ids).all():
+        bad.append(f"top_ids differ from the model's in rows {np.nonzero((ids.reshape(w_ids.shape) != w_ids).any(axis=1))[0].tolist()}")
+        err = np.inf
+    if n_top and not bad:
+        for b in range(len(w_lp)):
+            hit = np.nonzero(w_ids[b] == int(given[b]))[0] if int(given[b]) >= 0 else []
+            if len(hit) and np.float32(tok_lp[b]).tobytes() != np.float32(lps.reshape(w_lps.shape)[b, hit[0]]).tobytes():
+                bad.append(f"row {b}: the token's logprob is not bit-equal to its entry in the list")
+                err = np.inf
+    if not np.isfinite(err) and not bad:
+        bad.append("a non-finite, padded or out-of-range entry is not as specified")
+    return err, lm.tolerance(logits), bad
+
+
+def prompt_targets(tokens, n_rows, shift=1):
+    """the token entry i is scored for: tokens[i + shift] (shift = 1 is right)"""
+    return np.asarray([int(tokens[i + shift]) if 0 <= i + shift < len(tokens) else -1 for i in range(n_rows)], np.int64)
+
+
+def prompt_reference(logits, tokens, n_top, shift=1):
+    """(token_logprob [n], top_ids [n, n_top], top_logprobs [n, n_top]) of the prompt positions whose logits these are"""
+    return given_reference(logits, prompt_targets(tokens, len(logits), shift), n_top)
+
+
+def prompt_bound(rep):
+    """(2 tol_logit + logprobs_model.tolerance, E32) over the prompt rows, tol_logit as replay_model.judge_item computes it over
+    the generated rows: the scaled tolerance of the float32 restatement's error against the float64 forward, plus the rounding
+    flips of bf16 / fp8 storage where the spec has them.  Nothing from a kernel."""
+    if len(rep.rows) == 0:
+        return 0.0, 0.0
+    lg = rep.logits
+    e32 = float(np.abs(rep.logits32() - lg).max())
+    tol_logit = rm._scaled_tolerance(e32, float(np.abs(lg).max()))
+    e_flip = rep.flip_envelope(rm.FLIP_ROUNDS, seed=len(rep.x) * 1000003 + len(rep.rows))[1] if rep.spec.flips else 0.0
+    return 2.0 * (tol_logit + e_flip) + lm.tolerance(lg.astype(np.float32)), e32
+
+
+__all__ = ["S", "SHAPES", "FORMS", "FAMILIES", "segments_for", "queries", "query_vectors", "model_prompt", "oracle_prompt",
+           "scan_float64", "scan_mutant", "SCAN_MUTANTS", "prompt_replay", "given_reference", "compare_given", "prompt_targets", "prompt_reference", "prompt_bound"]
