@@ -190,6 +190,21 @@ int mli_engine_set_heads(mli_engine* engine, int n_heads);
  * looks at K / V columns. */
 int mli_engine_set_kv_heads(mli_engine* engine, int n_kv_heads);
 
+/* EXTENSION: ALiBi (mli_kernels.h: mli_paged_attention_lean_alibi).  Every decode scan of the engine adds
+ * slopes[h] * (s - (L - 1)) to query head h's scaled score of the row's slot s (L: the row's length, s absolute in the row).
+ * slopes_host: n floats in HOST memory, n == the engine's CURRENT n_heads (set the heads first), every one finite; a null
+ * pointer stands for the standard slopes of n_heads heads (mli_alibi_slopes; n is then ignored).  The engine keeps a device
+ * copy.  Pages, pool, projection, prefill and the decoder head never see the bias.  Before the first step or run;
+ * MLI_ENGINE_PAGED, MLI_ENGINE_PAGED_GEMM or MLI_ENGINE_PAGED_BF16 with lean layers.  Composes with mli_engine_set_heads (the
+ * same count again), _set_kv_heads, _set_window, _set_sinks, _set_page_release, _set_logprobs, sampling, both loops,
+ * n_forward_rounds and step graphs; every setter validates the combination, whichever comes last.  -1 with a message for a
+ * null engine, n_heads < 2 or n != n_heads, a non-finite slope, MLI_ENGINE_CONTIGUOUS and MLI_ENGINE_PAGED_FP8, a started
+ * engine, lean_layers = 0 (mli_engine_configure(e, 0, ...) afterwards is refused likewise, as is mli_engine_set_heads with
+ * another count), and an engine with prompt log-probabilities (mli_engine_set_prompt_logprobs afterwards is refused likewise:
+ * the prompt scan has no bias, and a prompt would be scored under another model than the one that decodes).  Without the call
+ * nothing changes anywhere. */
+int mli_engine_set_alibi(mli_engine* engine, const float* slopes_host, int n);
+
 /* EXTENSION: sliding-window attention (mli_kernels.h: mli_paged_attention_lean_window).  Every row attends its newest
  * `window` tokens only.  The window changes which slots the scan reads and nothing else: admission, page growth,
  * preemption, re-prefill, n_forward_rounds (the window follows the device-side length), step graphs, sampling and the

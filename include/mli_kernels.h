@@ -306,6 +306,42 @@ int mli_paged_attention_lean_gqa(void* const* page_table, const int* lengths, co
                                  int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
                                  int n_sink, int elem, void* workspace, size_t workspace_bytes, void* stream);
 
+/* EXTENSION: ALiBi, A LINEAR POSITION BIAS PER QUERY HEAD, for the multi-head scan (the alibi_slopes argument of other serving
+ * stacks' paged attention; the BLOOM / MPT / Baichuan family).  slopes: n_heads fp32 values in DEVICE memory, one per query
+ * head, finite, of any sign.  For row b with L = min(lengths[b], n_sequence), query head h, g = n_heads / n_kv_heads and an
+ * attended slot s:
+ *     x[h][s] = (q_h . K_{h/g}[s]) / sqrtf(head_dim) + slopes[h] * (s - (L - 1))
+ * s is the token's ABSOLUTE slot in the row -- not its position in the page, the item, or the virtual row of sink pages and
+ * window pages: the gap under sinks counts towards the distance.  The slope is the QUERY head's: under grouping the g heads of
+ * a group read the same K/V and carry different slopes.  The bias is 0 at the newest token and, with positive slopes, <= 0
+ * everywhere (fp32 scores stay small where the probability mass is).  The attended set for (window, n_sink), the softmax, p . V,
+ * the zero row for L == 0 and the never-read dead slots, gap slots and gap pages are mli_decode_scan_paged_gqa's.  Slopes all
+ * 0.0f give the bits of that call; L == 1, and a one-slot window without sinks, give V's row L - 1 bit for bit.
+ * One scan launch ("scan_heads_alibi"), the grid, item size, mli_tune keys and workspace
+ * (mli_attention_heads_workspace_bytes(n_batch, n_sequence, emb_dim, n_heads): one buffer serves plain and ALiBi calls) of
+ * the _gqa call.  Shapes: what that call takes with n_heads >= 2 -- head_dim 32, 64, 128 or 256, fp32 pages to emb_dim 512,
+ * bf16 pages to 1024; n_kv_heads == n_heads: no grouping.  MLI_ERR_BAD_ARG, decided before anything is launched: n_heads == 1
+ * (the single-head scans have no bias), fp8 pages, a null slopes, and every argument the _gqa call refuses.
+ * MLI_ERR_WORKSPACE as there. */
+int mli_decode_scan_paged_alibi(const float* q_output, const void* const* page_table, const int* lengths,
+                                float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads,
+                                int window, int n_sink, const float* slopes, int elem, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
+/* mli_paged_attention_lean_gqa with the bias: fill (n_new_items rows) -> latest -> the scan above.  Fill and projection never
+ * see the slopes. */
+int mli_paged_attention_lean_alibi(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                   const int* new_batch_idx, float* q_output, float* attention_result, int n_batch,
+                                   int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
+                                   int n_sink, const float* slopes, int elem, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
+/* The standard ALiBi slopes of n_heads heads, written to out_host (HOST memory, n_heads floats; a host function, no GPU).  With
+ * n = 2^floor(log2 n_heads): out[i] = (float)pow(2, -8 (i + 1) / n) for i < n; for n_heads > n the remaining n_heads - n are
+ * (float)pow(2, -4 (2 k + 1) / n), k = 0 ..., every other slope of the 2 n series.  n_heads < 1 or a null pointer:
+ * MLI_ERR_BAD_ARG. */
+int mli_alibi_slopes(int n_heads, float* out_host);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */
@@ -701,6 +737,7 @@ int mli_tune(const char* key, int value);
  *   "scan_chunked"           the single-head chunked scan, lean or materialising, every grid form
  *   "scan_heads_window"      the scans with several heads, a window, sinks or grouped K/V heads
  *   "scan_prompt"            the causal multi-query scan over prompt positions (mli_prompt_scan_paged)
+ *   "scan_heads_alibi"       the multi-head scans with a position bias per head (mli_decode_scan_paged_alibi)
  * Forms, counted beside the launch's kernel family:
  *   "latest_compact"         a decode projection over the compacted list of non-empty rows ("latest_compact"; the panel and
  *                            the LDS-DMA kernel have no such list)

@@ -2,6 +2,8 @@
 // order, issued back to back on one stream.
 //   src/kernels/self_attention_inference_optimized.cu:282-301
 //   src/kernels/paged_attention.cu:358-377, src/kernels/paged_attention_cublas.cu:260-280
+#include <cmath>
+
 #include "scan_launch.hpp"
 
 namespace mli {
@@ -70,6 +72,10 @@ int launch_window_decode(const float*, const void* const*, const int*, float*, i
 template <class E>
 int launch_heads_scan(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, ScanKind, int, int,
                       void*, size_t, hipStream_t);
+// ... and the multi-head scans with a position bias per head (attention_alibi.hpp: ..., n_sink, slopes)
+template <class E>
+int launch_heads_alibi_scan(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, ScanKind, int, int,
+                            const float*, void*, size_t, hipStream_t);
 
 // What every lean paged composition starts with, by page element type (MLI_ELEM_*; bf16 weights for bf16 and fp8 pages):
 // fill the n_new_items new rows, then project every non-empty row's last token (k, v appended, q to q_output)
@@ -164,6 +170,25 @@ static int sinks_front(int B, int S, int D, int n_heads, int window, int n_sink,
 static int gqa_front(int B, int S, int D, int n_heads, int n_kv_heads, int window, int n_sink, int elem) {
     if ((elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) || n_sink < 0 || S < 1) return MLI_ERR_BAD_ARG;
     return lean_scan_args(B, S, D, n_heads, n_kv_heads, window, n_sink, elem);
+}
+// _alibi: the _gqa front with two heads at least (the single-head scans have no bias) and the slopes given
+static int alibi_front(int B, int S, int D, int n_heads, int n_kv_heads, int window, int n_sink, const float* slopes, int elem) {
+    if (n_heads < 2 || slopes == nullptr) return MLI_ERR_BAD_ARG;
+    if (!gqa_shape_supported(B, S, D, n_heads, n_kv_heads, elem)) return MLI_ERR_BAD_ARG;   // (holds n_kv_heads and fp8 too)
+    return gqa_front(B, S, D, n_heads, n_kv_heads, window, n_sink, elem);
+}
+
+// the scan behind the _alibi entry points, after alibi_front (kind = its answer)
+static int launch_alibi_scan(int kind, const float* q, const void* const* page_table, const int* lengths, float* out, int B,
+                             int S, int D, int n_heads, int n_kv_heads, int window, int n_sink, const float* slopes, int elem,
+                             void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const WsBody body = ws_body(workspace, workspace_bytes);
+    const int lg = heads_lanes_log2(B, S, D, n_heads, elem);
+    const auto go = [&](auto e) {
+        return launch_heads_alibi_scan<decltype(e)>(q, page_table, lengths, out, B, S, D, n_heads, n_kv_heads, lg, (ScanKind)kind,
+                                                    window, n_sink, slopes, body.ptr, body.bytes, st);
+    };
+    return elem == MLI_ELEM_BF16 ? go(ElemBF16{}) : go(ElemF32{});
 }
 // ---- prompt log-probabilities (attention_prompt.hpp) ----------------------------------------------------------------------------
 int launch_prompt_project_q(int, const void* const*, const int*, const int*, const int*, const int*, const void*, void*, float*,
@@ -360,6 +385,41 @@ int mli_paged_attention_lean_gqa(void* const* page_table, const int* lengths, co
     return mli::launch_lean_attention(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_batch,
                                       n_sequence, emb_dim, n_new_items, n_heads, n_kv_heads, window, n_sink, workspace,
                                       workspace_bytes, mli::as_stream(stream));
+}
+
+int mli_decode_scan_paged_alibi(const float* q_output, const void* const* page_table, const int* lengths,
+                                float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads,
+                                int window, int n_sink, const float* slopes, int elem, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    const int kind = mli::alibi_front(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, slopes, elem);
+    if (kind < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_alibi_scan(kind, q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
+                                  n_kv_heads, window, n_sink, slopes, elem, workspace, workspace_bytes, mli::as_stream(stream));
+}
+
+int mli_paged_attention_lean_alibi(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                   const int* new_batch_idx, float* q_output, float* attention_result, int n_batch,
+                                   int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
+                                   int n_sink, const float* slopes, int elem, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    const int kind = mli::alibi_front(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, slopes, elem);
+    if (kind < 0) return MLI_ERR_BAD_ARG;
+    hipStream_t st = mli::as_stream(stream);
+    const int rc = mli::launch_fill_and_latest(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, n_batch,
+                                               n_sequence, emb_dim, n_new_items, st);
+    if (rc) return rc;
+    return mli::launch_alibi_scan(kind, q_output, reinterpret_cast<const void* const*>(page_table), lengths, attention_result,
+                                  n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, slopes, elem, workspace,
+                                  workspace_bytes, st);
+}
+
+int mli_alibi_slopes(int n_heads, float* out_host) {
+    if (n_heads < 1 || out_host == nullptr) return MLI_ERR_BAD_ARG;
+    int n = 1;
+    while (2 * n <= n_heads) n *= 2;
+    for (int i = 0; i < n; ++i) out_host[i] = (float)std::pow(2.0, -8.0 * (i + 1) / n);
+    for (int k = 0; n + k < n_heads; ++k) out_host[n + k] = (float)std::pow(2.0, -4.0 * (2 * k + 1) / n);
+    return 0;
 }
 
 int mli_get_latest_k_q_v_paged_lean(void* const* page_table, const int* lengths, const void* wk, const void* wq,

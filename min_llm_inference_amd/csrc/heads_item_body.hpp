@@ -58,12 +58,16 @@ __device__ __forceinline__ void heads_xor_step(float (&v)[NJ][16]) {
 // GQA = true (EXTENSION, attention_heads.hpp): grouped-query attention, gq = n_heads / n_kv_heads query heads per K/V head.  Only
 // the unit a lane LOADS changes (gqa_kv_unit, scan_plan.hpp): the lanes of query head h read the K and V columns of K/V head
 // h / gq.  q, the per-lane state, the all-reduce inside a group, the merges and H are those of n_heads heads.
-template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false, bool SINK = false, bool GQA = false>
+// ALIBI = true (EXTENSION, attention_alibi.hpp): a linear position bias per query head, slopes[h] * (s - (L_row - 1)) added to
+// the scaled score of the row's absolute slot s -- 0 at the newest token.  A lane keeps the slope of its own head per lane
+// load; the bias is one fmaf between div_by and the page maximum, on the page's first absolute slot, which the body has
+// already.  The bias is absolute in the row, so the (m, l) of a row's items live in one frame and the merges do not change.
+template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false, bool SINK = false, bool GQA = false, bool ALIBI = false>
 __device__ __forceinline__ void heads_scan_item(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ out, float2* ml, float* partial, int S, int D, int lg, int H, int ct, int nchunk_max, int direct,
     unsigned* arrivals, int b, int c, bool first_grid_row, unsigned char* smem_raw, int window = 0, int n_sink = 0,
-    int gq = 1) {
+    int gq = 1, const float* __restrict__ slopes = nullptr) {
     static_assert(!SINK || WIN, "sinks exist beside a window only");
     constexpr int EPL = E::EPL;
     constexpr int kRowF = NJ * kWave * EPL;   // floats one wave parks
@@ -94,6 +98,11 @@ __device__ __forceinline__ void heads_scan_item(
         else voff[j] = live ? (unsigned)u * 16u : 0x40000000u;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) qr[j][e] = live ? q[(int64_t)b * D + u * EPL + e] : 0.f;
+    }
+    float slope[NJ];   // ALIBI: the slope of the lane's head per lane load (dead lanes: no head, nothing read)
+    if constexpr (ALIBI) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) slope[j] = lane + j * kWave < Du ? slopes[(lane + j * kWave) >> lg] : 0.f;
     }
     const int L_row = min(lengths[b], S);
     const int lo = WIN ? max(0, L_row - window) : 0;   // first slot the row attends
@@ -195,6 +204,14 @@ __device__ __forceinline__ void heads_scan_item(
             nlo = lo - first;
             nk = n_sink - first;
         }
+        // ALIBI: the page's first slot relative to the row's newest token; (float)int + (float)t is exact below 2^24
+        float rel0 = 0.f;
+        if constexpr (ALIBI) {
+            int first_abs;
+            if constexpr (SINK) first_abs = sink_page(s0 / kPage + pi, ps, skip) * kPage;
+            else first_abs = kPage * (skip + s0 / kPage + pi);
+            rel0 = (float)(first_abs - (L_row - 1));
+        }
         float sp[NJ][16];   // partial scores, then scores, then the page's probabilities (of the lane's head for j)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
@@ -231,6 +248,7 @@ __device__ __forceinline__ void heads_scan_item(
 #pragma unroll
                         for (int t = 0; t < 16; ++t) {
                             sp[j][t] = div_by(sp[j][t], scale, inv_scale);
+                            if constexpr (ALIBI) sp[j][t] = fmaf(slope[j], rel0 + (float)t, sp[j][t]);
                             pm = slot_live<WIN, SINK>(t, nt, nlo, nk) ? fmaxf(pm, sp[j][t]) : pm;
                         }
                         const float m_new = fmaxf(run_m[j], pm);

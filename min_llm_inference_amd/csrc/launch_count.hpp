@@ -31,6 +31,7 @@ enum LaunchFamily {
     kLfScanRowsGridOrder, // ... and those in grid order
     kLfScanHeadsWindow,   // attention_heads.hpp / attention_window.hpp: several heads, a window, sinks, grouped heads
     kLfScanPrompt,        // attention_prompt.hpp: the causal multi-query scan over prompt positions
+    kLfScanHeadsAlibi,    // attention_alibi.hpp: the multi-head scans with a linear position bias per query head
     kLaunchFamilies
 };
 
@@ -39,7 +40,7 @@ constexpr const char* kLaunchFamilyNames[kLaunchFamilies] = {
     "gemm_bf16_rows64", "gemm_bf16_deep",   "gemm_bf16_rows128",     "gemm_bf16_dma",     "gemm_bf16_fill",
     "latest_compact",  "fill_flat",         "fill_per_row",          "prefill_fused",     "prefill_two_launch",
     "scan_equal_shares", "scan_chunked",    "scan_rows_ordered",     "scan_rows_grid_order", "scan_heads_window",
-    "scan_prompt",
+    "scan_prompt",     "scan_heads_alibi",
 };
 
 inline thread_local uint64_t g_launch_counts[kLaunchFamilies] = {};

@@ -39,7 +39,7 @@ def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
 class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
                  n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None,
-                 release_pages=False, n_kv_heads=None, logprobs=None, prompt_logprobs=False):
+                 release_pages=False, n_kv_heads=None, logprobs=None, prompt_logprobs=False, alibi=None):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -61,6 +61,8 @@ class Engine:
             self.set_logprobs(logprobs)
         if prompt_logprobs:
             self.set_prompt_logprobs(True)
+        if alibi is not None and alibi is not False:
+            self.set_alibi(None if alibi is True else alibi)
 
     def _check(self, rc):
         if rc != 0:
@@ -75,6 +77,16 @@ class Engine:
         serve the query heads; only the first n_kv_heads * emb_dim / n_heads output columns of wk / wv matter.  Before the
         first step or run, fp32 / bf16 paged kinds; n_kv_heads == n_heads changes nothing."""
         self._check(self._lib.mli_engine_set_kv_heads(self._h, int(n_kv_heads)))
+
+    def set_alibi(self, slopes=None):
+        """ALiBi (mli_engine_set_alibi): every decode scan adds slopes[h] * (s - (L - 1)) to query head h's scaled scores.
+        slopes: one finite value per head of the engine's n_heads (>= 2), or None for the standard slopes
+        (ops.alibi_slopes).  Before the first step or run, fp32 / bf16 paged kinds, not with prompt log-probabilities."""
+        if slopes is None:
+            self._check(self._lib.mli_engine_set_alibi(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(slopes, dtype=np.float32).reshape(-1)
+        self._check(self._lib.mli_engine_set_alibi(self._h, a.ctypes.data_as(ctypes.c_void_p), int(a.size)))
 
     def set_window(self, window):
         """Sliding-window attention (mli_engine_set_window): every row attends its newest `window` tokens.  Before the

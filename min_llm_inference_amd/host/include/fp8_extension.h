@@ -22,6 +22,7 @@ public:
 private:  // the fp8 scan has one head: of the option setters the layer has set_window, set_sinks and set_page_release
     using PagedAttentionOptionSetters::set_n_heads;
     using PagedAttentionOptionSetters::set_n_kv_heads;
+    using PagedAttentionOptionSetters::set_alibi_slopes;
 };
 
 class PagedAttentionFp8InferenceModel : public PagedInferenceModel {
@@ -34,6 +35,7 @@ public:
 private:
     using PagedAttentionOptionSetters::set_n_heads;  // as the layer
     using PagedAttentionOptionSetters::set_n_kv_heads;
+    using PagedAttentionOptionSetters::set_alibi_slopes;
     DecoderHead& decoder_head() override { return decoder_head_; }
     PagedAttentionFp8Layer attention_layer_;
     // lean only: the scratch of mli_decoder_scratch_bytes, and the logits buffer once sampling is set

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <memory>
+#include <vector>
 
 #include "kernels/paged_attention.h"
 #include "tensor.hpp"
@@ -52,12 +53,19 @@ struct PagedAttentionOptions {
     // row's live tokens only and follows no table entry of a dead page (mli_paged_prefill_window)
     bool page_release = false;
     PromptScoring* prompt_logprobs = nullptr;   // prompt log-probabilities: who scores the new rows' prompts (nullptr: nobody)
+    // ALiBi: one slope per query head ([n_heads], device memory, owned here; null: no bias) -- mli_paged_attention_lean_alibi
+    std::shared_ptr<TensorFloat> alibi_slopes;
 };
 
 // The setters of the option set, defined once for every class that has them: a layer owns the struct, a model hands out
-// its layer's.  A class whose scan has one head only (fp8 pages) takes set_n_heads / set_n_kv_heads out of its interface.
+// its layer's.  A class whose scan has one head only (fp8 pages) takes set_n_heads / set_n_kv_heads / set_alibi_slopes out
+// of its interface.
 class PagedAttentionOptionSetters {
 public:
+    // EXTENSION: ALiBi -- slopes[h] * (s - (L - 1)) added to query head h's scaled scores; n_heads finite values, uploaded
+    // to a device copy the option set owns.  An empty vector takes the bias away again.  A non-finite slope throws here; the
+    // count is held to n_heads (>= 2) at every forward, whichever setter came last (PagedAttentionLayerCore::check_alibi).
+    void set_alibi_slopes(const std::vector<float>& slopes);
     void set_n_heads(int n_heads) { options().n_heads = n_heads; }
     void set_n_kv_heads(int n_kv_heads) { options().n_kv_heads = n_kv_heads; }
     void set_window(int window) { options().window = window; }
@@ -92,6 +100,9 @@ protected:
     // with rows too wide for the single-pass kernel differs by element type
     int lean_scan(TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_batch_idx,
                   TensorFloat& attention_result, int n_new_items, int n_heads, int n_kv_heads);
+    // throws where slopes are set and are not one per head of n_heads >= 2 heads, or the lean layers are off: first thing in
+    // every forward, so that no scan reads past the slopes and no composition without a bias drops them
+    void check_alibi() const;
 
     int elem_;
     Weights wk_, wq_, wv_;

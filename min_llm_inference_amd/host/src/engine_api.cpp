@@ -1,5 +1,6 @@
 // extern "C" engine sessions (include/mli_engine.h): the reference's engine loops in resumable form, so a
 // host in another language -- or bench.py -- can step them and interleave the multi-GPU token gather.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -563,6 +564,8 @@ int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
                                      "compositions only");
         if (o.window > 0 && o.window < e->cfg.n_sequence && lean_layers == 0)
             throw std::runtime_error("sliding-window attention (mli_engine_set_window) has the lean compositions only");
+        if (o.alibi_slopes && lean_layers == 0)
+            throw std::runtime_error("ALiBi (mli_engine_set_alibi) has the lean compositions only");
         if (lean_layers >= 0) e->lean_layers = lean_layers != 0;
         if (step_graphs >= 0) e->step_graphs = step_graphs != 0;
         if (e->cfg.kind == MLI_ENGINE_PAGED_FP8 && !e->lean_layers)
@@ -591,6 +594,9 @@ int mli_engine_set_heads(mli_engine* e, int n_heads) {
             if (o.n_kv_heads != 0 && n_heads % o.n_kv_heads != 0)
                 throw std::runtime_error("mli_engine_set_heads: the stored n_kv_heads (mli_engine_set_kv_heads) does not divide "
                                          "n_heads");
+            if (o.alibi_slopes)
+                throw std::runtime_error("mli_engine_set_heads: the stored ALiBi slopes (mli_engine_set_alibi) are those of " +
+                                         std::to_string(o.n_heads) + " heads");
             o.n_heads = n_heads;
         }
     })
@@ -620,6 +626,38 @@ int mli_engine_set_kv_heads(mli_engine* e, int n_kv_heads) {
             }
             o.n_kv_heads = then;
         }
+    })
+}
+
+// The slopes are stored with the option set (the layer owns the device copy).  The shapes are the multi-head scan's, which
+// set_heads / set_kv_heads / set_window have validated; they are checked again here.
+int mli_engine_set_alibi(mli_engine* e, const float* slopes_host, int n) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (e->started) throw std::runtime_error("mli_engine_set_alibi after the engine has started");
+        if (!e->heads_kind())
+            throw std::runtime_error("mli_engine_set_alibi: ALiBi serves the fp32 and bf16 paged engines");
+        PagedAttentionOptions& o = e->options();
+        if (o.n_heads < 2)
+            throw std::runtime_error("mli_engine_set_alibi: n_heads must be >= 2 (mli_engine_set_heads comes first; the "
+                                     "single-head scans have no bias)");
+        if (slopes_host != nullptr && n != o.n_heads)
+            throw std::runtime_error("mli_engine_set_alibi: n must be the engine's n_heads (" + std::to_string(o.n_heads) + ")");
+        if (!e->lean_layers) throw std::runtime_error("mli_engine_set_alibi: ALiBi has the lean compositions only");
+        if (e->prompt_logprobs_wanted)
+            throw std::runtime_error("mli_engine_set_alibi: not with prompt log-probabilities (the prompt scan has no bias: the "
+                                     "prompt would be scored under another model than the one that decodes)");
+        std::vector<float> slopes((size_t)o.n_heads);
+        if (slopes_host != nullptr) std::copy(slopes_host, slopes_host + o.n_heads, slopes.begin());
+        else if (mli_alibi_slopes(o.n_heads, slopes.data()) != 0) throw std::runtime_error("mli_engine_set_alibi: mli_alibi_slopes");
+        for (float s : slopes)
+            if (!std::isfinite(s)) throw std::runtime_error("mli_engine_set_alibi: every slope must be finite");
+        const int n_kv_heads = o.n_kv_heads != 0 ? o.n_kv_heads : o.n_heads;
+        if (!mli::gqa_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, o.n_heads, n_kv_heads, e->elem()))
+            throw std::runtime_error("mli_engine_set_alibi: the scan does not take this (n_batch, n_sequence, emb_dim, n_heads, "
+                                     "n_kv_heads)");
+        mli::runtime::use_device(e->cfg.device);
+        e->paged->set_alibi_slopes(slopes);
     })
 }
 
@@ -808,6 +846,9 @@ int mli_engine_set_prompt_logprobs(mli_engine* e, int enabled) {
         if (e->release_pages)
             throw std::runtime_error("mli_engine_set_prompt_logprobs: not with page release (mli_engine_set_page_release: its "
                                      "prefill skips dead pages, so the prompt's K / V are not all there)");
+        if (enabled && e->options().alibi_slopes)
+            throw std::runtime_error("mli_engine_set_prompt_logprobs: not with ALiBi (mli_engine_set_alibi: the prompt scan has "
+                                     "no bias, so the prompt would be scored under another model than the one that decodes)");
         if (!e->prompt_shape_ok())
             throw std::runtime_error("mli_engine_set_prompt_logprobs: the prompt scan does not take this (n_batch, n_sequence, "
                                      "emb_dim, n_heads, n_kv_heads): rows of at most two 16-byte lane loads");

@@ -1,5 +1,9 @@
 #include "layers.h"
 
+#include <algorithm>
+#include <cmath>
+#include <stdexcept>
+#include <string>
 #include <utility>
 
 #include "bf16_extension.h"  // launch_paged_attention_decoder_multi_rounds_bf16
@@ -41,6 +45,20 @@ void SelfAttentionLayer::prefill(const TensorFloat& emb_table, const TensorFloat
                    n_new_items);
 }
 
+void PagedAttentionOptionSetters::set_alibi_slopes(const std::vector<float>& slopes) {
+    if (slopes.empty()) {
+        options().alibi_slopes.reset();
+        return;
+    }
+    for (float s : slopes)
+        if (!std::isfinite(s)) throw std::invalid_argument("set_alibi_slopes: every slope must be finite");
+    TensorFloat host(std::vector<size_t>{slopes.size()}, DeviceType::HOST, TensorDataType::SYNC_ALLOCATE);
+    std::copy(slopes.begin(), slopes.end(), host.data());
+    auto device = std::make_shared<TensorFloat>(std::vector<size_t>{slopes.size()}, DeviceType::DEVICE, TensorDataType::SYNC_ALLOCATE);
+    device->copy_from(host);
+    options().alibi_slopes = std::move(device);
+}
+
 template <class Weights>
 PagedAttentionLayerCore<Weights>::PagedAttentionLayerCore(int elem, Weights&& wk, Weights&& wq, Weights&& wv,
                                                           size_t n_batch, size_t emb_dim, size_t n_sequence)
@@ -65,15 +83,29 @@ void PagedAttentionLayerCore<Weights>::score_prompts(const TensorFloat& emb_tabl
                                     (int)emb_table.shape()[0]);
 }
 
+// The setters come in any order, so the slopes are held to the heads where they are used: at every forward, before anything
+// is launched.  n_heads >= 2 with lean layers off has thrown already (lean_paged_wanted); one head would take the
+// materialising composition, which has no bias, so slopes beside one head throw here instead of being dropped.
+template <class Weights>
+void PagedAttentionLayerCore<Weights>::check_alibi() const {
+    if (!options_.alibi_slopes) return;
+    if (options_.n_heads < 2 || options_.alibi_slopes->get_total_size() != (size_t)options_.n_heads)
+        throw std::runtime_error("ALiBi: " + std::to_string(options_.alibi_slopes->get_total_size()) + " slopes (set_alibi_slopes) "
+                                 "beside n_heads = " + std::to_string(options_.n_heads) + ": one slope per head, two heads at least");
+    if (!mli::runtime::lean_layers()) throw std::runtime_error("ALiBi exists in the lean composition only");
+}
+
 template <class Weights>
 int PagedAttentionLayerCore<Weights>::lean_scan(TensorFloatPoint& page_table, const TensorInt& lengths,
                                                 const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                                 int n_new_items, int n_heads, int n_kv_heads) {
+    check_alibi();
     return mli::runtime::lean_paged_attention(elem_, n_heads, options_.window, options_.n_sink,
                                               reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
                                               wk_.data(), wq_.data(), wv_.data(), new_batch_idx.data(), q_output_.data(),
                                               attention_result.data(), (int)page_table.shape()[0], (int)n_sequence_,
-                                              (int)wk_.shape()[0], n_new_items, n_kv_heads);
+                                              (int)wk_.shape()[0], n_new_items, n_kv_heads,
+                                              options_.alibi_slopes ? options_.alibi_slopes->data() : nullptr);
 }
 
 template class PagedAttentionLayerCore<TensorFloat>;
@@ -87,6 +119,7 @@ PagedAttentionFloatLayer::PagedAttentionFloatLayer(TensorFloat&& wk, TensorFloat
 bool PagedAttentionFloatLayer::forward_lean(TensorFloatPoint& page_table, const TensorInt& lengths,
                                             const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                             int n_new_items) {
+    check_alibi();
     if (!mli::runtime::lean_paged_wanted(options_.n_heads, options_.window, (int)n_sequence_)) return false;
     const int rc = lean_scan(page_table, lengths, new_batch_idx, attention_result, n_new_items, options_.n_heads,
                              options_.n_kv_heads);

@@ -8,6 +8,7 @@ Tensor shapes are derived from the torch shapes here in the same way.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from ._lib import MliError, load_library  # noqa: F401  (re-exported: ops.MliError, ops.load_library)
@@ -333,14 +334,47 @@ def decode_scan_paged_gqa(q_output, page_table, lengths, attention_result, n_hea
                (n_heads, n_kv_heads, window or 0, sinks or 0), n_heads, elem, q_output.device)
 
 
+def alibi_slopes(n_heads):
+    """The standard ALiBi slopes of n_heads heads (mli_alibi_slopes): a float32 numpy array; 2^(-8 (i + 1) / n) over the
+    largest power of two n <= n_heads, then every other slope of the 2 n series."""
+    out = np.empty(max(int(n_heads), 0), np.float32)
+    _check(load_library().mli_alibi_slopes(int(n_heads), out.ctypes.data_as(ctypes.c_void_p)), "mli_alibi_slopes")
+    return out
+
+
+def decode_scan_paged_alibi(q_output, page_table, lengths, attention_result, n_heads, n_kv_heads, window, sinks, slopes, elem,
+                            n_sequence):
+    """decode_scan_paged_gqa with ALiBi (mli_decode_scan_paged_alibi): slopes[h] * (s - (L - 1)) is added to query head h's
+    scaled score of the row's absolute slot s.  slopes: n_heads float32 values on the device; n_heads >= 2; n_kv_heads None
+    or n_heads: no grouping."""
+    B, D = q_output.shape
+    ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+    _check(load_library().mli_decode_scan_paged_alibi(_p(q_output), _p(page_table), _p(lengths), _p(attention_result), B,
+                                                      int(n_sequence), D, int(n_heads), int(n_kv_heads or n_heads),
+                                                      int(window or 0), int(sinks or 0), _p(slopes), int(elem), _p(ws), need,
+                                                      _stream()), "mli_decode_scan_paged_alibi")
+
+
 def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_new_items,
-                         n_sequence, elem=None, n_heads=1, window=None, sinks=None, n_kv_heads=None):
+                         n_sequence, elem=None, n_heads=1, window=None, sinks=None, n_kv_heads=None, alibi_slopes=None):
     """What the attention layers run: the paged composition without materialising scores / probabilities
     (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads != 1: the
     multi-head form (mli_paged_attention_lean_heads); window given: the sliding-window form
     (mli_paged_attention_lean_window); sinks given as well: the first `sinks` tokens of every row stay attended
     (mli_paged_attention_lean_sinks); n_kv_heads given: grouped-query attention with that many K/V heads
-    (mli_paged_attention_lean_gqa; wk / wv keep their [D, D] shape, their first n_kv_heads * D / n_heads columns matter)."""
+    (mli_paged_attention_lean_gqa; wk / wv keep their [D, D] shape, their first n_kv_heads * D / n_heads columns matter);
+    alibi_slopes given (n_heads float32 values on the device): the scan adds the position bias of decode_scan_paged_alibi
+    (mli_paged_attention_lean_alibi), with any of window, sinks and n_kv_heads."""
+    if alibi_slopes is not None:
+        if sinks is not None and window is None:
+            raise ValueError("sinks exist beside a window: pass window= as well")
+        B, D = page_table.shape[0], wk.shape[0]
+        ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+        _check(load_library().mli_paged_attention_lean_alibi(
+            _p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(new_batch_idx), _p(q_output), _p(attention_result), B,
+            int(n_sequence), D, int(n_new_items), int(n_heads), int(n_kv_heads or n_heads), int(window or 0), int(sinks or 0),
+            _p(alibi_slopes), _elem_of(wk, elem), _p(ws), need, _stream()), "mli_paged_attention_lean_alibi")
+        return
     if n_kv_heads is not None:
         if sinks is not None and window is None:
             raise ValueError("sinks exist beside a window: pass window= as well")
