@@ -205,6 +205,25 @@ int mli_engine_set_kv_heads(mli_engine* engine, int n_kv_heads);
  * nothing changes anywhere. */
 int mli_engine_set_alibi(mli_engine* engine, const float* slopes_host, int n);
 
+/* EXTENSION: rotary position embeddings (mli_kernels.h: mli_paged_prefill_rope, mli_paged_attention_lean_rope).  Every prefill
+ * and every decode projection of the engine rotates K (before its one rounding to the page's element type) and q by the
+ * token's absolute slot in its row; the scans, the pool, V, x and the decoder head do not change.  The position table
+ * (pos_table of mli_engine_create) is still added: a RoPE model passes zeros.  _set_rope builds the standard table
+ * (mli_rope_table) of theta for the engine's CURRENT n_heads (set the heads first; head_dim = emb_dim / n_heads, emb_dim for
+ * MLI_ENGINE_PAGED_FP8); _set_rope_table takes any table -- n_floats == n_sequence * head_dim floats of HOST memory,
+ * [n_sequence][head_dim / 2] (cos, sin), every one finite (the scaled variants are just another table; all (1, 0) gives the
+ * tokens of the engine without the call).  The engine keeps a device copy at a fixed address, so a captured step graph replays
+ * it.  Before the first step or run; MLI_ENGINE_PAGED, _PAGED_GEMM, _PAGED_BF16 and _PAGED_FP8 with lean layers.  Composes with
+ * heads, K/V heads, window, sinks, page release (positions are never renumbered), ALiBi, sampling, logprobs, both loops,
+ * n_forward_rounds and step graphs; a preempted item is prefilled again at the same slots.  -1 with a message for a null
+ * engine (or table), MLI_ENGINE_CONTIGUOUS, a started engine, lean_layers = 0 (mli_engine_configure(e, 0, ...) afterwards is
+ * refused likewise), an odd or fractional head_dim, a wrong n_floats, a non-finite entry or theta not finite or <= 0, an
+ * engine with prompt log-probabilities (mli_engine_set_prompt_logprobs afterwards is refused likewise: the prompt scan's q is
+ * not rotated), and mli_engine_set_heads with another count after a table was set.  Without the calls nothing changes
+ * anywhere. */
+int mli_engine_set_rope(mli_engine* engine, double theta);
+int mli_engine_set_rope_table(mli_engine* engine, const float* table_host, size_t n_floats);
+
 /* EXTENSION: sliding-window attention (mli_kernels.h: mli_paged_attention_lean_window).  Every row attends its newest
  * `window` tokens only.  The window changes which slots the scan reads and nothing else: admission, page growth,
  * preemption, re-prefill, n_forward_rounds (the window follows the device-side length), step graphs, sampling and the

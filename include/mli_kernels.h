@@ -342,6 +342,63 @@ int mli_paged_attention_lean_alibi(void* const* page_table, const int* lengths, 
  * MLI_ERR_BAD_ARG. */
 int mli_alibi_slopes(int n_heads, float* out_host);
 
+/* EXTENSION: ROTARY POSITION EMBEDDINGS (RoPE; the Llama / Mistral / Qwen / Gemma / Phi family) in the paged projection and the
+ * paged fills.  The columns of q and K are grouped in heads as for the scans: n_heads = H, hd = emb_dim / H, K/V head blocks
+ * at the same column offsets whatever n_kv_heads is.  The pairing is the INTERLEAVED one (GPT-J, Meta's Llama): inside every
+ * head, columns 2i and 2i + 1 form pair i, 0 <= i < hd / 2.  For the token at absolute slot s of its row, the GEMM's fp32
+ * accumulators a = y[2i], b = y[2i + 1] and (c, sn) = rope_table[s][i] give
+ *     y'[2i] = a c - b sn        y'[2i + 1] = b c + a sn
+ * computed in fp32 in the GEMM's epilogue (one product rounding, one fma rounding), BEFORE the one rounding of K to the page's
+ * element type; q stays fp32; V and the x segment are untouched.  s is the absolute slot in the row: L - 1 for the decode
+ * projection, the token's own slot for the fills -- under the flat row list too, and under a window the slot, not the live
+ * index.  Windows, sinks and page release never renumber positions (the convention of the ALiBi bias).  The scans do not
+ * change: a row's K is stored rotated by its slot and q is rotated by L - 1, so q . K depends on the distance alone.  wpe is
+ * still added by the prefill; a RoPE model passes zeros.
+ * rope_table: [n_sequence][hd / 2] pairs of fp32 (cos, sin) in DEVICE memory, 8-byte aligned, supplied by the caller -- the
+ * scaled variants (linear, NTK, YaRN, Llama-3) are just another table; a table of all (1, 0) gives the bytes of the entry
+ * point without the rotation in the whole pool and in q_output.  A table rather than sincosf in the kernel: fp32 range
+ * reduction at angles of thousands of radians, determinism, and the scaled variants.
+ * Kernels: the ROPE instantiations of the tiled MFMA GEMMs (every form their launchers select in the paged modes; the table is
+ * an argument of those instantiations alone).  The latency-shaped panel kernel and the LDS-DMA projection have no such switch
+ * yet: with a table their shapes take the tiled kernels.  Launch families "gemm_f32_rope" / "gemm_bf16_rope" are counted
+ * beside the family of the form that ran; the mli_tune keys of the un-rotated entry points apply.
+ * Shapes: what the un-rotated entry points take, with emb_dim % n_heads == 0 and hd even.  MLI_ERR_BAD_ARG, decided before
+ * anything is launched: a null rope_table, n_heads < 1, emb_dim % n_heads != 0, an odd hd, and everything the un-rotated
+ * call refuses.  No contiguous-cache form. */
+
+/* The standard table, written to out_host (HOST memory, n_sequence * head_dim floats; a host function, no GPU), in double:
+ * inv = pow(theta, -2.0 i / head_dim), ang = s * inv, out[s][i] = ((float)cos(ang), (float)sin(ang)).  MLI_ERR_BAD_ARG: a null
+ * pointer, n_sequence < 1, head_dim odd or < 2, theta not finite or <= 0. */
+int mli_rope_table(int n_sequence, int head_dim, double theta, float* out_host);
+
+/* mli_get_latest_k_q_v_paged_lean with the rotation: k (rotated, then rounded) and v appended to the page, q (rotated) to
+ * q_output, of every non-empty row's last token, slot L - 1. */
+int mli_get_latest_k_q_v_paged_rope(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                    float* q_output, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                    const float* rope_table, int elem, void* stream);
+
+/* mli_fill_new_k_v_cache_paged[_bf16] (and its fp8 form) with the rotation, reading x from the pages: K of every token of the
+ * n_new_items new rows, rotated by the token's slot; elem = MLI_ELEM_*. */
+int mli_fill_new_k_v_cache_paged_rope(void* const* page_table, const int* new_batch_idx, const int* lengths, const void* wk,
+                                      const void* wv, int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads,
+                                      const float* rope_table, int elem, void* stream);
+
+/* mli_paged_prefill_window's contract with rotated K: the prologue form and the two-launch form by mli_tune "prefill_fused",
+ * the flat list and the per-row grid by "fill_compact"; window == 0 (or no row with a dead page): no window. */
+int mli_paged_prefill_rope(const float* emb_table, const float* wpe, const int* inp, void* const* page_table, const int* lengths,
+                           const int* new_item_indices, const void* wk, const void* wv, int n_batch, int n_sequence, int emb_dim,
+                           int n_new_items, int window, int n_sink, int n_heads, const float* rope_table, int elem, void* stream);
+
+/* mli_paged_attention_lean_alibi with the rotation: fill_rope (n_new_items rows) -> latest_rope -> the existing scan router,
+ * unchanged.  slopes may be null, meaning no bias: the call then takes mli_paged_attention_lean_gqa's scans and rules, one
+ * head included -- and one head on fp8 pages, which the single-head scans take.  With slopes the rules are the _alibi call's.
+ * Additionally MLI_ERR_BAD_ARG as above. */
+int mli_paged_attention_lean_rope(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                  const int* new_batch_idx, float* q_output, float* attention_result, int n_batch,
+                                  int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
+                                  int n_sink, const float* slopes, const float* rope_table, int elem, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */
@@ -741,6 +798,8 @@ int mli_tune(const char* key, int value);
  * Forms, counted beside the launch's kernel family:
  *   "latest_compact"         a decode projection over the compacted list of non-empty rows ("latest_compact"; the panel and
  *                            the LDS-DMA kernel have no such list)
+ *   "gemm_f32_rope" / "gemm_bf16_rope"   a tiled fp32-MFMA / bf16-MFMA form with rotary position embeddings (the *_rope entry
+ *                            points; also at the shapes that would take "gemm_f32_panel" / "gemm_bf16_dma" without a table)
  *   "fill_flat" / "fill_per_row"   a prefill fill over the flat (new row, token) list / one tile grid per new row ("fill_compact")
  *   "prefill_fused" / "prefill_two_launch"   mli_prefill, mli_paged_prefill[_window] with new rows: the encoder as the fill's
  *                            prologue / encoder + fill ("prefill_fused")

@@ -76,6 +76,11 @@ SIGNATURES = {
     "mli_decode_scan_paged_alibi": [_P] * 4 + [_I] * 7 + [_P, _I, _P, _Z, _P],
     "mli_paged_attention_lean_alibi": [_P] * 8 + [_I] * 8 + [_P, _I, _P, _Z, _P],
     "mli_alibi_slopes": [_I, _P],
+    "mli_rope_table": [_I, _I, ctypes.c_double, _P],
+    "mli_get_latest_k_q_v_paged_rope": [_P] * 6 + [_I] * 4 + [_P, _I, _P],
+    "mli_fill_new_k_v_cache_paged_rope": [_P] * 5 + [_I] * 5 + [_P, _I, _P],
+    "mli_paged_prefill_rope": [_P] * 8 + [_I] * 7 + [_P, _I, _P],
+    "mli_paged_attention_lean_rope": [_P] * 8 + [_I] * 8 + [_P, _P, _I, _P, _Z, _P],
     "mli_get_latest_k_q_v_paged_lean": [_P] * 6 + [_I] * 4 + [_P],
     "mli_self_attention_lean": [_P] * 10 + [_I] * 5 + [_P, _Z, _P],
     "mli_decode_scan_contiguous": [_P] * 5 + [_I] * 3 + [_P, _Z, _P],
@@ -162,6 +167,8 @@ ENGINE_SIGNATURES = {
     "mli_engine_set_sinks": [_P, _I],
     "mli_engine_set_kv_heads": [_P, _I],
     "mli_engine_set_alibi": [_P, _P, _I],
+    "mli_engine_set_rope": [_P, ctypes.c_double],
+    "mli_engine_set_rope_table": [_P, _P, _Z],
     "mli_engine_set_page_release": [_P, _I],
     "mli_engine_get_page_stats": [_P, ctypes.POINTER(EnginePageStats)],
     "mli_engine_set_lean_layers": [_I],

@@ -77,6 +77,13 @@ template <class E>
 int launch_heads_alibi_scan(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, ScanKind, int, int,
                             const float*, void*, size_t, hipStream_t);
 
+// EXTENSION, rotary position embeddings (proj_gemm.hip): the projection and the fills with K and q rotated in the epilogue
+int rope_half(int D, int n_heads, const float* table);
+int launch_latest_paged_rope(int, void* const*, const int*, const void*, const void*, const void*, float*, int, int, int, int,
+                             const float*, hipStream_t);
+int launch_fill_paged_rope(int, const float*, const float*, const int*, void* const*, const int*, const int*, const void*,
+                           const void*, int, int, int, int, bool, int, int, int, const float*, hipStream_t);
+
 // What every lean paged composition starts with, by page element type (MLI_ELEM_*; bf16 weights for bf16 and fp8 pages):
 // fill the n_new_items new rows, then project every non-empty row's last token (k, v appended, q to q_output)
 static int launch_fill_and_latest(int elem, void* const* page_table, const int* lengths, const void* wk, const void* wq,
@@ -420,6 +427,86 @@ int mli_alibi_slopes(int n_heads, float* out_host) {
     for (int i = 0; i < n; ++i) out_host[i] = (float)std::pow(2.0, -8.0 * (i + 1) / n);
     for (int k = 0; n + k < n_heads; ++k) out_host[n + k] = (float)std::pow(2.0, -4.0 * (2 * k + 1) / n);
     return 0;
+}
+
+// ---- EXTENSION: rotary position embeddings ------------------------------------------------------------------------------------
+int mli_rope_table(int n_sequence, int head_dim, double theta, float* out_host) {
+    if (out_host == nullptr || n_sequence < 1 || head_dim < 2 || head_dim % 2 != 0 || !std::isfinite(theta) || theta <= 0.0)
+        return MLI_ERR_BAD_ARG;
+    const int half = head_dim / 2;
+    for (int i = 0; i < half; ++i) {
+        const double inv = std::pow(theta, -2.0 * i / head_dim);
+        for (int s = 0; s < n_sequence; ++s) {
+            const double ang = s * inv;
+            out_host[((size_t)s * half + i) * 2] = (float)std::cos(ang);
+            out_host[((size_t)s * half + i) * 2 + 1] = (float)std::sin(ang);
+        }
+    }
+    return 0;
+}
+
+int mli_paged_prefill_rope(const float* emb_table, const float* wpe, const int* inp, void* const* page_table, const int* lengths,
+                           const int* new_item_indices, const void* wk, const void* wv, int n_batch, int n_sequence, int emb_dim,
+                           int n_new_items, int window, int n_sink, int n_heads, const float* rope_table, int elem, void* stream) {
+    if (mli::rope_half(emb_dim, n_heads, rope_table) < 0 || window < 0 || n_sink < 0) return MLI_ERR_BAD_ARG;
+    if (emb_table == nullptr || wpe == nullptr || inp == nullptr || elem < MLI_ELEM_F32 || elem > MLI_ELEM_FP8) return MLI_ERR_BAD_ARG;
+    const bool win = mli::lean_scan_kind(n_sequence, window, n_sink) != mli::kScanPlain;   // else no row has a dead page
+    hipStream_t st = mli::as_stream(stream);
+    // the form is mli_paged_prefill[_window]'s: the prologue form, or encoder + fill beyond emb_dim 512 (fp8: always the prologue)
+    const bool fused = elem == MLI_ELEM_FP8 || mli::prefill_fuses(emb_dim);
+    int rc;
+    if (fused) {
+        rc = mli::launch_fill_paged_rope(elem, emb_table, wpe, inp, page_table, new_item_indices, lengths, wk, wv, n_batch,
+                                         n_sequence, emb_dim, n_new_items, win, window, n_sink, n_heads, rope_table, st);
+        if (!rc && n_new_items > 0) mli::count_launch(mli::kLfPrefillFused);
+        return rc;
+    }
+    if (n_new_items > 0 && (n_batch <= 0 || n_sequence % mli::kPage != 0 || emb_dim % (elem == MLI_ELEM_BF16 ? 8 : 4) != 0))
+        return MLI_ERR_BAD_ARG;   // what the fill refuses, before the encoder is launched
+    if (n_new_items > 0) mli::count_launch(mli::kLfPrefillTwoLaunch);
+    if (win)
+        rc = mli::launch_paged_encoder_window(emb_table, wpe, inp, page_table, lengths, new_item_indices, n_batch, n_sequence,
+                                              emb_dim, n_new_items, window, n_sink, elem, st);
+    else if (elem == MLI_ELEM_BF16)
+        rc = mli_paged_attention_encoder_bf16(emb_table, wpe, inp, reinterpret_cast<mli_bf16* const*>(page_table), lengths,
+                                              new_item_indices, n_batch, n_sequence, emb_dim, n_new_items, stream);
+    else
+        rc = mli_paged_attention_encoder(emb_table, wpe, inp, reinterpret_cast<float* const*>(page_table), lengths,
+                                         new_item_indices, n_batch, n_sequence, emb_dim, n_new_items, stream);
+    if (rc) return rc;
+    return mli::launch_fill_paged_rope(elem, nullptr, nullptr, nullptr, page_table, new_item_indices, lengths, wk, wv, n_batch,
+                                       n_sequence, emb_dim, n_new_items, win, window, n_sink, n_heads, rope_table, st);
+}
+
+// fill_rope -> latest_rope -> the scan router, unchanged: with slopes the _alibi scan under its front, without them the _gqa
+// call's (one head included; one head also on fp8 pages, which the single-head scans take and _gqa has no need to)
+int mli_paged_attention_lean_rope(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                  const int* new_batch_idx, float* q_output, float* attention_result, int n_batch,
+                                  int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
+                                  int n_sink, const float* slopes, const float* rope_table, int elem, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    if (mli::rope_half(emb_dim, n_heads, rope_table) < 0) return MLI_ERR_BAD_ARG;
+    int kind;
+    if (slopes != nullptr)
+        kind = mli::alibi_front(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, slopes, elem);
+    else if (elem == MLI_ELEM_FP8 && n_heads == 1 && n_kv_heads == 1 && n_sink >= 0 && n_sequence >= 1)
+        kind = mli::lean_scan_args(n_batch, n_sequence, emb_dim, 1, 1, window, n_sink, elem);
+    else
+        kind = mli::gqa_front(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, elem);
+    if (kind < 0) return MLI_ERR_BAD_ARG;
+    hipStream_t st = mli::as_stream(stream);
+    int rc = mli::launch_fill_paged_rope(elem, nullptr, nullptr, nullptr, page_table, new_batch_idx, lengths, wk, wv, n_batch,
+                                         n_sequence, emb_dim, n_new_items, false, 0, 0, n_heads, rope_table, st);
+    if (!rc)
+        rc = mli::launch_latest_paged_rope(elem, page_table, lengths, wk, wq, wv, q_output, n_batch, n_sequence, emb_dim, n_heads,
+                                           rope_table, st);
+    if (rc) return rc;
+    const void* const* pt = reinterpret_cast<const void* const*>(page_table);
+    if (slopes != nullptr)
+        return mli::launch_alibi_scan(kind, q_output, pt, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
+                                      n_kv_heads, window, n_sink, slopes, elem, workspace, workspace_bytes, st);
+    return mli::launch_lean_scan(q_output, pt, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads, n_kv_heads,
+                                 window, n_sink, elem, workspace, workspace_bytes, st);
 }
 
 int mli_get_latest_k_q_v_paged_lean(void* const* page_table, const int* lengths, const void* wk, const void* wq,

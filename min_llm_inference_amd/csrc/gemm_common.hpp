@@ -289,5 +289,34 @@ __device__ __forceinline__ RowDesc resolve_row(const GemmArgs& g, int m, int z, 
     return r;
 }
 
+// ---- EXTENSION: rotary position embeddings in the paged epilogues (the ROPE switch of the tiled MFMA kernels) -----------------
+// In those epilogues a lane holds column n = n0 + wn + (lane & 31) of 16 rows, so columns 2i and 2i + 1 of a head -- pair i
+// of the interleaved (GPT-J / Meta Llama) convention -- sit in lanes l and l ^ 1 of the same register: one DPP quad permute
+// (0xB1) hands each lane its partner's accumulator.  Tiles are multiples of 32 columns and hd is even, so no pair straddles a
+// tile; the frequency index is (n % hd) / 2.  The permute is issued before the n < N and null-row guards: a guarded-off
+// lane still serves its partner.
+__device__ __forceinline__ float rope_partner(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true));
+}
+// y'[2i] = a c - b sn, y'[2i + 1] = b c + a sn for (a, b) = (y[2i], y[2i + 1]) and cs = (c, sn) of the row's slot: `own` is this
+// lane's accumulator, `other` its partner's, `odd` whether the lane holds column 2i + 1.  One product rounding and one fma
+// rounding in fp32; an identity entry (1, 0) hands `own` back bit for bit.
+__device__ __forceinline__ float rope_rotate(float own, float other, bool odd, float2 cs) {
+    return __builtin_fmaf(odd ? other : -other, cs.y, own * cs.x);
+}
+// The absolute slot of the row that resolve_row<MODE>(g, m, ...) resolves -- L - 1 for the latest modes (m = batch row), the
+// token's own slot for the fills (m = token) -- held inside [0, n_sequence), so that it indexes the table whatever the
+// lengths say.  A row that resolves to nothing gets some slot that is never used.
+template <bool LATEST>
+__device__ __forceinline__ int rope_row_slot(const GemmArgs& g, int m) {
+    const int s = LATEST ? (m < g.B ? g.lengths[m] - 1 : 0) : m;
+    return min(max(s, 0), g.S - 1);
+}
+// the slots of the workgroup's rows, beside o_ptr (an LDS array only the ROPE instantiations have)
+template <int ROWS>
+__device__ __forceinline__ int* rope_slots() {
+    __shared__ int slots[ROWS];
+    return slots;
+}
 
 }  // namespace mli

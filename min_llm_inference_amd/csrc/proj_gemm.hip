@@ -26,371 +26,13 @@ constexpr int kGemmThreads = 256;
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-// VEC4: K % 4 == 0, N % 4 == 0 and 16-byte aligned rows -> float4 global loads.
-// BF16 (paged modes only): x, W and the K/V outputs are bfloat16, q and the accumulation fp32.  Operands are
-// widened to fp32 while they are staged into LDS, so the product is still the exact fp32 MFMA chain
-// (bf16 x bf16 products are exact in fp32); a native v_mfma_f32_32x32x16_bf16 tile is the next step.
-// MT: 32-row sub-tiles per wave along M.  MT = 2 (128x64 workgroup tile) shares every weight fragment between two
-// MFMAs with independent accumulators: 1.5 instead of 2 LDS fragment reads per MFMA and half the barriers per flop.
-// KQ: 32-deep k slabs staged per tile.  Only KQ = 1 is instantiated: 128 k per barrier pair (KQ = 4) was measured
-// SLOWER for the latency-bound fp32 shapes (config 4 logits 23.8 -> 26.0 us, D = 2048 logits 61.8 -> 70.2 us) --
-// unlike the bf16 kernel, whose deep tile is a win (proj_gemm_bf16.hip).
-// MODE_ = kPagedFillLive (launched by the windowed prefill only) is kPagedFill with WIN set: the fill of a row's live tokens
-// under a sliding window with sinks (gemm_common.hpp, page_live.hpp).
-template <int MODE_, bool BT, bool VEC4, bool BF16 = false, int MT = 1, bool SPLIT = false>
-__global__ __launch_bounds__(SPLIT ? 2 * kGemmThreads : kGemmThreads) void gemm_f32_mfma_kernel(GemmArgs g) {
-    constexpr bool WIN = MODE_ == kPagedFillLive;   // the windowed prefill's fill: kPagedFill over the live tokens
-    constexpr int MODE = WIN ? kPagedFill : MODE_;
-    constexpr int BM = 64 * MT;   // shadows the namespace-level 64: rows per workgroup
-    constexpr int BK = 32;        // k extent of a staged tile
-    constexpr int KQ = 1;
-    constexpr int LDA = BM + 1;
-    constexpr int kBufs = SPLIT ? 2 : 1;
-    constexpr int kThreads = SPLIT ? 2 * kGemmThreads : kGemmThreads;
-    __shared__ float As[kBufs * BK * LDA];
-    constexpr int LDBX = BT ? LDBT : LDB;
-    __shared__ __align__(16) float Bs[kBufs * BK * LDBX];
-    __shared__ const float* a_ptr[BM];
-    __shared__ float* o_ptr[BM];
-    constexpr bool kFillMode = MODE == kNaiveFill || MODE == kPagedFill;
-    __shared__ const float* e_ptr[kFillMode ? BM : 1];  // embedding prologue: emb_table / wpe row of every A row
-    __shared__ const float* p_ptr[kFillMode ? BM : 1];
-
-    const int tiles_n = (g.N + BN - 1) / BN;
-    const int wsel = blockIdx.x / tiles_n;
-    const int n0 = (blockIdx.x % tiles_n) * BN;
-    const int m0 = blockIdx.y * BM;
-    const int z = blockIdx.z;
-    const int out_id = g.out_id[wsel];
-    const float* __restrict__ Bmat = g.w[wsel];
-
-    constexpr bool kFill = MODE == kNaiveFill || MODE == kPagedFill;
-    constexpr bool kLatest = MODE == kNaiveLatest || MODE == kPagedLatest;
-    __shared__ std::conditional_t<kFill || kLatest, FillIndex, NoFillIndex> fill_index[1];
-    const int tid = threadIdx.x;
-    int fill_total = 0;
-    if (kFill || kLatest) {
-        if (g.compact) {
-            fill_total = build_fill_index<kThreads, kLatest, WIN>(g, fill_index[0]);
-            if (m0 >= fill_total) return;  // workgroup-uniform
-        } else if (kFill && m0 >= g.lengths[g.new_batch_idx[z]]) {
-            return;  // whole tile beyond the row's length: nothing to do (reference …optimized.cu:43-45)
-        } else if (kFill && WIN && fill_tile_dead(g, m0, BM, z)) {
-            return;  // ... or wholly in dead pages
-        }
-    }
-
-    const bool embed = kFillMode && !BF16 && g.emb_table != nullptr;
-    if (tid < BM) {  // BM <= 128 < 256 threads
-        RowDesc r{nullptr, nullptr, nullptr, nullptr};
-        if ((kFill || kLatest) && g.compact) {
-            if (m0 + tid < fill_total) {
-                int zz, ss;
-                if (WIN) fill_index_lookup_live(g, fill_index[0], m0 + tid, zz, ss);
-                else fill_index_lookup(fill_index[0], kLatest ? g.B : g.n_new, m0 + tid, zz, ss);
-                r = kLatest ? resolve_row<MODE, BF16>(g, zz, 0, out_id) : resolve_row<MODE, BF16>(g, ss, zz, out_id);
-            }
-        } else if (!WIN || !fill_token_dead(g, m0 + tid, z)) {
-            r = resolve_row<MODE, BF16>(g, m0 + tid, z, out_id);
-        }
-        a_ptr[tid] = r.a;
-        o_ptr[tid] = r.o;
-        if (kFillMode) {
-            e_ptr[tid] = r.e;
-            p_ptr[tid] = r.p;
-        }
-    }
-    // only the contiguous layout keeps K transposed (kt_cache[b, n, s]): element stride S along n
-    constexpr bool kCanTranspose = MODE == kNaiveLatest || MODE == kNaiveFill;
-    const bool transposed_out = kCanTranspose && out_id == 0;
-    const int64_t o_stride = transposed_out ? g.S : 1;
-    __syncthreads();
-
-    // SPLIT: threads 0..255 (waves 0-3) multiply, threads 256..511 (waves 4-7) move the next tile into the other LDS buffer
-    const bool is_loader = SPLIT && tid >= kGemmThreads;
-    const int st = is_loader ? tid - kGemmThreads : tid;   // index among the staging threads
-    const int lane = tid & 63;
-    const int wave = (tid >> 6) & 3;
-    const int wm = (wave >> 1) * 32 * MT;
-    const int wn = (wave & 1) * 32;
-
-    // global -> register staging coordinates
-    //   A tile [BM][BK]: 8 threads per row (float4 along k), 32 rows per pass, 2 passes
-    //   B tile [BK][BN]: 16 threads per k-row (float4 along n), 16 k-rows per pass, 2 passes
-    //   B^T tile (BT): rows are n, float4 along k -- same shape as the A tile
-    const int a_row = st >> 3, a_kq = (st & 7) * 4;
-    const int b_row = st >> 4, b_nq = (st & 15) * 4;
-    constexpr int AP = 2 * MT;  // A staging passes of 32 rows
-    float4 a_regs[KQ][AP], b_regs[KQ][2];
-    // this thread's source rows, kept in registers: re-reading them from LDS every tile put a wait-for-LDS and a
-    // branch per pass into every k step
-    const float* a_src[AP];
-    const float* e_src[AP];
-    const float* p_src[AP];
-#pragma unroll
-    for (int p = 0; p < AP; ++p) {
-        a_src[p] = a_ptr[a_row + p * 32];
-        e_src[p] = kFillMode ? e_ptr[a_row + p * 32] : nullptr;
-        p_src[p] = kFillMode ? p_ptr[a_row + p * 32] : nullptr;
-    }
-    const bool writes_x = blockIdx.x == 0;  // first column tile of the first weight: every A element passes once
-
-    auto load_slab = [&](int k0, float4 (&a_reg)[AP], float4 (&b_reg)[2]) {
-#pragma unroll
-        for (int p = 0; p < AP; ++p) {
-            const float* ap = a_src[p];
-            const int k = k0 + a_kq;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (kFillMode && embed && ap != nullptr) {
-                // encoder as prologue: x = emb[tok] + wpe[s], the sum the encoder kernel writes (one fp32 add)
-                if (VEC4) {
-                    if (k < g.K) {
-                        const float4 e4 = *reinterpret_cast<const float4*>(e_src[p] + k);
-                        const float4 p4 = *reinterpret_cast<const float4*>(p_src[p] + k);
-                        v = make_float4(e4.x + p4.x, e4.y + p4.y, e4.z + p4.z, e4.w + p4.w);
-                        if (writes_x) *reinterpret_cast<float4*>(const_cast<float*>(ap) + k) = v;
-                    }
-                } else {
-                    float t[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (k + i < g.K) {
-                            t[i] = e_src[p][k + i] + p_src[p][k + i];
-                            if (writes_x) const_cast<float*>(ap)[k + i] = t[i];
-                        }
-                    v = make_float4(t[0], t[1], t[2], t[3]);
-                }
-            } else if (ap != nullptr) {
-                if (BF16) {
-                    if (k < g.K) v = load4_bf16(reinterpret_cast<const uint16_t*>(ap) + k);
-                } else if (VEC4) {
-                    if (k < g.K) v = *reinterpret_cast<const float4*>(ap + k);
-                } else {
-                    if (k + 0 < g.K) v.x = ap[k + 0];
-                    if (k + 1 < g.K) v.y = ap[k + 1];
-                    if (k + 2 < g.K) v.z = ap[k + 2];
-                    if (k + 3 < g.K) v.w = ap[k + 3];
-                }
-            }
-            a_reg[p] = v;
-        }
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (BT) {
-                const int n = n0 + a_row + p * 32;
-                const int k = k0 + a_kq;
-                if (n < g.N) {
-                    const float* bp = Bmat + (int64_t)n * g.K + k;
-                    if (VEC4) {
-                        if (k < g.K) v = *reinterpret_cast<const float4*>(bp);
-                    } else {
-                        if (k + 0 < g.K) v.x = bp[0];
-                        if (k + 1 < g.K) v.y = bp[1];
-                        if (k + 2 < g.K) v.z = bp[2];
-                        if (k + 3 < g.K) v.w = bp[3];
-                    }
-                }
-            } else {
-                const int k = k0 + b_row + p * 16;
-                const int n = n0 + b_nq;
-                if (k < g.K) {
-                    const float* bp = Bmat + (int64_t)k * g.N + n;
-                    if (BF16) {
-                        if (n < g.N) v = load4_bf16(reinterpret_cast<const uint16_t*>(Bmat) + (int64_t)k * g.N + n);
-                    } else if (VEC4) {
-                        if (n < g.N) v = *reinterpret_cast<const float4*>(bp);
-                    } else {
-                        if (n + 0 < g.N) v.x = bp[0];
-                        if (n + 1 < g.N) v.y = bp[1];
-                        if (n + 2 < g.N) v.z = bp[2];
-                        if (n + 3 < g.N) v.w = bp[3];
-                    }
-                }
-            }
-            b_reg[p] = v;
-        }
-    };
-    auto load_tile = [&](int k0) {
-#pragma unroll
-        for (int q = 0; q < KQ; ++q) load_slab(k0 + q * 32, a_regs[q], b_regs[q]);
-    };
-
-    auto store_slab = [&](float* As_q, float* Bs_q, const float4 (&a_reg)[AP], const float4 (&b_reg)[2]) {
-#pragma unroll
-        for (int p = 0; p < AP; ++p) {
-            const int m = a_row + p * 32;
-            As_q[(a_kq + 0) * LDA + m] = a_reg[p].x;
-            As_q[(a_kq + 1) * LDA + m] = a_reg[p].y;
-            As_q[(a_kq + 2) * LDA + m] = a_reg[p].z;
-            As_q[(a_kq + 3) * LDA + m] = a_reg[p].w;
-        }
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            if (BT) {
-                const int n = a_row + p * 32;
-                Bs_q[(a_kq + 0) * LDBX + n] = b_reg[p].x;
-                Bs_q[(a_kq + 1) * LDBX + n] = b_reg[p].y;
-                Bs_q[(a_kq + 2) * LDBX + n] = b_reg[p].z;
-                Bs_q[(a_kq + 3) * LDBX + n] = b_reg[p].w;
-            } else {
-                *reinterpret_cast<float4*>(&Bs_q[(b_row + p * 16) * LDBX + b_nq]) = b_reg[p];
-            }
-        }
-    };
-    auto store_tile = [&]() {
-#pragma unroll
-        for (int q = 0; q < KQ; ++q) store_slab(As + q * 32 * LDA, Bs + q * 32 * LDBX, a_regs[q], b_regs[q]);
-    };
-
-    f32x16 acc[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[mt][i] = 0.f;
-
-    const int nk = (g.K + BK - 1) / BK;
-    const int lk = lane >> 5;   // which of the 2 k's of an MFMA step this lane feeds
-    const int li = lane & 31;   // row (A) / column (B) inside the 32x32 wave tile
-
-    auto multiply = [&](const float* A, const float* B) {
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            const float b = B[(kk + lk) * LDBX + wn + li];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const float a = A[(kk + lk) * LDA + wm + mt * 32 + li];
-                // the K output of the contiguous layout is stored transposed: swap operands so
-                // that the sequence index lands on the lane (coalesced kt_cache stores)
-                if (transposed_out) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(b, a, acc[mt], 0, 0, 0);
-                else acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[mt], 0, 0, 0);
-            }
-        }
-    };
-    if constexpr (!SPLIT) {
-        load_tile(0);
-        store_tile();
-        __syncthreads();
-        for (int t = 0; t < nk; ++t) {
-            if (t + 1 < nk) load_tile((t + 1) * BK);  // in flight under the MFMAs below
-            multiply(As, Bs);
-            __syncthreads();
-            if (t + 1 < nk) {
-                store_tile();
-                __syncthreads();
-            }
-        }
-    } else {
-        // One wave doing everything in turn (issue loads, wait, write LDS, read fragments, multiply) is overlapped only by
-        // the other waves of its SIMD; with about one workgroup per CU (logits of 1024 rows, prefill of a few hundred
-        // tokens: 256 tiles of 64 x 64) nothing overlaps and the matrix pipe idles half the time.  Here four waves only load
-        // (two tiles in flight in their registers) and four only multiply, one barrier per k step -- the structure round 2
-        // found on the bf16 projection (whose loaders have since become LDS-DMA issuers, proj_gemm_bf16.hip).  Same MFMA
-        // chain per output element: bit-identical results.
-        float* As1 = As + BK * LDA;
-        float* Bs1 = Bs + BK * LDBX;
-        if (is_loader) {
-            float4 a2[AP], b2[2];
-            load_slab(0, a_regs[0], b_regs[0]);
-            if (1 < nk) load_slab(BK, a2, b2);
-            store_slab(As, Bs, a_regs[0], b_regs[0]);
-            if (2 < nk) load_slab(2 * BK, a_regs[0], b_regs[0]);
-            __syncthreads();  // tile 0 is in buffer 0
-            for (int t = 0; t < nk; t += 2) {
-                if (t + 1 < nk) store_slab(As1, Bs1, a2, b2);                       // tile t + 1
-                if (t + 3 < nk) load_slab((t + 3) * BK, a2, b2);
-                __syncthreads();
-                if (t + 1 < nk) {
-                    if (t + 2 < nk) store_slab(As, Bs, a_regs[0], b_regs[0]);      // tile t + 2
-                    if (t + 4 < nk) load_slab((t + 4) * BK, a_regs[0], b_regs[0]);
-                    __syncthreads();
-                }
-            }
-        } else {
-            __syncthreads();  // tile 0 is in buffer 0
-            for (int t = 0; t < nk; t += 2) {
-                multiply(As, Bs);
-                __syncthreads();
-                if (t + 1 < nk) {
-                    multiply(As1, Bs1);
-                    __syncthreads();
-                }
-            }
-        }
-    }
-
-    // epilogue: accumulator register r of lane l is tile element
-    //   (row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), col = l & 31)
-    if (MODE == kPlain && g.row_best != nullptr) {
-        // argmax epilogue (decoder logits): a row of the wave's 32x32 sub-tile lies across 32 lanes of one register
-        // -> butterfly over the 5 low lane bits; the two waves that share the rows meet in LDS (the staging tiles are
-        // free after the k loop's last barrier); one (max, index) pair per (row, column tile) goes to memory
-        float* best_v = As;                                   // [BM][2]
-        int* best_i = reinterpret_cast<int*>(As + BM * 2);    // [BM][2]   (BK * LDA >= 4 * BM floats)
-        const int n = n0 + wn + li;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            if (is_loader) break;  // (wave-uniform: the loader waves only meet the barrier below)
-            // a score takes part only if it beats -FLT_MAX, as in decoder_argmax_kernel (NaN and -inf never win)
-            float v[16];
-            int ix[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const bool takes_part = n < g.N && acc[mt][r] > -3.402823466e+38f;
-                v[r] = takes_part ? acc[mt][r] : -3.402823466e+38f;
-                ix[r] = takes_part ? n : -1;
-            }
-            // Transposing butterfly over the 32 lanes that hold one row per register: at every step a lane keeps half
-            // of its rows and trades the other half with its partner (15 exchanges instead of 16 x 5), branch-free,
-            // so the exchanges of different rows overlap.  Afterwards lane li holds row register (li >> 1) & 15.
-            argmax_butterfly_step<8>(v, ix, (lane & 16) != 0, 16);
-            argmax_butterfly_step<4>(v, ix, (lane & 8) != 0, 8);
-            argmax_butterfly_step<2>(v, ix, (lane & 4) != 0, 4);
-            argmax_butterfly_step<1>(v, ix, (lane & 2) != 0, 2);
-            {
-                const float ov = __shfl_xor(v[0], 1, kWave);
-                const int oi = __shfl_xor(ix[0], 1, kWave);
-                argmax_take(v[0], ix[0], ov, oi);
-            }
-            if ((li & 1) == 0) {
-                const int r = (li >> 1) & 15;
-                const int row = wm + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                best_v[row * 2 + (wave & 1)] = v[0];
-                best_i[row * 2 + (wave & 1)] = ix[0];
-            }
-        }
-        __syncthreads();
-        if (!is_loader && tid < BM && m0 + tid < g.M) {
-            float v = best_v[tid * 2];
-            int i = best_i[tid * 2];
-            argmax_take(v, i, best_v[tid * 2 + 1], best_i[tid * 2 + 1]);
-            g.row_best[(int64_t)(m0 + tid) * tiles_n + blockIdx.x % tiles_n] = RowBest{v, i};
-        }
-        return;
-    }
-    if (is_loader) return;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int trow = (r & 3) + 8 * (r >> 2) + 4 * lk;
-            if (transposed_out) {
-                const int n = n0 + wn + trow;   // rows of the swapped product run along N
-                const int mi = wm + mt * 32 + li;
-                float* op = o_ptr[mi];
-                if (op != nullptr && n < g.N) op[(int64_t)n * o_stride] = acc[mt][r];
-            } else {
-                const int mi = wm + mt * 32 + trow;
-                const int n = n0 + wn + li;
-                float* op = o_ptr[mi];
-                if (op != nullptr && n < g.N) {
-                    if (BF16 && out_id != 1) reinterpret_cast<uint16_t*>(op)[n] = f32_to_bf16(acc[mt][r]);
-                    else op[n] = acc[mt][r];
-                }
-            }
-        }
-    }
-}
+// the tiled kernel, and (EXTENSION) the same kernel with rotary position embeddings in its epilogue
+#define MLI_GEMM_ROPE 0
+#include "gemm_f32_tile_body.hpp"
+#undef MLI_GEMM_ROPE
+#define MLI_GEMM_ROPE 1
+#include "gemm_f32_tile_body.hpp"
+#undef MLI_GEMM_ROPE
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -436,10 +78,49 @@ static void count_gemm_form(const GemmArgs& g) {
     else if ((MODE == kPagedLatest || MODE == kNaiveLatest) && g.compact) count_launch(kLfLatestCompact);
 }
 
+// EXTENSION: the rotary table of a *_rope entry point (null: none) and hd / 2.  With a table the launchers below take the tiled
+// kernels' ROPE instantiations -- also at the shapes of the panel kernel, which has no such switch -- and count
+// "gemm_f32_rope" beside the family of the form that ran.
+struct RopeArg {
+    const float2* table = nullptr;
+    int half = 0;
+};
+
+// the tiled kernels' forms with the rotation, chosen as launch_gemm chooses below
+template <int MODE>
+static int launch_gemm_rope(const GemmArgs& g, int rows, int z, bool vec4, RopeArg rope, hipStream_t st) {
+    const int tiles_x = ceil_div_i(g.N, BN) * g.n_out;
+    count_gemm_form<MODE>(g);
+    count_launch(kLfGemmF32Rope);
+    if constexpr (MODE == kPagedLatest) {  // as in launch_gemm: the fills keep 64-row tiles
+        if (vec4 && gemm_use_tall_tiles((int64_t)tiles_x * ceil_div_i(rows, 128) * z)) {
+            count_launch(kLfGemmF32Rows128);
+            hipLaunchKernelGGL((gemm_f32_mfma_rope_kernel<MODE, false, true, false, 2>), dim3(tiles_x, ceil_div_i(rows, 128), z),
+                               dim3(kGemmThreads), 0, st, g, rope.table, rope.half);
+            return launch_status();
+        }
+    }
+    dim3 grid(tiles_x, ceil_div_i(rows, BM), z);
+    if (g.compact && MODE != kPagedLatest) grid = dim3(tiles_x, ceil_div_i(rows * z, BM), 1);
+    if (vec4 && g_gemm_split && g.K >= 256) {
+        count_launch(kLfGemmF32Rows64Split);
+        hipLaunchKernelGGL((gemm_f32_mfma_rope_kernel<MODE, false, true, false, 1, true>), grid, dim3(2 * kGemmThreads), 0, st, g,
+                           rope.table, rope.half);
+        return launch_status();
+    }
+    count_launch(kLfGemmF32Rows64);
+    if (vec4) hipLaunchKernelGGL((gemm_f32_mfma_rope_kernel<MODE, false, true>), grid, dim3(kGemmThreads), 0, st, g, rope.table, rope.half);
+    else hipLaunchKernelGGL((gemm_f32_mfma_rope_kernel<MODE, false, false>), grid, dim3(kGemmThreads), 0, st, g, rope.table, rope.half);
+    return launch_status();
+}
+
 // rows = live extent of the M dimension (per z-slice)
 template <int MODE, bool BT>
-static int launch_gemm(const GemmArgs& g, int rows, int z, bool vec4, hipStream_t st) {
+static int launch_gemm(const GemmArgs& g, int rows, int z, bool vec4, hipStream_t st, RopeArg rope = {}) {
     if (g.N <= 0 || g.K <= 0 || rows <= 0 || z <= 0) return MLI_ERR_BAD_ARG;
+    if constexpr (!BT && (MODE == kPagedLatest || MODE == kPagedFill || MODE == kPagedFillLive)) {
+        if (rope.table != nullptr) return launch_gemm_rope<MODE>(g, rows, z, vec4, rope, st);
+    }
     constexpr bool kPanelMode = ((MODE == kPagedLatest || MODE == kNaiveLatest) && !BT) || (MODE == kPlain && BT);
     if constexpr (kPanelMode) {
         if (z == 1 && gemm_panel_wanted(rows, g.N * g.n_out, g.K, vec4)) return launch_gemm_panel<MODE, BT>(g, rows, st);
@@ -511,8 +192,8 @@ int launch_fill_naive(const float* inp, const int* new_idx, const int* lengths, 
                                    S, Din, Dout, n_new, st);
 }
 
-int launch_latest_paged(float* const* page_table, const int* lengths, const float* wk, const float* wq,
-                        const float* wv, float* q, int B, int S, int D, hipStream_t st) {
+static int latest_paged(float* const* page_table, const int* lengths, const float* wk, const float* wq, const float* wv, float* q,
+                        int B, int S, int D, RopeArg rope, hipStream_t st) {
     if (B <= 0 || S % kPage != 0 || D % 4 != 0) return MLI_ERR_BAD_ARG;
     GemmArgs g{};
     g.w[0] = wk; g.w[1] = wq; g.w[2] = wv; g.n_out = 3;
@@ -522,14 +203,19 @@ int launch_latest_paged(float* const* page_table, const int* lengths, const floa
     g.B = B; g.S = S;
     g.compact = latest_compact(B, D);
     const bool vec4 = aligned16(wk) && aligned16(wq) && aligned16(wv);
-    return launch_gemm<kPagedLatest, false>(g, B, 1, vec4, st);
+    return launch_gemm<kPagedLatest, false>(g, B, 1, vec4, st, rope);
+}
+
+int launch_latest_paged(float* const* page_table, const int* lengths, const float* wk, const float* wq,
+                        const float* wv, float* q, int B, int S, int D, hipStream_t st) {
+    return latest_paged(page_table, lengths, wk, wq, wv, q, B, S, D, RopeArg{}, st);
 }
 
 // WIN: the windowed prefill's fill (1 <= window, 0 <= n_sink, n_sink + window < S: the entry point hands everything else on)
 template <bool WIN>
 static int fill_paged_embed(const float* emb_table, const float* wpe, const int* tokens, float* const* page_table,
                             const int* new_idx, const int* lengths, const float* wk, const float* wv, int B, int S, int D,
-                            int n_new, int window, int n_sink, hipStream_t st) {
+                            int n_new, int window, int n_sink, hipStream_t st, RopeArg rope = {}) {
     if (n_new == 0) return 0;  // reference paged_attention.cu:100-102
     if (n_new < 0 || B <= 0 || S % kPage != 0 || D % 4 != 0) return MLI_ERR_BAD_ARG;
     GemmArgs g{};
@@ -541,10 +227,10 @@ static int fill_paged_embed(const float* emb_table, const float* wpe, const int*
     g.B = B; g.S = S;
     g.n_new = n_new; g.compact = fill_compact(n_new);
     const bool vec4 = aligned16(wk) && aligned16(wv) && (emb_table == nullptr || (aligned16(emb_table) && aligned16(wpe)));
-    if (!WIN) return launch_gemm<kPagedFill, false>(g, S, n_new, vec4, st);
+    if (!WIN) return launch_gemm<kPagedFill, false>(g, S, n_new, vec4, st, rope);
     g.fill_window = window; g.fill_sink = n_sink;
     // the flat list is at most live_tokens_bound pairs per row; the per-row grid keeps the row's extent
-    return launch_gemm<kPagedFillLive, false>(g, g.compact ? live_tokens_bound(S, window, n_sink) : S, n_new, vec4, st);
+    return launch_gemm<kPagedFillLive, false>(g, g.compact ? live_tokens_bound(S, window, n_sink) : S, n_new, vec4, st, rope);
 }
 
 int launch_fill_paged_embed(const float* emb_table, const float* wpe, const int* tokens, float* const* page_table,
@@ -572,11 +258,21 @@ int launch_latest_paged_bf16_native(uint16_t* const*, const int*, const uint16_t
                                     float*, int, int, int, hipStream_t);
 int launch_fill_paged_bf16_native(uint16_t* const*, const int*, const int*, const uint16_t*, const uint16_t*, int, int,
                                   int, int, hipStream_t);
+// proj_gemm_bf16.hip, EXTENSION: the native kernels' ROPE forms (table: [S][half] (cos, sin))
+int launch_latest_paged_16bit_rope(void* const*, const int*, const uint16_t*, const uint16_t*, const uint16_t*, float*, int, int,
+                                   int, const float2*, int, bool, hipStream_t);
+int launch_fill_paged_16bit_rope(const float*, const float*, const int*, void* const*, const int*, const int*, const uint16_t*,
+                                 const uint16_t*, int, int, int, int, int, int, const float2*, int, bool, hipStream_t);
 
-int launch_latest_paged_bf16(uint16_t* const* page_table, const int* lengths, const uint16_t* wk,
-                             const uint16_t* wq, const uint16_t* wv, float* q, int B, int S, int D, hipStream_t st) {
+static int latest_paged_bf16(uint16_t* const* page_table, const int* lengths, const uint16_t* wk, const uint16_t* wq,
+                             const uint16_t* wv, float* q, int B, int S, int D, RopeArg rope, hipStream_t st) {
     if (B <= 0 || S % kPage != 0 || D % 8 != 0) return MLI_ERR_BAD_ARG;
-    if (g_bf16_native_mfma) return launch_latest_paged_bf16_native(page_table, lengths, wk, wq, wv, q, B, S, D, st);
+    if (g_bf16_native_mfma) {
+        if (rope.table != nullptr)
+            return launch_latest_paged_16bit_rope(reinterpret_cast<void* const*>(page_table), lengths, wk, wq, wv, q, B, S, D,
+                                                  rope.table, rope.half, false, st);
+        return launch_latest_paged_bf16_native(page_table, lengths, wk, wq, wv, q, B, S, D, st);
+    }
     GemmArgs g{};
     g.w[0] = reinterpret_cast<const float*>(wk); g.w[1] = reinterpret_cast<const float*>(wq);
     g.w[2] = reinterpret_cast<const float*>(wv); g.n_out = 3;
@@ -588,8 +284,19 @@ int launch_latest_paged_bf16(uint16_t* const* page_table, const int* lengths, co
     dim3 grid(ceil_div_i(D, BN) * 3, ceil_div_i(B, BM), 1);
     count_launch(kLfGemmBf16Widened);
     count_gemm_form<kPagedLatest>(g);
+    if (rope.table != nullptr) {
+        count_launch(kLfGemmF32Rope);
+        hipLaunchKernelGGL((gemm_f32_mfma_rope_kernel<kPagedLatest, false, true, true>), grid, dim3(kGemmThreads), 0, st, g, rope.table,
+                           rope.half);
+        return launch_status();
+    }
     hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPagedLatest, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
     return launch_status();
+}
+
+int launch_latest_paged_bf16(uint16_t* const* page_table, const int* lengths, const uint16_t* wk,
+                             const uint16_t* wq, const uint16_t* wv, float* q, int B, int S, int D, hipStream_t st) {
+    return latest_paged_bf16(page_table, lengths, wk, wq, wv, q, B, S, D, RopeArg{}, st);
 }
 
 int launch_fill_paged_bf16_window_embed(const float*, const float*, const int*, uint16_t* const*, const int*, const int*,
@@ -597,9 +304,13 @@ int launch_fill_paged_bf16_window_embed(const float*, const float*, const int*, 
 
 template <bool WIN>
 static int fill_paged_bf16(uint16_t* const* page_table, const int* new_idx, const int* lengths, const uint16_t* wk,
-                           const uint16_t* wv, int B, int S, int D, int n_new, int window, int n_sink, hipStream_t st) {
+                           const uint16_t* wv, int B, int S, int D, int n_new, int window, int n_sink, hipStream_t st,
+                           RopeArg rope = {}) {
     if (n_new == 0) return 0;
     if (n_new < 0 || B <= 0 || S % kPage != 0 || D % 8 != 0) return MLI_ERR_BAD_ARG;
+    if (g_bf16_native_mfma && rope.table != nullptr)
+        return launch_fill_paged_16bit_rope(nullptr, nullptr, nullptr, reinterpret_cast<void* const*>(page_table), new_idx, lengths,
+                                            wk, wv, B, S, D, n_new, WIN ? window : 0, n_sink, rope.table, rope.half, false, st);
     if (g_bf16_native_mfma)
         return WIN ? launch_fill_paged_bf16_window_embed(nullptr, nullptr, nullptr, page_table, new_idx, lengths, wk, wv, B, S,
                                                          D, n_new, window, n_sink, st)
@@ -614,14 +325,23 @@ static int fill_paged_bf16(uint16_t* const* page_table, const int* new_idx, cons
     dim3 grid(ceil_div_i(D, BN) * 2, ceil_div_i(S, BM), n_new);
     count_launch(kLfGemmBf16Widened);
     count_gemm_form<kPagedFill>(g);
+    if (rope.table != nullptr) count_launch(kLfGemmF32Rope);
     if (!WIN) {
         if (g.compact) grid = dim3(ceil_div_i(D, BN) * 2, ceil_div_i(S * n_new, BM), 1);
-        hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPagedFill, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
+        if (rope.table != nullptr)
+            hipLaunchKernelGGL((gemm_f32_mfma_rope_kernel<kPagedFill, false, true, true>), grid, dim3(kGemmThreads), 0, st, g, rope.table,
+                               rope.half);
+        else
+            hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPagedFill, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
         return launch_status();
     }
     g.fill_window = window; g.fill_sink = n_sink;
     if (g.compact) grid = dim3(ceil_div_i(D, BN) * 2, ceil_div_i(live_tokens_bound(S, window, n_sink) * n_new, BM), 1);
-    hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPagedFillLive, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
+    if (rope.table != nullptr)
+        hipLaunchKernelGGL((gemm_f32_mfma_rope_kernel<kPagedFillLive, false, true, true>), grid, dim3(kGemmThreads), 0, st, g, rope.table,
+                           rope.half);
+    else
+        hipLaunchKernelGGL((gemm_f32_mfma_kernel<kPagedFillLive, false, true, true>), grid, dim3(kGemmThreads), 0, st, g);
     return launch_status();
 }
 
@@ -633,6 +353,54 @@ int launch_fill_paged_bf16(uint16_t* const* page_table, const int* new_idx, cons
 int launch_fill_paged_bf16_window(uint16_t* const* page_table, const int* new_idx, const int* lengths, const uint16_t* wk,
                                   const uint16_t* wv, int B, int S, int D, int n_new, int window, int n_sink, hipStream_t st) {
     return fill_paged_bf16<true>(page_table, new_idx, lengths, wk, wv, B, S, D, n_new, window, n_sink, st);
+}
+
+// ---- EXTENSION: rotary position embeddings (the *_rope entry points, include/mli_kernels.h) ---------------------------------
+// hd / 2 for a table that can be used, -1 for what every *_rope call refuses before it launches anything
+int rope_half(int D, int n_heads, const float* table) {
+    if (table == nullptr || n_heads < 1 || D < 1 || D % n_heads != 0 || (D / n_heads) % 2 != 0) return -1;
+    return D / n_heads / 2;
+}
+
+int launch_latest_paged_rope(int elem, void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                             const void* wv, float* q, int B, int S, int D, int n_heads, const float* table, hipStream_t st) {
+    const int half = rope_half(D, n_heads, table);
+    if (half < 0) return MLI_ERR_BAD_ARG;
+    const RopeArg rope{reinterpret_cast<const float2*>(table), half};
+    const uint16_t *k16 = static_cast<const uint16_t*>(wk), *q16 = static_cast<const uint16_t*>(wq), *v16 = static_cast<const uint16_t*>(wv);
+    if (elem == MLI_ELEM_FP8) return launch_latest_paged_16bit_rope(page_table, lengths, k16, q16, v16, q, B, S, D, rope.table, half, true, st);
+    if (elem == MLI_ELEM_BF16)
+        return latest_paged_bf16(reinterpret_cast<uint16_t* const*>(page_table), lengths, k16, q16, v16, q, B, S, D, rope, st);
+    if (elem == MLI_ELEM_F32)
+        return latest_paged(reinterpret_cast<float* const*>(page_table), lengths, static_cast<const float*>(wk),
+                            static_cast<const float*>(wq), static_cast<const float*>(wv), q, B, S, D, rope, st);
+    return MLI_ERR_BAD_ARG;
+}
+
+// emb_table null: the x rows are read from segment 0; else the encoder is the fill's prologue.  win: the windowed prefill's live
+// fill (the caller has held 1 <= window, 0 <= n_sink, n_sink + window < S), else every token of a new row.
+int launch_fill_paged_rope(int elem, const float* emb_table, const float* wpe, const int* tokens, void* const* page_table,
+                           const int* new_idx, const int* lengths, const void* wk, const void* wv, int B, int S, int D, int n_new,
+                           bool win, int window, int n_sink, int n_heads, const float* table, hipStream_t st) {
+    const int half = rope_half(D, n_heads, table);
+    if (half < 0 || (win && (window < 1 || n_sink < 0 || (int64_t)n_sink + window >= S))) return MLI_ERR_BAD_ARG;
+    const RopeArg rope{reinterpret_cast<const float2*>(table), half};
+    const uint16_t *k16 = static_cast<const uint16_t*>(wk), *v16 = static_cast<const uint16_t*>(wv);
+    if (elem == MLI_ELEM_FP8 || (elem == MLI_ELEM_BF16 && emb_table != nullptr))
+        return launch_fill_paged_16bit_rope(emb_table, wpe, tokens, page_table, new_idx, lengths, k16, v16, B, S, D, n_new,
+                                            win ? window : 0, n_sink, rope.table, half, elem == MLI_ELEM_FP8, st);
+    if (elem == MLI_ELEM_BF16) {
+        uint16_t* const* pt = reinterpret_cast<uint16_t* const*>(page_table);
+        return win ? fill_paged_bf16<true>(pt, new_idx, lengths, k16, v16, B, S, D, n_new, window, n_sink, st, rope)
+                   : fill_paged_bf16<false>(pt, new_idx, lengths, k16, v16, B, S, D, n_new, 0, 0, st, rope);
+    }
+    if (elem == MLI_ELEM_F32) {
+        float* const* pt = reinterpret_cast<float* const*>(page_table);
+        const float *k = static_cast<const float*>(wk), *v = static_cast<const float*>(wv);
+        return win ? fill_paged_embed<true>(emb_table, wpe, tokens, pt, new_idx, lengths, k, v, B, S, D, n_new, window, n_sink, st, rope)
+                   : fill_paged_embed<false>(emb_table, wpe, tokens, pt, new_idx, lengths, k, v, B, S, D, n_new, 0, 0, st, rope);
+    }
+    return MLI_ERR_BAD_ARG;
 }
 
 // C[M, N] = A[M, K] . Bt[N, K]^T
@@ -770,6 +538,21 @@ int mli_get_latest_k_q_v_paged_bf16(mli_bf16* const* page_table, const int* leng
                                     int n_sequence, int emb_dim, void* stream) {
     return mli::launch_latest_paged_bf16(page_table, lengths, wk, wq, wv, q_output, n_batch, n_sequence, emb_dim,
                                          mli::as_stream(stream));
+}
+
+int mli_get_latest_k_q_v_paged_rope(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                    float* q_output, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                    const float* rope_table, int elem, void* stream) {
+    return mli::launch_latest_paged_rope(elem, page_table, lengths, wk, wq, wv, q_output, n_batch, n_sequence, emb_dim, n_heads,
+                                         rope_table, mli::as_stream(stream));
+}
+
+int mli_fill_new_k_v_cache_paged_rope(void* const* page_table, const int* new_batch_idx, const int* lengths, const void* wk,
+                                      const void* wv, int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads,
+                                      const float* rope_table, int elem, void* stream) {
+    return mli::launch_fill_paged_rope(elem, nullptr, nullptr, nullptr, page_table, new_batch_idx, lengths, wk, wv, n_batch,
+                                       n_sequence, emb_dim, n_new_items, false, 0, 0, n_heads, rope_table,
+                                       mli::as_stream(stream));
 }
 
 }  // extern "C"

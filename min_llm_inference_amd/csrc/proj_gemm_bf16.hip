@@ -50,227 +50,13 @@ union Frag8 {
     s16x4_t h[2];
 };
 
-// MT = 32-row sub-tiles per wave (rows per workgroup = 64 * MT), KB = k extent of a staged tile (32 or 64)
-// FP8 = the pages hold OCP e4m3 bytes (MLI_ELEM_FP8): A rows are widened to bf16 on their way into LDS (exact), K / V rows
-// leave as fp8 (round to nearest even, saturating); the weights are bf16 and everything between is the bf16 kernel
-// MODE_ = kPagedFillLive: kPagedFill over the live tokens (the windowed prefill), as in gemm_f32_mfma_kernel
-template <int MODE_, int MT = 1, int KB = 32, bool FP8 = false>
-__global__ __launch_bounds__(kHThreads) void gemm_bf16_mfma_kernel(GemmArgs g) {
-    constexpr bool WIN = MODE_ == kPagedFillLive;   // the windowed prefill's fill: kPagedFill over the live tokens
-    constexpr int MODE = WIN ? kPagedFill : MODE_;
-    constexpr int HM = 64 * MT;              // shadows the namespace-level 64
-    constexpr int HK = KB;
-    constexpr int kLdaBytes = HK * 2 + 16;   // 80 / 144: ds_read_b128 fragment reads are conflict-free
-    constexpr int AP = HM * HK / (kHThreads * 8);   // 16-byte A loads per thread and tile
-    constexpr int BP = HK * HN / (kHThreads * 8);   // 16-byte B loads per thread and tile
-    constexpr int kAThreadsPerRow = HK / 8;
-    __shared__ __align__(16) unsigned char As[HM * kLdaBytes];
-    __shared__ __align__(16) unsigned char Bs[HK * kLdbBytes];
-    __shared__ const float* a_ptr[HM];
-    __shared__ float* o_ptr[HM];
-    constexpr bool kFillMode = MODE == kPagedFill;
-    __shared__ const float* e_ptr[kFillMode ? HM : 1];  // embedding prologue: fp32 emb_table / wpe row of every A row
-    __shared__ const float* p_ptr[kFillMode ? HM : 1];
-
-    const int tiles_n = (g.N + HN - 1) / HN;
-    const int wsel = blockIdx.x / tiles_n;
-    const int n0 = (blockIdx.x % tiles_n) * HN;
-    const int m0 = blockIdx.y * HM;
-    const int z = blockIdx.z;
-    const int out_id = g.out_id[wsel];
-    const uint16_t* __restrict__ W = reinterpret_cast<const uint16_t*>(g.w[wsel]);
-
-    constexpr bool kLatest = MODE == kPagedLatest;
-    __shared__ FillIndex fill_index[1];
-    const int tid = threadIdx.x;
-    int fill_total = 0;
-    if (g.compact) {
-        fill_total = build_fill_index<kHThreads, kLatest, WIN>(g, fill_index[0]);
-        if (m0 >= fill_total) return;  // workgroup-uniform: every lane leaves together
-    } else if (MODE == kPagedFill && m0 >= g.lengths[g.new_batch_idx[z]]) {
-        return;
-    } else if (MODE == kPagedFill && WIN && fill_tile_dead(g, m0, HM, z)) {
-        return;
-    }
-    const bool embed = kFillMode && g.emb_table != nullptr;
-    if (tid < HM) {
-        RowDesc r{nullptr, nullptr, nullptr, nullptr};
-        if (g.compact) {
-            if (m0 + tid < fill_total) {
-                int zz, ss;
-                if (WIN) fill_index_lookup_live(g, fill_index[0], m0 + tid, zz, ss);
-                else fill_index_lookup(fill_index[0], kLatest ? g.B : g.n_new, m0 + tid, zz, ss);
-                r = kLatest ? resolve_row<MODE, true, FP8>(g, zz, 0, out_id) : resolve_row<MODE, true, FP8>(g, ss, zz, out_id);
-            }
-        } else if (!WIN || !fill_token_dead(g, m0 + tid, z)) {
-            r = resolve_row<MODE, true, FP8>(g, m0 + tid, z, out_id);
-        }
-        a_ptr[tid] = r.a;
-        o_ptr[tid] = r.o;
-        if (kFillMode) {
-            e_ptr[tid] = r.e;
-            p_ptr[tid] = r.p;
-        }
-    }
-    __syncthreads();
-
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm = (wave >> 1) * 32 * MT;
-    const int wn = (wave & 1) * 32;
-
-    // staging coordinates: 16-byte loads, AP + BP per thread and tile
-    const int a_row = tid / kAThreadsPerRow, a_k8 = (tid % kAThreadsPerRow) * 8;  // A: rows x chunks of 8 k
-    constexpr int kARowsPerPass = kHThreads / kAThreadsPerRow;
-    const int b_row = tid >> 3, b_n8 = (tid & 7) * 8;                            // B: 32 k-rows x 8 chunks of 8 n
-    uint4 a_reg[AP], b_reg[BP];
-    const uint16_t* a_src[AP];
-    const float* e_src[AP];
-    const float* p_src[AP];
-#pragma unroll
-    for (int p = 0; p < AP; ++p) {
-        a_src[p] = reinterpret_cast<const uint16_t*>(a_ptr[a_row + p * kARowsPerPass]);
-        e_src[p] = kFillMode ? e_ptr[a_row + p * kARowsPerPass] : nullptr;
-        p_src[p] = kFillMode ? p_ptr[a_row + p * kARowsPerPass] : nullptr;
-    }
-    const bool writes_x = blockIdx.x == 0;  // first column tile of the first weight: every A element passes once
-
-    auto load_tile = [&](int k0) {
-#pragma unroll
-        for (int p = 0; p < AP; ++p) {
-            a_reg[p] = make_uint4(0, 0, 0, 0);
-            if (kFillMode && embed && a_src[p] != nullptr) {
-                // encoder as prologue: x = bf16(emb[tok] + wpe[s]) -- fp32 sum, one rounding, what the bf16 encoder
-                // kernel writes -- fed to the MFMA and, by the first column tile, written to the page's segment 0
-                if (k0 + a_k8 < g.K) {
-                    const float4 e0 = *reinterpret_cast<const float4*>(e_src[p] + k0 + a_k8);
-                    const float4 e1 = *reinterpret_cast<const float4*>(e_src[p] + k0 + a_k8 + 4);
-                    const float4 p0 = *reinterpret_cast<const float4*>(p_src[p] + k0 + a_k8);
-                    const float4 p1 = *reinterpret_cast<const float4*>(p_src[p] + k0 + a_k8 + 4);
-                    if constexpr (FP8) {   // x = fp8(emb[tok] + wpe[s]): fp32 sum, one rounding; the MFMA sees what the page holds
-                        const uint2 x8 = make_uint2(f32x4_to_fp8x4(e0.x + p0.x, e0.y + p0.y, e0.z + p0.z, e0.w + p0.w),
-                                                    f32x4_to_fp8x4(e1.x + p1.x, e1.y + p1.y, e1.z + p1.z, e1.w + p1.w));
-                        const uint2 lo = fp8x4_to_bf16x4(x8.x), hi = fp8x4_to_bf16x4(x8.y);
-                        a_reg[p] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                        if (writes_x)
-                            *reinterpret_cast<uint2*>(const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(a_src[p])) + k0 + a_k8) = x8;
-                    } else {
-                        uint4 x;
-                        x.x = f32_to_bf16(e0.x + p0.x) | ((uint32_t)f32_to_bf16(e0.y + p0.y) << 16);
-                        x.y = f32_to_bf16(e0.z + p0.z) | ((uint32_t)f32_to_bf16(e0.w + p0.w) << 16);
-                        x.z = f32_to_bf16(e1.x + p1.x) | ((uint32_t)f32_to_bf16(e1.y + p1.y) << 16);
-                        x.w = f32_to_bf16(e1.z + p1.z) | ((uint32_t)f32_to_bf16(e1.w + p1.w) << 16);
-                        a_reg[p] = x;
-                        if (writes_x) *reinterpret_cast<uint4*>(const_cast<uint16_t*>(a_src[p]) + k0 + a_k8) = x;
-                    }
-                }
-            } else if (a_src[p] != nullptr && k0 + a_k8 < g.K) {
-                if constexpr (FP8) {   // 8 fp8 (8 bytes) -> 8 bf16
-                    const uint2 x8 = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(a_src[p]) + k0 + a_k8);
-                    const uint2 lo = fp8x4_to_bf16x4(x8.x), hi = fp8x4_to_bf16x4(x8.y);
-                    a_reg[p] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                } else {
-                    a_reg[p] = *reinterpret_cast<const uint4*>(a_src[p] + k0 + a_k8);
-                }
-            }
-        }
-#pragma unroll
-        for (int p = 0; p < BP; ++p) {
-            b_reg[p] = make_uint4(0, 0, 0, 0);
-            const int k = k0 + b_row + p * 32, n = n0 + b_n8;
-            if (k < g.K && n < g.N) b_reg[p] = *reinterpret_cast<const uint4*>(W + (int64_t)k * g.N + n);
-        }
-    };
-    auto store_tile = [&]() {
-#pragma unroll
-        for (int p = 0; p < AP; ++p)
-            *reinterpret_cast<uint4*>(&As[(a_row + p * kARowsPerPass) * kLdaBytes + a_k8 * 2]) = a_reg[p];
-#pragma unroll
-        for (int p = 0; p < BP; ++p)
-            *reinterpret_cast<uint4*>(&Bs[(b_row + p * 32) * kLdbBytes + b_n8 * 2]) = b_reg[p];
-    };
-
-    f32x16_t acc[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[mt][i] = 0.f;
-
-    // fragment addresses (constant over the k loop)
-    const int li = lane & 31, lh = lane >> 5;
-    const unsigned a_off = (unsigned)((wm + li) * kLdaBytes + lh * 16);
-    // transposing read: lane 4q+p of a 16-lane group points at row q, columns 4p..4p+3 of the group's 4x16 block
-    const int grp_col = wn + 16 * ((lane >> 4) & 1);
-    const int tq = (lane >> 2) & 3, tp = lane & 3;
-    const unsigned b_off = (unsigned)((8 * lh + tq) * kLdbBytes + (grp_col + 4 * tp) * 2);
-
-    const int nk = (g.K + HK - 1) / HK;
-#ifdef MLI_GEMM_TRACE
-    unsigned long long gt_acc[5] = {0, 0, 0, 0, 0};
-    const unsigned long long gt_begin = clock64();
-#endif
-    load_tile(0);
-    store_tile();
-    __syncthreads();
-    for (int t = 0; t < nk; ++t) {
-        MLI_GT(g0);
-        if (t + 1 < nk) load_tile((t + 1) * HK);
-        MLI_GT(g1);
-        MLI_GT_ADD(0, g0, g1);
-#pragma unroll
-        for (int kk = 0; kk < HK; kk += 16) {
-            Frag8 b;
-            b.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(&Bs[b_off + kk * kLdbBytes]));
-            b.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(&Bs[b_off + (kk + 4) * kLdbBytes]));
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                Frag8 a;
-                a.u = *reinterpret_cast<const uint4*>(&As[a_off + mt * 32 * kLdaBytes + kk * 2]);
-                acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.v, acc[mt], 0, 0, 0);
-            }
-        }
-        MLI_GT(g2);
-        MLI_GT_ADD(1, g1, g2);
-        __syncthreads();
-        MLI_GT(g3);
-        MLI_GT_ADD(2, g2, g3);
-        if (t + 1 < nk) {
-            store_tile();
-            MLI_GT(g4);
-            MLI_GT_ADD(3, g3, g4);
-            __syncthreads();
-            MLI_GT(g5);
-            MLI_GT_ADD(4, g4, g5);
-        }
-    }
-#ifdef MLI_GEMM_TRACE
-    {
-        const unsigned wg = blockIdx.x + gridDim.x * blockIdx.y;
-        if (threadIdx.x == 0 && wg < (unsigned)kGemmTraceWgs) {
-            for (int i = 0; i < 5; ++i) mli_gemm_trace[wg * 8 + i] = gt_acc[i];
-            mli_gemm_trace[wg * 8 + 5] = clock64() - gt_begin;
-            mli_gemm_trace[wg * 8 + 6] = gt_begin;
-            mli_gemm_trace[wg * 8 + 7] = (unsigned long long)nk;
-        }
-    }
-#endif
-
-    // epilogue: register r of lane l is (row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), col = l & 31)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int mi = wm + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const int n = n0 + wn + li;
-            float* op = o_ptr[mi];
-            if (op != nullptr && n < g.N) {
-                if (out_id == 1) op[n] = acc[mt][r];                                         // q: fp32
-                else if (FP8) reinterpret_cast<uint8_t*>(op)[n] = (uint8_t)f32_to_fp8(acc[mt][r]);   // K / V: fp8 page rows
-                else reinterpret_cast<uint16_t*>(op)[n] = f32_to_bf16(acc[mt][r]);            // K / V: bf16 page rows
-            }
-        }
-    }
-}
+// the tiled kernel, and (EXTENSION) the same kernel with rotary position embeddings in its epilogue
+#define MLI_GEMM_ROPE 0
+#include "gemm_bf16_tile_body.hpp"
+#undef MLI_GEMM_ROPE
+#define MLI_GEMM_ROPE 1
+#include "gemm_bf16_tile_body.hpp"
+#undef MLI_GEMM_ROPE
 
 // ---- the large decode projection (>= 1024 rows at emb_dim >= 1024): LDS-DMA loader waves + MFMA waves ------------------
 // In the kernel above one wave does everything in turn -- issue the next tile's global loads (the issue itself takes the
@@ -720,6 +506,75 @@ int launch_fill_paged_bf16_window_embed(const float* emb_table, const float* wpe
                                         int n_sink, hipStream_t st) {
     return fill_paged_16bit_embed<false, true>(emb_table, wpe, tokens, reinterpret_cast<void* const*>(page_table), new_idx,
                                                lengths, wk, wv, B, S, D, n_new, window, n_sink, st);
+}
+
+// ---- EXTENSION: rotary position embeddings (the *_rope entry points) ------------------------------------------------------
+// The tiled kernel's ROPE forms, chosen as the launchers above and below choose the plain ones, for bf16 and (fp8) fp8 pages.
+// The shapes of the LDS-DMA kernel, which has no such switch, take the tiled forms too.  "gemm_bf16_rope" is counted
+// beside the family of the form that ran.
+int launch_latest_paged_16bit_rope(void* const* page_table, const int* lengths, const uint16_t* wk, const uint16_t* wq,
+                                   const uint16_t* wv, float* q, int B, int S, int D, const float2* rope, int half, bool fp8,
+                                   hipStream_t st) {
+    if (B <= 0 || S % kPage != 0 || D % (fp8 ? 16 : 8) != 0 || rope == nullptr || half < 1) return MLI_ERR_BAD_ARG;
+    GemmArgs g{};
+    g.w[0] = reinterpret_cast<const float*>(wk); g.w[1] = reinterpret_cast<const float*>(wq);
+    g.w[2] = reinterpret_cast<const float*>(wv); g.n_out = 3;
+    g.out_id[0] = 0; g.out_id[1] = 1; g.out_id[2] = 2;
+    g.M = B; g.N = D; g.K = D;
+    g.page_table = reinterpret_cast<float* const*>(page_table); g.q_output = q; g.lengths = lengths;
+    g.B = B; g.S = S;
+    g.compact = latest_compact(B, D);
+    const int tiles_x = ceil_div_i(D, HN) * 3;
+    if (g.compact) count_launch(kLfLatestCompact);
+    count_launch(kLfGemmBf16Rope);
+    const auto go = [&](auto f8) {
+        constexpr bool F8 = decltype(f8)::value;
+        if (gemm_use_tall_tiles((int64_t)tiles_x * ceil_div_i(B, 128))) {
+            count_launch(kLfGemmBf16Rows128);
+            hipLaunchKernelGGL((gemm_bf16_mfma_rope_kernel<kPagedLatest, 2, 64, F8>), dim3(tiles_x, ceil_div_i(B, 128), 1),
+                               dim3(kHThreads), 0, st, g, rope, half);
+            return launch_status();
+        }
+        dim3 grid(tiles_x, ceil_div_i(B, HM), 1);
+        count_launch(D >= 256 && D <= 1024 ? kLfGemmBf16Deep : kLfGemmBf16Rows64);
+        if (D >= 256 && D <= 1024)
+            hipLaunchKernelGGL((gemm_bf16_mfma_rope_kernel<kPagedLatest, 1, 128, F8>), grid, dim3(kHThreads), 0, st, g, rope, half);
+        else
+            hipLaunchKernelGGL((gemm_bf16_mfma_rope_kernel<kPagedLatest, 1, 32, F8>), grid, dim3(kHThreads), 0, st, g, rope, half);
+        return launch_status();
+    };
+    return fp8 ? go(std::true_type{}) : go(std::false_type{});
+}
+
+// window < 1: every token of a new row; else the windowed prefill's live fill (1 <= window, 0 <= n_sink, n_sink + window < S)
+int launch_fill_paged_16bit_rope(const float* emb_table, const float* wpe, const int* tokens, void* const* page_table,
+                                 const int* new_idx, const int* lengths, const uint16_t* wk, const uint16_t* wv, int B, int S,
+                                 int D, int n_new, int window, int n_sink, const float2* rope, int half, bool fp8,
+                                 hipStream_t st) {
+    if (rope == nullptr || half < 1) return MLI_ERR_BAD_ARG;
+    if (n_new == 0) return 0;
+    if (n_new < 0 || B <= 0 || S % kPage != 0 || D % (fp8 ? 16 : 8) != 0) return MLI_ERR_BAD_ARG;
+    const bool win = window >= 1;
+    GemmArgs g{};
+    g.emb_table = emb_table; g.wpe = wpe; g.inp = tokens;
+    g.w[0] = reinterpret_cast<const float*>(wk); g.w[1] = reinterpret_cast<const float*>(wv); g.n_out = 2;
+    g.out_id[0] = 0; g.out_id[1] = 2;
+    g.M = S; g.N = D; g.K = D;
+    g.page_table = reinterpret_cast<float* const*>(page_table); g.lengths = lengths; g.new_batch_idx = new_idx;
+    g.B = B; g.S = S;
+    g.n_new = n_new; g.compact = fill_compact(n_new);
+    if (win) { g.fill_window = window; g.fill_sink = n_sink; }
+    const int flat_rows = win ? live_tokens_bound(S, window, n_sink) : S;
+    dim3 grid(ceil_div_i(D, HN) * 2, ceil_div_i(S, HM), n_new);
+    if (g.compact) grid = dim3(ceil_div_i(D, HN) * 2, ceil_div_i(flat_rows * n_new, HM), 1);
+    count_launch(kLfGemmBf16Fill);
+    count_launch(kLfGemmBf16Rope);
+    count_launch(g.compact ? kLfFillFlat : kLfFillPerRow);
+    if (fp8 && win) hipLaunchKernelGGL((gemm_bf16_mfma_rope_kernel<kPagedFillLive, 1, 32, true>), grid, dim3(kHThreads), 0, st, g, rope, half);
+    else if (fp8) hipLaunchKernelGGL((gemm_bf16_mfma_rope_kernel<kPagedFill, 1, 32, true>), grid, dim3(kHThreads), 0, st, g, rope, half);
+    else if (win) hipLaunchKernelGGL((gemm_bf16_mfma_rope_kernel<kPagedFillLive, 1, 32, false>), grid, dim3(kHThreads), 0, st, g, rope, half);
+    else hipLaunchKernelGGL((gemm_bf16_mfma_rope_kernel<kPagedFill, 1, 32, false>), grid, dim3(kHThreads), 0, st, g, rope, half);
+    return launch_status();
 }
 
 // ---- fp8 (OCP e4m3) pages, bf16 weights: MLI_ELEM_FP8 of the lean entry points --------------------------------------

@@ -39,7 +39,8 @@ def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
 class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
                  n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None,
-                 release_pages=False, n_kv_heads=None, logprobs=None, prompt_logprobs=False, alibi=None):
+                 release_pages=False, n_kv_heads=None, logprobs=None, prompt_logprobs=False, alibi=None,
+                 rope=None):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -63,6 +64,8 @@ class Engine:
             self.set_prompt_logprobs(True)
         if alibi is not None and alibi is not False:
             self.set_alibi(None if alibi is True else alibi)
+        if rope is not None and rope is not False:
+            self.set_rope(10000.0 if rope is True else rope)
 
     def _check(self, rc):
         if rc != 0:
@@ -87,6 +90,18 @@ class Engine:
             return
         a = np.ascontiguousarray(slopes, dtype=np.float32).reshape(-1)
         self._check(self._lib.mli_engine_set_alibi(self._h, a.ctypes.data_as(ctypes.c_void_p), int(a.size)))
+
+    def set_rope(self, rope=10000.0):
+        """Rotary position embeddings (mli_engine_set_rope / mli_engine_set_rope_table): prefill and projection rotate K and q
+        by the token's absolute slot.  rope: theta (a number: the standard table for the engine's current n_heads), or a table
+        of n_sequence * head_dim floats ([n_sequence, head_dim // 2, 2] (cos, sin), e.g. ops.rope_table or a scaled variant).
+        Before the first step or run, paged kinds with lean layers, not with prompt log-probabilities; pass a zero
+        pos_table."""
+        if np.isscalar(rope):
+            self._check(self._lib.mli_engine_set_rope(self._h, float(rope)))
+            return
+        a = np.ascontiguousarray(rope, dtype=np.float32).reshape(-1)
+        self._check(self._lib.mli_engine_set_rope_table(self._h, a.ctypes.data_as(ctypes.c_void_p), int(a.size)))
 
     def set_window(self, window):
         """Sliding-window attention (mli_engine_set_window): every row attends its newest `window` tokens.  Before the

@@ -87,10 +87,12 @@ void launch_paged_prefill_window(const TensorFloat& emb_table, const TensorFloat
                                  const TensorFloat& wk, const TensorFloat& wv, int n_new_items, int window, int n_sink);
 // What the two above and every paged layer's prefill() run: pages of elem = MLI_ELEM_*, wk / wv that type's weights;
 // live_only = launch_paged_prefill_window under (window, n_sink).  n_new_items == 0 launches nothing.
+// rope_table (EXTENSION, [n_sequence][emb_dim / n_heads / 2] (cos, sin) in device memory; null: none): K is stored rotated by
+// the token's slot (mli_paged_prefill_rope), live_only or not.
 void launch_paged_prefill_elem(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,
                                TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
                                const void* wk, const void* wv, int n_new_items, int elem, bool live_only, int window,
-                               int n_sink);
+                               int n_sink, int n_heads = 1, const float* rope_table = nullptr);
 
 // "cuBLAS" variants: same results, produced by the same gather-GEMM-scatter MFMA kernel.  latest_emb and
 // temp_placeholder were scratch for the three cublasSgemm calls and are accepted but not used.

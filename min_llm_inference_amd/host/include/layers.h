@@ -55,6 +55,11 @@ struct PagedAttentionOptions {
     PromptScoring* prompt_logprobs = nullptr;   // prompt log-probabilities: who scores the new rows' prompts (nullptr: nobody)
     // ALiBi: one slope per query head ([n_heads], device memory, owned here; null: no bias) -- mli_paged_attention_lean_alibi
     std::shared_ptr<TensorFloat> alibi_slopes;
+    // Rotary position embeddings: [n_sequence][head_dim / 2] (cos, sin) pairs (device memory, owned here; null: none) --
+    // mli_paged_prefill_rope, mli_paged_attention_lean_rope.  n_sequence and emb_dim are the layer's, set by its constructor:
+    // set_rope sizes the table by them.
+    std::shared_ptr<TensorFloat> rope_table;
+    int n_sequence = 0, emb_dim = 0;
 };
 
 // The setters of the option set, defined once for every class that has them: a layer owns the struct, a model hands out
@@ -66,6 +71,14 @@ public:
     // to a device copy the option set owns.  An empty vector takes the bias away again.  A non-finite slope throws here; the
     // count is held to n_heads (>= 2) at every forward, whichever setter came last (PagedAttentionLayerCore::check_alibi).
     void set_alibi_slopes(const std::vector<float>& slopes);
+    // EXTENSION: rotary position embeddings -- prefill and projection rotate K (before its one rounding) and q by the token's
+    // absolute slot (include/mli_kernels.h).  set_rope builds the standard table (mli_rope_table) for the CURRENT n_heads at the
+    // layer's n_sequence: set the heads first.  set_rope_table takes any table, n_sequence * head_dim finite floats ((cos, sin)
+    // pairs; the scaled variants are just another table); an empty vector takes the rotation away again.  Either uploads a
+    // device copy the option set owns.  The count is held to n_sequence * head_dim at every forward, whichever setter came
+    // last (PagedAttentionLayerCore::check_rope).
+    void set_rope(double theta);
+    void set_rope_table(const std::vector<float>& table);
     void set_n_heads(int n_heads) { options().n_heads = n_heads; }
     void set_n_kv_heads(int n_kv_heads) { options().n_kv_heads = n_kv_heads; }
     void set_window(int window) { options().window = window; }
@@ -103,6 +116,9 @@ protected:
     // throws where slopes are set and are not one per head of n_heads >= 2 heads, or the lean layers are off: first thing in
     // every forward, so that no scan reads past the slopes and no composition without a bias drops them
     void check_alibi() const;
+    // throws where a rotary table is set and is not n_sequence * head_dim floats for an even head_dim = emb_dim / n_heads, or
+    // the lean layers are off (the materialising compositions have no rotation): first thing in every prefill and forward
+    void check_rope() const;
 
     int elem_;
     Weights wk_, wq_, wv_;

@@ -74,6 +74,7 @@ void PagedAttentionBf16Layer::forward(TensorFloatPoint& page_table, const Tensor
                                       const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                       int n_new_items) {
     check_alibi();
+    check_rope();
     if (mli::runtime::lean_paged_wanted(options_.n_heads, options_.window, (int)n_sequence_)) {
         const int rc = lean_scan(page_table, lengths, new_batch_idx, attention_result, n_new_items, options_.n_heads,
                                  options_.n_kv_heads);

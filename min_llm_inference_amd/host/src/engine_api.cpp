@@ -566,6 +566,8 @@ int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
             throw std::runtime_error("sliding-window attention (mli_engine_set_window) has the lean compositions only");
         if (o.alibi_slopes && lean_layers == 0)
             throw std::runtime_error("ALiBi (mli_engine_set_alibi) has the lean compositions only");
+        if (o.rope_table && lean_layers == 0)
+            throw std::runtime_error("RoPE (mli_engine_set_rope) has the lean compositions only");
         if (lean_layers >= 0) e->lean_layers = lean_layers != 0;
         if (step_graphs >= 0) e->step_graphs = step_graphs != 0;
         if (e->cfg.kind == MLI_ENGINE_PAGED_FP8 && !e->lean_layers)
@@ -596,6 +598,9 @@ int mli_engine_set_heads(mli_engine* e, int n_heads) {
                                          "n_heads");
             if (o.alibi_slopes)
                 throw std::runtime_error("mli_engine_set_heads: the stored ALiBi slopes (mli_engine_set_alibi) are those of " +
+                                         std::to_string(o.n_heads) + " heads");
+            if (o.rope_table)
+                throw std::runtime_error("mli_engine_set_heads: the stored rotary table (mli_engine_set_rope) is that of " +
                                          std::to_string(o.n_heads) + " heads");
             o.n_heads = n_heads;
         }
@@ -658,6 +663,46 @@ int mli_engine_set_alibi(mli_engine* e, const float* slopes_host, int n) {
                                      "n_kv_heads)");
         mli::runtime::use_device(e->cfg.device);
         e->paged->set_alibi_slopes(slopes);
+    })
+}
+
+// The table is stored with the option set (the layer owns the device copy); table_host null: the standard table of theta.
+static void engine_set_rope(mli_engine* e, const char* who, double theta, const float* table_host, size_t n_floats) {
+    const std::string name(who);
+    if (!e) throw std::runtime_error("null argument");
+    if (e->started) throw std::runtime_error(name + " after the engine has started");
+    if (!e->paged_kind()) throw std::runtime_error(name + ": RoPE serves the paged engines");
+    if (!e->lean_layers) throw std::runtime_error(name + ": RoPE has the lean compositions only");
+    if (e->prompt_logprobs_wanted)
+        throw std::runtime_error(name + ": not with prompt log-probabilities (the prompt scan's q is not rotated: the prompt "
+                                 "would be scored under another model than the one that decodes)");
+    PagedAttentionOptions& o = e->options();
+    const int H = o.n_heads > 0 ? o.n_heads : 1;
+    if (e->cfg.emb_dim % H != 0 || (e->cfg.emb_dim / H) % 2 != 0)
+        throw std::runtime_error(name + ": head_dim = emb_dim / n_heads must be an even integer");
+    const size_t want = (size_t)e->cfg.n_sequence * (size_t)(e->cfg.emb_dim / H);
+    std::vector<float> table(want);
+    if (table_host != nullptr) {
+        if (n_floats != want)
+            throw std::runtime_error(name + ": n_floats must be n_sequence * head_dim (" + std::to_string(want) + ")");
+        std::copy(table_host, table_host + want, table.begin());
+    } else if (mli_rope_table(e->cfg.n_sequence, e->cfg.emb_dim / H, theta, table.data()) != 0) {
+        throw std::runtime_error(name + ": theta must be finite and > 0");
+    }
+    for (float t : table)
+        if (!std::isfinite(t)) throw std::runtime_error(name + ": every entry must be finite");
+    mli::runtime::use_device(e->cfg.device);
+    e->paged->set_rope_table(table);
+}
+
+int mli_engine_set_rope(mli_engine* e, double theta) {
+    MLI_GUARD({ engine_set_rope(e, "mli_engine_set_rope", theta, nullptr, 0); })
+}
+
+int mli_engine_set_rope_table(mli_engine* e, const float* table_host, size_t n_floats) {
+    MLI_GUARD({
+        if (e && !table_host) throw std::runtime_error("null argument");
+        engine_set_rope(e, "mli_engine_set_rope_table", 0.0, table_host, n_floats);
     })
 }
 
@@ -849,6 +894,9 @@ int mli_engine_set_prompt_logprobs(mli_engine* e, int enabled) {
         if (enabled && e->options().alibi_slopes)
             throw std::runtime_error("mli_engine_set_prompt_logprobs: not with ALiBi (mli_engine_set_alibi: the prompt scan has "
                                      "no bias, so the prompt would be scored under another model than the one that decodes)");
+        if (enabled && e->options().rope_table)
+            throw std::runtime_error("mli_engine_set_prompt_logprobs: not with RoPE (mli_engine_set_rope: the prompt scan's q is "
+                                     "not rotated, so the prompt would be scored under another model than the one that decodes)");
         if (!e->prompt_shape_ok())
             throw std::runtime_error("mli_engine_set_prompt_logprobs: the prompt scan does not take this (n_batch, n_sequence, "
                                      "emb_dim, n_heads, n_kv_heads): rows of at most two 16-byte lane loads");

@@ -251,11 +251,15 @@ void paged_attention(TensorFloatPoint& page_table, const TensorInt& lengths, con
 void launch_paged_prefill_elem(const TensorFloat& emb_table, const TensorFloat& wpe, const TensorInt& inp,
                                TensorFloatPoint& page_table, const TensorInt& lengths, const TensorInt& new_item_indices,
                                const void* wk, const void* wv, int n_new_items, int elem, bool live_only, int window,
-                               int n_sink) {
+                               int n_sink, int n_heads, const float* rope_table) {
     if (n_new_items == 0) return;
     void* const* table = reinterpret_cast<void* const*>(pages(page_table));
     const int B = (int)inp.shape()[0], S = (int)inp.shape()[1], D = (int)emb_table.shape()[1];
-    if (live_only)   // the live tokens only; no table entry of a dead page is followed
+    if (rope_table != nullptr)   // window 0: every token of the new rows
+        HIP_CHECK(mli_paged_prefill_rope(emb_table.data(), wpe.data(), inp.data(), table, lengths.data(), new_item_indices.data(),
+                                         wk, wv, B, S, D, n_new_items, live_only && window > 0 ? window : 0,
+                                         live_only ? n_sink : 0, n_heads, rope_table, elem, stream()));
+    else if (live_only)   // the live tokens only; no table entry of a dead page is followed
         HIP_CHECK(mli_paged_prefill_window(emb_table.data(), wpe.data(), inp.data(), table, lengths.data(),
                                            new_item_indices.data(), wk, wv, B, S, D, n_new_items, window > 0 ? window : 0,
                                            n_sink, elem, stream()));
@@ -300,8 +304,14 @@ bool mli::runtime::lean_paged_wanted(int n_heads, int window, int n_sequence) {
 int mli::runtime::lean_paged_attention(int elem, int n_heads, int window, int n_sink, void* const* page_table,
                                        const int* lengths, const void* wk, const void* wq, const void* wv,
                                        const int* new_batch_idx, float* q_output, float* attention_result, int B, int S, int D,
-                                       int n_new_items, int n_kv_heads, const float* alibi_slopes) {
+                                       int n_new_items, int n_kv_heads, const float* alibi_slopes, const float* rope_table) {
     const Scratch ws = attention_scratch(B, S, D, n_heads > 1 ? n_heads : 1);
+    if (rope_table != nullptr) {   // every form behind one entry point; there is no materialising composition to hand back to
+        HIP_CHECK(mli_paged_attention_lean_rope(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B, S,
+                                                D, n_new_items, n_heads, n_kv_heads != 0 ? n_kv_heads : n_heads, window, n_sink,
+                                                alibi_slopes, rope_table, elem, ws.ptr, ws.bytes, stream()));
+        return 0;
+    }
     if (alibi_slopes != nullptr) {
         HIP_CHECK(mli_paged_attention_lean_alibi(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B, S,
                                                  D, n_new_items, n_heads, n_kv_heads != 0 ? n_kv_heads : n_heads, window, n_sink,

@@ -59,19 +59,50 @@ void PagedAttentionOptionSetters::set_alibi_slopes(const std::vector<float>& slo
     options().alibi_slopes = std::move(device);
 }
 
+void PagedAttentionOptionSetters::set_rope_table(const std::vector<float>& table) {
+    if (table.empty()) {
+        options().rope_table.reset();
+        return;
+    }
+    for (float t : table)
+        if (!std::isfinite(t)) throw std::invalid_argument("set_rope_table: every entry must be finite");
+    TensorFloat host(std::vector<size_t>{table.size()}, DeviceType::HOST, TensorDataType::SYNC_ALLOCATE);
+    std::copy(table.begin(), table.end(), host.data());
+    auto device = std::make_shared<TensorFloat>(std::vector<size_t>{table.size()}, DeviceType::DEVICE, TensorDataType::SYNC_ALLOCATE);
+    device->copy_from(host);
+    options().rope_table = std::move(device);
+}
+
+void PagedAttentionOptionSetters::set_rope(double theta) {
+    const PagedAttentionOptions& o = options();
+    if (o.n_heads < 1 || o.emb_dim < 1 || o.n_sequence < 1 || o.emb_dim % o.n_heads != 0)
+        throw std::invalid_argument("set_rope: emb_dim " + std::to_string(o.emb_dim) + " is no multiple of n_heads " +
+                                    std::to_string(o.n_heads));
+    const int hd = o.emb_dim / o.n_heads;
+    std::vector<float> table(hd % 2 == 0 ? (size_t)o.n_sequence * hd : 0);
+    if (table.empty() || mli_rope_table(o.n_sequence, hd, theta, table.data()) != 0)
+        throw std::invalid_argument("set_rope: head_dim must be even and theta finite and > 0");
+    set_rope_table(table);
+}
+
 template <class Weights>
 PagedAttentionLayerCore<Weights>::PagedAttentionLayerCore(int elem, Weights&& wk, Weights&& wq, Weights&& wv,
                                                           size_t n_batch, size_t emb_dim, size_t n_sequence)
     : elem_(elem), wk_(std::move(wk)), wq_(std::move(wq)), wv_(std::move(wv)),
-      q_output_(device_tensor({n_batch, emb_dim})), n_sequence_(n_sequence) {}
+      q_output_(device_tensor({n_batch, emb_dim})), n_sequence_(n_sequence) {
+    options_.n_sequence = (int)n_sequence;
+    options_.emb_dim = (int)emb_dim;
+}
 
 template <class Weights>
 void PagedAttentionLayerCore<Weights>::prefill(const TensorFloat& emb_table, const TensorFloat& pos_emb,
                                                const TensorInt& inp, TensorFloatPoint& page_table,
                                                const TensorInt& lengths, const TensorInt& new_item_indices,
                                                int n_new_items) {
+    check_rope();
     launch_paged_prefill_elem(emb_table, pos_emb, inp, page_table, lengths, new_item_indices, wk_.data(), wv_.data(),
-                              n_new_items, elem_, options_.page_release, options_.window, options_.n_sink);
+                              n_new_items, elem_, options_.page_release, options_.window, options_.n_sink, options_.n_heads,
+                              options_.rope_table ? options_.rope_table->data() : nullptr);
 }
 
 template <class Weights>
@@ -95,17 +126,32 @@ void PagedAttentionLayerCore<Weights>::check_alibi() const {
     if (!mli::runtime::lean_layers()) throw std::runtime_error("ALiBi exists in the lean composition only");
 }
 
+// As check_alibi: the setters come in any order, so the table is held to the heads where it is used.  A layer with a table and
+// the lean layers off throws: the materialising compositions (and an encoder launch of its own) have no rotation.
+template <class Weights>
+void PagedAttentionLayerCore<Weights>::check_rope() const {
+    if (!options_.rope_table) return;
+    const size_t D = wk_.shape()[0], H = (size_t)std::max(options_.n_heads, 1);
+    if (D % H != 0 || (D / H) % 2 != 0 || options_.rope_table->get_total_size() != n_sequence_ * (D / H))
+        throw std::runtime_error("RoPE: a table of " + std::to_string(options_.rope_table->get_total_size()) +
+                                 " floats (set_rope / set_rope_table) beside n_heads = " + std::to_string(options_.n_heads) +
+                                 ": n_sequence * head_dim floats for an even head_dim = emb_dim / n_heads");
+    if (!mli::runtime::lean_layers()) throw std::runtime_error("RoPE exists in the lean composition only");
+}
+
 template <class Weights>
 int PagedAttentionLayerCore<Weights>::lean_scan(TensorFloatPoint& page_table, const TensorInt& lengths,
                                                 const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                                 int n_new_items, int n_heads, int n_kv_heads) {
     check_alibi();
+    check_rope();
     return mli::runtime::lean_paged_attention(elem_, n_heads, options_.window, options_.n_sink,
                                               reinterpret_cast<void* const*>(page_table.data()), lengths.data(),
                                               wk_.data(), wq_.data(), wv_.data(), new_batch_idx.data(), q_output_.data(),
                                               attention_result.data(), (int)page_table.shape()[0], (int)n_sequence_,
                                               (int)wk_.shape()[0], n_new_items, n_kv_heads,
-                                              options_.alibi_slopes ? options_.alibi_slopes->data() : nullptr);
+                                              options_.alibi_slopes ? options_.alibi_slopes->data() : nullptr,
+                                              options_.rope_table ? options_.rope_table->data() : nullptr);
 }
 
 template class PagedAttentionLayerCore<TensorFloat>;
@@ -120,6 +166,7 @@ bool PagedAttentionFloatLayer::forward_lean(TensorFloatPoint& page_table, const 
                                             const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                             int n_new_items) {
     check_alibi();
+    check_rope();
     if (!mli::runtime::lean_paged_wanted(options_.n_heads, options_.window, (int)n_sequence_)) return false;
     const int rc = lean_scan(page_table, lengths, new_batch_idx, attention_result, n_new_items, options_.n_heads,
                              options_.n_kv_heads);

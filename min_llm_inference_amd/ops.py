@@ -342,6 +342,15 @@ def alibi_slopes(n_heads):
     return out
 
 
+def rope_table(n_sequence, head_dim, theta=10000.0):
+    """The standard rotary table (mli_rope_table): a float32 numpy array [n_sequence, head_dim // 2, 2] of (cos, sin) of
+    s * theta^(-2 i / head_dim), computed in double.  Copy it to the device for the rope= arguments."""
+    out = np.empty((max(int(n_sequence), 0), max(int(head_dim), 0) // 2, 2), np.float32)
+    _check(load_library().mli_rope_table(int(n_sequence), int(head_dim), float(theta), out.ctypes.data_as(ctypes.c_void_p)),
+           "mli_rope_table")
+    return out
+
+
 def decode_scan_paged_alibi(q_output, page_table, lengths, attention_result, n_heads, n_kv_heads, window, sinks, slopes, elem,
                             n_sequence):
     """decode_scan_paged_gqa with ALiBi (mli_decode_scan_paged_alibi): slopes[h] * (s - (L - 1)) is added to query head h's
@@ -356,7 +365,8 @@ def decode_scan_paged_alibi(q_output, page_table, lengths, attention_result, n_h
 
 
 def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_new_items,
-                         n_sequence, elem=None, n_heads=1, window=None, sinks=None, n_kv_heads=None, alibi_slopes=None):
+                         n_sequence, elem=None, n_heads=1, window=None, sinks=None, n_kv_heads=None, alibi_slopes=None,
+                         rope=None):
     """What the attention layers run: the paged composition without materialising scores / probabilities
     (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads != 1: the
     multi-head form (mli_paged_attention_lean_heads); window given: the sliding-window form
@@ -364,7 +374,19 @@ def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_outpu
     (mli_paged_attention_lean_sinks); n_kv_heads given: grouped-query attention with that many K/V heads
     (mli_paged_attention_lean_gqa; wk / wv keep their [D, D] shape, their first n_kv_heads * D / n_heads columns matter);
     alibi_slopes given (n_heads float32 values on the device): the scan adds the position bias of decode_scan_paged_alibi
-    (mli_paged_attention_lean_alibi), with any of window, sinks and n_kv_heads."""
+    (mli_paged_attention_lean_alibi), with any of window, sinks and n_kv_heads;
+    rope given (a [n_sequence, D / n_heads / 2, 2] float32 (cos, sin) table on the device): fill and projection rotate K and q
+    by the token's absolute slot (mli_paged_attention_lean_rope), with any of the above."""
+    if rope is not None:
+        if sinks is not None and window is None:
+            raise ValueError("sinks exist beside a window: pass window= as well")
+        B, D = page_table.shape[0], wk.shape[0]
+        ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+        _check(load_library().mli_paged_attention_lean_rope(
+            _p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(new_batch_idx), _p(q_output), _p(attention_result), B,
+            int(n_sequence), D, int(n_new_items), int(n_heads), int(n_kv_heads or n_heads), int(window or 0), int(sinks or 0),
+            _p(alibi_slopes), _p(rope), _elem_of(wk, elem), _p(ws), need, _stream()), "mli_paged_attention_lean_rope")
+        return
     if alibi_slopes is not None:
         if sinks is not None and window is None:
             raise ValueError("sinks exist beside a window: pass window= as well")
@@ -394,13 +416,21 @@ def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_outpu
 
 
 def paged_prefill(emb_table, wpe, inp, page_table, lengths, new_item_indices, wk, wv, n_new_items, elem=None, window=None,
-                  sinks=None):
+                  sinks=None, n_heads=1, rope=None):
     """Encoder + prefill fill in one launch (mli_paged_prefill); page element type = elem, default from the weights.
     window given (sinks beside it): the prefill of the rows' live tokens (mli_paged_prefill_window) -- pages between the
-    sink pages and the window's first page are neither looked up nor written."""
+    sink pages and the window's first page are neither looked up nor written.
+    rope given (a [S, D / n_heads / 2, 2] float32 (cos, sin) table on the device): K is stored rotated by the token's slot
+    (mli_paged_prefill_rope), with or without a window."""
     B, S = inp.shape
     if sinks is not None and window is None:
         raise ValueError("sinks exist beside a window: pass window= as well")
+    if rope is not None:
+        _check(load_library().mli_paged_prefill_rope(_p(emb_table), _p(wpe), _p(inp), _p(page_table), _p(lengths),
+                                                     _p(new_item_indices), _p(wk), _p(wv), B, S, emb_table.shape[1],
+                                                     n_new_items, window or 0, sinks or 0, int(n_heads), _p(rope),
+                                                     _elem_of(wk, elem), _stream()), "mli_paged_prefill_rope")
+        return
     if window is not None:
         _check(load_library().mli_paged_prefill_window(_p(emb_table), _p(wpe), _p(inp), _p(page_table), _p(lengths),
                                                        _p(new_item_indices), _p(wk), _p(wv), B, S, emb_table.shape[1],
@@ -761,9 +791,26 @@ def f32_to_fp8(src, dst=None):
     return dst
 
 
-def get_latest_k_q_v_paged_lean(page_table, lengths, wk, wq, wv, q_output, n_sequence, elem=None):
-    """The decode projection for any page element type (mli_get_latest_k_q_v_paged_lean)."""
+def get_latest_k_q_v_paged_lean(page_table, lengths, wk, wq, wv, q_output, n_sequence, elem=None, n_heads=1, rope=None):
+    """The decode projection for any page element type (mli_get_latest_k_q_v_paged_lean).  rope given (a [n_sequence,
+    D / n_heads / 2, 2] float32 (cos, sin) table on the device): k and q are rotated by slot L - 1
+    (mli_get_latest_k_q_v_paged_rope)."""
     B = page_table.shape[0]
+    if rope is not None:
+        _check(load_library().mli_get_latest_k_q_v_paged_rope(_p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(q_output),
+                                                              B, n_sequence, wq.shape[0], int(n_heads), _p(rope),
+                                                              _elem_of(wk, elem), _stream()),
+               "mli_get_latest_k_q_v_paged_rope")
+        return
     _check(load_library().mli_get_latest_k_q_v_paged_lean(_p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(q_output), B,
                                                           n_sequence, wq.shape[0], _elem_of(wk, elem), _stream()),
            "mli_get_latest_k_q_v_paged_lean")
+
+
+def fill_new_k_v_cache_paged_rope(page_table, new_batch_idx, lengths, wk, wv, n_new_items, n_sequence, n_heads, rope, elem=None):
+    """The prefill fill reading x from the pages, K rotated by the token's slot (mli_fill_new_k_v_cache_paged_rope)."""
+    B = page_table.shape[0]
+    _check(load_library().mli_fill_new_k_v_cache_paged_rope(_p(page_table), _p(new_batch_idx), _p(lengths), _p(wk), _p(wv), B,
+                                                            n_sequence, wk.shape[0], n_new_items, int(n_heads), _p(rope),
+                                                            _elem_of(wk, elem), _stream()),
+           "mli_fill_new_k_v_cache_paged_rope")
