@@ -224,6 +224,20 @@ int mli_engine_set_alibi(mli_engine* engine, const float* slopes_host, int n);
 int mli_engine_set_rope(mli_engine* engine, double theta);
 int mli_engine_set_rope_table(mli_engine* engine, const float* table_host, size_t n_floats);
 
+/* EXTENSION: attention logit soft-capping (mli_kernels.h: mli_paged_attention_lean_softcap).  Every decode scan of the engine
+ * -- and, with mli_engine_set_prompt_logprobs, every prompt scan -- replaces query head h's scaled score x of an attended slot
+ * by cap * tanh(x / cap): the engine scores its prompts under the model it decodes with.  cap: finite and > 0; 0 turns the cap
+ * off again.  Pages, pool, projection, prefill and the decoder head never see it.  Before the first step or run;
+ * MLI_ENGINE_PAGED, MLI_ENGINE_PAGED_GEMM or MLI_ENGINE_PAGED_BF16 with lean layers and two heads at least (set the heads
+ * first).  Composes with mli_engine_set_kv_heads, _set_window, _set_sinks, _set_page_release, _set_rope[_table],
+ * _set_logprobs, _set_prompt_logprobs, sampling, both loops, n_forward_rounds and step graphs; every setter validates the
+ * combination, whichever comes last.  -1 with a message for a null engine, a negative or non-finite cap, n_heads < 2
+ * (mli_engine_set_heads(e, 1) afterwards is refused likewise), MLI_ENGINE_CONTIGUOUS and MLI_ENGINE_PAGED_FP8, a started
+ * engine, lean_layers = 0 (mli_engine_configure(e, 0, ...) afterwards is refused likewise), and an engine with ALiBi
+ * (mli_engine_set_alibi afterwards is refused likewise: no order of bias and cap is defined).  Without the call nothing changes
+ * anywhere. */
+int mli_engine_set_softcap(mli_engine* engine, float cap);
+
 /* EXTENSION: sliding-window attention (mli_kernels.h: mli_paged_attention_lean_window).  Every row attends its newest
  * `window` tokens only.  The window changes which slots the scan reads and nothing else: admission, page growth,
  * preemption, re-prefill, n_forward_rounds (the window follows the device-side length), step graphs, sampling and the

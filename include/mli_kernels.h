@@ -399,6 +399,36 @@ int mli_paged_attention_lean_rope(void* const* page_table, const int* lengths, c
                                   int n_sink, const float* slopes, const float* rope_table, int elem, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* EXTENSION: ATTENTION LOGIT SOFT-CAPPING for the multi-head scan (the logits_soft_cap / attn_logit_softcapping argument of
+ * other serving stacks' paged attention; Gemma 2, Grok-1).  cap: one finite fp32 value > 0 per call, a HOST value.  For row b
+ * with L = min(lengths[b], n_sequence), query head h, g = n_heads / n_kv_heads and an attended slot s:
+ *     x[h][s] = cap * tanh( ((q_h . K_{h/g}[s]) / sqrtf(head_dim)) / cap )
+ * The cap is applied to the SCALED score, before the mask and the maximum; a masked slot stays excluded (it never becomes a
+ * finite score of -cap).  The attended set for (window, n_sink), the softmax, p . V, the zero row for L == 0 and the never-read
+ * dead slots, gap slots and gap pages are mli_decode_scan_paged_gqa's.  There is no cap that gives back the bits of that call;
+ * L == 1, and a one-slot window without sinks, give V's row L - 1 bit for bit whatever the cap.  tanh is evaluated in fp32 to
+ * about 3.5 * 2^-24 RELATIVE to the score, however small the score is beside the cap.
+ * One scan launch ("scan_heads_softcap"), the grid, item size, mli_tune keys and workspace
+ * (mli_attention_heads_workspace_bytes(n_batch, n_sequence, emb_dim, n_heads): one buffer serves plain and capped calls) of
+ * the _gqa call.  Shapes: what that call takes with n_heads >= 2 -- head_dim 32, 64, 128 or 256, fp32 pages to emb_dim 512,
+ * bf16 pages to 1024; n_kv_heads == n_heads: no grouping.  MLI_ERR_BAD_ARG, decided before anything is launched: n_heads == 1
+ * (the single-head scans have no cap), fp8 pages, cap <= 0, NaN or infinite, and every argument the _gqa call refuses.
+ * MLI_ERR_WORKSPACE as there.  Not combined with ALiBi (no published model uses both; the order of bias and cap would be an
+ * invention): there is no slopes argument. */
+int mli_decode_scan_paged_softcap(const float* q_output, const void* const* page_table, const int* lengths,
+                                  float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads,
+                                  int window, int n_sink, float cap, int elem, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+
+/* mli_paged_attention_lean_gqa with the cap: fill (n_new_items rows) -> latest -> the scan above.  rope_table: null, or the
+ * table of mli_paged_attention_lean_rope (then fill and latest are that call's: K and q rotated; Gemma 2 uses both).  Fill and
+ * projection never see the cap.  MLI_ERR_BAD_ARG as above and, with a table, as mli_paged_attention_lean_rope. */
+int mli_paged_attention_lean_softcap(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                     const int* new_batch_idx, float* q_output, float* attention_result, int n_batch,
+                                     int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
+                                     int n_sink, float cap, const float* rope_table, int elem, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */
@@ -622,6 +652,22 @@ int mli_paged_prompt_logprobs(const void* const* page_table, const int* inp, con
                               int n_kv_heads, int window, int n_sink, int elem, int n_top, void* scratch, size_t scratch_bytes,
                               void* stream);
 
+/* EXTENSION: the two calls above with logit soft-capping (mli_decode_scan_paged_softcap has the formula): query t of a segment
+ * gets what the capped decode scan gives a row of length t + 1, so a prompt is scored under the model that decodes.  One launch
+ * ("scan_prompt_softcap") with the SAME queries per workgroup as the uncapped variant: mli_prompt_scan_tq holds for both (the
+ * capped kernels compile without scratch at it).  Scratch: mli_prompt_logprobs_scratch_bytes.  MLI_ERR_BAD_ARG before any
+ * launch: n_heads == 1, cap <= 0, NaN or infinite, and everything the uncapped call refuses (fp8 pages among it). */
+int mli_prompt_scan_paged_softcap(const float* q, const void* const* page_table, const int* seg_row, const int* seg_first,
+                                  const int* seg_count, const int* seg_offset, float* out, int n_seg, int max_count, int n_q,
+                                  int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads, int window, int n_sink,
+                                  float cap, int elem, void* stream);
+int mli_paged_prompt_logprobs_softcap(const void* const* page_table, const int* inp, const void* wq, const float* emb_table,
+                                      const int* seg_row, const int* seg_first, const int* seg_count, const int* seg_offset,
+                                      float* token_logprob, int* top_ids, float* top_logprobs, int n_seg, int max_count,
+                                      int n_positions, int n_batch, int n_sequence, int emb_dim, int n_vocab, int n_heads,
+                                      int n_kv_heads, int window, int n_sink, float cap, int elem, int n_top, void* scratch,
+                                      size_t scratch_bytes, void* stream);
+
 /* PREFILL of the newly inserted rows in ONE launch: the encoder as the fill GEMM's prologue.  The A
  * tile rows are computed on the fly as emb_table[inp[b, s]] + wpe[s] -- nothing is read back from the input-embedding
  * segment -- multiplied by [Wk | Wv], and the workgroups of the first column tile also write those rows to segment 0
@@ -795,6 +841,8 @@ int mli_tune(const char* key, int value);
  *   "scan_heads_window"      the scans with several heads, a window, sinks or grouped K/V heads
  *   "scan_prompt"            the causal multi-query scan over prompt positions (mli_prompt_scan_paged)
  *   "scan_heads_alibi"       the multi-head scans with a position bias per head (mli_decode_scan_paged_alibi)
+ *   "scan_heads_softcap"     the multi-head scans with logit soft-capping (mli_decode_scan_paged_softcap)
+ *   "scan_prompt_softcap"    the prompt scan with logit soft-capping (mli_prompt_scan_paged_softcap)
  * Forms, counted beside the launch's kernel family:
  *   "latest_compact"         a decode projection over the compacted list of non-empty rows ("latest_compact"; the panel and
  *                            the LDS-DMA kernel have no such list)

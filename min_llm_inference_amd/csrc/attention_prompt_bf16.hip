@@ -4,4 +4,6 @@
 namespace mli {
 template int launch_prompt_scan<ElemBF16>(const float*, const void* const*, const int*, const int*, const int*, const int*, float*,
                                           int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
+template int launch_prompt_softcap_scan<ElemBF16>(const float*, const void* const*, const int*, const int*, const int*, const int*,
+                                                  float*, int, int, int, int, int, int, int, int, int, int, int, float, hipStream_t);
 }

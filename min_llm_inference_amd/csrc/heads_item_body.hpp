@@ -24,6 +24,32 @@ __device__ __forceinline__ float div_by(float x, float d, float r) {
     return fmaf(fmaf(-qt, d, x), r, qt);
 }
 
+// EXTENSION (attention_softcap.hpp): logit soft-capping, cap * tanh(x / cap) of a scaled score x; cap > 0 finite, r = 1 / cap.
+// The one evaluation of the cap on the device: the multi-head decode scan below and the prompt scan (attention_prompt.hpp) call
+// it between div_by and the page maximum, and nothing else does.  u = x / cap by div_by (half an ulp).  Below |u| = 0.5 an odd
+// polynomial u + u^3 P(u^2) (degree 4 in u^2, fitted at Chebyshev nodes; 1.1 * 2^-24 relative in fp32, and exactly u where u^3
+// vanishes beside u: the value is accurate RELATIVE to the score however small the score is beside the cap); from 0.5 on
+// 1 - 2 / (e^{2|u|} + 1) with the sign of u, whose absolute error of about 2^-24 is then relative too (tanh >= 0.46; 3.5 * 2^-24
+// measured).  Both are computed and one select picks: no branch, no table, two transcendental instructions.  e^{2|u|} = inf
+// gives 1 exactly; a NaN score stays NaN (the mask drops dead slots AFTER the cap, by select: tanh(-inf) = -1 never gets
+// the chance to make a dead slot a finite -cap).  Contraction is off inside: the closing product must be ROUNDED before the
+// softmax subtracts the maximum from it -- fused into that subtraction, a row's only score minus itself is no longer 0 and a row
+// of one token no longer returns V's row bit for bit.  (The fmaf calls are fused by their own text.)
+__device__ __forceinline__ float softcap_score(float x, float cap, float r) {
+#pragma clang fp contract(off)
+    const float u = div_by(x, cap, r);
+    const float a = fabsf(u);
+    const float z = u * u;
+    float p = fmaf(-0.00694699864834547f, z, 0.021472718566656113f);
+    p = fmaf(p, z, -0.05393378809094429f);
+    p = fmaf(p, z, 0.1333322674036026f);
+    p = fmaf(p, z, -0.3333333134651184f);
+    const float lo = fmaf(u * z, p, u);
+    const float e = __expf(2.f * a);
+    const float hi = copysignf(fmaf(-2.f, __builtin_amdgcn_rcpf(e + 1.f), 1.f), u);
+    return cap * (a < 0.5f ? lo : hi);
+}
+
 // The partner's value for one step of the all-reduce inside a lane group.  Distances 1 and 2 are DPP quad permutes; 4 and
 // 8 are the DPP mirrors of 8 and 16 lanes (lane i <-> 7 - i, i <-> 15 - i): after the earlier steps every lane of the
 // smaller group holds the same value, so the mirror pairs the same two groups the xor would.  No LDS crossbar trip and no
@@ -62,13 +88,18 @@ __device__ __forceinline__ void heads_xor_step(float (&v)[NJ][16]) {
 // the scaled score of the row's absolute slot s -- 0 at the newest token.  A lane keeps the slope of its own head per lane
 // load; the bias is one fmaf between div_by and the page maximum, on the page's first absolute slot, which the body has
 // already.  The bias is absolute in the row, so the (m, l) of a row's items live in one frame and the merges do not change.
-template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false, bool SINK = false, bool GQA = false, bool ALIBI = false>
+// SOFTCAP = true (EXTENSION, attention_softcap.hpp; never with ALIBI): logit soft-capping, the scaled score x becomes
+// cap * tanh(x / cap) (softcap_score) at the same place, between div_by and the page maximum; cap is a kernel argument.  A
+// pure function of the score: masks, (m, l) frames and merges do not change, and a masked slot stays masked.
+template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false, bool SINK = false, bool GQA = false, bool ALIBI = false,
+          bool SOFTCAP = false>
 __device__ __forceinline__ void heads_scan_item(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ out, float2* ml, float* partial, int S, int D, int lg, int H, int ct, int nchunk_max, int direct,
     unsigned* arrivals, int b, int c, bool first_grid_row, unsigned char* smem_raw, int window = 0, int n_sink = 0,
-    int gq = 1, const float* __restrict__ slopes = nullptr) {
+    int gq = 1, const float* __restrict__ slopes = nullptr, float cap = 0.f) {
     static_assert(!SINK || WIN, "sinks exist beside a window only");
+    static_assert(!(ALIBI && SOFTCAP), "the order of bias and cap would be an invention");
     constexpr int EPL = E::EPL;
     constexpr int kRowF = NJ * kWave * EPL;   // floats one wave parks
     constexpr int kRowU = NJ * kWave;         // lane units of a row
@@ -145,6 +176,7 @@ __device__ __forceinline__ void heads_scan_item(
 
     const float scale = sqrtf((float)(EPL << lg));   // sqrtf(head_dim)
     const float inv_scale = 1.f / scale;
+    const float inv_cap = SOFTCAP ? 1.f / cap : 0.f;
     const int64_t row_bytes = (int64_t)3 * D * E::kBytes;
     const int64_t seg_bytes = (int64_t)D * E::kBytes;
 
@@ -249,6 +281,7 @@ __device__ __forceinline__ void heads_scan_item(
                         for (int t = 0; t < 16; ++t) {
                             sp[j][t] = div_by(sp[j][t], scale, inv_scale);
                             if constexpr (ALIBI) sp[j][t] = fmaf(slope[j], rel0 + (float)t, sp[j][t]);
+                            if constexpr (SOFTCAP) sp[j][t] = softcap_score(sp[j][t], cap, inv_cap);
                             pm = slot_live<WIN, SINK>(t, nt, nlo, nk) ? fmaxf(pm, sp[j][t]) : pm;
                         }
                         const float m_new = fmaxf(run_m[j], pm);

@@ -34,6 +34,8 @@ enum LaunchFamily {
     kLfScanHeadsAlibi,    // attention_alibi.hpp: the multi-head scans with a linear position bias per query head
     kLfGemmF32Rope,       // proj_gemm.hip: a tiled fp32-MFMA form with rotary position embeddings (beside that form's family)
     kLfGemmBf16Rope,      // proj_gemm_bf16.hip: a tiled bf16-MFMA form with rotary position embeddings (beside that form's family)
+    kLfScanHeadsSoftcap,  // attention_softcap.hpp: the multi-head scans with logit soft-capping
+    kLfScanPromptSoftcap, // attention_prompt.hpp: the prompt scan with logit soft-capping
     kLaunchFamilies
 };
 
@@ -42,7 +44,8 @@ constexpr const char* kLaunchFamilyNames[kLaunchFamilies] = {
     "gemm_bf16_rows64", "gemm_bf16_deep",   "gemm_bf16_rows128",     "gemm_bf16_dma",     "gemm_bf16_fill",
     "latest_compact",  "fill_flat",         "fill_per_row",          "prefill_fused",     "prefill_two_launch",
     "scan_equal_shares", "scan_chunked",    "scan_rows_ordered",     "scan_rows_grid_order", "scan_heads_window",
-    "scan_prompt",     "scan_heads_alibi",  "gemm_f32_rope",         "gemm_bf16_rope",
+    "scan_prompt",     "scan_heads_alibi",  "gemm_f32_rope",         "gemm_bf16_rope",    "scan_heads_softcap",
+    "scan_prompt_softcap",
 };
 
 inline thread_local uint64_t g_launch_counts[kLaunchFamilies] = {};

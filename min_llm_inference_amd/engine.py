@@ -40,7 +40,7 @@ class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
                  n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None,
                  release_pages=False, n_kv_heads=None, logprobs=None, prompt_logprobs=False, alibi=None,
-                 rope=None):
+                 rope=None, softcap=None):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -66,6 +66,8 @@ class Engine:
             self.set_alibi(None if alibi is True else alibi)
         if rope is not None and rope is not False:
             self.set_rope(10000.0 if rope is True else rope)
+        if softcap is not None:
+            self.set_softcap(softcap)
 
     def _check(self, rc):
         if rc != 0:
@@ -90,6 +92,12 @@ class Engine:
             return
         a = np.ascontiguousarray(slopes, dtype=np.float32).reshape(-1)
         self._check(self._lib.mli_engine_set_alibi(self._h, a.ctypes.data_as(ctypes.c_void_p), int(a.size)))
+
+    def set_softcap(self, cap):
+        """Attention logit soft-capping (mli_engine_set_softcap): every decode scan -- and the prompt scan of an engine with
+        prompt log-probabilities -- replaces a scaled score x by cap * tanh(x / cap).  cap: finite and > 0; 0 turns it off.
+        Before the first step or run, fp32 / bf16 paged kinds with n_heads >= 2 and lean layers, not with ALiBi."""
+        self._check(self._lib.mli_engine_set_softcap(self._h, float(cap)))
 
     def set_rope(self, rope=10000.0):
         """Rotary position embeddings (mli_engine_set_rope / mli_engine_set_rope_table): prefill and projection rotate K and q

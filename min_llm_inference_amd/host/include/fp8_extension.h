@@ -23,6 +23,7 @@ private:  // the fp8 scan has one head: of the option setters the layer has set_
     using PagedAttentionOptionSetters::set_n_heads;
     using PagedAttentionOptionSetters::set_n_kv_heads;
     using PagedAttentionOptionSetters::set_alibi_slopes;
+    using PagedAttentionOptionSetters::set_softcap;
 };
 
 class PagedAttentionFp8InferenceModel : public PagedInferenceModel {
@@ -36,6 +37,7 @@ private:
     using PagedAttentionOptionSetters::set_n_heads;  // as the layer
     using PagedAttentionOptionSetters::set_n_kv_heads;
     using PagedAttentionOptionSetters::set_alibi_slopes;
+    using PagedAttentionOptionSetters::set_softcap;
     DecoderHead& decoder_head() override { return decoder_head_; }
     PagedAttentionFp8Layer attention_layer_;
     // lean only: the scratch of mli_decoder_scratch_bytes, and the logits buffer once sampling is set

@@ -60,11 +60,14 @@ struct PagedAttentionOptions {
     // set_rope sizes the table by them.
     std::shared_ptr<TensorFloat> rope_table;
     int n_sequence = 0, emb_dim = 0;
+    // Logit soft-capping: every scaled attention score x becomes softcap * tanh(x / softcap), in the decode scan and in the
+    // prompt scan (0: none) -- mli_paged_attention_lean_softcap, mli_paged_prompt_logprobs_softcap
+    float softcap = 0.f;
 };
 
 // The setters of the option set, defined once for every class that has them: a layer owns the struct, a model hands out
-// its layer's.  A class whose scan has one head only (fp8 pages) takes set_n_heads / set_n_kv_heads / set_alibi_slopes out
-// of its interface.
+// its layer's.  A class whose scan has one head only (fp8 pages) takes set_n_heads / set_n_kv_heads / set_alibi_slopes /
+// set_softcap out of its interface.
 class PagedAttentionOptionSetters {
 public:
     // EXTENSION: ALiBi -- slopes[h] * (s - (L - 1)) added to query head h's scaled scores; n_heads finite values, uploaded
@@ -79,6 +82,10 @@ public:
     // last (PagedAttentionLayerCore::check_rope).
     void set_rope(double theta);
     void set_rope_table(const std::vector<float>& table);
+    // EXTENSION: attention logit soft-capping -- cap * tanh(x / cap) on every scaled score of the decode scan and of the prompt
+    // scan; 0 takes the cap away again.  A negative or non-finite cap throws here; two heads at least, the lean layers and no
+    // slopes beside it are held at every forward, whichever setter came last (PagedAttentionLayerCore::check_softcap).
+    void set_softcap(float cap);
     void set_n_heads(int n_heads) { options().n_heads = n_heads; }
     void set_n_kv_heads(int n_kv_heads) { options().n_kv_heads = n_kv_heads; }
     void set_window(int window) { options().window = window; }
@@ -119,6 +126,9 @@ protected:
     // throws where a rotary table is set and is not n_sequence * head_dim floats for an even head_dim = emb_dim / n_heads, or
     // the lean layers are off (the materialising compositions have no rotation): first thing in every prefill and forward
     void check_rope() const;
+    // throws where a cap is set beside n_heads < 2, the lean layers off (the materialising composition has no cap and must
+    // never drop it silently) or ALiBi slopes (no order of bias and cap is defined): first thing in every forward
+    void check_softcap() const;
 
     int elem_;
     Weights wk_, wq_, wv_;

@@ -49,12 +49,14 @@ bool lean_layers();
 // query head has its own K/V head, the calls above; anything else is mli_paged_attention_lean_gqa.  alibi_slopes (EXTENSION,
 // n_heads floats in device memory; null: none): mli_paged_attention_lean_alibi, whatever the other options are.  rope_table
 // (EXTENSION, [n_sequence][head_dim / 2] (cos, sin) in device memory; null: none): mli_paged_attention_lean_rope, whatever the
-// other options are, slopes included; every failure throws.
+// other options are, slopes included; every failure throws.  softcap (EXTENSION, logit soft-capping; 0: none):
+// mli_paged_attention_lean_softcap, with or without a rotary table; slopes beside it throw.
 bool lean_paged_wanted(int n_heads, int window, int n_sequence);
 int lean_paged_attention(int elem, int n_heads, int window, int n_sink, void* const* page_table, const int* lengths,
                          const void* wk, const void* wq, const void* wv, const int* new_batch_idx, float* q_output,
                          float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_new_items,
-                         int n_kv_heads = 0, const float* alibi_slopes = nullptr, const float* rope_table = nullptr);
+                         int n_kv_heads = 0, const float* alibi_slopes = nullptr, const float* rope_table = nullptr,
+                         float softcap = 0.f);
 
 // Which loop start_paged_attention_*_inference_engine runs (default false): the pipelined loop
 // (pipelined_engine.h: the host one step behind the GPU, same tokens per item) wherever it applies -- up to

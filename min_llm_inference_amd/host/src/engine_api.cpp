@@ -233,7 +233,14 @@ struct mli_engine {
                 }
                 seg_device.copy_from(seg_host);
                 const int* d = seg_device.data();
-                const int rc = mli_paged_prompt_logprobs(
+                // (an engine with a cap scores its prompts under the model it decodes with: the capped prompt scan)
+                const int rc = o.softcap != 0.f
+                    ? mli_paged_prompt_logprobs_softcap(
+                          page_table, inp, wq, emb_table, d, d + limit, d + 2 * limit, d + 3 * limit, token_device.data(),
+                          n_top > 0 ? ids_device.data() : nullptr, n_top > 0 ? top_device.data() : nullptr, n_seg, pass.max_count,
+                          pass.n_positions, n_batch, n_sequence, emb_dim, n_vocab, o.n_heads, n_kv_heads, o.window, o.n_sink,
+                          o.softcap, elem, n_top, scratch.data(), scratch_bytes, mli::runtime::compute_stream())
+                    : mli_paged_prompt_logprobs(
                     page_table, inp, wq, emb_table, d, d + limit, d + 2 * limit, d + 3 * limit, token_device.data(),
                     n_top > 0 ? ids_device.data() : nullptr, n_top > 0 ? top_device.data() : nullptr, n_seg, pass.max_count,
                     pass.n_positions, n_batch, n_sequence, emb_dim, n_vocab, o.n_heads, n_kv_heads, o.window, o.n_sink, elem,
@@ -557,6 +564,8 @@ int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
     MLI_GUARD({
         if (e->started) throw std::runtime_error("mli_engine_configure after the engine has started");
         PagedAttentionOptions& o = e->options();
+        if (o.softcap != 0.f && lean_layers == 0)   // (named first: an engine with a cap has two heads at least)
+            throw std::runtime_error("logit soft-capping (mli_engine_set_softcap) has the lean compositions only");
         if (o.n_heads > 1 && lean_layers == 0)   // refused before anything is changed
             throw std::runtime_error("multi-head attention (mli_engine_set_heads) has the lean compositions only");
         if (o.n_kv_heads != 0 && lean_layers == 0)
@@ -602,6 +611,8 @@ int mli_engine_set_heads(mli_engine* e, int n_heads) {
             if (o.rope_table)
                 throw std::runtime_error("mli_engine_set_heads: the stored rotary table (mli_engine_set_rope) is that of " +
                                          std::to_string(o.n_heads) + " heads");
+            if (o.softcap != 0.f && n_heads < 2)
+                throw std::runtime_error("mli_engine_set_heads: the stored cap (mli_engine_set_softcap) needs two heads at least");
             o.n_heads = n_heads;
         }
     })
@@ -649,6 +660,9 @@ int mli_engine_set_alibi(mli_engine* e, const float* slopes_host, int n) {
         if (slopes_host != nullptr && n != o.n_heads)
             throw std::runtime_error("mli_engine_set_alibi: n must be the engine's n_heads (" + std::to_string(o.n_heads) + ")");
         if (!e->lean_layers) throw std::runtime_error("mli_engine_set_alibi: ALiBi has the lean compositions only");
+        if (o.softcap != 0.f)
+            throw std::runtime_error("mli_engine_set_alibi: not with logit soft-capping (mli_engine_set_softcap: no order of bias "
+                                     "and cap is defined)");
         if (e->prompt_logprobs_wanted)
             throw std::runtime_error("mli_engine_set_alibi: not with prompt log-probabilities (the prompt scan has no bias: the "
                                      "prompt would be scored under another model than the one that decodes)");
@@ -663,6 +677,35 @@ int mli_engine_set_alibi(mli_engine* e, const float* slopes_host, int n) {
                                      "n_kv_heads)");
         mli::runtime::use_device(e->cfg.device);
         e->paged->set_alibi_slopes(slopes);
+    })
+}
+
+// The cap is a field of the option set; the decode scan and the prompt scan of the engine read it there.  The shapes are the
+// multi-head scan's, which set_heads / set_kv_heads / set_window have validated; they are checked again here.
+int mli_engine_set_softcap(mli_engine* e, float cap) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (e->started) throw std::runtime_error("mli_engine_set_softcap after the engine has started");
+        if (!e->heads_kind())
+            throw std::runtime_error("mli_engine_set_softcap: logit soft-capping serves the fp32 and bf16 paged engines");
+        if (!std::isfinite(cap) || cap < 0.f)
+            throw std::runtime_error("mli_engine_set_softcap: the cap must be finite and >= 0 (0: none)");
+        PagedAttentionOptions& o = e->options();
+        if (cap != 0.f) {
+            if (o.n_heads < 2)
+                throw std::runtime_error("mli_engine_set_softcap: n_heads must be >= 2 (mli_engine_set_heads comes first; the "
+                                         "single-head scans have no cap)");
+            if (!e->lean_layers)
+                throw std::runtime_error("mli_engine_set_softcap: logit soft-capping has the lean compositions only");
+            if (o.alibi_slopes)
+                throw std::runtime_error("mli_engine_set_softcap: not with ALiBi (mli_engine_set_alibi: no order of bias and cap "
+                                         "is defined)");
+            const int n_kv_heads = o.n_kv_heads != 0 ? o.n_kv_heads : o.n_heads;
+            if (!mli::gqa_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, o.n_heads, n_kv_heads, e->elem()))
+                throw std::runtime_error("mli_engine_set_softcap: the scan does not take this (n_batch, n_sequence, emb_dim, "
+                                         "n_heads, n_kv_heads)");
+        }
+        e->paged->set_softcap(cap);
     })
 }
 

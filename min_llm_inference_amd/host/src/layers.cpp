@@ -59,6 +59,11 @@ void PagedAttentionOptionSetters::set_alibi_slopes(const std::vector<float>& slo
     options().alibi_slopes = std::move(device);
 }
 
+void PagedAttentionOptionSetters::set_softcap(float cap) {
+    if (!std::isfinite(cap) || cap < 0.f) throw std::invalid_argument("set_softcap: the cap must be finite and >= 0 (0: none)");
+    options().softcap = cap;
+}
+
 void PagedAttentionOptionSetters::set_rope_table(const std::vector<float>& table) {
     if (table.empty()) {
         options().rope_table.reset();
@@ -139,10 +144,24 @@ void PagedAttentionLayerCore<Weights>::check_rope() const {
     if (!mli::runtime::lean_layers()) throw std::runtime_error("RoPE exists in the lean composition only");
 }
 
+// As check_alibi.  One head would take the single-head scans or the materialising composition, which have no cap: a cap beside
+// one head, or with the lean layers off, throws here instead of being dropped.
+template <class Weights>
+void PagedAttentionLayerCore<Weights>::check_softcap() const {
+    if (options_.softcap == 0.f) return;
+    if (options_.n_heads < 2)
+        throw std::runtime_error("logit soft-capping (set_softcap) beside n_heads = " + std::to_string(options_.n_heads) +
+                                 ": two heads at least");
+    if (!mli::runtime::lean_layers()) throw std::runtime_error("logit soft-capping exists in the lean composition only");
+    if (options_.alibi_slopes)
+        throw std::runtime_error("logit soft-capping (set_softcap) and ALiBi (set_alibi_slopes) are not combined");
+}
+
 template <class Weights>
 int PagedAttentionLayerCore<Weights>::lean_scan(TensorFloatPoint& page_table, const TensorInt& lengths,
                                                 const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                                 int n_new_items, int n_heads, int n_kv_heads) {
+    check_softcap();
     check_alibi();
     check_rope();
     return mli::runtime::lean_paged_attention(elem_, n_heads, options_.window, options_.n_sink,
@@ -151,7 +170,7 @@ int PagedAttentionLayerCore<Weights>::lean_scan(TensorFloatPoint& page_table, co
                                               attention_result.data(), (int)page_table.shape()[0], (int)n_sequence_,
                                               (int)wk_.shape()[0], n_new_items, n_kv_heads,
                                               options_.alibi_slopes ? options_.alibi_slopes->data() : nullptr,
-                                              options_.rope_table ? options_.rope_table->data() : nullptr);
+                                              options_.rope_table ? options_.rope_table->data() : nullptr, options_.softcap);
 }
 
 template class PagedAttentionLayerCore<TensorFloat>;
@@ -165,6 +184,7 @@ PagedAttentionFloatLayer::PagedAttentionFloatLayer(TensorFloat&& wk, TensorFloat
 bool PagedAttentionFloatLayer::forward_lean(TensorFloatPoint& page_table, const TensorInt& lengths,
                                             const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                             int n_new_items) {
+    check_softcap();
     check_alibi();
     check_rope();
     if (!mli::runtime::lean_paged_wanted(options_.n_heads, options_.window, (int)n_sequence_)) return false;

@@ -364,9 +364,22 @@ def decode_scan_paged_alibi(q_output, page_table, lengths, attention_result, n_h
                                                       _stream()), "mli_decode_scan_paged_alibi")
 
 
+def decode_scan_paged_softcap(q_output, page_table, lengths, attention_result, n_heads, n_kv_heads, window, sinks, softcap, elem,
+                              n_sequence):
+    """decode_scan_paged_gqa with logit soft-capping (mli_decode_scan_paged_softcap): query head h's scaled score x of an
+    attended slot becomes softcap * tanh(x / softcap).  softcap: a finite float > 0; n_heads >= 2; n_kv_heads None or n_heads:
+    no grouping."""
+    B, D = q_output.shape
+    ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+    _check(load_library().mli_decode_scan_paged_softcap(_p(q_output), _p(page_table), _p(lengths), _p(attention_result), B,
+                                                        int(n_sequence), D, int(n_heads), int(n_kv_heads or n_heads),
+                                                        int(window or 0), int(sinks or 0), float(softcap), int(elem), _p(ws),
+                                                        need, _stream()), "mli_decode_scan_paged_softcap")
+
+
 def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_new_items,
                          n_sequence, elem=None, n_heads=1, window=None, sinks=None, n_kv_heads=None, alibi_slopes=None,
-                         rope=None):
+                         rope=None, softcap=None):
     """What the attention layers run: the paged composition without materialising scores / probabilities
     (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads != 1: the
     multi-head form (mli_paged_attention_lean_heads); window given: the sliding-window form
@@ -376,7 +389,21 @@ def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_outpu
     alibi_slopes given (n_heads float32 values on the device): the scan adds the position bias of decode_scan_paged_alibi
     (mli_paged_attention_lean_alibi), with any of window, sinks and n_kv_heads;
     rope given (a [n_sequence, D / n_heads / 2, 2] float32 (cos, sin) table on the device): fill and projection rotate K and q
-    by the token's absolute slot (mli_paged_attention_lean_rope), with any of the above."""
+    by the token's absolute slot (mli_paged_attention_lean_rope), with any of the above;
+    softcap given (a finite float > 0): the scan caps its scaled scores as decode_scan_paged_softcap does
+    (mli_paged_attention_lean_softcap), with any of window, sinks, n_kv_heads and rope, never with alibi_slopes."""
+    if softcap is not None:
+        if alibi_slopes is not None:
+            raise ValueError("logit soft-capping and ALiBi are not combined")
+        if sinks is not None and window is None:
+            raise ValueError("sinks exist beside a window: pass window= as well")
+        B, D = page_table.shape[0], wk.shape[0]
+        ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+        _check(load_library().mli_paged_attention_lean_softcap(
+            _p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(new_batch_idx), _p(q_output), _p(attention_result), B,
+            int(n_sequence), D, int(n_new_items), int(n_heads), int(n_kv_heads or n_heads), int(window or 0), int(sinks or 0),
+            float(softcap), _p(rope), _elem_of(wk, elem), _p(ws), need, _stream()), "mli_paged_attention_lean_softcap")
+        return
     if rope is not None:
         if sinks is not None and window is None:
             raise ValueError("sinks exist beside a window: pass window= as well")
@@ -550,16 +577,24 @@ def prompt_scan_tq(emb_dim, n_heads, elem):
 
 
 def prompt_scan_paged(q, page_table, segments, out, n_batch, n_sequence, elem, n_heads=1, n_kv_heads=None, window=None,
-                      sinks=None, seg_arrays=None):
+                      sinks=None, seg_arrays=None, softcap=None):
     """EXTENSION: the causal multi-query paged scan (mli_prompt_scan_paged).  segments = [(row, first position,
     count)]: query j of a segment is position first + j of its row and attends the slots s <= its position (inside the window or
     among the sinks); q and out [n_q, D] hold the queries in list order.  seg_arrays = (rows, first, count, offset, max_count)
-    device arrays replace the list."""
+    device arrays replace the list.  softcap given (a finite float > 0, n_heads >= 2): every scaled score x becomes
+    softcap * tanh(x / softcap) (mli_prompt_scan_paged_softcap)."""
     n_q, D = q.shape
     if seg_arrays is None:
         arrays, max_count, _ = _segments(segments, q.device)
     else:
         arrays, max_count = list(seg_arrays[:4]), int(seg_arrays[4])
+    if softcap is not None:
+        _check(load_library().mli_prompt_scan_paged_softcap(_p(q), _p(page_table), *map(_p, arrays), _p(out),
+                                                            int(arrays[0].numel()), max_count, n_q, int(n_batch), int(n_sequence),
+                                                            D, int(n_heads), int(n_kv_heads or n_heads), int(window or 0),
+                                                            int(sinks or 0), float(softcap), int(elem), _stream()),
+               "mli_prompt_scan_paged_softcap")
+        return out
     _check(load_library().mli_prompt_scan_paged(_p(q), _p(page_table), *map(_p, arrays), _p(out), int(arrays[0].numel()),
                                                 max_count, n_q, int(n_batch), int(n_sequence), D, int(n_heads),
                                                 int(n_kv_heads or n_heads), int(window or 0), int(sinks or 0), int(elem),
@@ -600,10 +635,11 @@ def score_tokens_logprobs(logits, targets, n_top=0):
 
 
 def paged_prompt_logprobs(page_table, inp, wq, emb_table, segments, n_batch, n_sequence, elem, n_top=0, n_heads=1,
-                          n_kv_heads=None, window=None, sinks=None):
+                          n_kv_heads=None, window=None, sinks=None, softcap=None):
     """EXTENSION: prompt log-probabilities for the positions of the segments from the pages a prefill has written
     (mli_paged_prompt_logprobs): projection, causal scan, logits, scoring of inp[row, position + 1].  Returns (token_logprob
-    [n], top_ids [n, n_top], top_logprobs [n, n_top]) in list order."""
+    [n], top_ids [n, n_top], top_logprobs [n, n_top]) in list order.  softcap given: the scan with logit soft-capping
+    (mli_paged_prompt_logprobs_softcap)."""
     lib = load_library()
     D, V = wq.shape[0], emb_table.shape[0]
     n_top = int(n_top)
@@ -611,6 +647,13 @@ def paged_prompt_logprobs(page_table, inp, wq, emb_table, segments, n_batch, n_s
     token_logprob, top_ids, top_logprobs = _score_outputs(n, n_top, wq.device)
     need = int(lib.mli_prompt_logprobs_scratch_bytes(n, D, V))
     sc = torch.empty(max(need, 16), dtype=torch.uint8, device=wq.device)
+    if softcap is not None:
+        _check(lib.mli_paged_prompt_logprobs_softcap(
+            _p(page_table), _p(inp), _p(wq), _p(emb_table), *map(_p, arrays), _p(token_logprob),
+            _p(top_ids) if n_top > 0 else None, _p(top_logprobs) if n_top > 0 else None, len(segments), max_count, n,
+            int(n_batch), int(n_sequence), D, V, int(n_heads), int(n_kv_heads or n_heads), int(window or 0), int(sinks or 0),
+            float(softcap), int(elem), n_top, _p(sc), need, _stream()), "mli_paged_prompt_logprobs_softcap")
+        return token_logprob, top_ids, top_logprobs
     _check(lib.mli_paged_prompt_logprobs(_p(page_table), _p(inp), _p(wq), _p(emb_table), *map(_p, arrays), _p(token_logprob),
                                          _p(top_ids) if n_top > 0 else None, _p(top_logprobs) if n_top > 0 else None,
                                          len(segments), max_count, n, int(n_batch), int(n_sequence), D, V, int(n_heads),
