@@ -625,6 +625,9 @@ int mli_paged_decoder_sampled_logprobs(const float* batch_result, const float* e
  * mli_prompt_project_q -- q[i] = x(row, pos) . Wq for every position of the segments: x from segment 0 of the pages, gathered
  *   into `gathered` (n_q * emb_dim page elements, 16-byte aligned) and multiplied by one MFMA GEMM launch; fp32 x and Wq on
  *   fp32 pages, bf16 x and Wq with fp32 accumulation on bf16 pages, q fp32: the decode projection's weights and rounding.
+ *   The one exception to "never written": the product covers all n_q rows, so a q row that belongs to no position (a hole
+ *   between segments, a tail, a skipped segment) is written too -- with the product of whatever `gathered` held in that row --
+ *   and `gathered` itself is scratch.  The scan reads the q rows of its queries only.  At most 65535 segments.
  * mli_score_tokens_logprobs -- the figures of mli_sample_tokens_logprobs (raw distribution, finite candidates, the same
  *   summation order, n_top <= MLI_MAX_TOP_LOGPROBS alternatives ordered by (logit, index)) for the token targets[i] it is
  *   GIVEN.  A target outside [0, n_vocab) reports -inf for the token and the alternatives all the same.  Where the target is

@@ -25,6 +25,8 @@ static int prompt_scan_elem(const float* q, const void* const* page_table, const
     if (n_seg < 0 || window < 0 || n_sink < 0 || !prompt_scan_shape_ok(B, S, D, H, Hkv, elem)) return MLI_ERR_BAD_ARG;
     if (n_seg == 0) return 0;
     if (max_count < 1 || max_count > S || n_q < 1) return MLI_ERR_BAD_ARG;
+    const int epl = elem == MLI_ELEM_BF16 ? 8 : 4;
+    if (!prompt_scan_grid_ok(n_seg, max_count, prompt_scan_tq(epl, plan_ceil_div(D / epl, kPlanWave), H > 1))) return MLI_ERR_BAD_ARG;
     if (q == nullptr || page_table == nullptr || seg_row == nullptr || seg_first == nullptr || seg_count == nullptr ||
         seg_offset == nullptr || out == nullptr)
         return MLI_ERR_BAD_ARG;

@@ -44,7 +44,7 @@ int launch_prompt_softcap_scan(const float* q, const void* const* page_table, co
     const auto go = [&](auto NJ) {
         constexpr int TQ = prompt_scan_tq(E::EPL, NJ(), true);
         const int nb = ceil_div_i(max_count, TQ);
-        if ((long long)n_seg * nb > 0x7fffffffLL) return (int)MLI_ERR_BAD_ARG;
+        if (!prompt_scan_grid_ok(n_seg, max_count, TQ)) return (int)MLI_ERR_BAD_ARG;   // (the entry points refuse it first)
         count_launch(kLfScanPromptSoftcap);
         hipLaunchKernelGGL((prompt_softcap_scan_kernel<E, NJ(), TQ>), dim3((unsigned)(n_seg * nb)), dim3(kFuThreads), 0, st, q,
                            page_table, seg_row, seg_first, seg_count, seg_offset, out, nb, n_q, B, S, D, lg, H / Hkv, window,
@@ -65,7 +65,7 @@ int launch_prompt_scan(const float* q, const void* const* page_table, const int*
     const auto go = [&](auto NJ, auto HEADS) {
         constexpr int TQ = prompt_scan_tq(E::EPL, NJ(), HEADS());
         const int nb = ceil_div_i(max_count, TQ);
-        if ((long long)n_seg * nb > 0x7fffffffLL) return (int)MLI_ERR_BAD_ARG;
+        if (!prompt_scan_grid_ok(n_seg, max_count, TQ)) return (int)MLI_ERR_BAD_ARG;   // (the entry points refuse it first)
         count_launch(kLfScanPrompt);
         hipLaunchKernelGGL((prompt_scan_kernel<E, NJ(), TQ, HEADS()>), dim3((unsigned)(n_seg * nb)), dim3(kFuThreads), 0, st, q,
                            page_table, seg_row, seg_first, seg_count, seg_offset, out, nb, n_q, B, S, D, lg, H / Hkv, window,

@@ -228,8 +228,13 @@ int launch_prompt_scan_elem(const float*, const void* const*, const int*, const 
 int launch_prompt_softcap_scan_elem(const float*, const void* const*, const int*, const int*, const int*, const int*, float*, int,
                                     int, int, int, int, int, int, int, int, int, float, int, hipStream_t);   // attention_prompt.hip
 int launch_gemm_nt(const float*, const float*, float*, int, int, int, hipStream_t);
+int launch_score_tokens_skipping(const float*, const int*, float*, int*, float*, int, int, int, int, void*);   // decoder_sample.hip
 
-// the token that FOLLOWS every scored position: targets[offset + j] = inp[row, first + j + 1], -1 beyond the sequence
+// the token that FOLLOWS every scored position: targets[offset + j] = inp[row, first + j + 1], -1 beyond the sequence and for
+// a negative token id (scored as -inf either way).  Every target is kPromptNoRow before this kernel runs, so the rows of a
+// skipped segment keep that mark and the scoring leaves them alone: a dense row that belongs to no query is never written.
+constexpr int kPromptNoRowByte = 0x80;
+constexpr int kPromptNoRow = (int)0x80808080u;
 __global__ __launch_bounds__(256) void prompt_targets_kernel(const int* __restrict__ inp, const int* __restrict__ seg_row,
                                                              const int* __restrict__ seg_first, const int* __restrict__ seg_count,
                                                              const int* __restrict__ seg_offset, int* __restrict__ targets,
@@ -242,7 +247,8 @@ __global__ __launch_bounds__(256) void prompt_targets_kernel(const int* __restri
     const int b = seg_row[seg], first = seg_first[seg], off = seg_offset[seg];
     if (b < 0 || b >= B || first < 0 || (int64_t)first + cnt > S || off < 0 || (int64_t)off + cnt > n_q) return;
     const int s = first + j + 1;
-    targets[off + j] = s < S ? inp[(int64_t)b * S + s] : -1;
+    const int token = s < S ? inp[(int64_t)b * S + s] : -1;
+    targets[off + j] = token < 0 ? -1 : token;
 }
 
 // scratch of mli_paged_prompt_logprobs: gathered x | q | attention | logits | targets, each region 256-byte aligned
@@ -292,8 +298,14 @@ static int prompt_logprobs(const void* const* page_table, const int* inp, const 
         !mli::prompt_scan_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, elem))
         return MLI_ERR_BAD_ARG;
     if (n_seg == 0) return 0;
-    if (max_count < 1 || max_count > n_sequence || n_positions < 1 || inp == nullptr || wq == nullptr || emb_table == nullptr)
+    // the list's own limits, the projection's (a segment per y of the gather's grid) and the scan's grid among them: with the
+    // shapes, before any pointer is looked at and before the projection is launched
+    if (max_count < 1 || max_count > n_sequence || n_positions < 1 || n_seg > 65535) return MLI_ERR_BAD_ARG;
+    const int epl = elem == MLI_ELEM_BF16 ? 8 : 4;
+    if (!mli::prompt_scan_grid_ok(n_seg, max_count,
+                                  mli::prompt_scan_tq(epl, mli::plan_ceil_div(emb_dim / epl, mli::kPlanWave), n_heads > 1)))
         return MLI_ERR_BAD_ARG;
+    if (inp == nullptr || wq == nullptr || emb_table == nullptr) return MLI_ERR_BAD_ARG;
     const mli::PromptScratch p = mli::prompt_scratch(n_positions, emb_dim, n_vocab);
     if (scratch == nullptr || scratch_bytes < p.total) return MLI_ERR_WORKSPACE;
     hipStream_t st = mli::as_stream(stream);
@@ -316,11 +328,15 @@ static int prompt_logprobs(const void* const* page_table, const int* inp, const 
     if (rc) return rc;
     rc = mli::launch_gemm_nt(attn, emb_table, logits, n_positions, n_vocab, emb_dim, st);
     if (rc) return rc;
+    (void)hipMemsetAsync(targets, mli::kPromptNoRowByte, (size_t)n_positions * sizeof(int), st);
+    rc = mli::launch_status();   // (the status of the runtime's last call, as after a launch)
+    if (rc) return rc;
     hipLaunchKernelGGL(mli::prompt_targets_kernel, dim3(mli::ceil_div_i(n_seg * max_count, 256)), dim3(256), 0, st, inp, seg_row,
                        seg_first, seg_count, seg_offset, targets, n_seg, max_count, n_positions, n_batch, n_sequence);
     rc = mli::launch_status();
     if (rc) return rc;
-    return mli_score_tokens_logprobs(logits, targets, token_logprob, top_ids, top_logprobs, n_positions, n_vocab, n_top, stream);
+    return mli::launch_score_tokens_skipping(logits, targets, token_logprob, top_ids, top_logprobs, n_positions, n_vocab, n_top,
+                                                mli::kPromptNoRow, stream);
 }
 
 int mli_paged_prompt_logprobs(const void* const* page_table, const int* inp, const void* wq, const float* emb_table,

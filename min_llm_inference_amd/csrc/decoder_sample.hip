@@ -409,12 +409,14 @@ __global__ __launch_bounds__(kThreads) void decoder_sample_kernel(
 
 // The figures of mli_sample_tokens_logprobs for a token the caller GIVES (prompt log-probabilities): row_logprobs on the
 // row staged as sample_row stages it, so a target that is the token the head emits reports the same bits.  A target outside
-// [0, V) reports -inf for the token and the alternatives all the same.
+// [0, V) reports -inf for the token and the alternatives all the same.  skipping: a row whose target is no_row belongs to no
+// query (mli_paged_prompt_logprobs: a segment the device checks skipped); its logits were never written, and nothing of it is.
 __global__ __launch_bounds__(kThreads) void score_tokens_kernel(const float* __restrict__ logits, const int* __restrict__ targets,
-                                                                int V, const LogprobOut<true> out) {
+                                                                int V, const LogprobOut<true> out, int no_row, bool skipping) {
     extern __shared__ float stage[];
     __shared__ SampleShared sh;
     const int b = blockIdx.x;
+    if (skipping && targets[b] == no_row) return;   // workgroup-uniform
     const float* x = logits + (int64_t)b * V;
     if (V <= kStageMax) {
         for (int v = threadIdx.x; v < V; v += kThreads) stage[v] = x[v];
@@ -479,7 +481,7 @@ int mli_score_tokens_logprobs(const float* logits, const int* targets, float* to
     if (n == 0) return 0;
     if (logits == nullptr || targets == nullptr) return MLI_ERR_BAD_ARG;
     hipLaunchKernelGGL(mli::score_tokens_kernel, dim3(n), dim3(mli::kThreads), mli::stage_bytes(n_vocab), mli::as_stream(stream),
-                       logits, targets, n_vocab, mli::LogprobOut<true>{token_logprob, top_ids, top_logprobs, n_top});
+                       logits, targets, n_vocab, mli::LogprobOut<true>{token_logprob, top_ids, top_logprobs, n_top}, 0, false);
     return mli::launch_status();
 }
 
@@ -489,6 +491,18 @@ size_t mli_decoder_sampled_scratch_bytes(int n_batch, int n_vocab) {
 }
 
 }  // extern "C"
+
+namespace mli {
+// mli_score_tokens_logprobs for mli_paged_prompt_logprobs (compose.hip): rows whose target is no_row are left alone
+int launch_score_tokens_skipping(const float* logits, const int* targets, float* token_logprob, int* top_ids,
+                                float* top_logprobs, int n, int n_vocab, int n_top, int no_row, void* stream) {
+    if (!logprob_args_ok(token_logprob, top_ids, top_logprobs, n_top)) return MLI_ERR_BAD_ARG;
+    if (n <= 0 || n_vocab <= 0 || logits == nullptr || targets == nullptr) return MLI_ERR_BAD_ARG;
+    hipLaunchKernelGGL(score_tokens_kernel, dim3(n), dim3(kThreads), stage_bytes(n_vocab), as_stream(stream),
+                       logits, targets, n_vocab, LogprobOut<true>{token_logprob, top_ids, top_logprobs, n_top}, no_row, true);
+    return launch_status();
+}
+}  // namespace mli
 
 // layout: 0 = contiguous (inp_embedding), 1 = paged fp32, 2 = paged bf16, 3 = paged fp8
 template <bool LOGPROBS>

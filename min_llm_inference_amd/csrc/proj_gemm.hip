@@ -418,7 +418,9 @@ int launch_gemm_nt(const float* A, const float* Bt, float* C, int M, int N, int 
 // seg_offset + j for position seg_first + j of row seg_row.  A gather of the x rows (segment 0 of the pages, where the prefill
 // has just written them) into `gathered` ([n_q, D] page elements), then the plain product of this file's template over it: fp32 x
 // and Wq, or (BF16) bf16 x and Wq widened to fp32 while they are staged -- the exact k-ordered fp32 MFMA chain either way.
-// A position outside its row's pages or the q array gathers nothing; its q row is then whatever `gathered` held.
+// A position outside its row's pages or the q array gathers nothing; its q row is then whatever `gathered` held -- and so is
+// every q row that belongs to no position at all (a hole between segments, a tail, a skipped segment): the product covers all
+// n_q rows.  That is this entry point's contract (include/mli_kernels.h); the scan reads the q rows of its queries only.
 template <int EB>   // bytes per page element
 __global__ __launch_bounds__(256) void prompt_gather_x_kernel(const void* const* __restrict__ page_table,
                                                               const int* __restrict__ seg_row, const int* __restrict__ seg_first,

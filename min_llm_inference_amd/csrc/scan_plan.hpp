@@ -263,5 +263,11 @@ constexpr int prompt_scan_tq(int epl, int nj, bool heads) {
     if (heads) return (epl == 4 ? 8 : 4) / nj;   // fp32: 8 / 4 for rows of one / two lane loads; bf16: 4 / 2
     return epl == 8 && nj == 2 ? 4 : 8;
 }
+// The grid: n_seg * ceil(max_count / TQ) workgroups of 256 threads in x.  The HIP runtime launches fewer than 2^32 work items
+// per grid dimension (hip_runtime_api.h, hipModuleLaunchKernel: "gridDim.x * blockDim.x ... always less than 2^32"), that is
+// at most 2^24 - 1 workgroups; a larger call is refused with the other shapes, before any pointer is looked at.
+inline bool prompt_scan_grid_ok(int n_seg, int max_count, int tq) {
+    return (long long)n_seg * plan_ceil_div(max_count, tq) * (kPlanWaves * kPlanWave) < (1LL << 32);
+}
 
 }  // namespace mli

@@ -89,6 +89,14 @@ int main() {
                 const int tq = prompt_scan_tq(epl, nj, heads);
                 CHECK(tq == 2 || tq == 4 || tq == 8, "TQ %d for epl %d nj %d heads %d", tq, epl, nj, (int)heads);
             }
+    // the grid: fewer than 2^32 work items in x, that is at most 2^24 - 1 workgroups of 256 threads
+    for (int tq : {2, 4, 8}) {
+        const int nb = (4096 + tq - 1) / tq;
+        const int last = ((1 << 24) - 1) / nb;   // the most segments of max_count 4096
+        CHECK(prompt_scan_grid_ok(last, 4096, tq) && !prompt_scan_grid_ok(last + 1, 4096, tq), "grid at TQ %d: %d segments", tq, last);
+    }
+    CHECK(prompt_scan_grid_ok((1 << 24) - 1, 1, 8) && !prompt_scan_grid_ok(1 << 24, 1, 8), "grid with one block per segment");
+    CHECK(prompt_scan_grid_ok(0x7fffffff / 4096, 1, 8) && !prompt_scan_grid_ok(0x7fffffff, 4096, 2), "no overflow in the product");
     if (failures == 0) std::printf("prompt_plan_test: all checks passed\n");
     return failures == 0 ? 0 : 1;
 }

@@ -45,13 +45,13 @@ def _score_direction(qh):
 
 def apply_family_row(q, K, family):
     """accuracy_cases.apply_family on one row (or one head's columns of it), in place: q [d], K [L, d]."""
-    L = K.shape[0]
     if family == "flat":
         return
     if family == "peaked":
         q *= np.float32(12.0)
         return
     u = _score_direction(q)
+    L = K.shape[0]
     if family in ("offset+", "offset-"):
         K += np.float32(200.0 if family == "offset+" else -200.0) * u[None, :]
     elif family in ("late_peak", "early_peak"):
@@ -66,11 +66,14 @@ class SparseCase:
     layout rule; table [B, S / 16] of page numbers (-1: none).  families: {row: family or one family per head}; every other
     row is flat."""
 
-    def __init__(self, seed, lengths, S, D, families=None, H=1):
-        assert S % PAGE == 0 and D % H == 0
-        self.S, self.D, self.H = S, D, H
+    def __init__(self, seed, lengths, S, D, families=None, H=1, Hkv=None, full_rows=False):
+        """Hkv < H: grouped heads -- a row's families are one per K/V head, applied to K block j and the group's first query
+        head as gqa_model.apply_gqa_families does (the group's other heads are FACTORS[i] times the first where the family
+        modifies K).  full_rows: a row may hold n_sequence tokens (the prompt scan scores position n_sequence - 1)."""
+        assert S % PAGE == 0 and D % H == 0 and H % (Hkv or H) == 0
+        self.S, self.D, self.H, self.Hkv = S, D, H, Hkv or H
         self.lengths = np.asarray(lengths, np.int32).copy()
-        assert ((self.lengths >= 0) & (self.lengths < S)).all(), "rows keep one slot free, as the reference's do"
+        assert ((self.lengths >= 0) & (self.lengths < S + bool(full_rows))).all(), "rows keep one slot free, as the reference's do"
         L = self.lengths.astype(np.int64)
         self.B = B = len(L)
         rng = np.random.default_rng(seed)
@@ -81,13 +84,21 @@ class SparseCase:
         self.V = (rng.random((T, D), dtype=np.float32) * 2 - 1).astype(np.float32)
         self.families = {}
         hd = D // H
+        g = H // self.Hkv
         for b, fam in (families or {}).items():
-            fams = (fam,) * H if isinstance(fam, str) else tuple(fam)
-            assert len(fams) == H and L[b] > 0
-            self.families[int(b)] = fams
+            fams = (fam,) * self.Hkv if isinstance(fam, str) else tuple(fam)
+            assert len(fams) == self.Hkv and L[b] > 0
+            self.families[int(b)] = tuple(fams[h // g] for h in range(H))
             Kb = self.K[self.start[b]:self.start[b + 1]]
-            for h, f in enumerate(fams):
-                apply_family_row(self.q[b, h * hd:(h + 1) * hd], Kb[:, h * hd:(h + 1) * hd], f)
+            for j, f in enumerate(fams):
+                first = self.q[b, j * g * hd:(j * g + 1) * hd]
+                apply_family_row(first, Kb[:, j * hd:(j + 1) * hd], f)
+                for i in range(1, g):
+                    qh = self.q[b, (j * g + i) * hd:(j * g + i + 1) * hd]
+                    if f in ("flat", "peaked"):
+                        apply_family_row(qh, None, f)
+                    else:
+                        qh[:] = np.float32(1.0 + 0.125 * (i % 8)) * first
         # pages: the reference's allocation, from a shuffled pool
         self.row_pages = np.where(L > 0, -(-np.minimum(L + 1, S) // PAGE), 0)
         self.page_start = np.concatenate([[0], np.cumsum(self.row_pages)])
@@ -153,28 +164,74 @@ def attended(L, window=0, sinks=0):
     return s[(s >= lo) | (s < sinks)]
 
 
-def row_truth(oracle, q, K, V, H=1, Hkv=None, window=0, sinks=0):
+def _biased_head(qh, Kh, Vh, idx, L, slope, cap, dtype):
+    """(o [1, hd], o_scale) of one head over the attended slots with every operation in `dtype`, as alibi_model / softcap_model
+    state it: x = q . K / sqrt(hd); with a cap x = cap tanh(x / cap); with a slope x += slope (s - (L - 1)); softmax; p . V"""
+    qh, Kh, Vh = (np.asarray(a).astype(dtype) for a in (qh, Kh, Vh))
+    x = ((Kh @ qh).astype(dtype) / dtype(np.sqrt(len(qh)))).astype(dtype)
+    if cap is not None:
+        x = (dtype(cap) * np.tanh((x / dtype(cap)).astype(dtype)).astype(dtype)).astype(dtype)
+    if slope is not None:
+        x = (x + dtype(np.float32(slope)) * (idx - (L - 1)).astype(dtype)).astype(dtype)
+    e = np.exp(x - x.max())
+    p = (e / e.sum(dtype=dtype)).astype(dtype)
+    return (p @ Vh).astype(dtype)[None], float((p.astype(np.float64) @ np.abs(Vh.astype(np.float64))).max())
+
+
+def row_truth(oracle, q, K, V, H=1, Hkv=None, window=0, sinks=0, slopes=None, cap=None):
     """[(columns, f64_model.Model, (x, p, o) of the fp32 oracle)] per head for one row: q [D], K / V [L, D] as the pages hold
-    them.  Head h attends the slots attended(L, window, sinks) with K / V head h // (H // Hkv)."""
+    them.  Head h attends the slots attended(L, window, sinks) with K / V head h // (H // Hkv).
+    slopes [H] (ALiBi: slopes[h] * (s - (L - 1)) is added to the scaled score of slot s) or cap (soft-capping: the scaled score
+    x becomes cap * tanh(x / cap), before the mask): the model is then the float64 evaluation of that expression (o, o_scale
+    and lengths, what f64_model.attention_error reads) and the oracle's place is taken by the same expression in float32
+    numpy, as alibi_model / softcap_model take their tolerance: (None, None, o32)."""
     D = len(q)
     hd = D // H
     g = H // (Hkv or H)
-    idx = attended(K.shape[0], window, sinks)
+    L = K.shape[0]
+    idx = attended(L, window, sinks)
+    K, V = (K, V) if len(idx) == L else (K[idx], V[idx])
     out = []
     for h in range(H):
         cols = slice(h * hd, (h + 1) * hd)
         kv = slice((h // g) * hd, (h // g + 1) * hd)
+        if slopes is not None or cap is not None:
+            slope = None if slopes is None else np.asarray(slopes, np.float32)[h]
+            o64, scale = _biased_head(q[cols], K[:, kv], V[:, kv], idx, L, slope, cap, np.float64)
+            o32, _ = _biased_head(q[cols], K[:, kv], V[:, kv], idx, L, slope, cap, np.float32)
+            model = SimpleNamespace(o=o64, o_scale=np.asarray([scale]), lengths=np.asarray([len(idx)], np.int64))
+            out.append((cols, model, (None, None, o32)))
+            continue
         qh = np.ascontiguousarray(q[cols])[None]
-        kt = np.ascontiguousarray(K[idx][:, kv].T)[None]
-        v = np.ascontiguousarray(V[idx][:, kv])[None]
+        kt = np.ascontiguousarray(K[:, kv].T)[None]
+        v = np.ascontiguousarray(V[:, kv])[None]
         n = np.asarray([len(idx)], np.int32)
         out.append((cols, fm.Model(qh, kt, v, n), oracle_scan(oracle, qh, kt, v, n)))
     return out
 
 
-def judge_rows(oracle, case, values_of, got, rows, H=1, Hkv=None, window=0, sinks=0):
+def largest_score(case, H=1, Hkv=None):
+    """softcap_model.largest_score on sparse rows: the largest |q_h . K_{h // g}[s] / sqrt(hd)| over every token of every row"""
+    hd, g = case.D // H, H // (Hkv or H)
+    tok_row = np.repeat(np.arange(case.B), case.lengths.astype(np.int64))
+    top = 0.0
+    for h in range(H):
+        q = case.q[tok_row, h * hd:(h + 1) * hd].astype(np.float64)
+        k = case.K[:, (h // g) * hd:(h // g + 1) * hd].astype(np.float64)
+        top = max(top, float(np.abs((q * k).sum(axis=1)).max()) / np.sqrt(hd))
+    return top
+
+
+def scaled_q(case, target, H=1, Hkv=None):
+    """softcap_model.scale_q on sparse rows: case.q (float32) scaled so that largest_score is `target`"""
+    return (case.q * np.float32(target / largest_score(case, H, Hkv))).astype(np.float32)
+
+
+def judge_rows(oracle, case, values_of, got, rows, H=1, Hkv=None, window=0, sinks=0, slopes=None, cap=None, q=None):
     """{family: (kernel errors, oracle errors)} of attention_result `got` [B, D] over the (row, head) pairs of `rows`;
-    values_of(b) = (K, V) as the pages hold them.  Rows of length 0: inf unless exactly 0."""
+    values_of(b) = (K, V) as the pages hold them.  Rows of length 0: inf unless exactly 0.  slopes / cap: row_truth's; q: the
+    queries the launch was given where they are not case.q (scaled_q)."""
+    q = case.q if q is None else q
     out = {}
     for b in rows:
         if case.lengths[b] == 0:
@@ -184,7 +241,7 @@ def judge_rows(oracle, case, values_of, got, rows, H=1, Hkv=None, window=0, sink
             rec[1].append(0.0)
             continue
         K, V = values_of(b)
-        for h, (cols, model, (_, _, o)) in enumerate(row_truth(oracle, case.q[b], K, V, H, Hkv, window, sinks)):
+        for h, (cols, model, (_, _, o)) in enumerate(row_truth(oracle, q[b], K, V, H, Hkv, window, sinks, slopes, cap)):
             rec = out.setdefault(case.family(b, h if case.H == H else 0), ([], []))
             rec[0].append(float(fm.attention_error(np.asarray(got[b][cols])[None], model)[0]))
             rec[1].append(float(fm.attention_error(o, model)[0]))
@@ -426,6 +483,51 @@ LIMITS = [
            (CSRC + "scan_item_body.hpp", "float* o = direct ? out + (int64_t)b * D : partial + ((int64_t)b * nchunk_max + c) * D;"),
            "f32 (16384, 4096, 2048) chunk_tokens 64: partial rows of 8 GiB, rows 16380 .. 16383 live", "-",
            "scan_chunked; the last rows right", NO_RULE, [on("test_offsets_beyond_2_31_paged")], []),
+    _limit("offsets beyond 2^31, prompt logits", "mli_paged_prompt_logprobs",
+           (CSRC + "compose.hip", "p.targets = p.logits + up((size_t)n * V * sizeof(float));"),
+           "n_positions 16384, n_vocab 131072, emb_dim 64: logits of 8 GiB inside the scratch, the last eight positions judged", "-",
+           "scan_prompt; the figures right", NO_RULE, [on("test_offsets_beyond_2_31_prompt_logits")], []),
+    # ---- the prompt scan, ALiBi, rotary embeddings and soft-capping ----
+    _limit("prompt scan, one head, row width", "mli_prompt_scan_paged, mli_paged_prompt_logprobs",
+           (CSRC + "scan_plan.hpp", "return plan_ceil_div(D / epl, kPlanWave) <= 2;"),
+           "f32 (4, 128, 512), bf16 (4, 128, 1024)", "f32 D 516, bf16 D 1032", "scan_prompt, two lane loads", REFUSED,
+           [on("test_prompt_scan_widest_rows", "PROMPT_WIDE", ("f32", 512)), on("test_prompt_scan_widest_rows", "PROMPT_WIDE", ("bf16", 1024))], []),
+    _limit("prompt scan, rows", "mli_prompt_scan_paged / _softcap",
+           (CSRC + "scan_plan.hpp", "if (!window_plain_shape_ok(B, S, D, elem)) return false;"),
+           "(16384, 64, 64) H 1 and (16384, 64, 128) H 2, segments on rows 0, 8191 and 16383", "(16385, 64, .)",
+           "scan_prompt / scan_prompt_softcap", REFUSED,
+           [on("test_prompt_scan_on_the_last_row", "PROMPT_ROWS", (1, None)), on("test_prompt_scan_on_the_last_row", "PROMPT_ROWS", (2, None)),
+            on("test_prompt_scan_on_the_last_row", "PROMPT_ROWS", (2, 5.0))], []),
+    _limit("prompt scan, page types", "mli_prompt_scan_paged / _softcap, mli_paged_prompt_logprobs",
+           (CSRC + "scan_plan.hpp", "if (elem != MLI_ELEM_F32 && elem != MLI_ELEM_BF16) return false;"),
+           "fp32 and bf16 pages", "fp8 pages", "scan_prompt", REFUSED,
+           [on("test_prompt_scan_widest_rows", "PROMPT_WIDE", ("f32", 512)), on("test_prompt_scan_widest_rows", "PROMPT_WIDE", ("bf16", 1024))], []),
+    _limit("prompt scan, window hand-off", "mli_prompt_scan_paged",
+           (CSRC + "attention_prompt.hip", "const ScanKind kind = lean_scan_kind(S, window, n_sink);"),
+           "(4, 64, 64) W 63; W 4095 at n_sequence 4096 in tests/test_prompt_long_gpu.py", "W 64 (there: W 4096)",
+           "scan_prompt; the query at 63 drops slot 0", "scan_prompt with the plain mask: the bits of W 0",
+           [on("test_prompt_window_hand_off", "PROMPT_WINDOWS", (63, True))], [on("test_prompt_window_hand_off", "PROMPT_WINDOWS", (64, False))]),
+    _limit("prompt scan, grid", "mli_prompt_scan_paged / _softcap, mli_paged_prompt_logprobs",
+           (CSRC + "scan_plan.hpp", "return (long long)n_seg * plan_ceil_div(max_count, tq) * (kPlanWaves * kPlanWave) < (1LL << 32);"),
+           "2^24 - 1 workgroups (the runtime launches fewer than 2^32 work items per grid dimension); not run at the limit: every prompt case lies inside it",
+           "n_seg 32768, max_count 4096 at 8 queries per workgroup: 2^24 workgroups", "scan_prompt", REFUSED,
+           [on("test_prompt_scan_on_the_last_row", "PROMPT_ROWS", (1, None))], []),
+    _limit("prompt q projection, segments", "mli_prompt_project_q, mli_paged_prompt_logprobs",
+           (CSRC + "proj_gemm.hip", "if (max_count < 1 || max_count > S || n_q < 1 || n_seg > 65535) return MLI_ERR_BAD_ARG;"),
+           "65535 segments of one position over (16, 4096, 64)", "65536 segments", "gemm_f32_rows64 / gemm_bf16_widened; q right", REFUSED,
+           [on("test_prompt_project_q_at_the_last_segment", "PROJECT_ELEMS", "f32"), on("test_prompt_project_q_at_the_last_segment", "PROJECT_ELEMS", "bf16")], []),
+    _limit("ALiBi, heads and slopes", "mli_decode_scan_paged_alibi, mli_paged_attention_lean_alibi",
+           (CSRC + "compose.hip", "if (n_heads < 2 || slopes == nullptr) return MLI_ERR_BAD_ARG;"),
+           "(16384, 64, 128) H 2, H 2 on 1", "H 1; a null slopes pointer", "scan_heads_alibi", REFUSED,
+           [on("test_heads_family_on_the_last_row", "HEAD_FORMS", "alibi"), on("test_heads_family_on_the_last_row", "HEAD_FORMS", "alibi_gqa")], []),
+    _limit("soft-cap, heads and cap", "mli_decode_scan_paged_softcap, mli_prompt_scan_paged_softcap",
+           (CSRC + "compose.hip", "if (n_heads < 2 || !(cap > 0.f) || !std::isfinite(cap)) return MLI_ERR_BAD_ARG;"),
+           "(16384, 64, 128) H 2, H 2 on 1, cap 5", "H 1; cap 0, -1, inf, NaN", "scan_heads_softcap", REFUSED,
+           [on("test_heads_family_on_the_last_row", "HEAD_FORMS", "softcap"), on("test_heads_family_on_the_last_row", "HEAD_FORMS", "softcap_gqa")], []),
+    _limit("rotary head size", "every *_rope entry point",
+           (CSRC + "proj_gemm.hip", "if (table == nullptr || n_heads < 1 || D < 1 || D % n_heads != 0 || (D / n_heads) % 2 != 0) return -1;"),
+           "head size 2: (70, 64, 64) H 32", "head size 17 (D 68, H 4) and 33 (D 132, H 4)",
+           "gemm_f32_rope / gemm_bf16_rope", REFUSED, [on("test_rope_at_the_smallest_head_size")], []),
 ]
 
 # Every call the launchers must refuse before anything is launched: (entry point, arguments after the pointers, limit,
@@ -434,6 +536,8 @@ LIMITS = [
 # | sinks(B, S, D, H, W, K, elem) | gqa(B, S, D, H, Hkv, W, K, elem) | contiguous(B, S, D), contiguous_kt4: the same with
 # kt_cache 4 bytes off | qkt_paged / qkt_paged_bf16 / qkt (B, S, D)
 _W, _H, _P = "row width, fp32 / bf16", "several heads, kPlanMaxRows", "merge statistics in the launch's LDS, plain scan"
+_PW, _PR, _PT, _PG = "prompt scan, one head, row width", "prompt scan, rows", "prompt scan, page types", "prompt scan, grid"
+_AH, _SH, _RH = "ALiBi, heads and slopes", "soft-cap, heads and cap", "rotary head size"
 REFUSALS = [
     ("scan", (8, 128, 2052, 0, 3), _W, 0), ("scan", (8, 128, 2052, 0, 5), _W, 0), ("scan", (8, 128, 2052, 0, 7), _W, 0),
     ("scan", (8, 128, 4104, 1, 3), _W, 0), ("scan", (8, 128, 4104, 1, 5), _W, 0), ("scan", (8, 128, 4104, 1, 7), _W, 0),
@@ -458,13 +562,51 @@ REFUSALS = [
     ("qkt_paged", (2, 64, 16364), "standalone qkt_paged, q in LDS", 0),
     ("qkt_paged_bf16", (2, 64, 16368), "standalone qkt_paged_bf16, q in LDS", 0),
     ("qkt", (2, 64, 15345), "standalone qkt, q in LDS", 0),
+    # the prompt scan: prompt / prompt_softcap (n_seg, max_count, n_q, B, S, D, H, Hkv, W, K[, cap], elem) |
+    # prompt_logprobs (n_seg, max_count, n_positions, B, S, D, V, H, Hkv, W, K, elem) | prompt_project_q (n_seg, max_count, n_q, B, S, D, elem)
+    ("prompt", (1, 1, 1, 4, 128, 516, 1, 1, 0, 0, 0), _PW, 0), ("prompt", (1, 1, 1, 4, 128, 1032, 1, 1, 0, 0, 1), _PW, 0),
+    ("prompt_logprobs", (1, 1, 1, 4, 128, 516, 1030, 1, 1, 0, 0, 0), _PW, 0), ("prompt_logprobs", (1, 1, 1, 4, 128, 1032, 1030, 1, 1, 40, 4, 1), _PW, 0),
+    ("prompt", (1, 1, 1, 16385, 64, 64, 1, 1, 0, 0, 0), _PR, 0), ("prompt", (1, 1, 1, 16385, 64, 64, 1, 1, 17, 0, 1), _PR, 0),
+    ("prompt", (1, 1, 1, 16385, 64, 128, 2, 2, 0, 0, 0), _PR, 0), ("prompt", (1, 1, 1, 16385, 64, 128, 2, 1, 0, 0, 1), _PR, 0),
+    ("prompt_softcap", (1, 1, 1, 16385, 64, 128, 2, 2, 0, 0, 5.0, 0), _PR, 0),
+    ("prompt_logprobs", (1, 1, 1, 16385, 64, 64, 512, 1, 1, 0, 0, 0), _PR, 0),
+    ("prompt", (1, 1, 1, 4, 128, 64, 1, 1, 0, 0, 2), _PT, 0), ("prompt", (1, 1, 1, 4, 128, 128, 2, 2, 0, 0, 2), _PT, 0),
+    ("prompt_softcap", (1, 1, 1, 4, 128, 128, 2, 2, 0, 0, 5.0, 2), _PT, 0), ("prompt_logprobs", (1, 1, 1, 4, 128, 64, 512, 1, 1, 0, 0, 2), _PT, 0),
+    ("prompt", (32768, 4096, 1, 8, 4096, 64, 1, 1, 0, 0, 0), _PG, 0), ("prompt", (32768, 4096, 1, 8, 4096, 128, 4, 4, 1000, 20, 0), _PG, 0),
+    ("prompt", (16384, 4096, 1, 8, 4096, 1024, 1, 1, 0, 0, 1), _PG, 0), ("prompt_softcap", (8192, 4096, 1, 8, 4096, 1024, 16, 2, 0, 0, 5.0, 1), _PG, 0),
+    ("prompt_logprobs", (32768, 4096, 1, 8, 4096, 64, 512, 1, 1, 0, 0, 0), _PG, 0),
+    ("prompt_logprobs", (16384, 4096, 1, 8, 4096, 1024, 512, 1, 1, 0, 0, 1), _PG, 0),
+    ("prompt_logprobs", (65536, 1, 65536, 16, 4096, 64, 512, 1, 1, 0, 0, 0), "prompt q projection, segments", 0),
+    ("prompt_project_q", (65536, 1, 65536, 16, 4096, 64, 0), "prompt q projection, segments", 0),
+    ("prompt_project_q", (65536, 1, 65536, 16, 4096, 64, 1), "prompt q projection, segments", 0),
+    # alibi (B, S, D, H, Hkv, W, K, slopes given?, elem) | softcap (B, S, D, H, Hkv, W, K, cap, elem)
+    ("alibi", (8, 64, 128, 1, 1, 0, 0, True, 0), _AH, 0), ("alibi", (8, 64, 64, 1, 1, 17, 0, True, 1), _AH, 0),
+    ("alibi", (8, 64, 128, 2, 2, 0, 0, False, 0), _AH, 0), ("alibi", (8, 64, 128, 2, 1, 16, 4, False, 1), _AH, 0),
+    ("softcap", (8, 64, 128, 1, 1, 0, 0, 5.0, 0), _SH, 0), ("softcap", (8, 64, 128, 2, 2, 0, 0, 0.0, 0), _SH, 0),
+    ("softcap", (8, 64, 128, 2, 2, 0, 0, -1.0, 1), _SH, 0), ("softcap", (8, 64, 128, 2, 1, 17, 0, float("inf"), 0), _SH, 0),
+    ("softcap", (8, 64, 128, 2, 2, 16, 4, float("nan"), 0), _SH, 0),
+    ("prompt_softcap", (1, 1, 1, 4, 128, 128, 1, 1, 0, 0, 5.0, 0), _SH, 0), ("prompt_softcap", (1, 1, 1, 4, 128, 128, 2, 2, 0, 0, 0.0, 0), _SH, 0),
+    ("prompt_softcap", (1, 1, 1, 4, 128, 128, 2, 2, 0, 0, float("nan"), 1), _SH, 0),
+    # latest_rope (B, S, D, H, elem) | fill_rope (B, S, D, n_new, H, elem) | prefill_rope (B, S, D, n_new, W, K, H, elem) |
+    # lean_rope (B, S, D, n_new, H, Hkv, W, K, elem): a table pointer that is not null, head sizes 17 and 33
+    ("latest_rope", (8, 64, 68, 4, 0), _RH, 0), ("latest_rope", (8, 64, 132, 4, 0), _RH, 0), ("latest_rope", (8, 64, 136, 8, 1), _RH, 0),
+    ("latest_rope", (8, 64, 272, 16, 2), _RH, 0),
+    ("fill_rope", (8, 64, 68, 2, 4, 0), _RH, 0), ("fill_rope", (8, 64, 136, 2, 8, 1), _RH, 0), ("fill_rope", (8, 64, 132, 2, 4, 0), _RH, 0),
+    ("prefill_rope", (8, 64, 68, 2, 0, 0, 4, 0), _RH, 0), ("prefill_rope", (8, 64, 136, 2, 32, 4, 8, 1), _RH, 0),
+    ("prefill_rope", (8, 64, 272, 2, 0, 0, 16, 2), _RH, 0),
+    ("lean_rope", (8, 64, 68, 2, 4, 4, 0, 0, 0), _RH, 0), ("lean_rope", (8, 64, 132, 2, 4, 2, 17, 0, 0), _RH, 0),
 ]
 
 
-def call_refusal(lib, entry, args, workspace=None, workspace_bytes=1 << 40, stream=None):
+def call_refusal(lib, entry, args, workspace=None, workspace_bytes=1 << 40, stream=None, data=None):
     """One REFUSALS call with null data pointers.  `workspace`: an address that is not null, with a size claimed beyond any
     need, so that no refusal is the workspace's; it also stands in where a null pointer would be refused before the shape is
-    looked at (qkt_output of the materialising form)."""
+    looked at (qkt_output of the materialising form).
+    data: the address given for EVERY data pointer of the newer entry points (prompt, ALiBi, soft-cap, rotary) instead of null.
+    Those launchers answer MLI_ERR_BAD_ARG for a null pointer too, so with null pointers a refusal says nothing of where the
+    shape rule stands; with `data` set the pointer checks pass and only the shape rule can refuse.  Used WITHOUT a GPU only
+    (tests/test_shape_limits_cpu.py): had the rule let the shape through, the launch fails there with a HIP error, which is
+    not MLI_ERR_BAD_ARG.  On the device the pointers stay null, so that nothing can ever follow them."""
     tail = (workspace, workspace_bytes, stream)
     if entry == "scan":
         B, S, D, elem, phases = args
@@ -475,6 +617,34 @@ def call_refusal(lib, entry, args, workspace=None, workspace_bytes=1 << 40, stre
         return lib.mli_decode_scan_contiguous(None, (workspace or 4096) + 4, None, None, None, *args, *tail)
     if entry in ("qkt_paged", "qkt_paged_bf16", "qkt"):
         return getattr(lib, "mli_" + entry)(None, None, None, None, *args, stream)
+    # the newer entry points: `workspace` also stands in for the slopes, the rotary table and token_logprob, which are
+    # refused when null before the shape is looked at and are never followed by a launcher
+    d = data
+    if entry == "prompt":
+        return lib.mli_prompt_scan_paged(*(d,) * 7, *args, stream)
+    if entry == "prompt_softcap":
+        return lib.mli_prompt_scan_paged_softcap(*(d,) * 7, *args, stream)
+    if entry == "prompt_project_q":
+        return lib.mli_prompt_project_q(*(d,) * 8, *args, stream)
+    if entry == "prompt_logprobs":
+        return lib.mli_paged_prompt_logprobs(*(d,) * 8, workspace, None, None, *args, 0, workspace, workspace_bytes, stream)
+    if entry == "alibi":
+        *shape, slopes, elem = args
+        return lib.mli_decode_scan_paged_alibi(d, d, d, d, *shape, workspace if slopes else None, elem, *tail)
+    if entry == "softcap":
+        return lib.mli_decode_scan_paged_softcap(d, d, d, d, *args, *tail)
+    if entry == "latest_rope":
+        B, S, D, H, elem = args
+        return lib.mli_get_latest_k_q_v_paged_rope(*(d,) * 6, B, S, D, H, workspace, elem, stream)
+    if entry == "fill_rope":
+        B, S, D, n_new, H, elem = args
+        return lib.mli_fill_new_k_v_cache_paged_rope(*(d,) * 5, B, S, D, n_new, H, workspace, elem, stream)
+    if entry == "prefill_rope":
+        B, S, D, n_new, W, K, H, elem = args
+        return lib.mli_paged_prefill_rope(*(d,) * 8, B, S, D, n_new, W, K, H, workspace, elem, stream)
+    if entry == "lean_rope":
+        B, S, D, n_new, H, Hkv, W, K, elem = args
+        return lib.mli_paged_attention_lean_rope(*(d,) * 8, B, S, D, n_new, H, Hkv, W, K, None, workspace, elem, *tail)
     name = {"heads": "mli_decode_scan_paged_heads", "window": "mli_decode_scan_paged_window",
             "sinks": "mli_decode_scan_paged_sinks", "gqa": "mli_decode_scan_paged_gqa"}[entry]
     return getattr(lib, name)(None, None, None, None, *args, *tail)

@@ -14,6 +14,8 @@ tokens[i + 1].
 MUTANTS are the faults such a kernel and its host actually have, each as a wrong model the comparison must reject.
 
 TEST INFRASTRUCTURE, like heads_model.py: never used by the product."""
+from types import SimpleNamespace
+
 import numpy as np
 
 import gqa_model as gm
@@ -210,6 +212,167 @@ def prompt_bound(rep):
     tol_logit = rm._scaled_tolerance(e32, float(np.abs(lg).max()))
     e_flip = rep.flip_envelope(rm.FLIP_ROUNDS, seed=len(rep.x) * 1000003 + len(rep.rows))[1] if rep.spec.flips else 0.0
     return 2.0 * (tol_logit + e_flip) + lm.tolerance(lg.astype(np.float32)), e32
+
+
+# ---- long prompts: n_sequence 4096 (tests/test_prompt_long_gpu.py, tests/test_prompt_long_cpu.py) -------------------------------
+# Dense virtual rows [n_q, D, S] do not fit at S 4096 and D 1024: the rows are a limit_cases.SparseCase and every query is judged
+# on its own with limit_cases.row_truth on K[:t + 1], V[:t + 1].
+LONG_S = 4096
+# (window, n_sink): plain | a dropped run of about 190 pages for the late queries | two sink pages, the second partly live | the
+# sink run ends on a page edge | a single-page window | lo <= n_sink for every early query | the hand-off's near side (only the
+# query at 4095 drops slot 0) | its far side (the plain mask)
+LONG_FORMS = ((0, 0), (1000, 0), (1000, 20), (1000, 16), (16, 0), (24, 40), (4095, 0), (4096, 0))
+LONG_MAX_COUNT = 4 * 16 + 3
+LONG_K = 150                       # the block at 16 k - 1: its later queries alone see page k
+_EDGE_ROWS = (4, 7)
+
+
+def _edge_window(W):
+    """the window whose start the two edge segments are placed by (a window beyond them starts at slot 0 for every query)"""
+    return W if 0 < W <= 1000 else 0
+
+
+def long_segments(tq, W, S=LONG_S):
+    """[(row, first, count)] at n_sequence 4096 for a variant of tq queries per workgroup under window W, rows in permuted order:
+    the max_count of the call (4 * 16 + 3 queries from position 1000) beside a segment of one query; the last query at
+    n_sequence - 1; a continuation starting at 3000; a block on each side of 2047 / 2048; a block at 16 k - 1; a segment whose
+    first query's window starts on a page edge (t0 + 1 - W a multiple of 16) and one where it starts at slot 15."""
+    e = 1024 + _edge_window(W)
+    return [(5, 1000, LONG_MAX_COUNT), (2, 0, 1), (0, S - (3 * tq + 1), 3 * tq + 1), (6, 3000 - (tq + 3), tq + 3),
+            (3, 2047 - tq, 2 * tq + 1), (1, 16 * LONG_K - 1, tq + 1), (6, 3000, 2 * tq), (_EDGE_ROWS[0], e - 1, tq + 1),
+            (_EDGE_ROWS[1], e + 14, tq + 1)]
+
+
+def long_lengths(tq, S=LONG_S):
+    """tokens per row: the last scored position + 1 over the segment lists of every form (the edge rows' segments move with W)"""
+    lengths = np.zeros(8, np.int32)
+    for W, _ in LONG_FORMS:
+        for r, f, n in long_segments(tq, W, S):
+            lengths[r] = max(lengths[r], f + n)
+    assert lengths.max() == S and (lengths > 0).all()
+    return lengths
+
+
+def long_families(H, Hkv):
+    """{row: families}: one head -- late_peak and early_peak by row (they force the most rescaling: a late peak rescales every
+    accumulator at the end of the walk, an early peak is what sinks keep and a window drops); several heads -- the mixed
+    assignment of heads_model.ASSIGNMENTS on the K/V heads."""
+    if H == 1:
+        # row 0 holds the query at n_sequence - 1: with the peak on slots 0 .. 15 the one slot W 4095 drops for it carries weight
+        return {0: "early_peak", 1: "late_peak", 3: "late_peak", 4: "early_peak", 5: "late_peak", 6: "early_peak", 7: "late_peak"}
+    return {r: hm.families_of("mixed", Hkv) for r in range(8)}
+
+
+def long_case(seed, D, H, Hkv, tq):
+    import limit_cases as lc
+    return lc.SparseCase(seed, long_lengths(tq), LONG_S, D, families=long_families(H, Hkv), H=H, Hkv=Hkv, full_rows=True)
+
+
+def _signature(t, W, K):
+    """what the attended set of query t depends on"""
+    lo = max(0, t + 1 - W) if W > 0 else 0
+    return (t, lo, min(K, lo) if lo > 0 else 0)
+
+
+def long_truth(oracle, case, values_of, qv, rows, pos, H, Hkv, W, K, cap=None, cache=None):
+    """[per query: [(columns, model, oracle attention, family) per head]] by limit_cases.row_truth on the row's first t + 1
+    tokens.  cache: a dict shared between the forms of one case and one q -- two forms under which a query attends the same
+    slots (W 0 and W 4096; W 4095 for every query but the one at 4095) share its truth."""
+    import limit_cases as lc
+    cache = {} if cache is None else cache
+    held = {}
+    out = []
+    for i in range(len(rows)):
+        b, t = int(rows[i]), int(pos[i])
+        key = (i, cap) + _signature(t, W, K)
+        if key not in cache:
+            if b not in held:
+                held[b] = values_of(b)
+            Kb, Vb = held[b]
+            assert len(Kb) > t, "the row holds the query's position"
+            truth = lc.row_truth(oracle, qv[i], Kb[:t + 1], Vb[:t + 1], H, Hkv, W, K, cap=cap)
+            cache[key] = [(cols, SimpleNamespace(o=m.o, o_scale=m.o_scale, lengths=m.lengths), o, case.family(b, h if case.H == H else 0))
+                          for h, (cols, m, (_, _, o)) in enumerate(truth)]
+        out.append(cache[key])
+    return out
+
+
+def long_compare(got, truth, what="", report=print):
+    """[(family, worst, tolerance)] of `got` [n_q, D]: per score family the worst condition-scaled error over (query, head)
+    against f64_model.tolerance of the oracle's error on the same tokens.  A query without a truth would be skipped: there is
+    none (every query attends at least itself), and that is asserted."""
+    import f64_model as fm
+    err, e_or = {}, {}
+    assert len(truth) == len(got) and all(len(heads) > 0 for heads in truth), "no query is skipped"
+    for i, heads in enumerate(truth):
+        for cols, model, o, family in heads:
+            err.setdefault(family, []).append(float(fm.attention_error(np.asarray(got[i][cols])[None], model)[0]))
+            e_or.setdefault(family, []).append(float(fm.attention_error(o, model)[0]))
+    out = []
+    for family in sorted(err):
+        tol = fm.tolerance(np.asarray(e_or[family]))
+        worst = float(np.max(err[family]))
+        report(f"PROMPT LONG {what} | {family}: got {worst:.3e}  oracle {float(np.max(e_or[family])):.3e}  tol {tol:.3e}")
+        out.append((family, worst, tol))
+    return out
+
+
+def long_distance(a, b, truth):
+    """{family: worst max_d |a - b| over a head's columns in units of the model's condition scale}"""
+    out = {}
+    for i, heads in enumerate(truth):
+        for cols, model, _, family in heads:
+            d = float(np.abs(a[i][cols].astype(np.float64) - b[i][cols]).max() / model.o_scale[0])
+            out[family] = max(out.get(family, 0.0), d)
+    return out
+
+
+# wrong models that only long rows can show, beside SCAN_MUTANTS
+LONG_MUTANTS = {
+    "every fourth page from the fifth on is skipped": "stride",       # a wave that loses its stride
+    "the sink run is one page short": "sink_page",                    # slots [16 (ps - 1), n_sink) dropped
+    "the dropped run is one page too long": "window_page",            # the first window page lost
+}
+
+
+def long_mutant(name, segments, lengths, qv_i, Kb, Vb, i, pos, H, Hkv, W, K):
+    """(float64 attention [D] of query i under the wrong scan, whether the fault changes the slots query i attends)"""
+    D = len(qv_i)
+    hd, g = D // H, H // Hkv
+    t = int(pos[i])
+    kw = dict(SCAN_MUTANTS.get(name, {}))
+    t_as = int(restarted_positions(segments)[i]) if kw.get("positions") == "restarted" else t
+    top = min(t_as + kw.get("hi_shift", 0), len(Kb) - 1)
+    s = np.arange(top + 1)
+    right = np.arange(t + 1)
+    if W > 0:
+        lo = max(0, t_as + 1 - W)
+        right = right[(right >= max(0, t + 1 - W)) | (right < K)]
+        live = (s >= lo + kw.get("lo_shift", 0)) | (s < kw.get("n_sink", K))
+        kind = LONG_MUTANTS.get(name)
+        ps = -(-K // 16)
+        if kind == "sink_page" and K > 0:
+            live &= ~((s >= 16 * (ps - 1)) & (s < K) & (s < lo))
+        if kind == "window_page" and lo // 16 > min(ps, lo // 16):
+            live &= ~((s // 16 == lo // 16) & (s >= K))
+        s = s[live]
+    if LONG_MUTANTS.get(name) == "stride":
+        pages = np.unique(s // 16)
+        lost = pages[4::4]
+        s = s[~np.isin(s // 16, lost)]
+    group = kw.get("group", True)
+    applies = not np.array_equal(s, right) or (not group and Hkv < H)
+    out = np.zeros(D, np.float64)
+    if len(s) == 0:
+        return out, True
+    whole = len(s) == s[-1] + 1
+    Ks, Vs = (Kb[:len(s)], Vb[:len(s)]) if whole else (Kb[s], Vb[s])
+    for h in range(H):
+        qs, ks = hm.head_slice(h, H, D), hm.head_slice(h // g if group else h, H, D)
+        x = (Ks[:, ks].astype(np.float64) @ qv_i[qs].astype(np.float64)) / np.sqrt(hd)
+        p = np.exp(x - x.max())
+        out[qs] = (p / p.sum()) @ Vs[:, ks].astype(np.float64)
+    return out, applies
 
 
 __all__ = ["S", "SHAPES", "FORMS", "FAMILIES", "segments_for", "queries", "query_vectors", "model_prompt", "oracle_prompt",

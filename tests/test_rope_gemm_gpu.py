@@ -94,11 +94,18 @@ def _call(mli, dev, c, mode, H, knobs, table, W=0, K=0, shift=False):
     return (p.view(gm.BITS[fmt]) if fmt == "bf16" else p), host(q).copy()
 
 
-def _check(oracle, mli, dev, label, c, mode, H, knobs, families, W=0, K=0, shift=False):
+def _check(oracle, mli, dev, label, c, mode, H, knobs, families, W=0, K=0, shift=False, library_table=False):
+    """library_table: rotate by the table mli_rope_table writes (held to rope_model's restatement within an ulp of 1 here,
+    bit for bit in tests/test_rope_abi.py where the two libms agree) instead of the restatement"""
     fmt = c.fmt
     composition = mode == "fill" and fmt == "fp8"
     Hc = 1 if composition else H
     std, ident = rp.standard_table(c.S, c.Din // Hc), rp.identity_table(c.S, c.Din // Hc)
+    if library_table:
+        from min_llm_inference_amd import ops
+        lib_table = ops.rope_table(c.S, c.Din // Hc, 10000.0)
+        assert lib_table.shape == std.shape and np.abs(lib_table.astype(np.float64) - std).max() <= 2.0 ** -23
+        std = lib_table
     assert mli.mli_launch_counts_reset() == 0
     pool, q = _call(mli, dev, c, mode, Hc, knobs, std, W, K, shift)
     rope_family = "gemm_f32_rope" if fmt == "f32" or knobs.get("native") == 0 else "gemm_bf16_rope"
@@ -231,3 +238,29 @@ def test_live_fill_under_a_window(oracle, mli, dev, fmt, fc, pf):
     fused = "prefill_fused" if pf == 2 or fmt == "fp8" else "prefill_two_launch"
     _check(oracle, mli, dev, f"{fmt}-live-fill-fc{fc}-pf{pf}", c, "prefill", 4, {"fc": fc, "pf": pf, "split": 0},
            (gemm, "fill_flat" if fc else "fill_per_row", fused), W=W, K=K)
+
+
+# ---- positions past slot 127 and the smallest head sizes ----------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", ["f32", "bf16", "fp8"])
+def test_long_prefill_then_latest(oracle, mli, dev, fmt):
+    """n_sequence 4096, emb_dim 128, 4 heads, the table of mli_rope_table(4096, 32, 10000): new rows of 4095, 2049 and 17 tokens
+    through mli_fill_new_k_v_cache_paged_rope (fp8 pages: the lean composition, one head of 128), then
+    mli_get_latest_k_q_v_paged_rope at those lengths -- slots 4094, 2048 and 16.  Every K row the fill writes (slots 0, 127, 128,
+    2048 and 4094 among them, not a sample) and q are judged; V, x and slot 0 keep the bytes of the un-rotated call.
+    "gemm_f32_rope" / "gemm_bf16_rope" counts the launch."""
+    c, mode = gm.fill_case(4000, fmt, "signed", 3, 4096, 128, mode="fill", lengths=[4095, 2049, 17])
+    _check(oracle, mli, dev, f"{fmt}-fill-S4096-H4", c, mode, 4, {}, (), library_table=True)
+    _check(oracle, mli, dev, f"{fmt}-latest-S4096-H4", c, "latest", 4, {"lc": 0}, (), library_table=True)
+
+
+SMALL_HEADS = [(fmt, H) for fmt in ("f32", "bf16", "fp8") for H in (32, 16, 8)]
+
+
+@pytest.mark.parametrize("fmt,H", SMALL_HEADS)
+def test_smallest_head_sizes(oracle, mli, dev, fmt, H):
+    """emb_dim 64 with 32, 16 and 8 heads -- head sizes 2 (one pair per head: rope_half 1), 4 and 8, the near side of the rule
+    in rope_half -- at n_sequence 64: the decode projection and the prefill.  The epilogue pairs columns with a quad permute
+    whatever the head size; the frequency index is what changes.  The rope counter counts each launch."""
+    _check(oracle, mli, dev, f"{fmt}-latest-D64-H{H}", _latest_case(5000 + H, fmt, 70, 64, 64), "latest", H, {"lc": 0}, ())
+    c, mode = gm.fill_case(5100 + H, fmt, "signed", 8, 64, 64, mode="prefill")
+    _check(oracle, mli, dev, f"{fmt}-prefill-D64-H{H}", c, mode, H, {}, ())

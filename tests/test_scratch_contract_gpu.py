@@ -29,7 +29,10 @@ import torch
 import f64_model as fm
 import gemm_model as gm
 import gqa_model as gqa
+import alibi_model as alm
 import logprobs_model as lpm
+import prompt_model as pm
+import softcap_model as scm
 import sampling_cases
 import scratch_fence as sf
 from accuracy_cases import apply_family, base_case, oracle_scan, poison_contiguous
@@ -157,8 +160,10 @@ class Paged:
     """q, lengths and the pages of a case in a score family (an assignment of families for several heads), the float64
     model and the fp32 oracle of what the pages hold.  place() carves all of it from an arena."""
 
-    def __init__(self, oracle, dev, seed, B, S, D, elem, family, lengths, H=1, Hkv=1, W=0, K=0):
+    def __init__(self, oracle, dev, seed, B, S, D, elem, family, lengths, H=1, Hkv=1, W=0, K=0, slopes=None, cap=None):
+        """slopes [H] float32: the ALiBi call; cap: the soft-capped call, q scaled by softcap_model.scale_q's rule"""
         self.B, self.S, self.D, self.elem, self.H, self.Hkv, self.W, self.K = B, S, D, elem, H, Hkv, W, K
+        self.slopes, self.cap = slopes, cap
         c = base_case(seed, B, S, D, lengths)
         if H == 1:
             q, kt = apply_family(c, family)
@@ -166,6 +171,8 @@ class Paged:
         else:
             q, kt = gqa.apply_gqa_families(c, H, Hkv, family)
             self.fams = gqa.head_families(family, H, Hkv)
+        if cap is not None:
+            q = scm.scale_q(q, kt, c["lengths"], H, Hkv)
         self.q, self.L, self.table = q, c["lengths"], c["table"]
         self.pool, values = pages_on_device(oracle, dev, c, q, kt, c["v_cache"], elem, "nan")
         self.k_rows = fm.gather_pages(values, self.table, self.L, S, D, 1)
@@ -176,12 +183,14 @@ class Paged:
     def room(self, qkt=False):
         B, S, D = self.B, self.S, self.D
         return [self.q.nbytes, self.L.nbytes, self.pool.numel() * self.pool.element_size(), self.table.size * 8, B * D * 4] + \
-               ([B * S * 4] if qkt else [])
+               ([B * S * 4] if qkt else []) + ([self.slopes.nbytes] if self.slopes is not None else [])
 
     def place(self, arena, p="", qkt=False):
         arena.carve_from(p + "q", self.q)
         arena.carve_from(p + "lengths", self.L)
         place_pool(arena, self.pool, self.table, self.elem, p)
+        if self.slopes is not None:
+            arena.carve_from(p + "slopes", self.slopes)
         arena.carve(p + "out", self.B * self.D * 4)
         arena.view(p + "out", torch.float32).fill_(SENTINEL)
         if qkt:
@@ -200,6 +209,10 @@ class Paged:
             return mli.mli_decode_scan_paged_window(*front, a("out"), B, S, D, self.H, self.W, e, *tail)
         if entry == "sinks":
             return mli.mli_decode_scan_paged_sinks(*front, a("out"), B, S, D, self.H, self.W, self.K, e, *tail)
+        if entry == "alibi":
+            return mli.mli_decode_scan_paged_alibi(*front, a("out"), B, S, D, self.H, self.Hkv, self.W, self.K, a("slopes"), e, *tail)
+        if entry == "softcap":
+            return mli.mli_decode_scan_paged_softcap(*front, a("out"), B, S, D, self.H, self.Hkv, self.W, self.K, self.cap, e, *tail)
         assert entry == "gqa", entry
         return mli.mli_decode_scan_paged_gqa(*front, a("out"), B, S, D, self.H, self.Hkv, self.W, self.K, e, *tail)
 
@@ -207,6 +220,12 @@ class Paged:
         """e: attention_result against the float64 model, tolerance from the fp32 oracle's own error."""
         H, Hkv = self.H if H is None else H, self.Hkv if Hkv is None else Hkv
         W, K = self.W if W is None else W, self.K if K is None else K
+        if H > 1 and (self.slopes is not None or self.cap is not None):      # the derived bound of alibi_model / softcap_model
+            m, arg = (alm, self.slopes) if self.slopes is not None else (scm, self.cap)
+            model = (m.AlibiModel if m is alm else m.SoftcapModel)(self.q, self.ktm, self.v_rows, self.L, H, Hkv, arg, W, K)
+            worst, tol = m.compare(out, m.eval_fp32(self.q, self.ktm, self.v_rows, self.L, H, Hkv, arg, W, K), model, what=what)
+            assert worst <= tol, f"{what}: {worst:.3e} > tol {tol:.3e}"
+            return
         model = gqa.model_gqa(self.q, self.ktm, self.v_rows, self.L, H, Hkv, W, K)
         o_or = gqa.oracle_gqa(self.oracle, self.q, self.ktm, self.v_rows, self.L, H, Hkv, W, K)
         fams = self.fams if H == self.H else (self.fams[0],) * H
@@ -357,7 +376,10 @@ def test_equal_shares_scan(oracle, mli, dev, others, S, elem, split):
 # ---- the lean variants: heads, window, sinks, grouped K/V heads -------------------------------------------------------------------
 # W 40 spans 64 tokens: one item per windowed row at chunk_tokens 64 (no body); W 100 spans 128: two items and the merge
 LEAN = [("heads", 2, 2, 0, 0), ("window", 1, 1, 40, 0), ("window", 2, 2, 40, 0), ("window", 1, 1, 100, 0), ("window", 2, 2, 100, 0),
-        ("sinks", 1, 1, 40, 4), ("sinks", 2, 2, 40, 4), ("gqa", 2, 1, 0, 0), ("gqa", 2, 1, 40, 4)]
+        ("sinks", 1, 1, 40, 4), ("sinks", 2, 2, 40, 4), ("gqa", 2, 1, 0, 0), ("gqa", 2, 1, 40, 4),
+        # the biased and the capped scan (their own kernel families): plain, grouped under a window with sinks / a two-item window
+        ("alibi", 2, 2, 0, 0), ("alibi", 2, 1, 40, 4), ("softcap", 2, 2, 0, 0), ("softcap", 2, 1, 100, 0)]
+LEAN_FAMILY = {"alibi": "scan_heads_alibi", "softcap": "scan_heads_softcap"}
 
 
 def _lean_grid():
@@ -369,14 +391,15 @@ def _lean_grid():
 def test_lean_variants(oracle, mli, dev, others, entry, elem, H, Hkv, W, K):
     B, S, D = 12, 256, 128
     L = length_vectors(1400 + H + W, B, S)[0]
-    pb = Paged(oracle, dev, 1500 + 7 * H + W + K, B, S, D, elem, "mixed" if H > 1 else "offset+", L, H, Hkv, W, K)
+    extra = {"alibi": dict(slopes=alm.standard_slopes(H)), "softcap": dict(cap=scm.CAPS[1])}.get(entry, {})
+    pb = Paged(oracle, dev, 1500 + 7 * H + W + K, B, S, D, elem, "mixed" if H > 1 else "offset+", L, H, Hkv, W, K, **extra)
     need = heads_need(mli, pb)
     what = f"decode_scan_paged_{entry} {elem} ({B}, {S}, {D}) H {H} Hkv {Hkv} W {W} K {K}"
     other = others["plain" if H > 1 else "heads"]
     with knobs(mli, chunk_tokens=64):
         assert mli.mli_launch_counts_reset() == 0
         arena, out, _ = scan_case(mli, dev, pb, other, what, entry, need)
-        assert launches(mli, "scan_heads_window") >= 4, f"{what}: handed to another kernel"
+        assert launches(mli, LEAN_FAMILY.get(entry, "scan_heads_window")) >= 4, f"{what}: handed to another kernel"
         pb.judge(out, what)
         # the single-head call uses the same buffer directly afterwards, as "keep", then with a zero body: the same bits
         images = sf.save(arena, ["out"])
@@ -509,10 +532,17 @@ def test_softmax_v_paged(oracle, mli, dev, others, elem):
 
 
 # ---- the compositions: fill (three new rows) -> latest -> scan ----------------------------------------------------------------------
-def judge_memory(oracle, q, k_rows, v_rows, L, out, what, H=1, Hkv=1, W=0, K=0):
+def judge_memory(oracle, q, k_rows, v_rows, L, out, what, H=1, Hkv=1, W=0, K=0, slopes=None, cap=None):
     """e for a composition: attention_result against the float64 model of what the call left in memory -- its q_output and
-    the K / V rows of the pages or caches, the appended row included -- tolerance from the fp32 oracle on the same."""
+    the K / V rows of the pages or caches, the appended row included -- tolerance from the fp32 oracle on the same (with
+    slopes or a cap: alibi_model's / softcap_model's model and derived bound)."""
     ktm = np.ascontiguousarray(k_rows).transpose(0, 2, 1)
+    if slopes is not None or cap is not None:
+        m, arg = (alm, slopes) if slopes is not None else (scm, cap)
+        model = (m.AlibiModel if m is alm else m.SoftcapModel)(q, ktm, v_rows, L, H, Hkv, arg, W, K)
+        worst, tol = m.compare(out, m.eval_fp32(q, ktm, v_rows, L, H, Hkv, arg, W, K), model, what=what)
+        assert worst <= tol, f"{what}: {worst:.3e} > tol {tol:.3e}"
+        return
     model = gqa.model_gqa(q, ktm, v_rows, L, H, Hkv, W, K)
     o_or = gqa.oracle_gqa(oracle, np.ascontiguousarray(q), ktm, v_rows, L, H, Hkv, W, K)
     gqa.assert_within(gqa.compare(out, o_or, model, ("flat",) * H, what=what), what)
@@ -574,13 +604,20 @@ PAGED_COMPOSITIONS = [("paged_attention", "f32", 64, 12, -1), ("paged_attention_
                       ("paged_attention", "f32", 2052, 8, 1), ("paged_attention", "f32", 2052, 8, 0),
                       ("paged_attention_bf16", "bf16", 4104, 8, 1), ("paged_attention_bf16", "bf16", 4104, 8, 0),
                       ("lean", "f32", 64, 12, -1), ("lean", "bf16", 64, 12, -1), ("lean", "fp8", 64, 12, -1),
-                      ("lean_gqa", "f32", 128, 12, -1), ("lean_gqa", "bf16", 128, 12, -1)]
+                      ("lean_gqa", "f32", 128, 12, -1), ("lean_gqa", "bf16", 128, 12, -1),
+                      # the biased, the capped and the rotated composition: two heads on one K/V head under W 40 with 4 sinks
+                      ("lean_alibi", "f32", 128, 12, -1), ("lean_alibi", "bf16", 128, 12, -1),
+                      ("lean_softcap", "f32", 128, 12, -1), ("lean_softcap", "bf16", 128, 12, -1),
+                      ("lean_rope", "f32", 128, 12, -1), ("lean_rope", "bf16", 128, 12, -1)]
+GROUPED = ("lean_gqa", "lean_alibi", "lean_softcap", "lean_rope")
 
 
 @pytest.mark.parametrize("entry,elem,D,B,fused", PAGED_COMPOSITIONS, ids=lambda v: str(v))
 def test_paged_compositions(oracle, mli, dev, others, entry, elem, D, B, fused):
     S, n_new = 256, 3
-    H, Hkv, W, K = (2, 1, 40, 4) if entry == "lean_gqa" else (1, 1, 0, 0)
+    H, Hkv, W, K = (2, 1, 40, 4) if entry in GROUPED else (1, 1, 0, 0)
+    slopes = alm.standard_slopes(H) if entry == "lean_alibi" else None
+    cap = scm.CAPS[1] if entry == "lean_softcap" else None
     L = length_vectors(1900 + D, B, S)[0]
     c = paged_case(1901 + D, B, S, D, conditioned=True, lengths=L)
     new_idx = c["new_batch_idx"].copy()
@@ -592,6 +629,11 @@ def test_paged_compositions(oracle, mli, dev, others, entry, elem, D, B, fused):
     other = others["heads" if H == 1 else "plain"]
     n_other = heads_need(mli, other)
     inputs = {"wk": w["wk"], "wq": w["wq"], "wv": w["wv"], "new_idx": new_idx, "lengths": L}
+    if slopes is not None:
+        inputs["slopes"] = slopes
+    if entry == "lean_rope":
+        import rope_model
+        inputs["rope"] = rope_model.standard_table(S, D // H)
     outs = {"q": (B * D * 4, torch.float32, SENTINEL), "out": (B * D * 4, torch.float32, SENTINEL)}
     if materialising:
         outs["qkt"] = (B * S * 4, torch.float32, SENTINEL)
@@ -611,6 +653,13 @@ def test_paged_compositions(oracle, mli, dev, others, entry, elem, D, B, fused):
             return mli.mli_paged_attention_bf16(*front, a("qkt"), a("out"), B, S, D, n_new, *tail)
         if entry == "lean":
             return mli.mli_paged_attention_lean(*front, a("out"), B, S, D, n_new, ELEM[elem], *tail)
+        shape = (B, S, D, n_new, H, Hkv, W, K)
+        if entry == "lean_alibi":
+            return mli.mli_paged_attention_lean_alibi(*front, a("out"), *shape, a("slopes"), ELEM[elem], *tail)
+        if entry == "lean_softcap":
+            return mli.mli_paged_attention_lean_softcap(*front, a("out"), *shape, cap, None, ELEM[elem], *tail)
+        if entry == "lean_rope":
+            return mli.mli_paged_attention_lean_rope(*front, a("out"), *shape, None, a("rope"), ELEM[elem], *tail)
         return mli.mli_paged_attention_lean_gqa(*front, a("out"), B, S, D, n_new, H, Hkv, W, K, ELEM[elem], *tail)
     what = f"{entry} {elem} ({B}, {S}, {D})" + (f" H {H} Hkv {Hkv} W {W} K {K}" if H > 1 else "") + \
            (f" fused_softmax {fused}" if fused >= 0 else "")
@@ -620,6 +669,11 @@ def test_paged_compositions(oracle, mli, dev, others, entry, elem, D, B, fused):
         assert mli.mli_launch_counts_reset() == 0
         first = contract(arena, what, call, images, outputs, need, other=other_call(mli, arena, other, need))
         record_refusal(arena, what, call, need, images)
+        family = {"lean_alibi": "scan_heads_alibi", "lean_softcap": "scan_heads_softcap", "lean_rope": "scan_heads_window"}.get(entry)
+        if family:
+            assert launches(mli, family) >= 3, f"{what}: handed to another kernel"
+        if entry == "lean_rope":
+            assert launches(mli, "gemm_f32_rope") + launches(mli, "gemm_bf16_rope") >= 6, f"{what}: fill and projection rotate"
         if materialising:     # which form ran: the single-pass scan counts as "scan_chunked", the separate passes as nothing
             assert (launches(mli, "scan_chunked") == 0) == (fused >= 0), f"{what}: {launches(mli, 'scan_chunked')} scan launches"
     out, q = f32(first["out"], (B, D)), f32(first["q"], (B, D))
@@ -627,7 +681,7 @@ def test_paged_compositions(oracle, mli, dev, others, entry, elem, D, B, fused):
     assert np.isfinite(q).all() and not (q[L > 0] == SENTINEL).any(), f"{what}: q_output"
     values = page_values(first["pool"], elem)
     k_rows, v_rows = fm.gather_pages(values, c["table"], L, S, D, 1), fm.gather_pages(values, c["table"], L, S, D, 2)
-    judge_memory(oracle, q, k_rows, v_rows, L, out, what, H, Hkv, W, K)
+    judge_memory(oracle, q, k_rows, v_rows, L, out, what, H, Hkv, W, K, slopes=slopes, cap=cap)
     if materialising:
         probs = f32(first["qkt"], (B, S))
         model = fm.Model(q, k_rows.transpose(0, 2, 1), v_rows, L)
@@ -1122,3 +1176,170 @@ def test_sample_tokens(mli, dev, V):
     assert (runs[0] == runs[1]).all()
     sampling_cases.check_against_reference(x, T, K, P, seed, lengths, runs[0], f"sample_tokens V={V}")
     assert (runs[0][lengths == 0] == -1).all() and not (runs[0] == ISENTINEL).any()
+
+
+# ---- mli_paged_prompt_logprobs[_softcap]: five regions carved from one scratch buffer -----------------------------------------------
+PROMPT_CALLS = [(elem, H, Hkv, n_top, capped) for elem in ("f32", "bf16") for H, Hkv in ((1, 1), (4, 2)) for n_top in (0, 8)
+                for capped in (False, True) if H > 1 or not capped]
+WORKSPACE = -12          # MLI_ERR_WORKSPACE
+
+
+def _segment_arrays(segs):
+    """(rows, first, count, offset) int32 of [(row, first, count)] with dense offsets in list order, and the positions in all"""
+    counts = [n for _, _, n in segs]
+    off = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    return [np.asarray(a, np.int32) for a in ([r for r, _, _ in segs], [f for _, f, _ in segs], counts, off)], int(sum(counts))
+
+
+@pytest.mark.parametrize("elem,H,Hkv,n_top,capped", PROMPT_CALLS, ids=lambda v: str(v))
+def test_paged_prompt_logprobs(oracle, mli, dev, elem, H, Hkv, n_top, capped):
+    """(4, 64, 128) with n_vocab 1030: pages, tokens, Wq, the embedding table, the segment arrays, the three output arrays and
+    the scratch (gathered x | q | attention | logits | targets) in one arena.  Exactly mli_prompt_logprobs_scratch_bytes is
+    enough; with 256 bytes fewer the call answers MLI_ERR_WORKSPACE and not one byte of the arena has changed; the guards are
+    intact; the outputs are bit-identical with the scratch body zero, 0xFF and left behind by a call of another shape; the
+    figures are within prompt_model.compare_given of the float64 forward over what the pages hold; the output rows of a
+    segment the device checks skip (its row lies outside the batch) keep their sentinels.  "scan_prompt" /
+    "scan_prompt_softcap" counts the scan."""
+    B, S, D, V = 4, 64, 128, 1030
+    cap = scm.CAPS[1] if capped else None
+    L = np.asarray([63, 40, 17, 33], np.int32)
+    c = paged_case(2800 + H, B, S, D, conditioned=True, lengths=L)
+    pool, values = pages_on_device(oracle, dev, c, c["q_output"], c["kt_cache"], c["v_cache"], elem, "nan")
+    rng = np.random.default_rng(2801 + H)
+    emb = (rng.standard_normal((V, D)) * 0.5).astype(np.float32)
+    inp = rng.integers(0, V, size=(B, S)).astype(np.int32)
+    w32 = (rng.standard_normal((D, D)) * (2.0 / np.sqrt(D))).astype(np.float32)
+    wq = w32 if elem == "f32" else bf16_bits(w32).reshape(D, D)
+    w_values = gm.decode(wq, "f32" if elem == "f32" else "bf16").astype(np.float64)
+    # the third segment names row 7 of a batch of 4: skipped whole by every kernel of the call
+    segs = [(2, 0, 17), (0, 50, 13), (7, 0, 4), (3, 5, 20), (0, 20, 9)]
+    arrays, n = _segment_arrays(segs)
+    skipped = np.zeros(n, bool)
+    skipped[int(arrays[3][2]):int(arrays[3][2]) + 4] = True
+    other_segs = [(1, 3, 30), (3, 0, 2)]
+    o_arrays, o_n = _segment_arrays(other_segs)
+    V_other = 515
+    need = int(mli.mli_prompt_logprobs_scratch_bytes(n, D, V))
+    n_other = int(mli.mli_prompt_logprobs_scratch_bytes(o_n, D, V_other))
+    assert 0 < n_other < need
+    inputs = {"inp": inp, "wq": wq, "emb": emb}
+    inputs.update({f"seg{i}": a for i, a in enumerate(arrays)})
+    inputs.update({f"o.seg{i}": a for i, a in enumerate(o_arrays)})
+    outs = {"lp": (n * 4, torch.float32, SENTINEL), "o.lp": (o_n * 4, torch.float32, SENTINEL)}
+    if n_top:
+        outs.update({"ids": (n * n_top * 4, torch.int32, ISENTINEL), "tops": (n * n_top * 4, torch.float32, SENTINEL)})
+    arena = sf.Arena(sf.Arena.room(*[nbytes_of(a) for a in inputs.values()], *[b for b, _, _ in outs.values()], nbytes_of(pool),
+                                   c["table"].size * 8, need), dev)
+    place_all(arena, inputs, outs)
+    place_pool(arena, pool, c["table"], elem)
+    arena.carve("ws", need)
+    a = arena.ptr
+
+    def run(p, lp, n_pos, vocab, top, count, n_seg, scratch_bytes):
+        front = (a("table"), a("inp"), a("wq"), a("emb"), a(p + "seg0"), a(p + "seg1"), a(p + "seg2"), a(p + "seg3"), a(lp),
+                 a("ids") if top else None, a("tops") if top else None)
+        shape = (n_seg, count, n_pos, B, S, D, vocab, H, Hkv, 0, 0)
+        tail = (ELEM[elem], top, arena.ptr("ws"), scratch_bytes, stream())
+        if capped:
+            return mli.mli_paged_prompt_logprobs_softcap(*front, *shape, cap, *tail)
+        return mli.mli_paged_prompt_logprobs(*front, *shape, *tail)
+
+    def call(nbytes):
+        return run("", "lp", n, V, n_top, 20, len(segs), nbytes)
+
+    def other():
+        arena.resize("ws", n_other)
+        rc = run("o.", "o.lp", o_n, V_other, 0, 30, len(other_segs), n_other)
+        arena.assert_guards_intact("the other call")
+        arena.resize("ws", need)
+        return rc
+
+    what = f"paged_prompt_logprobs{'_softcap' if capped else ''} {elem} ({B}, {S}, {D}, {V}) H {H} Hkv {Hkv} n_top {n_top}"
+    outputs = [k for k in outs if not k.startswith("o.")]
+    images = sf.save(arena, outputs)
+    assert mli.mli_launch_counts_reset() == 0
+    first = contract(arena, what, call, images, outputs, need, other=other, counters=0)
+    family, idle = ("scan_prompt_softcap", "scan_prompt") if capped else ("scan_prompt", "scan_prompt_softcap")
+    assert launches(mli, family) == 4 and launches(mli, idle) == 0, f"{what}: three calls and the other one, handed to another kernel"
+    rungs = sf.run_ladder(arena, "ws", [need - 256, need], call, images, outputs, first, 0, what)
+    assert rungs == [(need - 256, WORKSPACE), (need, 0)], rungs
+    # the skipped segment's rows keep their sentinels in every output array
+    lp = f32(first["lp"], (n,))
+    assert (lp[skipped] == SENTINEL).all(), f"{what}: token_logprob of a skipped segment was written: {lp[skipped]}"
+    ids = tops = np.zeros((n, 0))
+    if n_top:
+        ids, tops = first["ids"].view(np.int32).reshape(n, n_top), f32(first["tops"], (n, n_top))
+        assert (ids[skipped] == ISENTINEL).all() and (tops[skipped] == SENTINEL).all(), f"{what}: top_* of a skipped segment"
+    # the float64 forward over what the pages hold: q = x . Wq, the causal scan, attention . emb^T
+    live = [s for s in segs if s[0] < B]
+    rows, pos = pm.queries(live)
+    x_rows = fm.gather_pages(values, c["table"], L, S, D, 0).astype(np.float64)
+    ktm = fm.gather_pages(values, c["table"], L, S, D, 1).transpose(0, 2, 1)
+    v_rows = fm.gather_pages(values, c["table"], L, S, D, 2)
+    q64 = x_rows[rows, pos] @ w_values
+    if capped:
+        attn = scm.prompt_model(q64, ktm, v_rows, rows, pos, H, Hkv, cap).o
+    else:
+        attn = pm.scan_float64(q64, ktm, v_rows, rows, pos, H, Hkv, 0, 0)
+    logits = (attn @ emb.astype(np.float64).T).astype(np.float32)
+    given = np.asarray([inp[r, t + 1] if t + 1 < S else -1 for r, t in zip(rows, pos)], np.int64)
+    err, tol, bad = pm.compare_given((lp[~skipped], ids[~skipped], tops[~skipped]), logits, given, n_top)
+    print(f"SCRATCH {what} | figures: error {err:.3e}  tolerance {tol:.3e}")
+    assert not bad and err <= tol, (what, err, tol, bad)
+
+
+# ---- entry points without scratch: the prompt projection and the prompt scan ---------------------------------------------------------
+@pytest.mark.parametrize("elem,H,Hkv", [("f32", 1, 1), ("bf16", 1, 1), ("f32", 4, 2), ("bf16", 4, 2)])
+def test_prompt_project_q_and_scan(oracle, mli, dev, elem, H, Hkv):
+    """mli_prompt_project_q, then mli_prompt_scan_paged on its q, at (4, 64, 128) under W 40 with 4 sinks: pages, Wq, the segment
+    arrays, `gathered`, q and the scan's output between guards (b); a dense row that belongs to no query keeps its sentinel
+    in the scan's output, every row of a query is finite (d); q against float64 x . Wq at the fp32 chain's own bound
+    D 2^-24 sum |x w|, the attention against the float64 model of what the pages hold and the q the projection left (e).
+    "gemm_f32_rows64" / "gemm_bf16_widened" and "scan_prompt" count the launches."""
+    B, S, D, W, K = 4, 64, 128, 40, 4
+    L = np.asarray([63, 40, 17, 33], np.int32)
+    c = paged_case(2900 + H, B, S, D, conditioned=True, lengths=L)
+    pool, values = pages_on_device(oracle, dev, c, c["q_output"], c["kt_cache"], c["v_cache"], elem, "nan")
+    w32 = ((np.random.default_rng(2901).random((D, D), dtype=np.float32) * 2 - 1) / np.sqrt(D)).astype(np.float32)
+    wq = w32 if elem == "f32" else bf16_bits(w32).reshape(D, D)
+    segs = [(2, 0, 17), (0, 50, 13), (3, 5, 20), (0, 20, 9)]
+    arrays, n = _segment_arrays(segs)
+    arrays[3][2:] += 1                                    # a hole of one dense row behind the second segment
+    n_q = n + 2                                           # ... and a tail
+    rows, pos = pm.queries(segs)
+    where = np.concatenate([np.arange(o, o + cnt) for o, cnt in zip(arrays[3], arrays[2])])
+    nobody = np.setdiff1d(np.arange(n_q), where)
+    inputs = {"wq": wq}
+    inputs.update({f"seg{i}": a for i, a in enumerate(arrays)})
+    outs = {"gathered": (n_q * D * ESIZE[elem], torch.uint8, 0xFF), "q": (n_q * D * 4, torch.float32, SENTINEL),
+            "out": (n_q * D * 4, torch.float32, SENTINEL)}
+    arena = sf.Arena(sf.Arena.room(*[nbytes_of(a) for a in inputs.values()], *[b for b, _, _ in outs.values()], nbytes_of(pool),
+                                   c["table"].size * 8), dev)
+    place_all(arena, inputs, outs)
+    place_pool(arena, pool, c["table"], elem)
+    a = arena.ptr
+    seg = (a("seg0"), a("seg1"), a("seg2"), a("seg3"))
+    what = f"prompt_project_q + prompt_scan_paged {elem} ({B}, {S}, {D}) H {H} Hkv {Hkv}"
+    assert mli.mli_launch_counts_reset() == 0
+    assert mli.mli_prompt_project_q(a("table"), *seg, a("wq"), a("gathered"), a("q"), len(segs), 20, n_q, B, S, D, ELEM[elem], stream()) == 0
+    arena.assert_guards_intact(what + ": projection")
+    assert mli.mli_prompt_scan_paged(a("q"), a("table"), *seg, a("out"), len(segs), 20, n_q, B, S, D, H, Hkv, W, K, ELEM[elem], stream()) == 0
+    arena.assert_guards_intact(what + ": scan")
+    assert launches(mli, "gemm_f32_rows64" if elem == "f32" else "gemm_bf16_widened") == 1 and launches(mli, "scan_prompt") == 1
+    q, out = f32(sf.bits(arena.view("q")), (n_q, D)), f32(sf.bits(arena.view("out")), (n_q, D))
+    # (the projection's GEMM covers all n_q rows: a q row of no position is the product of whatever `gathered` held)
+    assert (out[nobody] == SENTINEL).all(), f"{what}: a dense row of the output that belongs to no query was written"
+    for name, got in (("q", q), ("out", out)):
+        assert np.isfinite(got[where]).all() and (got[where] != SENTINEL).any(axis=1).all(), f"{what}: {name}"
+    x = fm.gather_pages(values, c["table"], L, S, D, 0)[rows, pos].astype(np.float64)
+    w64 = gm.decode(wq, "f32" if elem == "f32" else "bf16").astype(np.float64)
+    bound = D * 2.0 ** -24 * (np.abs(x) @ np.abs(w64))
+    worst = float((np.abs(q[where] - x @ w64) / bound).max())
+    print(f"SCRATCH {what} | q: worst error {worst:.3e} of the bound D 2^-24 sum |x w|")
+    assert worst <= 1.0
+    ktm = fm.gather_pages(values, c["table"], L, S, D, 1).transpose(0, 2, 1)
+    v_rows = fm.gather_pages(values, c["table"], L, S, D, 2)
+    qv = np.ascontiguousarray(q[where])
+    model = pm.model_prompt(qv, ktm, v_rows, rows, pos, H, Hkv, W, K)
+    o_or = pm.oracle_prompt(oracle, qv, ktm, v_rows, rows, pos, H, Hkv, W, K)
+    gqa.assert_within(gqa.compare(out[where], o_or, model, ("flat",) * H, what=what), what)

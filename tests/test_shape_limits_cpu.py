@@ -115,6 +115,31 @@ def test_row_truth_is_the_dense_models(oracle, H, Hkv, W, K):
             assert np.array_equal(o[0], want_oracle[b, cols]), (b, h)
 
 
+@pytest.mark.parametrize("H,Hkv,W,K", [(2, 2, 0, 0), (2, 2, 17, 0), (2, 2, 16, 4), (2, 1, 0, 0), (4, 2, 33, 5), (4, 2, 24, 20)])
+def test_row_truth_with_slopes_and_with_a_cap_is_the_dense_models(oracle, H, Hkv, W, K):
+    """limit_cases.row_truth with `slopes` / `cap` against alibi_model / softcap_model on a dense case (alibi_model.slope_sets: standard, negative, mixed;
+    caps 50, 5 and 1 on q scaled by scale_q): the float64 attention and its condition scale agree to 1e-12, and
+    the float32 evaluation that sets row_truth's tolerance passes the dense model's own tolerance."""
+    import alibi_model as am
+    import softcap_model as sc
+    lengths = [1, 16, 17, 18, 40, 63, 33, 21]
+    S, D = 64, 128
+    case = lc.SparseCase(32, lengths, S, D, H=H, Hkv=Hkv, families={4: ("offset-", "late_peak")[:Hkv], 5: "early_peak"})
+    kt, v = case.dense()
+    q_cap = sc.scale_q(case.q, kt, case.lengths, H, Hkv)
+    forms = [("slopes", s, case.q) for s in am.slope_sets(H).values()] + [("cap", c, q_cap) for c in sc.CAPS]
+    for kind, arg, q in forms:
+        m_, kw = (am, dict(slopes=arg)) if kind == "slopes" else (sc, dict(cap=arg))
+        model = (am.AlibiModel if kind == "slopes" else sc.SoftcapModel)(q, kt, v, case.lengths, H, Hkv, arg, W, K)
+        tol = m_.tolerance(model, m_.eval_fp32(q, kt, v, case.lengths, H, Hkv, arg, W, K))
+        for b in range(len(lengths)):
+            K_, V_ = case.rows(b)
+            for h, (cols, m, (_, _, o)) in enumerate(lc.row_truth(oracle, q[b], K_, V_, H, Hkv, W, K, **kw)):
+                assert np.abs(m.o[0] - model.o[b, cols]).max() <= 1e-12 * max(1.0, np.abs(model.o[b, cols]).max()), (kind, arg, b, h)
+                assert abs(m.o_scale[0] - model.o_scale[b, h]) <= 1e-12 * model.o_scale[b, h], (kind, arg, b, h)
+                assert fm.attention_error(o, m)[0] <= tol, (kind, arg, b, h)
+
+
 def test_restated_lds_sum_gives_the_figures_worked_out_from_the_source():
     assert lc.stream_lds_bytes(2048, 12288, 512, "f32", 256) == 73988      # 72.25 KiB
     assert lc.stream_lds_bytes(2048, 16384, 512, "f32", 256) == 82180      # 80.25 KiB
@@ -186,13 +211,19 @@ def test_softmax_v_lds_does_not_grow_with_the_width():
 @pytest.mark.parametrize("entry,args,limit,ct", lc.REFUSALS)
 def test_refusals_without_a_gpu(mli, entry, args, limit, ct):
     """A workspace pointer that is not null and a size beyond any need: the refusal is the shape's, not the workspace's.  No
-    pointer is dereferenced by a launcher; a launch, had the rule let the shape through, fails here and returns a HIP error."""
+    pointer is dereferenced by a launcher; a launch, had the rule let the shape through, fails here and returns a HIP error.
+    The newer entry points (prompt, ALiBi, soft-cap, rotary) also refuse a null data pointer, so each of their rows runs twice:
+    with null pointers, as on the device, and with every data pointer set to an address that is never followed -- then the
+    pointer checks pass, and the answer shows that the shape rule stands ahead of them and of every launch."""
     from min_llm_inference_amd import ops
     assert mli.mli_launch_counts_reset() == 0
     try:
         assert mli.mli_tune(b"chunk_tokens", ct) == 0
         assert lc.call_refusal(mli, entry, args, workspace=4096) == lc.BAD_ARG
+        assert lc.call_refusal(mli, entry, args, workspace=4096, data=4096) == lc.BAD_ARG, "refused by a pointer check, not the shape"
     finally:
         assert mli.mli_tune(b"chunk_tokens", 0) == 0
-    for family in ("scan_equal_shares", "scan_chunked", "scan_heads_window"):
-        assert ops.launch_count(family) == 0
+    for family in ("scan_equal_shares", "scan_chunked", "scan_heads_window", "scan_heads_alibi", "scan_heads_softcap", "scan_prompt",
+                   "scan_prompt_softcap", "gemm_f32_rows64", "gemm_bf16_widened", "gemm_f32_rope", "gemm_bf16_rope", "fill_flat",
+                   "fill_per_row", "prefill_fused", "prefill_two_launch"):
+        assert ops.launch_count(family) == 0, family

@@ -19,6 +19,8 @@ import torch
 
 import f64_model as fm
 import limit_cases as lc
+import prompt_model as pm
+import softcap_model as sc
 import stream_model as sm
 from accuracy_cases import poison_contiguous
 from accuracy_gpu import Checker
@@ -27,7 +29,12 @@ from helpers import assert_equal, fp8_decode
 
 pytestmark = pytest.mark.gpu
 
-SCAN_FAMILIES = ("scan_equal_shares", "scan_chunked", "scan_rows_ordered", "scan_rows_grid_order", "scan_heads_window")
+SCAN_FAMILIES = ("scan_equal_shares", "scan_chunked", "scan_rows_ordered", "scan_rows_grid_order", "scan_heads_window",
+                 "scan_heads_alibi", "scan_heads_softcap", "scan_prompt", "scan_prompt_softcap")
+# what a refusal must not have launched either: the projections and fills behind the prompt and rotary entry points
+OTHER_FAMILIES = ("gemm_f32_rows64", "gemm_bf16_widened", "gemm_f32_rope", "gemm_bf16_rope", "fill_flat", "fill_per_row",
+                  "prefill_fused", "prefill_two_launch")
+CAP = 5.0
 _WS = {}
 
 
@@ -40,7 +47,7 @@ def _release_memory():
     yield
     _WS.clear()
     _pages.cache_clear()
-    for f in (_rows_case, _longest_case, _order_case, _shares_case, _heads_case, _merge_case, _offsets_case, _wide_case, _window_case, _lds_case):
+    for f in (_scaled_q, _x_pages, _hand_off_case, _rows_case, _longest_case, _order_case, _shares_case, _heads_case, _merge_case, _offsets_case, _wide_case, _window_case, _lds_case):
         f.cache_clear()
     torch.cuda.empty_cache()
 
@@ -111,17 +118,38 @@ def _tune(mli, **knobs):
 DEFAULTS = dict(chunk_tokens=0, scan_stream=1, scan_stream_min_tokens=1 << 21, scan_row_order=1)
 
 
-def _call(mli, dev, x, entry, extra, elem, out, qkt=None, phases=7, H=1):
-    """one launch through the C ABI; returns the status"""
+def _call(mli, dev, x, entry, extra, elem, out, qkt=None, phases=7, H=1, q=None):
+    """one launch through the C ABI; returns the status.  alibi: extra = (H, Hkv, W, K, slopes on the device); softcap: extra =
+    (H, Hkv, W, K, cap); q: the queries where they are not the case's (limit_cases.scaled_q)"""
     c = x.case
+    q = x.q if q is None else q
     ws, need = _workspace(mli, dev, c.B, c.S, c.D, H)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = lambda t: ctypes.c_void_p(0 if t is None else t.data_ptr())
     if entry == "scan":
-        return mli.mli_decode_scan_paged(p(x.q), p(x.table), p(x.L), p(qkt), p(out), c.B, c.S, c.D, lc.ELEM[elem], phases, p(ws), need, st)
-    name = {"heads": "mli_decode_scan_paged_heads", "window": "mli_decode_scan_paged_window",
-            "sinks": "mli_decode_scan_paged_sinks", "gqa": "mli_decode_scan_paged_gqa"}[entry]
-    return getattr(mli, name)(p(x.q), p(x.table), p(x.L), p(out), c.B, c.S, c.D, *extra, lc.ELEM[elem], p(ws), need, st)
+        return mli.mli_decode_scan_paged(p(q), p(x.table), p(x.L), p(qkt), p(out), c.B, c.S, c.D, lc.ELEM[elem], phases, p(ws), need, st)
+    if entry == "alibi":
+        return mli.mli_decode_scan_paged_alibi(p(q), p(x.table), p(x.L), p(out), c.B, c.S, c.D, *extra[:4], p(extra[4]), lc.ELEM[elem],
+                                               p(ws), need, st)
+    name = {"heads": "mli_decode_scan_paged_heads", "window": "mli_decode_scan_paged_window", "sinks": "mli_decode_scan_paged_sinks",
+            "gqa": "mli_decode_scan_paged_gqa", "softcap": "mli_decode_scan_paged_softcap"}[entry]
+    return getattr(mli, name)(p(q), p(x.table), p(x.L), p(out), c.B, c.S, c.D, *extra, lc.ELEM[elem], p(ws), need, st)
+
+
+def _biased(entry, case, H, Hkv, W, K, dev):
+    """(arguments behind emb_dim, q on the device or None, the judge's keywords, the launch counter) of an ALiBi call with the
+    slopes of mli_alibi_slopes or a soft-capped call at cap 5 with q scaled so that the largest score is 25 (scale_q's rule)"""
+    from min_llm_inference_amd import ops
+    if entry == "alibi":
+        slopes = ops.alibi_slopes(H)
+        return (H, Hkv, W, K, _t(slopes, dev)), None, dict(slopes=slopes), "scan_heads_alibi"
+    q = _scaled_q(case, H, Hkv)
+    return (H, Hkv, W, K, CAP), _t(q, dev), dict(cap=CAP, q=q), "scan_heads_softcap"
+
+
+@functools.lru_cache(maxsize=2)
+def _scaled_q(case, H, Hkv):
+    return lc.scaled_q(case, sc.CAPS[0] / 2, H, Hkv)
 
 
 def _counts():
@@ -129,7 +157,7 @@ def _counts():
     return {f: ops.launch_count(f) for f in SCAN_FAMILIES}
 
 
-def _lean_twice(mli, dev, x, elem, what, want_counts, entry="scan", extra=(), H=1):
+def _lean_twice(mli, dev, x, elem, what, want_counts, entry="scan", extra=(), H=1, q=None):
     """Two launches with equal bits, the counters zero after each, the launch counters as wanted (per launch); returns the
     result on the host."""
     from min_llm_inference_amd import ops
@@ -138,7 +166,7 @@ def _lean_twice(mli, dev, x, elem, what, want_counts, entry="scan", extra=(), H=
     res = []
     for _ in range(2):
         out = torch.full((c.B, c.D), lc.SENTINEL, device=dev)
-        assert _call(mli, dev, x, entry, extra, elem, out, H=H) == 0, what
+        assert _call(mli, dev, x, entry, extra, elem, out, H=H, q=q) == 0, what
         res.append(host(out).copy())
         _counters_are_zero(_WS["ws"], what)
     assert_equal(res[1], res[0], what=f"{what}: second launch")
@@ -150,8 +178,8 @@ def _lean_twice(mli, dev, x, elem, what, want_counts, entry="scan", extra=(), H=
     return res[0]
 
 
-def _judge(oracle, x, got, rows, path, elem, H=1, Hkv=None, window=0, sinks=0):
-    res = lc.judge_rows(oracle, x.case, x.values_of, got, rows, H, Hkv, window, sinks)
+def _judge(oracle, x, got, rows, path, elem, H=1, Hkv=None, window=0, sinks=0, **biased):
+    res = lc.judge_rows(oracle, x.case, x.values_of, got, rows, H, Hkv, window, sinks, **biased)
     failures = []
     for family, (err, e_or) in sorted(res.items()):
         ck = Checker(family, elem)
@@ -484,7 +512,12 @@ def _heads_case(D):
 # (entry point, arguments behind emb_dim, emb_dim, H, Hkv, W, K)
 HEAD_FORMS = {"heads": ("heads", (2,), 128, 2, 2, 0, 0), "window": ("window", (2, 17), 128, 2, 2, 17, 0),
               "sinks": ("sinks", (2, 16, 4), 128, 2, 2, 16, 4), "gqa": ("gqa", (2, 1, 0, 0), 128, 2, 1, 0, 0),
-              "window_one_head": ("window", (1, 17), 64, 1, 1, 17, 0), "sinks_one_head": ("sinks", (1, 16, 4), 64, 1, 1, 16, 4)}
+              "window_one_head": ("window", (1, 17), 64, 1, 1, 17, 0), "sinks_one_head": ("sinks", (1, 16, 4), 64, 1, 1, 16, 4),
+              # the biased and the capped scan: separate instantiations of heads_scan_item (arguments: _biased)
+              "alibi": ("alibi", None, 128, 2, 2, 0, 0), "alibi_gqa": ("alibi", None, 128, 2, 1, 0, 0),
+              "alibi_sinks": ("alibi", None, 128, 2, 2, 16, 4),
+              "softcap": ("softcap", None, 128, 2, 2, 0, 0), "softcap_gqa": ("softcap", None, 128, 2, 1, 0, 0),
+              "softcap_window": ("softcap", None, 128, 2, 2, 17, 0)}
 
 
 @pytest.mark.parametrize("elem", ["f32", "bf16"])
@@ -496,8 +529,11 @@ def test_heads_family_on_the_last_row(oracle, mli, dev, form, elem):
     entry, extra, D, H, Hkv, W, K = HEAD_FORMS[form]
     case, named = _heads_case(D)
     x = _pages(case, elem, dev)
-    got = _lean_twice(mli, dev, x, elem, f"{form} {elem}", {"scan_heads_window": 1}, entry=entry, extra=extra, H=H)
-    _judge(oracle, x, got, lc.sample_rows(case.B, named), f"limits: B 16384, {form}", elem, H=H, Hkv=Hkv, window=W, sinks=K)
+    counter, q, kw = "scan_heads_window", None, {}
+    if extra is None:
+        extra, q, kw, counter = _biased(entry, case, H, Hkv, W, K, dev)
+    got = _lean_twice(mli, dev, x, elem, f"{form} {elem}", {counter: 1}, entry=entry, extra=extra, H=H, q=q)
+    _judge(oracle, x, got, lc.sample_rows(case.B, named), f"limits: B 16384, {form}", elem, H=H, Hkv=Hkv, window=W, sinks=K, **kw)
 
 
 @pytest.mark.parametrize("elem", ["f32", "bf16"])
@@ -510,10 +546,14 @@ def test_heads_on_the_last_arrival_counter(oracle, mli, dev, elem):
     rows = lc.sample_rows(case.B, named)
     try:
         _tune(mli, chunk_tokens=64)
-        for entry, extra, W in (("heads", (2,), 0), ("window", (2, 100), 100), ("window", (1, 100), 100)):
+        for entry, extra, W in (("heads", (2,), 0), ("window", (2, 100), 100), ("window", (1, 100), 100), ("alibi", None, 0),
+                                ("softcap", None, 0), ("alibi", None, 100), ("softcap", None, 100)):
+            counter, q, kw = "scan_heads_window", None, {}
+            if extra is None:
+                extra, q, kw, counter = _biased(entry, case, 2, 2, W, 0, dev)
             H = extra[0]
-            got = _lean_twice(mli, dev, x, elem, f"B 16384 {entry} H {H} {elem}", {"scan_heads_window": 1}, entry=entry, extra=extra, H=H)
-            _judge(oracle, x, got, rows, f"limits: B 16384, two items, {entry} H {H}", elem, H=H, window=W)
+            got = _lean_twice(mli, dev, x, elem, f"B 16384 {entry} H {H} W {W} {elem}", {counter: 1}, entry=entry, extra=extra, H=H, q=q)
+            _judge(oracle, x, got, rows, f"limits: B 16384, two items, {entry} H {H} W {W}", elem, H=H, window=W, **kw)
     finally:
         _tune(mli, **DEFAULTS)
 
@@ -524,7 +564,7 @@ def _merge_case():
     return lc.SparseCase(4700, [16383, 129], 16384, 1024, families={0: fams, 1: fams}, H=32)
 
 
-MERGE_FORMS = ["heads", "window"]
+MERGE_FORMS = ["heads", "window", "alibi", "softcap"]
 
 
 @pytest.mark.parametrize("form", MERGE_FORMS)
@@ -533,9 +573,12 @@ def test_merge_statistics_fill_their_lds(oracle, mli, dev, form):
     pairs, all the LDS the merge has; plain and under W 8192.  early_peak on odd heads, late_peak on even ones.  Both rows
     judged, head by head."""
     x = _pages(_merge_case(), "bf16", dev)
-    entry, extra, W = ("heads", (32,), 0) if form == "heads" else ("window", (32, 8192), 8192)
-    got = _lean_twice(mli, dev, x, "bf16", f"32 heads {form}", {"scan_heads_window": 1}, entry=entry, extra=extra, H=32)
-    _judge(oracle, x, got, [0, 1], f"limits: 32 heads, {form}", "bf16", H=32, window=W)
+    entry, extra, W = {"heads": ("heads", (32,), 0), "window": ("window", (32, 8192), 8192)}.get(form, (form, None, 0))
+    counter, q, kw = "scan_heads_window", None, {}
+    if extra is None:
+        extra, q, kw, counter = _biased(entry, x.case, 32, 32, 0, 0, dev)
+    got = _lean_twice(mli, dev, x, "bf16", f"32 heads {form}", {counter: 1}, entry=entry, extra=extra, H=32, q=q)
+    _judge(oracle, x, got, [0, 1], f"limits: 32 heads, {form}", "bf16", H=32, window=W, **kw)
 
 
 # ---- contiguous scan ---------------------------------------------------------------------------------------------------------
@@ -802,6 +845,22 @@ def test_window_extremes(oracle, mli, dev, elem, H, entry, W, K, windowed):
                 assert np.array_equal(got[b], x.values_of(b)[1][-1]), f"W 1: row {b} is not V's newest row"
 
 
+BIASED_WINDOW_CALLS = [(e, W, K, w) for e in ("alibi", "softcap") for W, K, w in ((63, 0, True), (64, 0, False), (59, 4, True), (60, 4, False))]
+
+
+@pytest.mark.parametrize("entry,W,K,windowed", BIASED_WINDOW_CALLS)
+@pytest.mark.parametrize("elem", ["f32", "bf16"])
+def test_window_extremes_biased(oracle, mli, dev, elem, entry, W, K, windowed):
+    """test_window_extremes for the biased and the capped scan at two heads: W 63 and K 4 + W 59 are the last windows they take,
+    W 64 and K 4 + W 60 the plain mask (the same kernel family counts either way: the result is the evidence).  All rows judged."""
+    case = _window_case()
+    x = _pages(case, elem, dev)
+    extra, q, kw, counter = _biased(entry, case, 2, 2, W, K, dev)
+    got = _lean_twice(mli, dev, x, elem, f"{entry} W {W} K {K} {elem}", {counter: 1}, entry=entry, extra=extra, H=2, q=q)
+    _judge(oracle, x, got, list(range(case.B)), f"limits: window extremes, {entry} W {W} K {K}", elem, H=2,
+           window=W if windowed else 0, sinks=K if windowed else 0, **kw)
+
+
 # ---- the merge statistics against the launch's LDS -----------------------------------------------------------------------------
 @functools.lru_cache(maxsize=1)
 def _lds_case():
@@ -839,6 +898,17 @@ def test_heads_widest_rows(oracle, mli, dev, elem, D, H):
     x = _pages(_wide_case(D), elem, dev)
     got = _lean_twice(mli, dev, x, elem, f"heads D {D} {elem}", {"scan_heads_window": 1}, entry="heads", extra=(H,), H=H)
     _judge(oracle, x, got, list(range(8)), "limits: several heads, widest rows", elem, H=H)
+
+
+@pytest.mark.parametrize("entry", ["alibi", "softcap"])
+@pytest.mark.parametrize("elem,D,H", HEADS_WIDE)
+def test_heads_widest_rows_biased(oracle, mli, dev, elem, D, H, entry):
+    """test_heads_widest_rows with the ALiBi bias and with the cap: the widest rows of their own kernel families
+    ("scan_heads_alibi" / "scan_heads_softcap" counts the launch).  All rows judged."""
+    x = _pages(_wide_case(D), elem, dev)
+    extra, q, kw, counter = _biased(entry, x.case, H, H, 0, 0, dev)
+    got = _lean_twice(mli, dev, x, elem, f"{entry} D {D} {elem}", {counter: 1}, entry=entry, extra=extra, H=H, q=q)
+    _judge(oracle, x, got, list(range(8)), f"limits: several heads, widest rows, {entry}", elem, H=H, **kw)
 
 
 # ---- standalone launchers ------------------------------------------------------------------------------------------------------
@@ -918,6 +988,203 @@ def test_softmax_v_vector_and_scalar_form(oracle, mli, dev, B, S, D):
     ck.done()
 
 
+# ---- the causal prompt scan ----------------------------------------------------------------------------------------------------
+def _prompt_twice(dev, x, segs, qv, elem, H, Hkv, W, K, cap, what):
+    """mli_prompt_scan_paged[_softcap] twice: the same bits, one launch of the family each, nothing else; [n_q, D] on the host"""
+    from min_llm_inference_amd import ops
+    c = x.case
+    q_dev = _t(qv, dev)
+    ops.reset_launch_counts()
+    res = []
+    for _ in range(2):
+        out = torch.full(qv.shape, lc.SENTINEL, device=dev)
+        ops.prompt_scan_paged(q_dev, x.table, segs, out, c.B, c.S, lc.ELEM[elem], n_heads=H, n_kv_heads=Hkv, window=W, sinks=K, softcap=cap)
+        res.append(host(out).copy())
+    assert_equal(res[1], res[0], what=f"{what}: second launch")
+    want = {f: 0 for f in SCAN_FAMILIES}
+    want["scan_prompt" if cap is None else "scan_prompt_softcap"] = 2
+    assert _counts() == want, f"{what}: launch counters {_counts()}"
+    assert np.isfinite(res[0]).all() and (res[0] != lc.SENTINEL).any(axis=1).all(), what
+    return res[0]
+
+
+def _prompt_judged(oracle, dev, x, segs, elem, H, Hkv, W, K, what, cap=None, q_rows=None):
+    rows, pos = pm.queries(segs)
+    qv = pm.query_vectors(x.case.q if q_rows is None else q_rows, rows, pos)
+    got = _prompt_twice(dev, x, segs, qv, elem, H, Hkv, W, K, cap, what)
+    truth = pm.long_truth(oracle, x.case, x.values_of, qv, rows, pos, H, Hkv, W, K, cap=cap)
+    pm.hm.assert_within(pm.long_compare(got, truth, what=what), what)
+    return got
+
+
+PROMPT_WIDE = [("f32", 512), ("bf16", 1024)]
+
+
+@pytest.mark.parametrize("elem,D", PROMPT_WIDE)
+def test_prompt_scan_widest_rows(oracle, mli, dev, elem, D):
+    """One head at (4, 128, D) with two 16-byte lane loads per row, the widest the prompt scan takes (fp32 emb_dim 512, bf16
+    1024; 516 / 1032 and fp8 pages are refused: REFUSALS), plain and under W 40 with 4 sinks.  Every query judged; "scan_prompt"
+    counts the launch."""
+    from min_llm_inference_amd import ops
+    tq = ops.prompt_scan_tq(D, 1, lc.ELEM[elem])
+    case = lc.SparseCase(5300 + D, [128, 100, 64, 17], 128, D, families={0: "late_peak", 1: "early_peak"}, full_rows=True)
+    x = _pages(case, elem, dev)
+    segs = [(1, 90, 10), (0, 128 - (tq + 1), tq + 1), (3, 15, 2), (2, 0, 2 * tq + 1)]
+    for W, K in ((0, 0), (40, 4)):
+        _prompt_judged(oracle, dev, x, segs, elem, 1, 1, W, K, f"limits: prompt scan, widest rows, D {D} {elem} W {W} K {K}")
+
+
+PROMPT_ROWS = [(1, None), (2, None), (2, CAP)]
+
+
+@pytest.mark.parametrize("elem", ["f32", "bf16"])
+@pytest.mark.parametrize("H,cap", PROMPT_ROWS)
+def test_prompt_scan_on_the_last_row(oracle, mli, dev, H, cap, elem):
+    """n_batch 16384, the last the prompt scan takes (16385 is refused: REFUSALS), with segments on rows 0, 8191 and 16383 and
+    on a short row, one head and two, and two heads under the cap.  Every query judged; "scan_prompt" / "scan_prompt_softcap"
+    counts the launch."""
+    from min_llm_inference_amd import ops
+    D = 64 * H
+    case, _ = _heads_case(D)
+    x = _pages(case, elem, dev)
+    tq = ops.prompt_scan_tq(D, H, lc.ELEM[elem])
+    segs = [(16383, 62 - tq, tq + 1), (7, 30, 3), (0, 0, 2 * tq + 1), (8191, 40, tq)]
+    _prompt_judged(oracle, dev, x, segs, elem, H, H, 0, 0, f"limits: prompt scan, B 16384, H {H} cap {cap} {elem}", cap=cap,
+                   q_rows=None if cap is None else _scaled_q(case, H, H))
+
+
+@functools.lru_cache(maxsize=1)
+def _hand_off_case(D):
+    return lc.SparseCase(5400, [64, 40, 17, 64], 64, D, families={0: "early_peak"}, full_rows=True)
+
+
+PROMPT_WINDOWS = [(63, True), (64, False)]
+
+
+@pytest.mark.parametrize("W,windowed", PROMPT_WINDOWS)
+@pytest.mark.parametrize("elem,H", [("f32", 1), ("bf16", 1), ("f32", 2)])
+def test_prompt_window_hand_off(oracle, mli, dev, elem, H, W, windowed):
+    """(4, 64, 64): W 63 is the last window the prompt scan masks by -- only the query at position 63 drops slot 0, which on
+    row 0 carries an early peak -- and W 64 is the plain mask: the bits of W 0.  Every query judged."""
+    x = _pages(_hand_off_case(64), elem, dev)
+    segs = [(3, 0, 64), (1, 33, 7), (0, 56, 8)]
+    what = f"limits: prompt scan, hand-off W {W} H {H} {elem}"
+    got = _prompt_judged(oracle, dev, x, segs, elem, H, H, W, 0, what)
+    rows, pos = pm.queries(segs)
+    plain = _prompt_twice(dev, x, segs, pm.query_vectors(x.case.q, rows, pos), elem, H, H, 0, 0, None, what + " plain")
+    differs = (got != plain).any(axis=1)
+    if windowed:
+        assert differs[pos == 63].all(), "the queries at position 63 drop slot 0"
+    else:
+        assert not differs.any(), "W = n_sequence is the plain mask"
+
+
+@functools.lru_cache(maxsize=1)
+def _x_pages(elem, dev, B=16, S=4096, D=64):
+    """pages of (16, 4096, 64) with x, K and V random in [-1, 1) on the device, every row whole, pages in shuffled order"""
+    gen = torch.Generator(device=dev).manual_seed(5500)
+    pool = torch.rand((B * S // 16, 16, 3, D), generator=gen, device=dev) * 2 - 1
+    pool = pool if elem == "f32" else pool.to(torch.bfloat16)
+    order = np.random.default_rng(5501).permutation(B * S // 16).reshape(B, S // 16)
+    table = _t(pool.data_ptr() + order.astype(np.int64) * (16 * 3 * D * lc.ESIZE[elem]), dev)
+    return pool, order, table
+
+
+def _slots(pool, order, rows, pos):
+    """float32 [n, 3, D]: x, K, V of the (row, position) pairs as the pages hold them"""
+    pages = torch.from_numpy(order[np.asarray(rows), np.asarray(pos) // 16]).to(pool.device)
+    return pool[pages, torch.from_numpy(np.asarray(pos) % 16).to(pool.device)].float().cpu().numpy()
+
+
+PROJECT_ELEMS = ["f32", "bf16"]
+
+
+@pytest.mark.parametrize("elem", PROJECT_ELEMS)
+def test_prompt_project_q_at_the_last_segment(mli, dev, elem):
+    """mli_prompt_project_q with 65535 segments of one position, the last count it takes (the gather's grid has a segment per
+    y; 65536 are refused: REFUSALS), over (16, 4096, 64), offsets in reversed order.  q of segments 0, 32767, 65534 and a fixed
+    sample of 64 against float64 x . Wq at the fp32 chain's own bound D 2^-24 sum |x w|; every q row finite;
+    "gemm_f32_rows64" / "gemm_bf16_widened" counts the product."""
+    from helpers import bf16_round
+    from min_llm_inference_amd import ops
+    B, S, D, n = 16, 4096, 64, 65535
+    pool, order, table = _x_pages(elem, dev)
+    i = np.arange(n, dtype=np.int64)
+    rows, first, offs = (i * 7) % B, (i * 2654435761) % S, n - 1 - i
+    w = ((np.random.default_rng(5502).random((D, D), dtype=np.float32) * 2 - 1) / np.sqrt(D)).astype(np.float32)
+    w = w if elem == "f32" else bf16_round(w)
+    wq = _t(w, dev).to(torch.float32 if elem == "f32" else torch.bfloat16)
+    arrays = [_t(a.astype(np.int32), dev) for a in (rows, first, np.ones(n, np.int64), offs)]
+    gathered = torch.empty(n * D, dtype=torch.float32, device=dev)
+    q = torch.full((n, D), lc.SENTINEL, device=dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    ops.reset_launch_counts()
+    rc = mli.mli_prompt_project_q(p(table), *map(p, arrays), p(wq), p(gathered), p(q), n, 1, n, B, S, D, lc.ELEM[elem],
+                                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0
+    family = "gemm_f32_rows64" if elem == "f32" else "gemm_bf16_widened"
+    assert ops.launch_count(family) == 1 and not any(_counts().values())
+    got = host(q)
+    assert np.isfinite(got).all() and (got != lc.SENTINEL).any(axis=1).all()
+    judged = lc.sample_rows(n, [0, 32767, 65534])
+    xs = _slots(pool, order, rows[judged], first[judged])[:, 0].astype(np.float64)
+    exact = xs @ w.astype(np.float64)
+    bound = D * 2.0 ** -24 * (np.abs(xs) @ np.abs(w).astype(np.float64))
+    worst = float((np.abs(got[offs[judged]].astype(np.float64) - exact) / bound).max())
+    print(f"PROJECT Q 65535 segments {elem}: worst error {worst:.3e} of the bound D 2^-24 sum |x w|")
+    assert worst <= 1.0
+
+
+def test_offsets_beyond_2_31_prompt_logits(oracle, mli, dev):
+    """mli_paged_prompt_logprobs with n_positions 16384 and n_vocab 131072 at emb_dim 64: the logits inside the scratch are 2^31
+    floats (8 GiB), so the rows of the last positions lie beyond 2^31 elements.  Four whole rows of (16, 4096, 64) are scored.
+    Judged: the last eight positions -- prompt_model.compare_given against the float64 forward of those positions over what
+    the pages hold (projection, causal softmax over the row, logits), at compare_given's own tolerance; the position at
+    n_sequence - 1 reports -inf.
+    "scan_prompt" counts the scan.  Skips when less than twice the scratch is free."""
+    from min_llm_inference_amd import ops
+    B, S, D, V = 16, 4096, 64, 131072
+    need = int(mli.mli_prompt_logprobs_scratch_bytes(4 * S, D, V))
+    assert need > 8 << 30
+    _WS.clear()
+    torch.cuda.empty_cache()
+    _needs(dev, need, "the scratch of 16384 positions x 131072 tokens")
+    pool, order, table = _x_pages("f32", dev)
+    rng = np.random.default_rng(5600)
+    emb = _t((rng.standard_normal((V, D)) * 0.5).astype(np.float32), dev)
+    inp = rng.integers(0, V, size=(B, S)).astype(np.int32)
+    wq = _t((rng.standard_normal((D, D)) * (2.0 / np.sqrt(D))).astype(np.float32), dev)
+    segs = [(3, 0, S), (9, 0, S), (0, 0, S), (15, 0, S)]
+    ops.reset_launch_counts()
+    got = host(ops.paged_prompt_logprobs(table, _t(inp, dev), wq, emb, segs, B, S, lc.ELEM["f32"])[0]).copy()
+    assert ops.launch_count("scan_prompt") == 1 and ops.launch_count("scan_prompt_softcap") == 0
+    ends = np.arange(len(got)) % S == S - 1                 # the position at n_sequence - 1 of every row has no next token
+    assert not np.isnan(got).any() and (got[~ends] > -np.inf).all() and (got[ends] == -np.inf).all()
+    # the float64 forward of the last eight positions of row 15, from what the pages hold: q = x . Wq, the causal softmax over
+    # the row's first t + 1 tokens, attention . emb^T -- nothing of it is a kernel's output
+    slots = _slots(pool, order, np.full(S, 15), np.arange(S)).astype(np.float64)          # [S, 3, D]: x, K, V
+    x64, K64, V64 = slots[:, 0], slots[:, 1], slots[:, 2]
+    w64, e64 = host(wq).astype(np.float64), host(emb).astype(np.float64)
+    logits = np.zeros((8, V))
+    for i, t in enumerate(range(S - 8, S)):
+        score = K64[:t + 1] @ (x64[t] @ w64) / np.sqrt(D)
+        prob = np.exp(score - score.max())
+        logits[i] = ((prob / prob.sum()) @ V64[:t + 1]) @ e64.T
+    given = np.asarray([inp[15, t + 1] if t + 1 < S else -1 for t in range(S - 8, S)], np.int64)
+    zero = np.zeros((8, 0))
+    err, tol, bad = pm.compare_given((got[-8:], zero, zero), logits.astype(np.float32), given, 0)
+    print(f"PROMPT LOGITS beyond 2^31: worst error {err:.3e}, bound {tol:.3e}")
+    assert not bad and err <= tol, (err, tol, bad)
+    torch.cuda.empty_cache()
+
+
+def test_rope_at_the_smallest_head_size(oracle, mli, dev):
+    """head size 2 (emb_dim 64, 32 heads: one pair per head), the near side of rope_half's rule; 17 and 33 are refused
+    (REFUSALS).  tests/test_rope_gemm_gpu.py's whole check of the decode projection; "gemm_f32_rope" counts the launch."""
+    from test_rope_gemm_gpu import R64, _check, _latest_case
+    _check(oracle, mli, dev, "limits: head size 2", _latest_case(5700, "f32", 70, 64, 64), "latest", 32, R64, ())
+
+
 # ---- refusals ----------------------------------------------------------------------------------------------------------------
 def test_refusals_launch_nothing(mli, dev):
     """Every refusal of the table on the device: MLI_ERR_BAD_ARG, no launch counted, the workspace's counters untouched.  (The
@@ -934,4 +1201,5 @@ def test_refusals_launch_nothing(mli, dev):
     finally:
         _tune(mli, **DEFAULTS)
     assert not any(_counts().values()), _counts()
+    assert not any(ops.launch_count(f) for f in OTHER_FAMILIES), {f: ops.launch_count(f) for f in OTHER_FAMILIES}
     assert not host(ws).any()
