@@ -238,6 +238,23 @@ int mli_engine_set_rope_table(mli_engine* engine, const float* table_host, size_
  * anywhere. */
 int mli_engine_set_softcap(mli_engine* engine, float cap);
 
+/* EXTENSION: learned attention-sink logits (mli_kernels.h: mli_paged_attention_lean_sink_logits has the formula and the
+ * anchors).  Every decode scan of the engine -- and, with mli_engine_set_prompt_logprobs, every prompt scan -- counts
+ * logits_host[h] as one more logit of query head h's softmax without a value row: the engine scores its prompts under the model
+ * it decodes with.  n must equal the engine's current n_heads (set the heads first; two at least); every value finite or -inf
+ * (-inf: no sink for that head; all -inf gives the tokens and log-probabilities of the engine without the call, bit for bit).
+ * logits_host null turns the switch off again.  The engine keeps a device copy at a fixed address, so step graphs replay it.
+ * Pages, pool, projection, prefill and the decoder head never see the logits.  Before the first step or run;
+ * MLI_ENGINE_PAGED, MLI_ENGINE_PAGED_GEMM or MLI_ENGINE_PAGED_BF16 with lean layers.  Composes with mli_engine_set_kv_heads,
+ * _set_window, _set_sinks (sink TOKENS, another switch), _set_page_release, _set_rope[_table], _set_logprobs,
+ * _set_prompt_logprobs, sampling, both loops, n_forward_rounds, step graphs and preemption; every setter validates the
+ * combination, whichever comes last.  -1 with a message naming the reason for a null or started engine, MLI_ENGINE_CONTIGUOUS
+ * and MLI_ENGINE_PAGED_FP8, n_heads < 2 (mli_engine_set_heads to another count afterwards is refused likewise), n != n_heads,
+ * NaN or +inf, lean_layers = 0 (mli_engine_configure(e, 0, ...) afterwards is refused likewise), and an engine with ALiBi or
+ * with a soft cap (mli_engine_set_alibi and mli_engine_set_softcap afterwards are refused likewise: no model defines the
+ * combination).  Without the call nothing changes anywhere. */
+int mli_engine_set_sink_logits(mli_engine* engine, const float* logits_host, int n);
+
 /* EXTENSION: sliding-window attention (mli_kernels.h: mli_paged_attention_lean_window).  Every row attends its newest
  * `window` tokens only.  The window changes which slots the scan reads and nothing else: admission, page growth,
  * preemption, re-prefill, n_forward_rounds (the window follows the device-side length), step graphs, sampling and the

@@ -429,6 +429,40 @@ int mli_paged_attention_lean_softcap(void* const* page_table, const int* lengths
                                      int n_sink, float cap, const float* rope_table, int elem, void* workspace,
                                      size_t workspace_bytes, void* stream);
 
+/* EXTENSION: LEARNED ATTENTION-SINK LOGITS for the multi-head scan (the per-head `sinks` parameter of the gpt-oss attention
+ * block; z = 0 for every head is the "off-by-one" / "quiet" softmax).  sink_logits: n_heads fp32 values in DEVICE memory, each
+ * finite or -inf.  For row b with L = min(lengths[b], n_sequence) >= 1, query head h, g = n_heads / n_kv_heads, the attended set
+ * A of the call's form (plain, window, window + n_sink tokens), x[s] = (q_h . K_{h/g}[s]) / sqrtf(head_dim) and z = sink_logits[h]:
+ *     m     = max( max_{s in A} x[s], z )
+ *     out_h = sum_{s in A} exp(x[s] - m) V_{h/g}[s]  /  ( sum_{s in A} exp(x[s] - m) + exp(z - m) )
+ * z takes part in head h's softmax as one more logit WITHOUT a value row: its probability mass is dropped.  It is the QUERY
+ * head's logit (the heads of a K/V group have different ones), it is not scaled by 1 / sqrt(head_dim), no window masks it, and it
+ * counts ONCE per (row, head) however the row is split.  It is NOT n_sink, which keeps the first tokens of a row attended; the two
+ * are used together.  z = -inf: no sink.  Anchors: all logits -inf give the BITS of mli_decode_scan_paged_gqa; a logit of -1e30
+ * in head h gives that call's bits in head h's columns; a logit of +1e30 gives exactly 0.0f there on every non-empty row, without
+ * NaN or inf (the maximum takes the sink in before any exponential).  +inf and NaN are outside the contract (the values live in
+ * device memory; mli_engine_set_sink_logits refuses them).  L == 0 gives the zero row; dead slots, gap slots and gap pages are
+ * never read, as in the _gqa call.
+ * One scan launch ("scan_heads_sink_logits"), the grid, item size, mli_tune keys and workspace
+ * (mli_attention_heads_workspace_bytes(n_batch, n_sequence, emb_dim, n_heads)) of the _gqa call.  Shapes: what that call takes
+ * with n_heads >= 2.  MLI_ERR_BAD_ARG, decided before anything is launched: n_heads == 1, fp8 pages, a bad head count, an
+ * unsupported shape, a negative n_sink, a null sink_logits or data pointer.  MLI_ERR_WORKSPACE as there.  Not combined with ALiBi
+ * or soft-capping (no model defines that): there is no slopes and no cap argument. */
+int mli_decode_scan_paged_sink_logits(const float* q_output, const void* const* page_table, const int* lengths,
+                                      float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                      int n_kv_heads, int window, int n_sink, const float* sink_logits, int elem, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+
+/* mli_paged_attention_lean_gqa with the sink logits: fill (n_new_items rows) -> latest -> the scan above.  rope_table: null, or
+ * the table of mli_paged_attention_lean_rope (then fill and latest are that call's: K and q rotated; gpt-oss uses both).  Fill
+ * and projection never see the logits.  MLI_ERR_BAD_ARG as above, for a null weight pointer and, with a table, as
+ * mli_paged_attention_lean_rope. */
+int mli_paged_attention_lean_sink_logits(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                         const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                         int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads,
+                                         int window, int n_sink, const float* sink_logits, const float* rope_table, int elem,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */
@@ -671,6 +705,23 @@ int mli_paged_prompt_logprobs_softcap(const void* const* page_table, const int* 
                                       int n_kv_heads, int window, int n_sink, float cap, int elem, int n_top, void* scratch,
                                       size_t scratch_bytes, void* stream);
 
+/* EXTENSION: mli_prompt_scan_paged and mli_paged_prompt_logprobs with learned sink logits (mli_decode_scan_paged_sink_logits has
+ * the formula): query t of a segment gets what the decode scan with the same logits gives a row of length t + 1, so a prompt is
+ * scored under the model that decodes.  One launch ("scan_prompt_sink_logits") with the SAME queries per workgroup as the plain
+ * variant: mli_prompt_scan_tq holds.  All logits -inf give the plain call's bits.  Scratch: mli_prompt_logprobs_scratch_bytes.
+ * MLI_ERR_BAD_ARG before any launch: n_heads == 1, a null sink_logits, and everything the plain call refuses (fp8 pages among
+ * it). */
+int mli_prompt_scan_paged_sink_logits(const float* q, const void* const* page_table, const int* seg_row, const int* seg_first,
+                                      const int* seg_count, const int* seg_offset, float* out, int n_seg, int max_count, int n_q,
+                                      int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads, int window,
+                                      int n_sink, const float* sink_logits, int elem, void* stream);
+int mli_paged_prompt_logprobs_sink_logits(const void* const* page_table, const int* inp, const void* wq, const float* emb_table,
+                                          const int* seg_row, const int* seg_first, const int* seg_count, const int* seg_offset,
+                                          float* token_logprob, int* top_ids, float* top_logprobs, int n_seg, int max_count,
+                                          int n_positions, int n_batch, int n_sequence, int emb_dim, int n_vocab, int n_heads,
+                                          int n_kv_heads, int window, int n_sink, const float* sink_logits, int elem, int n_top,
+                                          void* scratch, size_t scratch_bytes, void* stream);
+
 /* PREFILL of the newly inserted rows in ONE launch: the encoder as the fill GEMM's prologue.  The A
  * tile rows are computed on the fly as emb_table[inp[b, s]] + wpe[s] -- nothing is read back from the input-embedding
  * segment -- multiplied by [Wk | Wv], and the workgroups of the first column tile also write those rows to segment 0
@@ -846,6 +897,8 @@ int mli_tune(const char* key, int value);
  *   "scan_heads_alibi"       the multi-head scans with a position bias per head (mli_decode_scan_paged_alibi)
  *   "scan_heads_softcap"     the multi-head scans with logit soft-capping (mli_decode_scan_paged_softcap)
  *   "scan_prompt_softcap"    the prompt scan with logit soft-capping (mli_prompt_scan_paged_softcap)
+ *   "scan_heads_sink_logits" the multi-head scans with a learned sink logit per query head (mli_decode_scan_paged_sink_logits)
+ *   "scan_prompt_sink_logits" the prompt scan with a learned sink logit per query head (mli_prompt_scan_paged_sink_logits)
  * Forms, counted beside the launch's kernel family:
  *   "latest_compact"         a decode projection over the compacted list of non-empty rows ("latest_compact"; the panel and
  *                            the LDS-DMA kernel have no such list)

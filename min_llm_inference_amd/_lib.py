@@ -78,6 +78,8 @@ SIGNATURES = {
     "mli_alibi_slopes": [_I, _P],
     "mli_decode_scan_paged_softcap": [_P] * 4 + [_I] * 7 + [ctypes.c_float, _I, _P, _Z, _P],
     "mli_paged_attention_lean_softcap": [_P] * 8 + [_I] * 8 + [ctypes.c_float, _P, _I, _P, _Z, _P],
+    "mli_decode_scan_paged_sink_logits": [_P] * 4 + [_I] * 7 + [_P, _I, _P, _Z, _P],
+    "mli_paged_attention_lean_sink_logits": [_P] * 8 + [_I] * 8 + [_P, _P, _I, _P, _Z, _P],
     "mli_rope_table": [_I, _I, ctypes.c_double, _P],
     "mli_get_latest_k_q_v_paged_rope": [_P] * 6 + [_I] * 4 + [_P, _I, _P],
     "mli_fill_new_k_v_cache_paged_rope": [_P] * 5 + [_I] * 5 + [_P, _I, _P],
@@ -105,6 +107,8 @@ SIGNATURES = {
     "mli_paged_prompt_logprobs": [_P] * 11 + [_I] * 13 + [_P, _Z, _P],
     "mli_prompt_scan_paged_softcap": [_P] * 7 + [_I] * 10 + [ctypes.c_float, _I, _P],
     "mli_paged_prompt_logprobs_softcap": [_P] * 11 + [_I] * 11 + [ctypes.c_float, _I, _I, _P, _Z, _P],
+    "mli_prompt_scan_paged_sink_logits": [_P] * 7 + [_I] * 10 + [_P, _I, _P],
+    "mli_paged_prompt_logprobs_sink_logits": [_P] * 11 + [_I] * 11 + [_P, _I, _I, _P, _Z, _P],
     "mli_paged_prefill": [_P] * 8 + [_I] * 5 + [_P],
     "mli_paged_prefill_window": [_P] * 8 + [_I] * 7 + [_P],
     "mli_prefill": [_P] * 10 + [_I] * 5 + [_P],
@@ -172,6 +176,7 @@ ENGINE_SIGNATURES = {
     "mli_engine_set_kv_heads": [_P, _I],
     "mli_engine_set_alibi": [_P, _P, _I],
     "mli_engine_set_softcap": [_P, ctypes.c_float],
+    "mli_engine_set_sink_logits": [_P, _P, _I],
     "mli_engine_set_rope": [_P, ctypes.c_double],
     "mli_engine_set_rope_table": [_P, _P, _Z],
     "mli_engine_set_page_release": [_P, _I],

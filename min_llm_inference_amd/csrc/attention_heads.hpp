@@ -85,13 +85,32 @@ __global__ __launch_bounds__(kFuThreads, 2) void heads_softcap_scan_kernel(
                                                                                  smem_raw, window, n_sink, gq, nullptr, cap);
 }
 
+// EXTENSION (attention_sink_logits.hpp): the same kernel with the body's SINKLOGIT switch on and the sink logits (n_heads floats
+// in device memory) as one more argument, again under a name of its own.
+template <class E, int NJ, bool NT, bool WIN, bool SINK, bool GQA>
+__global__ __launch_bounds__(kFuThreads, 2) void heads_sink_logits_scan_kernel(
+    const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
+    float* __restrict__ out, float2* ml, float* partial, int S, int D, int lg, int H, int ct, int nchunk_max, int direct,
+    unsigned* arrivals, int window, int n_sink, int gq, const float* __restrict__ sink_logits) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const int c = blockIdx.y;
+    int b = (int)((blockIdx.x + (unsigned)c) % gridDim.x);
+    if (direct == 2) b = longest_first_row<WIN, SINK>(lengths, (int)gridDim.x, S, (int)blockIdx.x, window, n_sink);
+    constexpr int PD = (NJ == 2 && E::EPL == 8) ? 2 : 3;   // as heads_decode_scan_kernel
+    heads_scan_item<E, NJ, NT, NJ == 1 ? 8 : 4, PD, WIN, SINK, GQA, false, false, true>(
+        q, page_table, lengths, out, ml, partial, S, D, lg, H, ct, nchunk_max, direct, arrivals, b, c, c == 0, smem_raw, window,
+        n_sink, gq, nullptr, 0.f, sink_logits);
+}
+
 // Grid, item size, workspace and LDS: scan_plan.hpp, at the span the form leaves and the read width Dkv (D without GQA).
 // ALIBI (slopes: n_heads floats in device memory): heads_alibi_scan_kernel on the same plan, counted in a family of its own.
 // SOFTCAP (cap: a finite host value > 0): heads_softcap_scan_kernel likewise ("scan_heads_softcap").
-template <class E, bool WIN, bool SINK, bool GQA, bool ALIBI = false, bool SOFTCAP = false>
+// SINKLOGIT (sink_logits: n_heads floats in device memory): heads_sink_logits_scan_kernel likewise ("scan_heads_sink_logits").
+template <class E, bool WIN, bool SINK, bool GQA, bool ALIBI = false, bool SOFTCAP = false, bool SINKLOGIT = false>
 static int launch_heads_scan_t(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S,
                                int D, int H, int Hkv, int lg, int window, int n_sink, void* ws, size_t ws_bytes,
-                               hipStream_t st, const float* slopes = nullptr, float cap = 0.f) {
+                               hipStream_t st, const float* slopes = nullptr, float cap = 0.f,
+                               const float* sink_logits = nullptr) {
     const int nj = ceil_div_i(D / E::EPL, kWave);   // 1 or 2
     const int span = SINK ? sink_span(S, window, n_sink) : WIN ? window_span(S, window) : S;
     const ScanPlan p = plan_chunked_scan(scan_tune(), B, S, span, D, D / H * Hkv, H, E::kBytes);
@@ -100,9 +119,14 @@ static int launch_heads_scan_t(const float* q, const void* const* page_table, co
     // page pointers of the item | the waves' parked rows and statistics, later the row's (item, head) statistics
     const size_t smem = scan_lds_bytes(p.ct, heads_reduction_bytes(nj, E::EPL), heads_merge_stat_bytes(p.nchunk, H));
     if (!scan_lds_fits(smem)) return MLI_ERR_BAD_ARG;   // (kMaxMergeStats keeps every accepted shape far inside)
-    count_launch(SOFTCAP ? kLfScanHeadsSoftcap : ALIBI ? kLfScanHeadsAlibi : kLfScanHeadsWindow);
+    count_launch(SINKLOGIT ? kLfScanHeadsSinkLogits
+                 : SOFTCAP ? kLfScanHeadsSoftcap : ALIBI ? kLfScanHeadsAlibi : kLfScanHeadsWindow);
     dispatch_scan_variant<E>(ScanVariant{nj, false, 1}, p.nt, [&](auto NJ, auto, auto, auto NT) {
-        if constexpr (SOFTCAP)
+        if constexpr (SINKLOGIT)
+            hipLaunchKernelGGL((heads_sink_logits_scan_kernel<E, NJ(), NT(), WIN, SINK, GQA>), dim3(B, p.grid_y),
+                               dim3(kFuThreads), smem, st, q, page_table, lengths, out, w.ml, w.partial, S, D, lg, H, p.ct,
+                               p.nchunk, p.direct, w.arrivals, window, n_sink, H / Hkv, sink_logits);
+        else if constexpr (SOFTCAP)
             hipLaunchKernelGGL((heads_softcap_scan_kernel<E, NJ(), NT(), WIN, SINK, GQA>), dim3(B, p.grid_y), dim3(kFuThreads),
                                smem, st, q, page_table, lengths, out, w.ml, w.partial, S, D, lg, H, p.ct, p.nchunk, p.direct,
                                w.arrivals, window, n_sink, H / Hkv, cap);

@@ -27,12 +27,41 @@
 
 namespace mli {
 
+#define MLI_PROMPT_SINK_LOGITS 0
 #define MLI_PROMPT_SOFTCAP 0
 #include "prompt_scan_body.hpp"   // prompt_scan_kernel
 #undef MLI_PROMPT_SOFTCAP
 #define MLI_PROMPT_SOFTCAP 1
 #include "prompt_scan_body.hpp"   // prompt_softcap_scan_kernel (EXTENSION, attention_softcap.hpp)
 #undef MLI_PROMPT_SOFTCAP
+#undef MLI_PROMPT_SINK_LOGITS
+#define MLI_PROMPT_SOFTCAP 0
+#define MLI_PROMPT_SINK_LOGITS 1
+#include "prompt_scan_body.hpp"   // prompt_sink_logits_scan_kernel (EXTENSION, attention_sink_logits.hpp)
+#undef MLI_PROMPT_SINK_LOGITS
+#undef MLI_PROMPT_SOFTCAP
+
+// The launch with sink logits for an accepted shape with H > 1 (prompt_scan_shape_ok), sink_logits non-null: launch_prompt_scan's
+// grid with the same TQ (prompt_scan_tq), counted as "scan_prompt_sink_logits".
+template <class E>
+int launch_prompt_sink_logits_scan(const float* q, const void* const* page_table, const int* seg_row, const int* seg_first,
+                                   const int* seg_count, const int* seg_offset, float* out, int n_seg, int max_count, int n_q,
+                                   int B, int S, int D, int H, int Hkv, int lg, int window, int n_sink, const float* sink_logits,
+                                   hipStream_t st) {
+    const int nj = ceil_div_i(D / E::EPL, kWave);   // 1 or 2
+    const auto go = [&](auto NJ) {
+        constexpr int TQ = prompt_scan_tq(E::EPL, NJ(), true);
+        const int nb = ceil_div_i(max_count, TQ);
+        if (!prompt_scan_grid_ok(n_seg, max_count, TQ)) return (int)MLI_ERR_BAD_ARG;   // (the entry points refuse it first)
+        count_launch(kLfScanPromptSinkLogits);
+        hipLaunchKernelGGL((prompt_sink_logits_scan_kernel<E, NJ(), TQ>), dim3((unsigned)(n_seg * nb)), dim3(kFuThreads), 0, st,
+                           q, page_table, seg_row, seg_first, seg_count, seg_offset, out, nb, n_q, B, S, D, lg, H / Hkv, window,
+                           n_sink, sink_logits);
+        return launch_status();
+    };
+    using std::integral_constant;
+    return nj == 1 ? go(integral_constant<int, 1>{}) : go(integral_constant<int, 2>{});
+}
 
 // The capped launch for an accepted shape with H > 1 (prompt_scan_shape_ok), cap > 0 finite: launch_prompt_scan's grid with
 // the same TQ (prompt_scan_tq: the capped kernels compile without scratch at it), counted as "scan_prompt_softcap".

@@ -80,6 +80,10 @@ int launch_heads_alibi_scan(const float*, const void* const*, const int*, float*
 template <class E>
 int launch_heads_softcap_scan(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, ScanKind, int,
                               int, float, void*, size_t, hipStream_t);
+// ... and with a learned sink logit per query head (attention_sink_logits.hpp: ..., n_sink, sink_logits)
+template <class E>
+int launch_heads_sink_logits_scan(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, ScanKind,
+                                  int, int, const float*, void*, size_t, hipStream_t);
 
 // EXTENSION, rotary position embeddings (proj_gemm.hip): the projection and the fills with K and q rotated in the epilogue
 int rope_half(int D, int n_heads, const float* table);
@@ -220,7 +224,32 @@ static int launch_softcap_scan(int kind, const float* q, const void* const* page
     };
     return elem == MLI_ELEM_BF16 ? go(ElemBF16{}) : go(ElemF32{});
 }
+// _sink_logits: the _gqa front with two heads at least (the single-head scans have no sink logit), the logits given and no null
+// data pointer
+static int sink_logits_front(int B, int S, int D, int n_heads, int n_kv_heads, int window, int n_sink, const float* sink_logits,
+                             const void* q, const void* page_table, const void* lengths, const void* out, int elem) {
+    if (n_heads < 2 || sink_logits == nullptr) return MLI_ERR_BAD_ARG;
+    if (!gqa_shape_supported(B, S, D, n_heads, n_kv_heads, elem)) return MLI_ERR_BAD_ARG;   // (holds n_kv_heads and fp8 too)
+    if (q == nullptr || page_table == nullptr || lengths == nullptr || out == nullptr) return MLI_ERR_BAD_ARG;
+    return gqa_front(B, S, D, n_heads, n_kv_heads, window, n_sink, elem);
+}
+
+// the scan behind the _sink_logits entry points, after sink_logits_front (kind = its answer)
+static int launch_sink_logits_scan(int kind, const float* q, const void* const* page_table, const int* lengths, float* out, int B,
+                                   int S, int D, int n_heads, int n_kv_heads, int window, int n_sink, const float* sink_logits,
+                                   int elem, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const WsBody body = ws_body(workspace, workspace_bytes);
+    const int lg = heads_lanes_log2(B, S, D, n_heads, elem);
+    const auto go = [&](auto e) {
+        return launch_heads_sink_logits_scan<decltype(e)>(q, page_table, lengths, out, B, S, D, n_heads, n_kv_heads, lg,
+                                                          (ScanKind)kind, window, n_sink, sink_logits, body.ptr, body.bytes, st);
+    };
+    return elem == MLI_ELEM_BF16 ? go(ElemBF16{}) : go(ElemF32{});
+}
 // ---- prompt log-probabilities (attention_prompt.hpp) ----------------------------------------------------------------------------
+int launch_prompt_sink_logits_scan_elem(const float*, const void* const*, const int*, const int*, const int*, const int*, float*,
+                                        int, int, int, int, int, int, int, int, int, int, const float*, int,
+                                        hipStream_t);   // attention_prompt.hip
 int launch_prompt_project_q(int, const void* const*, const int*, const int*, const int*, const int*, const void*, void*, float*,
                             int, int, int, int, int, int, hipStream_t);   // proj_gemm.hip
 int launch_prompt_scan_elem(const float*, const void* const*, const int*, const int*, const int*, const int*, float*, int, int,
@@ -289,8 +318,9 @@ static int prompt_logprobs(const void* const* page_table, const int* inp, const 
                               float* token_logprob, int* top_ids, float* top_logprobs, int n_seg, int max_count,
                               int n_positions, int n_batch, int n_sequence, int emb_dim, int n_vocab, int n_heads,
                               int n_kv_heads, int window, int n_sink, int elem, int n_top, void* scratch, size_t scratch_bytes,
-                              void* stream, bool capped, float cap) {
+                              void* stream, bool capped, float cap, bool sunk = false, const float* sink_logits = nullptr) {
     if (capped && (n_heads < 2 || !(cap > 0.f) || !std::isfinite(cap))) return MLI_ERR_BAD_ARG;
+    if (sunk && (n_heads < 2 || sink_logits == nullptr)) return MLI_ERR_BAD_ARG;
     if (n_top < 0 || n_top > MLI_MAX_TOP_LOGPROBS || token_logprob == nullptr ||
         (n_top > 0 && (top_ids == nullptr || top_logprobs == nullptr)))
         return MLI_ERR_BAD_ARG;
@@ -317,7 +347,11 @@ static int prompt_logprobs(const void* const* page_table, const int* inp, const 
     int rc = mli::launch_prompt_project_q(elem, page_table, seg_row, seg_first, seg_count, seg_offset, wq, base + p.gathered, q,
                                           n_seg, max_count, n_positions, n_batch, n_sequence, emb_dim, st);
     if (rc) return rc;
-    if (capped)
+    if (sunk)
+        rc = mli::launch_prompt_sink_logits_scan_elem(q, page_table, seg_row, seg_first, seg_count, seg_offset, attn, n_seg,
+                                                      max_count, n_positions, n_batch, n_sequence, emb_dim, n_heads, n_kv_heads,
+                                                      window, n_sink, sink_logits, elem, st);
+    else if (capped)
         rc = mli::launch_prompt_softcap_scan_elem(q, page_table, seg_row, seg_first, seg_count, seg_offset, attn, n_seg, max_count,
                                                   n_positions, n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink,
                                                   cap, elem, st);
@@ -359,6 +393,17 @@ int mli_paged_prompt_logprobs_softcap(const void* const* page_table, const int* 
     return prompt_logprobs(page_table, inp, wq, emb_table, seg_row, seg_first, seg_count, seg_offset, token_logprob, top_ids,
                            top_logprobs, n_seg, max_count, n_positions, n_batch, n_sequence, emb_dim, n_vocab, n_heads, n_kv_heads,
                            window, n_sink, elem, n_top, scratch, scratch_bytes, stream, true, cap);
+}
+
+int mli_paged_prompt_logprobs_sink_logits(const void* const* page_table, const int* inp, const void* wq, const float* emb_table,
+                                          const int* seg_row, const int* seg_first, const int* seg_count, const int* seg_offset,
+                                          float* token_logprob, int* top_ids, float* top_logprobs, int n_seg, int max_count,
+                                          int n_positions, int n_batch, int n_sequence, int emb_dim, int n_vocab, int n_heads,
+                                          int n_kv_heads, int window, int n_sink, const float* sink_logits, int elem, int n_top,
+                                          void* scratch, size_t scratch_bytes, void* stream) {
+    return prompt_logprobs(page_table, inp, wq, emb_table, seg_row, seg_first, seg_count, seg_offset, token_logprob, top_ids,
+                           top_logprobs, n_seg, max_count, n_positions, n_batch, n_sequence, emb_dim, n_vocab, n_heads, n_kv_heads,
+                           window, n_sink, elem, n_top, scratch, scratch_bytes, stream, false, 0.f, true, sink_logits);
 }
 
 int mli_abi_version(void) { return 4; }
@@ -615,6 +660,47 @@ int mli_paged_attention_lean_softcap(void* const* page_table, const int* lengths
     return mli::launch_softcap_scan(kind, q_output, reinterpret_cast<const void* const*>(page_table), lengths, attention_result,
                                     n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, cap, elem, workspace,
                                     workspace_bytes, st);
+}
+
+// ---- EXTENSION: learned attention-sink logits (attention_sink_logits.hpp) ------------------------------------------------------
+int mli_decode_scan_paged_sink_logits(const float* q_output, const void* const* page_table, const int* lengths,
+                                      float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                      int n_kv_heads, int window, int n_sink, const float* sink_logits, int elem, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    const int kind = mli::sink_logits_front(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, sink_logits,
+                                            q_output, page_table, lengths, attention_result, elem);
+    if (kind < 0) return MLI_ERR_BAD_ARG;
+    return mli::launch_sink_logits_scan(kind, q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim,
+                                        n_heads, n_kv_heads, window, n_sink, sink_logits, elem, workspace, workspace_bytes,
+                                        mli::as_stream(stream));
+}
+
+// fill -> latest (both rotated where a table is given) -> the scan with sink logits.  Fill and projection never see them.
+int mli_paged_attention_lean_sink_logits(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                         const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                         int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads,
+                                         int window, int n_sink, const float* sink_logits, const float* rope_table, int elem,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    const int kind = mli::sink_logits_front(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink, sink_logits,
+                                            q_output, page_table, lengths, attention_result, elem);
+    if (kind < 0 || wk == nullptr || wq == nullptr || wv == nullptr) return MLI_ERR_BAD_ARG;
+    if (rope_table != nullptr && mli::rope_half(emb_dim, n_heads, rope_table) < 0) return MLI_ERR_BAD_ARG;
+    hipStream_t st = mli::as_stream(stream);
+    int rc;
+    if (rope_table != nullptr) {
+        rc = mli::launch_fill_paged_rope(elem, nullptr, nullptr, nullptr, page_table, new_batch_idx, lengths, wk, wv, n_batch,
+                                         n_sequence, emb_dim, n_new_items, false, 0, 0, n_heads, rope_table, st);
+        if (!rc)
+            rc = mli::launch_latest_paged_rope(elem, page_table, lengths, wk, wq, wv, q_output, n_batch, n_sequence, emb_dim,
+                                               n_heads, rope_table, st);
+    } else {
+        rc = mli::launch_fill_and_latest(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, n_batch, n_sequence,
+                                         emb_dim, n_new_items, st);
+    }
+    if (rc) return rc;
+    return mli::launch_sink_logits_scan(kind, q_output, reinterpret_cast<const void* const*>(page_table), lengths,
+                                        attention_result, n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink,
+                                        sink_logits, elem, workspace, workspace_bytes, st);
 }
 
 int mli_get_latest_k_q_v_paged_lean(void* const* page_table, const int* lengths, const void* wk, const void* wq,

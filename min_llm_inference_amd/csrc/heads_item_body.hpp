@@ -91,15 +91,23 @@ __device__ __forceinline__ void heads_xor_step(float (&v)[NJ][16]) {
 // SOFTCAP = true (EXTENSION, attention_softcap.hpp; never with ALIBI): logit soft-capping, the scaled score x becomes
 // cap * tanh(x / cap) (softcap_score) at the same place, between div_by and the page maximum; cap is a kernel argument.  A
 // pure function of the score: masks, (m, l) frames and merges do not change, and a masked slot stays masked.
+// SINKLOGIT = true (EXTENSION, attention_sink_logits.hpp; never with ALIBI or SOFTCAP): a learned attention-sink logit per QUERY
+// head, sink_logits[h] (n_heads floats in device memory, each finite or -inf).  It takes part in head h's softmax as one more
+// logit without a value row: m = max(m, z) and l += exp(z - m), exactly once per (row, head).  So it enters only where a row's
+// FINAL (m, l) of a head is formed -- the wave merge of a row with one workgroup (direct), or the last arriver's merge over the
+// items -- and never what an item publishes.  The maximum takes the sink in BEFORE any exp of a difference (a logit far above
+// every score gives zeros, not inf / NaN); z = -inf leaves m and l as they were, bit for bit (fmaxf(m, -inf) = m, l + 0 = l).
+// The page loop, the prefetch, the plan, the workspace, the LDS size and the arrival counters do not change.
 template <class E, int NJ, bool NT, int TBR, int PD, bool WIN = false, bool SINK = false, bool GQA = false, bool ALIBI = false,
-          bool SOFTCAP = false>
+          bool SOFTCAP = false, bool SINKLOGIT = false>
 __device__ __forceinline__ void heads_scan_item(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ out, float2* ml, float* partial, int S, int D, int lg, int H, int ct, int nchunk_max, int direct,
     unsigned* arrivals, int b, int c, bool first_grid_row, unsigned char* smem_raw, int window = 0, int n_sink = 0,
-    int gq = 1, const float* __restrict__ slopes = nullptr, float cap = 0.f) {
+    int gq = 1, const float* __restrict__ slopes = nullptr, float cap = 0.f, const float* __restrict__ sink_logits = nullptr) {
     static_assert(!SINK || WIN, "sinks exist beside a window only");
     static_assert(!(ALIBI && SOFTCAP), "the order of bias and cap would be an invention");
+    static_assert(!(SINKLOGIT && (ALIBI || SOFTCAP)), "no model defines a sink logit beside a position bias or a cap");
     constexpr int EPL = E::EPL;
     constexpr int kRowF = NJ * kWave * EPL;   // floats one wave parks
     constexpr int kRowU = NJ * kWave;         // lane units of a row
@@ -332,6 +340,15 @@ __device__ __forceinline__ void heads_scan_item(
         float m = -INFINITY;
 #pragma unroll
         for (int w = 0; w < kFuWaves; ++w) m = fmaxf(m, wave_ml[w * kRowU + u].x);
+        // SINKLOGIT, a row of one workgroup: this IS the row's final (m, l).  The four elements of a thread share a head, so
+        // they share z; the sink joins the maximum before the waves' weights are formed.  (An item that publishes keeps -inf.)
+        float zsink = -INFINITY;
+        if constexpr (SINKLOGIT) {
+            if (direct) {
+                zsink = sink_logits[i >> hd_shift];
+                m = fmaxf(m, zsink);
+            }
+        }
         float wsc[kFuWaves];
         float l = 0.f;
 #pragma unroll
@@ -339,6 +356,9 @@ __device__ __forceinline__ void heads_scan_item(
             const float2 s = wave_ml[w * kRowU + u];
             wsc[w] = s.x == -INFINITY ? 0.f : expf(s.x - m);
             l += s.y * wsc[w];
+        }
+        if constexpr (SINKLOGIT) {
+            if (direct) l += expf(zsink - m);   // the sink's share of the denominator; it has no value row
         }
         const float norm = direct ? 1.f / l : 1.f;
         float r[4];
@@ -383,8 +403,15 @@ __device__ __forceinline__ void heads_scan_item(
         const int h = d >> hd_shift;
         float mm = -INFINITY;
         for (int i = 0; i < nc; ++i) mm = fmaxf(mm, ml_sh[i * H + h].x);
+        // SINKLOGIT: the row's final (m, l) over its items -- the sink joins the maximum first, then the sum, once
+        float zsink = -INFINITY;
+        if constexpr (SINKLOGIT) {
+            zsink = sink_logits[h];
+            mm = fmaxf(mm, zsink);
+        }
         float ll = 0.f;
         for (int i = 0; i < nc; ++i) ll = fmaf(ml_sh[i * H + h].y, expf(ml_sh[i * H + h].x - mm), ll);
+        if constexpr (SINKLOGIT) ll += expf(zsink - mm);
         const float inv_l = 1.f / ll;
         float r[4] = {0.f, 0.f, 0.f, 0.f};
         for (int i0 = 0; i0 < nc; i0 += 8) {   // up to 8 partial rows in flight

@@ -36,6 +36,8 @@ enum LaunchFamily {
     kLfGemmBf16Rope,      // proj_gemm_bf16.hip: a tiled bf16-MFMA form with rotary position embeddings (beside that form's family)
     kLfScanHeadsSoftcap,  // attention_softcap.hpp: the multi-head scans with logit soft-capping
     kLfScanPromptSoftcap, // attention_prompt.hpp: the prompt scan with logit soft-capping
+    kLfScanHeadsSinkLogits,   // attention_sink_logits.hpp: the multi-head scans with a learned sink logit per query head
+    kLfScanPromptSinkLogits,  // attention_prompt.hpp: the prompt scan with a learned sink logit per query head
     kLaunchFamilies
 };
 
@@ -45,7 +47,7 @@ constexpr const char* kLaunchFamilyNames[kLaunchFamilies] = {
     "latest_compact",  "fill_flat",         "fill_per_row",          "prefill_fused",     "prefill_two_launch",
     "scan_equal_shares", "scan_chunked",    "scan_rows_ordered",     "scan_rows_grid_order", "scan_heads_window",
     "scan_prompt",     "scan_heads_alibi",  "gemm_f32_rope",         "gemm_bf16_rope",    "scan_heads_softcap",
-    "scan_prompt_softcap",
+    "scan_prompt_softcap", "scan_heads_sink_logits", "scan_prompt_sink_logits",
 };
 
 inline thread_local uint64_t g_launch_counts[kLaunchFamilies] = {};

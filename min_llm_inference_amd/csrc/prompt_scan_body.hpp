@@ -1,15 +1,27 @@
-// The kernel of the causal multi-query prompt scan (attention_prompt.hpp has the account), included twice by that file:
+// The kernel of the causal multi-query prompt scan (attention_prompt.hpp has the account), included three times by that file:
 //   MLI_PROMPT_SOFTCAP 0   prompt_scan_kernel<E, NJ, TQ, HEADS>, the text the kernel has always had;
 //   MLI_PROMPT_SOFTCAP 1   prompt_softcap_scan_kernel<E, NJ, TQ> (EXTENSION, attention_softcap.hpp; several heads only): logit
 //                          soft-capping, every scaled score x becomes cap * tanh(x / cap) (softcap_score, heads_item_body.hpp)
 //                          between div_by and the page maximum, as in the decode scan -- query t of a segment gets what the
 //                          capped decode scan gives a row of length t + 1.  One more argument: float cap.
-// Two kernels of one text, so that the kernel with the switch has a name of its own and the kernels without it keep their
+//   MLI_PROMPT_SINK_LOGITS 1   (with MLI_PROMPT_SOFTCAP 0) prompt_sink_logits_scan_kernel<E, NJ, TQ> (EXTENSION,
+//                          attention_sink_logits.hpp; several heads only): a learned sink logit per query head joins the maximum
+//                          and the denominator where a query's final (m, l) is formed -- the wave merge, in front of the norm.
+//                          One more argument: const float* sink_logits (n_heads floats in device memory).
+// Three kernels of one text, so that the kernel with the switch has a name of its own and the kernels without it keep their
 // symbols and their device code (a body shared through a device function moves their early exits and with them the registers).
 // No include guard.
 
 // lg: log2 lanes per head (HEADS), gq = n_heads / n_kv_heads (HEADS; 1 = no grouping); window 0 = none (then n_sink 0)
-#if MLI_PROMPT_SOFTCAP
+#if MLI_PROMPT_SINK_LOGITS
+template <class E, int NJ, int TQ>
+__global__ __launch_bounds__(kFuThreads) void prompt_sink_logits_scan_kernel(
+    const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ seg_row,
+    const int* __restrict__ seg_first, const int* __restrict__ seg_count, const int* __restrict__ seg_offset,
+    float* __restrict__ out, int n_blocks_per_seg, int n_q, int B, int S, int D, int lg, int gq, int window, int n_sink,
+    const float* __restrict__ sink_logits) {
+    constexpr bool HEADS = true;
+#elif MLI_PROMPT_SOFTCAP
 template <class E, int NJ, int TQ>
 __global__ __launch_bounds__(kFuThreads) void prompt_softcap_scan_kernel(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ seg_row,
@@ -277,6 +289,12 @@ __global__ __launch_bounds__(kFuThreads) void prompt_scan_kernel(
                 float m = -INFINITY;
 #pragma unroll
                 for (int w = 0; w < kFuWaves; ++w) m = fmaxf(m, wave_ml[w * kRowU + u].x);
+#if MLI_PROMPT_SINK_LOGITS
+                // the query's final (m, l): the four elements of a thread share a head, hence z; the sink joins the maximum
+                // before the waves' weights are formed
+                const float zsink = sink_logits[i >> (lg + (EPL == 8 ? 3 : 2))];
+                m = fmaxf(m, zsink);
+#endif
                 float wsc[kFuWaves];
                 float l = 0.f;
 #pragma unroll
@@ -285,6 +303,9 @@ __global__ __launch_bounds__(kFuThreads) void prompt_scan_kernel(
                     wsc[w] = s.x == -INFINITY ? 0.f : expf(s.x - m);
                     l += s.y * wsc[w];
                 }
+#if MLI_PROMPT_SINK_LOGITS
+                l += expf(zsink - m);   // the sink's share of the denominator; it has no value row
+#endif
                 const float norm = 1.f / l;
                 float r[4];
 #pragma unroll

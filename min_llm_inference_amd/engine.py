@@ -40,7 +40,7 @@ class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
                  n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None,
                  release_pages=False, n_kv_heads=None, logprobs=None, prompt_logprobs=False, alibi=None,
-                 rope=None, softcap=None):
+                 rope=None, softcap=None, sink_logits=None):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -68,6 +68,8 @@ class Engine:
             self.set_rope(10000.0 if rope is True else rope)
         if softcap is not None:
             self.set_softcap(softcap)
+        if sink_logits is not None:
+            self.set_sink_logits(sink_logits)
 
     def _check(self, rc):
         if rc != 0:
@@ -98,6 +100,17 @@ class Engine:
         prompt log-probabilities -- replaces a scaled score x by cap * tanh(x / cap).  cap: finite and > 0; 0 turns it off.
         Before the first step or run, fp32 / bf16 paged kinds with n_heads >= 2 and lean layers, not with ALiBi."""
         self._check(self._lib.mli_engine_set_softcap(self._h, float(cap)))
+
+    def set_sink_logits(self, values):
+        """Learned attention-sink logits (mli_engine_set_sink_logits): values[h] takes part in query head h's softmax as one
+        more logit without a value row, in every decode scan and in the prompt scan of an engine with prompt log-probabilities.
+        values: n_heads floats, each finite or -inf (-inf: no sink for that head); None turns the switch off.  Before the
+        first step or run, fp32 / bf16 paged kinds with n_heads >= 2 and lean layers, not with ALiBi or a soft cap."""
+        if values is None:
+            self._check(self._lib.mli_engine_set_sink_logits(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        self._check(self._lib.mli_engine_set_sink_logits(self._h, a.ctypes.data_as(ctypes.c_void_p), int(a.size)))
 
     def set_rope(self, rope=10000.0):
         """Rotary position embeddings (mli_engine_set_rope / mli_engine_set_rope_table): prefill and projection rotate K and q

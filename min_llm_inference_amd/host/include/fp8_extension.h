@@ -24,6 +24,7 @@ private:  // the fp8 scan has one head: of the option setters the layer has set_
     using PagedAttentionOptionSetters::set_n_kv_heads;
     using PagedAttentionOptionSetters::set_alibi_slopes;
     using PagedAttentionOptionSetters::set_softcap;
+    using PagedAttentionOptionSetters::set_sink_logits;
 };
 
 class PagedAttentionFp8InferenceModel : public PagedInferenceModel {
@@ -38,6 +39,7 @@ private:
     using PagedAttentionOptionSetters::set_n_kv_heads;
     using PagedAttentionOptionSetters::set_alibi_slopes;
     using PagedAttentionOptionSetters::set_softcap;
+    using PagedAttentionOptionSetters::set_sink_logits;
     DecoderHead& decoder_head() override { return decoder_head_; }
     PagedAttentionFp8Layer attention_layer_;
     // lean only: the scratch of mli_decoder_scratch_bytes, and the logits buffer once sampling is set

@@ -63,11 +63,15 @@ struct PagedAttentionOptions {
     // Logit soft-capping: every scaled attention score x becomes softcap * tanh(x / softcap), in the decode scan and in the
     // prompt scan (0: none) -- mli_paged_attention_lean_softcap, mli_paged_prompt_logprobs_softcap
     float softcap = 0.f;
+    // Learned attention-sink logits: one per query head ([n_heads], device memory at a fixed address, owned here; null: none),
+    // one more logit of the head's softmax without a value row, in the decode scan and in the prompt scan --
+    // mli_paged_attention_lean_sink_logits, mli_paged_prompt_logprobs_sink_logits
+    std::shared_ptr<TensorFloat> sink_logits;
 };
 
 // The setters of the option set, defined once for every class that has them: a layer owns the struct, a model hands out
 // its layer's.  A class whose scan has one head only (fp8 pages) takes set_n_heads / set_n_kv_heads / set_alibi_slopes /
-// set_softcap out of its interface.
+// set_softcap / set_sink_logits out of its interface.
 class PagedAttentionOptionSetters {
 public:
     // EXTENSION: ALiBi -- slopes[h] * (s - (L - 1)) added to query head h's scaled scores; n_heads finite values, uploaded
@@ -86,6 +90,13 @@ public:
     // scan; 0 takes the cap away again.  A negative or non-finite cap throws here; two heads at least, the lean layers and no
     // slopes beside it are held at every forward, whichever setter came last (PagedAttentionLayerCore::check_softcap).
     void set_softcap(float cap);
+    // EXTENSION: learned attention-sink logits -- host[h] joins query head h's softmax as one more logit without a value row
+    // (maximum and denominator, once per row and head), in the decode scan and in the prompt scan.  n values, each finite or
+    // -inf (-inf: no sink for that head), uploaded to a device copy the option set owns: its address stays fixed, so a captured
+    // step graph replays it.  host null or n == 0 takes the switch away again.  NaN or +inf throws here; the count is held to
+    // n_heads (>= 2), the lean layers and neither slopes nor a cap beside it at every forward, whichever setter came last
+    // (PagedAttentionLayerCore::check_sink_logits).
+    void set_sink_logits(const float* host, int n);
     void set_n_heads(int n_heads) { options().n_heads = n_heads; }
     void set_n_kv_heads(int n_kv_heads) { options().n_kv_heads = n_kv_heads; }
     void set_window(int window) { options().window = window; }
@@ -129,6 +140,10 @@ protected:
     // throws where a cap is set beside n_heads < 2, the lean layers off (the materialising composition has no cap and must
     // never drop it silently) or ALiBi slopes (no order of bias and cap is defined): first thing in every forward
     void check_softcap() const;
+    // throws where sink logits are set and are not one per head of n_heads >= 2 heads, the lean layers are off (the
+    // materialising composition has no sink logit and must never drop it silently), or ALiBi slopes or a cap stand beside them
+    // (no model defines that): first thing in every forward
+    void check_sink_logits() const;
 
     int elem_;
     Weights wk_, wq_, wv_;

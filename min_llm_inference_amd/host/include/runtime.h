@@ -50,13 +50,15 @@ bool lean_layers();
 // n_heads floats in device memory; null: none): mli_paged_attention_lean_alibi, whatever the other options are.  rope_table
 // (EXTENSION, [n_sequence][head_dim / 2] (cos, sin) in device memory; null: none): mli_paged_attention_lean_rope, whatever the
 // other options are, slopes included; every failure throws.  softcap (EXTENSION, logit soft-capping; 0: none):
-// mli_paged_attention_lean_softcap, with or without a rotary table; slopes beside it throw.
+// mli_paged_attention_lean_softcap, with or without a rotary table; slopes beside it throw.  sink_logits (EXTENSION, n_heads
+// floats in device memory; null: none): mli_paged_attention_lean_sink_logits, with or without a rotary table; slopes or a cap
+// beside them throw.
 bool lean_paged_wanted(int n_heads, int window, int n_sequence);
 int lean_paged_attention(int elem, int n_heads, int window, int n_sink, void* const* page_table, const int* lengths,
                          const void* wk, const void* wq, const void* wv, const int* new_batch_idx, float* q_output,
                          float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_new_items,
                          int n_kv_heads = 0, const float* alibi_slopes = nullptr, const float* rope_table = nullptr,
-                         float softcap = 0.f);
+                         float softcap = 0.f, const float* sink_logits = nullptr);
 
 // Which loop start_paged_attention_*_inference_engine runs (default false): the pipelined loop
 // (pipelined_engine.h: the host one step behind the GPU, same tokens per item) wherever it applies -- up to

@@ -73,6 +73,7 @@ PagedAttentionBf16Layer::PagedAttentionBf16Layer(TensorBf16&& wk, TensorBf16&& w
 void PagedAttentionBf16Layer::forward(TensorFloatPoint& page_table, const TensorInt& lengths,
                                       const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                       int n_new_items) {
+    check_sink_logits();
     check_softcap();
     check_alibi();
     check_rope();

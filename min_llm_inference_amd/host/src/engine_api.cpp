@@ -234,7 +234,13 @@ struct mli_engine {
                 seg_device.copy_from(seg_host);
                 const int* d = seg_device.data();
                 // (an engine with a cap scores its prompts under the model it decodes with: the capped prompt scan)
-                const int rc = o.softcap != 0.f
+                const int rc = o.sink_logits
+                    ? mli_paged_prompt_logprobs_sink_logits(   // (likewise with learned sink logits)
+                          page_table, inp, wq, emb_table, d, d + limit, d + 2 * limit, d + 3 * limit, token_device.data(),
+                          n_top > 0 ? ids_device.data() : nullptr, n_top > 0 ? top_device.data() : nullptr, n_seg, pass.max_count,
+                          pass.n_positions, n_batch, n_sequence, emb_dim, n_vocab, o.n_heads, n_kv_heads, o.window, o.n_sink,
+                          o.sink_logits->data(), elem, n_top, scratch.data(), scratch_bytes, mli::runtime::compute_stream())
+                    : o.softcap != 0.f
                     ? mli_paged_prompt_logprobs_softcap(
                           page_table, inp, wq, emb_table, d, d + limit, d + 2 * limit, d + 3 * limit, token_device.data(),
                           n_top > 0 ? ids_device.data() : nullptr, n_top > 0 ? top_device.data() : nullptr, n_seg, pass.max_count,
@@ -564,6 +570,8 @@ int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
     MLI_GUARD({
         if (e->started) throw std::runtime_error("mli_engine_configure after the engine has started");
         PagedAttentionOptions& o = e->options();
+        if (o.sink_logits && lean_layers == 0)   // (named first: an engine with sink logits has two heads at least)
+            throw std::runtime_error("attention-sink logits (mli_engine_set_sink_logits) have the lean compositions only");
         if (o.softcap != 0.f && lean_layers == 0)   // (named first: an engine with a cap has two heads at least)
             throw std::runtime_error("logit soft-capping (mli_engine_set_softcap) has the lean compositions only");
         if (o.n_heads > 1 && lean_layers == 0)   // refused before anything is changed
@@ -610,6 +618,9 @@ int mli_engine_set_heads(mli_engine* e, int n_heads) {
                                          std::to_string(o.n_heads) + " heads");
             if (o.rope_table)
                 throw std::runtime_error("mli_engine_set_heads: the stored rotary table (mli_engine_set_rope) is that of " +
+                                         std::to_string(o.n_heads) + " heads");
+            if (o.sink_logits)
+                throw std::runtime_error("mli_engine_set_heads: the stored sink logits (mli_engine_set_sink_logits) are those of " +
                                          std::to_string(o.n_heads) + " heads");
             if (o.softcap != 0.f && n_heads < 2)
                 throw std::runtime_error("mli_engine_set_heads: the stored cap (mli_engine_set_softcap) needs two heads at least");
@@ -663,6 +674,9 @@ int mli_engine_set_alibi(mli_engine* e, const float* slopes_host, int n) {
         if (o.softcap != 0.f)
             throw std::runtime_error("mli_engine_set_alibi: not with logit soft-capping (mli_engine_set_softcap: no order of bias "
                                      "and cap is defined)");
+        if (o.sink_logits)
+            throw std::runtime_error("mli_engine_set_alibi: not with attention-sink logits (mli_engine_set_sink_logits: no model "
+                                     "defines a sink logit beside a position bias)");
         if (e->prompt_logprobs_wanted)
             throw std::runtime_error("mli_engine_set_alibi: not with prompt log-probabilities (the prompt scan has no bias: the "
                                      "prompt would be scored under another model than the one that decodes)");
@@ -700,12 +714,53 @@ int mli_engine_set_softcap(mli_engine* e, float cap) {
             if (o.alibi_slopes)
                 throw std::runtime_error("mli_engine_set_softcap: not with ALiBi (mli_engine_set_alibi: no order of bias and cap "
                                          "is defined)");
+            if (o.sink_logits)
+                throw std::runtime_error("mli_engine_set_softcap: not with attention-sink logits (mli_engine_set_sink_logits: no "
+                                         "model defines a sink logit beside a cap)");
             const int n_kv_heads = o.n_kv_heads != 0 ? o.n_kv_heads : o.n_heads;
             if (!mli::gqa_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, o.n_heads, n_kv_heads, e->elem()))
                 throw std::runtime_error("mli_engine_set_softcap: the scan does not take this (n_batch, n_sequence, emb_dim, "
                                          "n_heads, n_kv_heads)");
         }
         e->paged->set_softcap(cap);
+    })
+}
+
+// The logits are stored with the option set (the layer owns the device copy, whose address a captured step graph replays); the
+// decode scan and the prompt scan of the engine read them there.  logits_host null: the switch is turned off again.
+int mli_engine_set_sink_logits(mli_engine* e, const float* logits_host, int n) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (e->started) throw std::runtime_error("mli_engine_set_sink_logits after the engine has started");
+        if (!e->heads_kind())
+            throw std::runtime_error("mli_engine_set_sink_logits: attention-sink logits serve the fp32 and bf16 paged engines");
+        PagedAttentionOptions& o = e->options();
+        if (logits_host != nullptr) {
+            if (o.n_heads < 2)
+                throw std::runtime_error("mli_engine_set_sink_logits: n_heads must be >= 2 (mli_engine_set_heads comes first; the "
+                                         "single-head scans have no sink logit)");
+            if (n != o.n_heads)
+                throw std::runtime_error("mli_engine_set_sink_logits: n must be the engine's n_heads (" + std::to_string(o.n_heads) +
+                                         ")");
+            for (int h = 0; h < n; ++h)
+                if (std::isnan(logits_host[h]) || logits_host[h] == INFINITY)
+                    throw std::runtime_error("mli_engine_set_sink_logits: every logit must be finite or -inf (NaN and +inf are "
+                                             "refused)");
+            if (!e->lean_layers)
+                throw std::runtime_error("mli_engine_set_sink_logits: attention-sink logits have the lean compositions only");
+            if (o.alibi_slopes)
+                throw std::runtime_error("mli_engine_set_sink_logits: not with ALiBi (mli_engine_set_alibi: no model defines a sink "
+                                         "logit beside a position bias)");
+            if (o.softcap != 0.f)
+                throw std::runtime_error("mli_engine_set_sink_logits: not with logit soft-capping (mli_engine_set_softcap: no model "
+                                         "defines a sink logit beside a cap)");
+            const int n_kv_heads = o.n_kv_heads != 0 ? o.n_kv_heads : o.n_heads;
+            if (!mli::gqa_shape_supported(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, o.n_heads, n_kv_heads, e->elem()))
+                throw std::runtime_error("mli_engine_set_sink_logits: the scan does not take this (n_batch, n_sequence, emb_dim, "
+                                         "n_heads, n_kv_heads)");
+            mli::runtime::use_device(e->cfg.device);
+        }
+        e->paged->set_sink_logits(logits_host, logits_host != nullptr ? n : 0);
     })
 }
 

@@ -305,8 +305,16 @@ int mli::runtime::lean_paged_attention(int elem, int n_heads, int window, int n_
                                        const int* lengths, const void* wk, const void* wq, const void* wv,
                                        const int* new_batch_idx, float* q_output, float* attention_result, int B, int S, int D,
                                        int n_new_items, int n_kv_heads, const float* alibi_slopes, const float* rope_table,
-                                       float softcap) {
+                                       float softcap, const float* sink_logits) {
     const Scratch ws = attention_scratch(B, S, D, n_heads > 1 ? n_heads : 1);
+    if (sink_logits != nullptr) {   // with or without a rotary table; never with slopes or a cap (the entry point takes none)
+        if (alibi_slopes != nullptr) throw std::runtime_error("attention-sink logits and ALiBi are not combined");
+        if (softcap != 0.f) throw std::runtime_error("attention-sink logits and logit soft-capping are not combined");
+        HIP_CHECK(mli_paged_attention_lean_sink_logits(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
+                                                       B, S, D, n_new_items, n_heads, n_kv_heads != 0 ? n_kv_heads : n_heads,
+                                                       window, n_sink, sink_logits, rope_table, elem, ws.ptr, ws.bytes, stream()));
+        return 0;
+    }
     if (softcap != 0.f) {   // with or without a rotary table; never with slopes (the entry point takes none)
         if (alibi_slopes != nullptr) throw std::runtime_error("logit soft-capping and ALiBi are not combined");
         HIP_CHECK(mli_paged_attention_lean_softcap(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B,

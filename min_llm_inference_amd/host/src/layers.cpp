@@ -64,6 +64,22 @@ void PagedAttentionOptionSetters::set_softcap(float cap) {
     options().softcap = cap;
 }
 
+void PagedAttentionOptionSetters::set_sink_logits(const float* values, int n) {
+    if (values == nullptr || n == 0) {
+        options().sink_logits.reset();
+        return;
+    }
+    if (n < 0) throw std::invalid_argument("set_sink_logits: a negative count");
+    for (int h = 0; h < n; ++h)
+        if (std::isnan(values[h]) || values[h] == INFINITY)
+            throw std::invalid_argument("set_sink_logits: every logit must be finite or -inf (NaN and +inf are refused)");
+    TensorFloat host(std::vector<size_t>{(size_t)n}, DeviceType::HOST, TensorDataType::SYNC_ALLOCATE);
+    std::copy(values, values + n, host.data());
+    auto device = std::make_shared<TensorFloat>(std::vector<size_t>{(size_t)n}, DeviceType::DEVICE, TensorDataType::SYNC_ALLOCATE);
+    device->copy_from(host);
+    options().sink_logits = std::move(device);
+}
+
 void PagedAttentionOptionSetters::set_rope_table(const std::vector<float>& table) {
     if (table.empty()) {
         options().rope_table.reset();
@@ -157,10 +173,26 @@ void PagedAttentionLayerCore<Weights>::check_softcap() const {
         throw std::runtime_error("logit soft-capping (set_softcap) and ALiBi (set_alibi_slopes) are not combined");
 }
 
+// As check_alibi: the logits are held to the heads where they are used, and never dropped by a composition without them.
+template <class Weights>
+void PagedAttentionLayerCore<Weights>::check_sink_logits() const {
+    if (!options_.sink_logits) return;
+    if (options_.n_heads < 2 || options_.sink_logits->get_total_size() != (size_t)options_.n_heads)
+        throw std::runtime_error("attention-sink logits: " + std::to_string(options_.sink_logits->get_total_size()) +
+                                 " logits (set_sink_logits) beside n_heads = " + std::to_string(options_.n_heads) +
+                                 ": one logit per head, two heads at least");
+    if (!mli::runtime::lean_layers()) throw std::runtime_error("attention-sink logits exist in the lean composition only");
+    if (options_.alibi_slopes)
+        throw std::runtime_error("attention-sink logits (set_sink_logits) and ALiBi (set_alibi_slopes) are not combined");
+    if (options_.softcap != 0.f)
+        throw std::runtime_error("attention-sink logits (set_sink_logits) and logit soft-capping (set_softcap) are not combined");
+}
+
 template <class Weights>
 int PagedAttentionLayerCore<Weights>::lean_scan(TensorFloatPoint& page_table, const TensorInt& lengths,
                                                 const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                                 int n_new_items, int n_heads, int n_kv_heads) {
+    check_sink_logits();
     check_softcap();
     check_alibi();
     check_rope();
@@ -170,7 +202,8 @@ int PagedAttentionLayerCore<Weights>::lean_scan(TensorFloatPoint& page_table, co
                                               attention_result.data(), (int)page_table.shape()[0], (int)n_sequence_,
                                               (int)wk_.shape()[0], n_new_items, n_kv_heads,
                                               options_.alibi_slopes ? options_.alibi_slopes->data() : nullptr,
-                                              options_.rope_table ? options_.rope_table->data() : nullptr, options_.softcap);
+                                              options_.rope_table ? options_.rope_table->data() : nullptr, options_.softcap,
+                                              options_.sink_logits ? options_.sink_logits->data() : nullptr);
 }
 
 template class PagedAttentionLayerCore<TensorFloat>;
@@ -184,6 +217,7 @@ PagedAttentionFloatLayer::PagedAttentionFloatLayer(TensorFloat&& wk, TensorFloat
 bool PagedAttentionFloatLayer::forward_lean(TensorFloatPoint& page_table, const TensorInt& lengths,
                                             const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                             int n_new_items) {
+    check_sink_logits();
     check_softcap();
     check_alibi();
     check_rope();

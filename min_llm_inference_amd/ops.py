@@ -377,9 +377,30 @@ def decode_scan_paged_softcap(q_output, page_table, lengths, attention_result, n
                                                         need, _stream()), "mli_decode_scan_paged_softcap")
 
 
+def _sink_logits_alone(alibi_slopes, softcap):
+    if alibi_slopes is not None:
+        raise ValueError("attention-sink logits and ALiBi are not combined")
+    if softcap is not None:
+        raise ValueError("attention-sink logits and logit soft-capping are not combined")
+
+
+def decode_scan_paged_sink_logits(q_output, page_table, lengths, attention_result, n_heads, n_kv_heads, window, sinks, sink_logits,
+                                  elem, n_sequence):
+    """decode_scan_paged_gqa with a learned attention-sink logit per query head (mli_decode_scan_paged_sink_logits):
+    sink_logits[h] takes part in head h's softmax as one more logit without a value row -- it enters the maximum and the
+    denominator, once per (row, head).  sink_logits: n_heads float32 values on the device, each finite or -inf (-inf: no sink);
+    n_heads >= 2; n_kv_heads None or n_heads: no grouping.  `sinks` is the count of sink TOKENS, another switch."""
+    B, D = q_output.shape
+    ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+    _check(load_library().mli_decode_scan_paged_sink_logits(_p(q_output), _p(page_table), _p(lengths), _p(attention_result), B,
+                                                            int(n_sequence), D, int(n_heads), int(n_kv_heads or n_heads),
+                                                            int(window or 0), int(sinks or 0), _p(sink_logits), int(elem), _p(ws),
+                                                            need, _stream()), "mli_decode_scan_paged_sink_logits")
+
+
 def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_new_items,
                          n_sequence, elem=None, n_heads=1, window=None, sinks=None, n_kv_heads=None, alibi_slopes=None,
-                         rope=None, softcap=None):
+                         rope=None, softcap=None, sink_logits=None):
     """What the attention layers run: the paged composition without materialising scores / probabilities
     (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads != 1: the
     multi-head form (mli_paged_attention_lean_heads); window given: the sliding-window form
@@ -391,7 +412,21 @@ def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_outpu
     rope given (a [n_sequence, D / n_heads / 2, 2] float32 (cos, sin) table on the device): fill and projection rotate K and q
     by the token's absolute slot (mli_paged_attention_lean_rope), with any of the above;
     softcap given (a finite float > 0): the scan caps its scaled scores as decode_scan_paged_softcap does
-    (mli_paged_attention_lean_softcap), with any of window, sinks, n_kv_heads and rope, never with alibi_slopes."""
+    (mli_paged_attention_lean_softcap), with any of window, sinks, n_kv_heads and rope, never with alibi_slopes;
+    sink_logits given (n_heads float32 values on the device): the scan counts a learned sink logit per query head as
+    decode_scan_paged_sink_logits does (mli_paged_attention_lean_sink_logits), with any of window, sinks, n_kv_heads and rope,
+    never with alibi_slopes or softcap."""
+    if sink_logits is not None:
+        _sink_logits_alone(alibi_slopes, softcap)
+        if sinks is not None and window is None:
+            raise ValueError("sinks exist beside a window: pass window= as well")
+        B, D = page_table.shape[0], wk.shape[0]
+        ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads)
+        _check(load_library().mli_paged_attention_lean_sink_logits(
+            _p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(new_batch_idx), _p(q_output), _p(attention_result), B,
+            int(n_sequence), D, int(n_new_items), int(n_heads), int(n_kv_heads or n_heads), int(window or 0), int(sinks or 0),
+            _p(sink_logits), _p(rope), _elem_of(wk, elem), _p(ws), need, _stream()), "mli_paged_attention_lean_sink_logits")
+        return
     if softcap is not None:
         if alibi_slopes is not None:
             raise ValueError("logit soft-capping and ALiBi are not combined")
@@ -577,17 +612,28 @@ def prompt_scan_tq(emb_dim, n_heads, elem):
 
 
 def prompt_scan_paged(q, page_table, segments, out, n_batch, n_sequence, elem, n_heads=1, n_kv_heads=None, window=None,
-                      sinks=None, seg_arrays=None, softcap=None):
+                      sinks=None, seg_arrays=None, softcap=None, sink_logits=None):
     """EXTENSION: the causal multi-query paged scan (mli_prompt_scan_paged).  segments = [(row, first position,
     count)]: query j of a segment is position first + j of its row and attends the slots s <= its position (inside the window or
     among the sinks); q and out [n_q, D] hold the queries in list order.  seg_arrays = (rows, first, count, offset, max_count)
     device arrays replace the list.  softcap given (a finite float > 0, n_heads >= 2): every scaled score x becomes
-    softcap * tanh(x / softcap) (mli_prompt_scan_paged_softcap)."""
+    softcap * tanh(x / softcap) (mli_prompt_scan_paged_softcap).  sink_logits given (n_heads float32 values on the device,
+    n_heads >= 2; never with softcap): query t gets what decode_scan_paged_sink_logits gives a row of length t + 1
+    (mli_prompt_scan_paged_sink_logits)."""
+    if sink_logits is not None:
+        _sink_logits_alone(None, softcap)
     n_q, D = q.shape
     if seg_arrays is None:
         arrays, max_count, _ = _segments(segments, q.device)
     else:
         arrays, max_count = list(seg_arrays[:4]), int(seg_arrays[4])
+    if sink_logits is not None:
+        _check(load_library().mli_prompt_scan_paged_sink_logits(_p(q), _p(page_table), *map(_p, arrays), _p(out),
+                                                                int(arrays[0].numel()), max_count, n_q, int(n_batch),
+                                                                int(n_sequence), D, int(n_heads), int(n_kv_heads or n_heads),
+                                                                int(window or 0), int(sinks or 0), _p(sink_logits), int(elem),
+                                                                _stream()), "mli_prompt_scan_paged_sink_logits")
+        return out
     if softcap is not None:
         _check(load_library().mli_prompt_scan_paged_softcap(_p(q), _p(page_table), *map(_p, arrays), _p(out),
                                                             int(arrays[0].numel()), max_count, n_q, int(n_batch), int(n_sequence),
@@ -635,11 +681,14 @@ def score_tokens_logprobs(logits, targets, n_top=0):
 
 
 def paged_prompt_logprobs(page_table, inp, wq, emb_table, segments, n_batch, n_sequence, elem, n_top=0, n_heads=1,
-                          n_kv_heads=None, window=None, sinks=None, softcap=None):
+                          n_kv_heads=None, window=None, sinks=None, softcap=None, sink_logits=None):
     """EXTENSION: prompt log-probabilities for the positions of the segments from the pages a prefill has written
     (mli_paged_prompt_logprobs): projection, causal scan, logits, scoring of inp[row, position + 1].  Returns (token_logprob
     [n], top_ids [n, n_top], top_logprobs [n, n_top]) in list order.  softcap given: the scan with logit soft-capping
-    (mli_paged_prompt_logprobs_softcap)."""
+    (mli_paged_prompt_logprobs_softcap).  sink_logits given (never with softcap): the scan with a learned sink logit per query
+    head (mli_paged_prompt_logprobs_sink_logits)."""
+    if sink_logits is not None:
+        _sink_logits_alone(None, softcap)
     lib = load_library()
     D, V = wq.shape[0], emb_table.shape[0]
     n_top = int(n_top)
@@ -647,6 +696,13 @@ def paged_prompt_logprobs(page_table, inp, wq, emb_table, segments, n_batch, n_s
     token_logprob, top_ids, top_logprobs = _score_outputs(n, n_top, wq.device)
     need = int(lib.mli_prompt_logprobs_scratch_bytes(n, D, V))
     sc = torch.empty(max(need, 16), dtype=torch.uint8, device=wq.device)
+    if sink_logits is not None:
+        _check(lib.mli_paged_prompt_logprobs_sink_logits(
+            _p(page_table), _p(inp), _p(wq), _p(emb_table), *map(_p, arrays), _p(token_logprob),
+            _p(top_ids) if n_top > 0 else None, _p(top_logprobs) if n_top > 0 else None, len(segments), max_count, n,
+            int(n_batch), int(n_sequence), D, V, int(n_heads), int(n_kv_heads or n_heads), int(window or 0), int(sinks or 0),
+            _p(sink_logits), int(elem), n_top, _p(sc), need, _stream()), "mli_paged_prompt_logprobs_sink_logits")
+        return token_logprob, top_ids, top_logprobs
     if softcap is not None:
         _check(lib.mli_paged_prompt_logprobs_softcap(
             _p(page_table), _p(inp), _p(wq), _p(emb_table), *map(_p, arrays), _p(token_logprob),
