@@ -178,13 +178,34 @@ def _biased_head(qh, Kh, Vh, idx, L, slope, cap, dtype):
     return (p @ Vh).astype(dtype)[None], float((p.astype(np.float64) @ np.abs(Vh.astype(np.float64))).max())
 
 
-def row_truth(oracle, q, K, V, H=1, Hkv=None, window=0, sinks=0, slopes=None, cap=None):
+def _sunk_head(qh, Kh, Vh, z, dtype):
+    """(o [1, hd], o_scale) of one head over the attended slots with the learned sink logit z (finite or -inf), every
+    operation in `dtype`, as attention_sink_logits.hpp and sink_logits_model state it: x = q . K / sqrt(hd); m = max(max x, z);
+    o = sum exp(x - m) V / (sum exp(x - m) + exp(z - m)) -- one more logit of the softmax without a value row.  The condition
+    scale is 1 where the sink takes the whole mass (the value is then exactly 0), as sink_logits_model's is."""
+    qh, Kh, Vh = (np.asarray(a).astype(dtype) for a in (qh, Kh, Vh))
+    x = ((Kh @ qh).astype(dtype) / dtype(np.sqrt(len(qh)))).astype(dtype)
+    z = dtype(np.float32(z))
+    m = np.maximum(x.max(), z)
+    with np.errstate(over="ignore", invalid="ignore"):
+        e = np.exp(x - m)
+        ez = np.exp(z - m)
+    denom = (e.sum(dtype=dtype) + ez).astype(dtype)
+    p = (e / denom).astype(dtype)
+    scale = float((p.astype(np.float64) @ np.abs(Vh.astype(np.float64))).max())
+    return (p @ Vh).astype(dtype)[None], scale if scale > 0 else 1.0
+
+
+def row_truth(oracle, q, K, V, H=1, Hkv=None, window=0, sinks=0, slopes=None, cap=None, sink=None):
     """[(columns, f64_model.Model, (x, p, o) of the fp32 oracle)] per head for one row: q [D], K / V [L, D] as the pages hold
     them.  Head h attends the slots attended(L, window, sinks) with K / V head h // (H // Hkv).
     slopes [H] (ALiBi: slopes[h] * (s - (L - 1)) is added to the scaled score of slot s) or cap (soft-capping: the scaled score
     x becomes cap * tanh(x / cap), before the mask): the model is then the float64 evaluation of that expression (o, o_scale
     and lengths, what f64_model.attention_error reads) and the oracle's place is taken by the same expression in float32
-    numpy, as alibi_model / softcap_model take their tolerance: (None, None, o32)."""
+    numpy, as alibi_model / softcap_model take their tolerance: (None, None, o32).
+    sink [H] float32, each finite or -inf (learned attention-sink logits: _sunk_head): the same arrangement; never beside
+    slopes or a cap, as the launchers have it."""
+    assert sink is None or (slopes is None and cap is None), "no model defines a sink logit beside a position bias or a cap"
     D = len(q)
     hd = D // H
     g = H // (Hkv or H)
@@ -195,6 +216,13 @@ def row_truth(oracle, q, K, V, H=1, Hkv=None, window=0, sinks=0, slopes=None, ca
     for h in range(H):
         cols = slice(h * hd, (h + 1) * hd)
         kv = slice((h // g) * hd, (h // g + 1) * hd)
+        if sink is not None:
+            z = np.asarray(sink, np.float32)[h]
+            o64, scale = _sunk_head(q[cols], K[:, kv], V[:, kv], z, np.float64)
+            o32, _ = _sunk_head(q[cols], K[:, kv], V[:, kv], z, np.float32)
+            model = SimpleNamespace(o=o64, o_scale=np.asarray([scale]), lengths=np.asarray([len(idx)], np.int64))
+            out.append((cols, model, (None, None, o32)))
+            continue
         if slopes is not None or cap is not None:
             slope = None if slopes is None else np.asarray(slopes, np.float32)[h]
             o64, scale = _biased_head(q[cols], K[:, kv], V[:, kv], idx, L, slope, cap, np.float64)
@@ -227,10 +255,66 @@ def scaled_q(case, target, H=1, Hkv=None):
     return (case.q * np.float32(target / largest_score(case, H, Hkv))).astype(np.float32)
 
 
-def judge_rows(oracle, case, values_of, got, rows, H=1, Hkv=None, window=0, sinks=0, slopes=None, cap=None, q=None):
+def judged_lse(case, values_of, rows, H, Hkv=None, window=0, sinks=0, q=None, lengths=None):
+    """[len(rows), H] float64: log sum_{s attended} exp(x_s) of every judged (row, head), -inf for a row of length 0 --
+    sink_logits_model.log_sum_exp on sparse rows.  lengths: the tokens of each judged row that count, where that is not the
+    row's own length (the prompt scan: a query at position t attends the row's first t + 1 tokens); q: [len(rows), D] then."""
+    hd, g = case.D // H, H // (Hkv or H)
+    out = np.full((len(rows), H), -np.inf)
+    held = {}
+    for i, b in enumerate(rows):
+        n = int(case.lengths[b] if lengths is None else lengths[i])
+        if n == 0:
+            continue
+        if b not in held:
+            held[b] = values_of(b)[0]
+        idx = attended(n, window, sinks)
+        Kb = held[b][:n][idx].astype(np.float64)
+        qb = (case.q[b] if q is None else q[i] if lengths is not None else q[b]).astype(np.float64)
+        for h in range(H):
+            x = Kb[:, (h // g) * hd:(h // g + 1) * hd] @ qb[h * hd:(h + 1) * hd] / np.sqrt(hd)
+            out[i, h] = x.max() + np.log(np.exp(x - x.max()).sum())
+    return out
+
+
+def learned_sparse(lse):
+    """sink_logits_model.learned on sparse rows: per head the median of judged_lse over the judged non-empty rows plus that
+    module's per-head offset, float32 [H]"""
+    from sink_logits_model import head_offsets
+    live = np.isfinite(lse[:, 0])
+    centre = np.median(lse[live], axis=0) if live.any() else np.zeros(lse.shape[1])
+    return (centre + head_offsets(lse.shape[1])).astype(np.float32)
+
+
+def sink_share(lse, sink):
+    """[len(rows), H] float64: the sink's share of every judged (row, head)'s softmax, exp(z - m) / (sum exp(x - m) + exp(z - m))
+    = 1 / (1 + exp(lse - z)) -- sink_logits_model.SinkLogitsModel.share on sparse rows; NaN for a row of length 0"""
+    z = np.asarray(sink, np.float32).astype(np.float64)[None, :]
+    with np.errstate(over="ignore", invalid="ignore"):
+        share = 1.0 / (1.0 + np.exp(lse - z))
+    return np.where(np.isfinite(lse), share, np.nan)
+
+
+def biting(lse, sink, what="", heads=None):
+    """sink_logits_model.conditioned on sparse rows: asserts that the sink's share lies in SHARE_BAND on at least MIN_BITING of
+    the judged non-empty (row, head) pairs of `heads` (default: every head whose logit is finite and below 1e29 in magnitude --
+    the -inf, +-1e30 anchors are judged by their own assertions and do not count); returns the fraction"""
+    from sink_logits_model import MIN_BITING, SHARE_BAND
+    z = np.asarray(sink, np.float32)
+    heads = [h for h in range(len(z)) if np.isfinite(z[h]) and abs(z[h]) < 1e29] if heads is None else list(heads)
+    s = sink_share(lse, sink)[:, heads]
+    s = s[np.isfinite(s)]
+    assert s.size, f"{what}: no judged pair carries a finite learned logit"
+    f = float(((s >= SHARE_BAND[0]) & (s <= SHARE_BAND[1])).mean())
+    assert f >= MIN_BITING, f"{what}: the sink's share lies in {SHARE_BAND} on {f:.2f} of the judged (row, head) pairs only"
+    return f
+
+
+def judge_rows(oracle, case, values_of, got, rows, H=1, Hkv=None, window=0, sinks=0, slopes=None, cap=None, q=None, sink=None,
+               heads=None):
     """{family: (kernel errors, oracle errors)} of attention_result `got` [B, D] over the (row, head) pairs of `rows`;
-    values_of(b) = (K, V) as the pages hold them.  Rows of length 0: inf unless exactly 0.  slopes / cap: row_truth's; q: the
-    queries the launch was given where they are not case.q (scaled_q)."""
+    values_of(b) = (K, V) as the pages hold them.  Rows of length 0: inf unless exactly 0.  slopes / cap / sink: row_truth's;
+    q: the queries the launch was given where they are not case.q (scaled_q); heads: the heads judged (default: all)."""
     q = case.q if q is None else q
     out = {}
     for b in rows:
@@ -241,11 +325,57 @@ def judge_rows(oracle, case, values_of, got, rows, H=1, Hkv=None, window=0, sink
             rec[1].append(0.0)
             continue
         K, V = values_of(b)
-        for h, (cols, model, (_, _, o)) in enumerate(row_truth(oracle, q[b], K, V, H, Hkv, window, sinks, slopes, cap)):
+        for h, (cols, model, (_, _, o)) in enumerate(row_truth(oracle, q[b], K, V, H, Hkv, window, sinks, slopes, cap, sink)):
+            if heads is not None and h not in heads:
+                continue
             rec = out.setdefault(case.family(b, h if case.H == H else 0), ([], []))
             rec[0].append(float(fm.attention_error(np.asarray(got[b][cols])[None], model)[0]))
             rec[1].append(float(fm.attention_error(o, model)[0]))
     return out
+
+
+# ---- the cases the sink-logit kernels run at the frontier, shared by the GPU tests and their small siblings on the CPU ---------
+def heads_case(D, B=16384):
+    """(B, 64, D): rows 0, B / 2 - 1 and B - 1 with 63 tokens, lengths 0, 1, 16 .. 18, 20, 21, 33 around the window and sink
+    edges, the rest 0 .. 40 tokens with four in ten empty; (case, the named rows)"""
+    rng = np.random.default_rng(4600)
+    L = rng.integers(0, 41, size=B).astype(np.int32)
+    L[rng.random(B) < 0.4] = 0
+    named = {0: 63, B // 2 - 1: 63, B - 1: 63, 1: 0, 2: 1, 3: 16, 4: 17, 5: 18, 6: 21, 7: 33, B - 2: 20, B - 3: 0}
+    for b, n in named.items():
+        L[b] = n
+    return SparseCase(4601, L, 64, D), sorted(named)
+
+
+def merge_case(lengths=(16383, 129)):
+    """bf16 (., 16384, 1024) with 32 heads: early_peak on odd heads, late_peak on even ones"""
+    fams = tuple("early_peak" if h % 2 else "late_peak" for h in range(32))
+    return SparseCase(4700, list(lengths), 16384, 1024, families={b: fams for b in range(len(lengths))}, H=32)
+
+
+def wide_case(D, flat=False):
+    """flat: no score families -- the sink-logit launches take one logit per head for the whole batch, and the condition on it
+    (biting) needs rows whose log-sum-exp lie within a few units of each other"""
+    fams = None if flat else {6: "late_peak", 7: "offset-", 4: "early_peak"}
+    return SparseCase(4200 + D, [0, 1, 16, 17, 63, 64, 127, 100], 128, D, families=fams)
+
+
+def window_case(D=64, flat=False):
+    """flat: as wide_case's"""
+    fams = None if flat else {11: "late_peak", 10: "offset-"}
+    return SparseCase(4980, [0, 1, 2, 15, 16, 17, 31, 32, 33, 48, 62, 63], 64, D, families=fams)
+
+
+# the score families against the sink: (., 1024, 256) with 8 heads on 2 K/V heads; a K/V head keeps ONE family over all rows (its
+# query heads have one logit each for the whole launch), so the six families are three cases of two
+SINK_FAMILY_PAIRS = (("flat", "peaked"), ("offset+", "offset-"), ("late_peak", "early_peak"))
+
+
+def sink_family_case(pair, B=24):
+    """lengths 1, 63, 64, 65, 1008, 1023, 0 and random ones in 1 .. 1023; K/V head j of every row in family pair[j]"""
+    i = SINK_FAMILY_PAIRS.index(tuple(pair))
+    L = np.concatenate([[1, 63, 64, 65, 1008, 1023, 0], np.random.default_rng(5800 + i).integers(1, 1024, size=B - 7)]).astype(np.int32)
+    return SparseCase(5810 + i, L, 1024, 256, families={b: tuple(pair) for b in range(B) if L[b] > 0}, H=8, Hkv=2)
 
 
 def whole_output_faults(case, got):
@@ -524,6 +654,23 @@ LIMITS = [
            (CSRC + "compose.hip", "if (n_heads < 2 || !(cap > 0.f) || !std::isfinite(cap)) return MLI_ERR_BAD_ARG;"),
            "(16384, 64, 128) H 2, H 2 on 1, cap 5", "H 1; cap 0, -1, inf, NaN", "scan_heads_softcap", REFUSED,
            [on("test_heads_family_on_the_last_row", "HEAD_FORMS", "softcap"), on("test_heads_family_on_the_last_row", "HEAD_FORMS", "softcap_gqa")], []),
+    _limit("sink logits, heads and logits", "mli_decode_scan_paged_sink_logits, mli_paged_attention_lean_sink_logits",
+           (CSRC + "compose.hip", "if (n_heads < 2 || sink_logits == nullptr) return MLI_ERR_BAD_ARG;"),
+           "(16384, 64, 128) H 2, H 2 on 1, W 17, W 16 K 4", "H 1; a null logits pointer", "scan_heads_sink_logits", REFUSED,
+           [on("test_heads_family_on_the_last_row", "HEAD_FORMS", "sink_logits"), on("test_heads_family_on_the_last_row", "HEAD_FORMS", "sink_logits_gqa"),
+            on("test_heads_family_on_the_last_row", "HEAD_FORMS", "sink_logits_window"),
+            on("test_heads_family_on_the_last_row", "HEAD_FORMS", "sink_logits_sinks")], []),
+    _limit("sink logits, heads and logits, prompt scan", "mli_prompt_scan_paged_sink_logits",
+           (CSRC + "attention_prompt.hip", "if (sunk && (H < 2 || sink_logits == nullptr)) return MLI_ERR_BAD_ARG;"),
+           "(16384, 64, 128) H 2, segments on rows 0, 8191 and 16383; bf16 D 1024 H 8 on 2, f32 D 512 H 4", "H 1; a null logits pointer",
+           "scan_prompt_sink_logits", REFUSED,
+           [on("test_prompt_scan_on_the_last_row", "PROMPT_ROWS", (2, "sink_logits")),
+            on("test_prompt_scan_widest_rows", "PROMPT_WIDE", ("f32", 512)), on("test_prompt_scan_widest_rows", "PROMPT_WIDE", ("bf16", 1024))], []),
+    _limit("sink logits, heads and logits, prompt scoring", "mli_paged_prompt_logprobs_sink_logits",
+           (CSRC + "compose.hip", "if (sunk && (n_heads < 2 || sink_logits == nullptr)) return MLI_ERR_BAD_ARG;"),
+           "the scan behind the scoring at (16384, 64, 128) H 2, segments on rows 0, 8191 and 16383 (the scoring itself: tests/test_sink_logits_prompt_gpu.py)",
+           "H 1; a null logits pointer", "scan_prompt_sink_logits", REFUSED,
+           [on("test_prompt_scan_on_the_last_row", "PROMPT_ROWS", (2, "sink_logits"))], []),
     _limit("rotary head size", "every *_rope entry point",
            (CSRC + "proj_gemm.hip", "if (table == nullptr || n_heads < 1 || D < 1 || D % n_heads != 0 || (D / n_heads) % 2 != 0) return -1;"),
            "head size 2: (70, 64, 64) H 32", "head size 17 (D 68, H 4) and 33 (D 132, H 4)",
@@ -538,6 +685,7 @@ LIMITS = [
 _W, _H, _P = "row width, fp32 / bf16", "several heads, kPlanMaxRows", "merge statistics in the launch's LDS, plain scan"
 _PW, _PR, _PT, _PG = "prompt scan, one head, row width", "prompt scan, rows", "prompt scan, page types", "prompt scan, grid"
 _AH, _SH, _RH = "ALiBi, heads and slopes", "soft-cap, heads and cap", "rotary head size"
+_ZH, _ZS, _ZP = ("sink logits, heads and logits" + s for s in ("", ", prompt scan", ", prompt scoring"))
 REFUSALS = [
     ("scan", (8, 128, 2052, 0, 3), _W, 0), ("scan", (8, 128, 2052, 0, 5), _W, 0), ("scan", (8, 128, 2052, 0, 7), _W, 0),
     ("scan", (8, 128, 4104, 1, 3), _W, 0), ("scan", (8, 128, 4104, 1, 5), _W, 0), ("scan", (8, 128, 4104, 1, 7), _W, 0),
@@ -595,6 +743,45 @@ REFUSALS = [
     ("prefill_rope", (8, 64, 68, 2, 0, 0, 4, 0), _RH, 0), ("prefill_rope", (8, 64, 136, 2, 32, 4, 8, 1), _RH, 0),
     ("prefill_rope", (8, 64, 272, 2, 0, 0, 16, 2), _RH, 0),
     ("lean_rope", (8, 64, 68, 2, 4, 4, 0, 0, 0), _RH, 0), ("lean_rope", (8, 64, 132, 2, 4, 2, 17, 0, 0), _RH, 0),
+    # sink_logits / lean_sink_logits (B, S, D, H, Hkv, W, K, logits given?, elem) | prompt_sink_logits (n_seg, max_count, n_q, B, S,
+    # D, H, Hkv, W, K, logits given?, elem) | prompt_logprobs_sink_logits (n_seg, max_count, n_positions, B, S, D, V, H, Hkv, W, K,
+    # logits given?, elem).  One head and null logits are the rule's own far side; fp8 pages, head size 48 and K/V heads that do
+    # not divide the heads are what the front refuses right behind it (no sink logit exists there); the rest are the shared
+    # plans' limits, reached through the sink-logit entry points.
+    ("sink_logits", (8, 64, 128, 1, 1, 0, 0, True, 0), _ZH, 0), ("sink_logits", (8, 64, 64, 1, 1, 17, 0, True, 1), _ZH, 0),
+    ("sink_logits", (8, 64, 128, 2, 2, 0, 0, False, 0), _ZH, 0), ("sink_logits", (8, 64, 128, 2, 1, 16, 4, False, 1), _ZH, 0),
+    ("sink_logits", (8, 64, 128, 2, 2, 0, 0, True, 2), _ZH, 0), ("sink_logits", (8, 64, 96, 2, 2, 0, 0, True, 0), _ZH, 0),
+    ("sink_logits", (8, 64, 256, 8, 3, 0, 0, True, 1), _ZH, 0),
+    ("sink_logits", (16385, 64, 128, 2, 2, 0, 0, True, 0), _H, 0), ("sink_logits", (16385, 64, 128, 2, 1, 17, 0, True, 1), _H, 0),
+    ("sink_logits", (2, 64, 1056, 33, 33, 0, 0, True, 1), "several heads, row width", 0),
+    ("sink_logits", (2, 131088, 1024, 32, 32, 0, 0, True, 1), "several heads, kMaxMergeStats", 0),
+    ("sink_logits", (2, 131088, 1024, 32, 8, 8192, 0, True, 1), "several heads, kMaxMergeStats", 0),
+    ("lean_sink_logits", (8, 64, 128, 1, 1, 0, 0, True, 0), _ZH, 0), ("lean_sink_logits", (8, 64, 128, 2, 2, 0, 0, False, 0), _ZH, 0),
+    ("lean_sink_logits", (8, 64, 128, 2, 2, 16, 4, True, 2), _ZH, 0), ("lean_sink_logits", (8, 64, 96, 2, 2, 0, 0, True, 1), _ZH, 0),
+    ("lean_sink_logits", (8, 64, 256, 8, 3, 0, 0, True, 0), _ZH, 0),
+    ("lean_sink_logits", (16385, 64, 128, 2, 2, 0, 0, True, 0), _H, 0),
+    ("lean_sink_logits", (2, 64, 1056, 33, 33, 0, 0, True, 1), "several heads, row width", 0),
+    ("lean_sink_logits", (2, 131088, 1024, 32, 32, 0, 0, True, 1), "several heads, kMaxMergeStats", 0),
+    ("prompt_sink_logits", (1, 1, 1, 4, 128, 128, 1, 1, 0, 0, True, 0), _ZS, 0), ("prompt_sink_logits", (1, 1, 1, 4, 128, 128, 2, 2, 0, 0, False, 0), _ZS, 0),
+    ("prompt_sink_logits", (1, 1, 1, 4, 128, 128, 2, 1, 40, 4, False, 1), _ZS, 0),
+    ("prompt_sink_logits", (1, 1, 1, 4, 128, 128, 2, 2, 0, 0, True, 2), _PT, 0), ("prompt_sink_logits", (1, 1, 1, 4, 128, 96, 2, 2, 0, 0, True, 0), _ZS, 0),
+    ("prompt_sink_logits", (1, 1, 1, 4, 128, 256, 8, 3, 0, 0, True, 1), _ZS, 0),
+    ("prompt_sink_logits", (1, 1, 1, 16385, 64, 128, 2, 2, 0, 0, True, 0), _PR, 0), ("prompt_sink_logits", (1, 1, 1, 16385, 64, 128, 2, 1, 17, 0, True, 1), _PR, 0),
+    ("prompt_sink_logits", (1, 1, 1, 2, 64, 1056, 33, 33, 0, 0, True, 1), "several heads, row width", 0),
+    ("prompt_sink_logits", (1, 1, 1, 2, 131088, 1024, 32, 32, 0, 0, True, 1), "several heads, kMaxMergeStats", 0),
+    ("prompt_sink_logits", (32768, 4096, 1, 8, 4096, 128, 4, 4, 1000, 20, True, 0), _PG, 0),
+    ("prompt_sink_logits", (8192, 4096, 1, 8, 4096, 1024, 16, 2, 0, 0, True, 1), _PG, 0),
+    ("prompt_logprobs_sink_logits", (1, 1, 1, 4, 128, 128, 512, 1, 1, 0, 0, True, 0), _ZP, 0),
+    ("prompt_logprobs_sink_logits", (1, 1, 1, 4, 128, 128, 512, 2, 2, 0, 0, False, 0), _ZP, 0),
+    ("prompt_logprobs_sink_logits", (1, 1, 1, 4, 128, 128, 512, 2, 1, 40, 4, False, 1), _ZP, 0),
+    ("prompt_logprobs_sink_logits", (1, 1, 1, 4, 128, 128, 512, 2, 2, 0, 0, True, 2), _PT, 0),
+    ("prompt_logprobs_sink_logits", (1, 1, 1, 4, 128, 96, 512, 2, 2, 0, 0, True, 0), _ZP, 0),
+    ("prompt_logprobs_sink_logits", (1, 1, 1, 4, 128, 256, 512, 8, 3, 0, 0, True, 1), _ZP, 0),
+    ("prompt_logprobs_sink_logits", (1, 1, 1, 16385, 64, 128, 512, 2, 2, 0, 0, True, 0), _PR, 0),
+    ("prompt_logprobs_sink_logits", (1, 1, 1, 2, 64, 1056, 512, 33, 33, 0, 0, True, 1), "several heads, row width", 0),
+    ("prompt_logprobs_sink_logits", (1, 1, 1, 2, 131088, 1024, 512, 32, 32, 0, 0, True, 1), "several heads, kMaxMergeStats", 0),
+    ("prompt_logprobs_sink_logits", (32768, 4096, 1, 8, 4096, 128, 512, 4, 4, 0, 0, True, 0), _PG, 0),
+    ("prompt_logprobs_sink_logits", (8192, 4096, 1, 8, 4096, 1024, 512, 16, 2, 0, 0, True, 1), _PG, 0),
 ]
 
 
@@ -602,7 +789,8 @@ def call_refusal(lib, entry, args, workspace=None, workspace_bytes=1 << 40, stre
     """One REFUSALS call with null data pointers.  `workspace`: an address that is not null, with a size claimed beyond any
     need, so that no refusal is the workspace's; it also stands in where a null pointer would be refused before the shape is
     looked at (qkt_output of the materialising form).
-    data: the address given for EVERY data pointer of the newer entry points (prompt, ALiBi, soft-cap, rotary) instead of null.
+    data: the address given for EVERY data pointer of the newer entry points (prompt, ALiBi, soft-cap, rotary, sink logits)
+    instead of null (the sink logits themselves are `workspace` or, where the row says they are not given, null).
     Those launchers answer MLI_ERR_BAD_ARG for a null pointer too, so with null pointers a refusal says nothing of where the
     shape rule stands; with `data` set the pointer checks pass and only the shape rule can refuse.  Used WITHOUT a GPU only
     (tests/test_shape_limits_cpu.py): had the rule let the shape through, the launch fails there with a HIP error, which is
@@ -645,6 +833,21 @@ def call_refusal(lib, entry, args, workspace=None, workspace_bytes=1 << 40, stre
     if entry == "lean_rope":
         B, S, D, n_new, H, Hkv, W, K, elem = args
         return lib.mli_paged_attention_lean_rope(*(d,) * 8, B, S, D, n_new, H, Hkv, W, K, None, workspace, elem, *tail)
+    # the sink-logit entry points: `data` for every pointer but the logits, which are `workspace` (never followed) or null
+    if entry in ("sink_logits", "lean_sink_logits"):
+        *shape, given, elem = args
+        B, S, D, *heads = shape
+        z = workspace if given else None
+        if entry == "sink_logits":
+            return lib.mli_decode_scan_paged_sink_logits(d, d, d, d, B, S, D, *heads, z, elem, *tail)
+        return lib.mli_paged_attention_lean_sink_logits(*(d,) * 5, None, d, d, B, S, D, 0, *heads, z, None, elem, *tail)
+    if entry == "prompt_sink_logits":
+        *shape, given, elem = args
+        return lib.mli_prompt_scan_paged_sink_logits(*(d,) * 7, *shape, workspace if given else None, elem, stream)
+    if entry == "prompt_logprobs_sink_logits":
+        *shape, given, elem = args
+        return lib.mli_paged_prompt_logprobs_sink_logits(*(d,) * 8, workspace, None, None, *shape, workspace if given else None, elem,
+                                                         0, workspace, workspace_bytes, stream)
     name = {"heads": "mli_decode_scan_paged_heads", "window": "mli_decode_scan_paged_window",
             "sinks": "mli_decode_scan_paged_sinks", "gqa": "mli_decode_scan_paged_gqa"}[entry]
     return getattr(lib, name)(None, None, None, None, *args, *tail)

@@ -243,6 +243,14 @@ def long_segments(tq, W, S=LONG_S):
             (_EDGE_ROWS[1], e + 14, tq + 1)]
 
 
+def long_reaching_segments(tq):
+    """long_segments without the two mid-row blocks and the window-edge segments: the segments that reach the long paths (the
+    last query at 4095, the block at 16 k - 1, the max_count segment beside the single query, the continuation at 3000) -- for
+    the variants whose truth costs two evaluations per query (the cap, the sink logits); the plain test has the rest"""
+    keep = {5, 2, 0, 6, 1}
+    return [s for s in long_segments(tq, 0) if s[0] in keep]
+
+
 def long_lengths(tq, S=LONG_S):
     """tokens per row: the last scored position + 1 over the segment lists of every form (the edge rows' segments move with W)"""
     lengths = np.zeros(8, np.int32)
@@ -263,9 +271,19 @@ def long_families(H, Hkv):
     return {r: hm.families_of("mixed", Hkv) for r in range(8)}
 
 
-def long_case(seed, D, H, Hkv, tq):
+def long_sink_families(Hkv):
+    """{row: families} for the scan with sink logits, which takes ONE logit per head for every query of a launch: the families
+    whose log-sum-exp stays within a few units from query to query (an offset of 200 or an early peak of 30 times the
+    per-position factor of query_vectors moves it by more than that, and the sink would be invisible or total on most
+    queries) -- peaked, flat and late_peak (the queries at the end of a row see the peak: every accumulator rescaled at the end
+    of the walk; the peak is beyond the band for them, so it is the third K/V head's, where there are four), by K/V head."""
+    fams = tuple(("peaked", "flat", "late_peak", "flat")[j % 4] for j in range(Hkv))
+    return {r: fams for r in range(8)}
+
+
+def long_case(seed, D, H, Hkv, tq, families=None):
     import limit_cases as lc
-    return lc.SparseCase(seed, long_lengths(tq), LONG_S, D, families=long_families(H, Hkv), H=H, Hkv=Hkv, full_rows=True)
+    return lc.SparseCase(seed, long_lengths(tq), LONG_S, D, families=families or long_families(H, Hkv), H=H, Hkv=Hkv, full_rows=True)
 
 
 def _signature(t, W, K):
@@ -274,23 +292,24 @@ def _signature(t, W, K):
     return (t, lo, min(K, lo) if lo > 0 else 0)
 
 
-def long_truth(oracle, case, values_of, qv, rows, pos, H, Hkv, W, K, cap=None, cache=None):
+def long_truth(oracle, case, values_of, qv, rows, pos, H, Hkv, W, K, cap=None, cache=None, sink=None):
     """[per query: [(columns, model, oracle attention, family) per head]] by limit_cases.row_truth on the row's first t + 1
     tokens.  cache: a dict shared between the forms of one case and one q -- two forms under which a query attends the same
-    slots (W 0 and W 4096; W 4095 for every query but the one at 4095) share its truth."""
+    slots (W 0 and W 4096; W 4095 for every query but the one at 4095) share its truth.  sink: row_truth's learned sink logits."""
     import limit_cases as lc
+    zkey = None if sink is None else np.asarray(sink, np.float32).tobytes()
     cache = {} if cache is None else cache
     held = {}
     out = []
     for i in range(len(rows)):
         b, t = int(rows[i]), int(pos[i])
-        key = (i, cap) + _signature(t, W, K)
+        key = (i, cap, zkey) + _signature(t, W, K)
         if key not in cache:
             if b not in held:
                 held[b] = values_of(b)
             Kb, Vb = held[b]
             assert len(Kb) > t, "the row holds the query's position"
-            truth = lc.row_truth(oracle, qv[i], Kb[:t + 1], Vb[:t + 1], H, Hkv, W, K, cap=cap)
+            truth = lc.row_truth(oracle, qv[i], Kb[:t + 1], Vb[:t + 1], H, Hkv, W, K, cap=cap, sink=sink)
             cache[key] = [(cols, SimpleNamespace(o=m.o, o_scale=m.o_scale, lengths=m.lengths), o, case.family(b, h if case.H == H else 0))
                           for h, (cols, m, (_, _, o)) in enumerate(truth)]
         out.append(cache[key])

@@ -187,6 +187,11 @@ def largest_score(q, kt, lengths, H, Hkv, W=0, K=0):
     return max(float(np.where(mask, _scores(q, kt, h, H, Hkv, np.float64), -np.inf).max()) for h in range(H))
 
 
+def head_offsets(H):
+    """LEARNED's offset per head: in [-1, 1], of alternating sign, different from head to head"""
+    return np.linspace(-1.0, 1.0, H) * np.where(np.arange(H) % 2 == 0, 1.0, -1.0)
+
+
 def learned(q, kt, lengths, H, Hkv, W=0, K=0):
     """LEARNED for a case: finite float32 logits spread over the heads -- head h's logit is the median log-sum-exp of head h's
     scores over the non-empty rows plus an offset in [-1, 1] that differs from head to head (the share of a sink at the
@@ -194,8 +199,7 @@ def learned(q, kt, lengths, H, Hkv, W=0, K=0):
     lse = log_sum_exp(q, kt, lengths, H, Hkv, W, K)
     rows = np.isfinite(lse[:, 0])
     centre = np.median(lse[rows], axis=0) if rows.any() else np.zeros(H)
-    offsets = np.linspace(-1.0, 1.0, H) * np.where(np.arange(H) % 2 == 0, 1.0, -1.0)
-    return (centre + offsets).astype(np.float32)
+    return (centre + head_offsets(H)).astype(np.float32)
 
 
 def none(H):

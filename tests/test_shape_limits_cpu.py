@@ -212,7 +212,7 @@ def test_softmax_v_lds_does_not_grow_with_the_width():
 def test_refusals_without_a_gpu(mli, entry, args, limit, ct):
     """A workspace pointer that is not null and a size beyond any need: the refusal is the shape's, not the workspace's.  No
     pointer is dereferenced by a launcher; a launch, had the rule let the shape through, fails here and returns a HIP error.
-    The newer entry points (prompt, ALiBi, soft-cap, rotary) also refuse a null data pointer, so each of their rows runs twice:
+    The newer entry points (prompt, ALiBi, soft-cap, rotary, sink logits) also refuse a null data pointer, so each of their rows runs twice:
     with null pointers, as on the device, and with every data pointer set to an address that is never followed -- then the
     pointer checks pass, and the answer shows that the shape rule stands ahead of them and of every launch."""
     from min_llm_inference_amd import ops
@@ -224,6 +224,6 @@ def test_refusals_without_a_gpu(mli, entry, args, limit, ct):
     finally:
         assert mli.mli_tune(b"chunk_tokens", 0) == 0
     for family in ("scan_equal_shares", "scan_chunked", "scan_heads_window", "scan_heads_alibi", "scan_heads_softcap", "scan_prompt",
-                   "scan_prompt_softcap", "gemm_f32_rows64", "gemm_bf16_widened", "gemm_f32_rope", "gemm_bf16_rope", "fill_flat",
+                   "scan_prompt_softcap", "scan_heads_sink_logits", "scan_prompt_sink_logits", "gemm_f32_rows64", "gemm_bf16_widened", "gemm_f32_rope", "gemm_bf16_rope", "fill_flat",
                    "fill_per_row", "prefill_fused", "prefill_two_launch"):
         assert ops.launch_count(family) == 0, family

@@ -30,12 +30,14 @@ from helpers import assert_equal, fp8_decode
 pytestmark = pytest.mark.gpu
 
 SCAN_FAMILIES = ("scan_equal_shares", "scan_chunked", "scan_rows_ordered", "scan_rows_grid_order", "scan_heads_window",
-                 "scan_heads_alibi", "scan_heads_softcap", "scan_prompt", "scan_prompt_softcap")
+                 "scan_heads_alibi", "scan_heads_softcap", "scan_prompt", "scan_prompt_softcap", "scan_heads_sink_logits",
+                 "scan_prompt_sink_logits")
 # what a refusal must not have launched either: the projections and fills behind the prompt and rotary entry points
 OTHER_FAMILIES = ("gemm_f32_rows64", "gemm_bf16_widened", "gemm_f32_rope", "gemm_bf16_rope", "fill_flat", "fill_per_row",
                   "prefill_fused", "prefill_two_launch")
 CAP = 5.0
 _WS = {}
+SINK_RATIOS = []      # got / tol of every sink-logit comparison of this module, reported at its end
 
 
 def _t(a, dev):
@@ -45,9 +47,12 @@ def _t(a, dev):
 @pytest.fixture(scope="module", autouse=True)
 def _release_memory():
     yield
+    if SINK_RATIOS:
+        print(f"SINK_LOGITS limits: worst got/tol over {len(SINK_RATIOS)} comparisons {max(SINK_RATIOS):.3f}")
+    SINK_RATIOS.clear()
     _WS.clear()
     _pages.cache_clear()
-    for f in (_scaled_q, _x_pages, _hand_off_case, _rows_case, _longest_case, _order_case, _shares_case, _heads_case, _merge_case, _offsets_case, _wide_case, _window_case, _lds_case):
+    for f in (_family_case, _scaled_q, _x_pages, _hand_off_case, _rows_case, _longest_case, _order_case, _shares_case, _heads_case, _merge_case, _offsets_case, _wide_case, _window_case, _lds_case):
         f.cache_clear()
     torch.cuda.empty_cache()
 
@@ -128,18 +133,40 @@ def _call(mli, dev, x, entry, extra, elem, out, qkt=None, phases=7, H=1, q=None)
     p = lambda t: ctypes.c_void_p(0 if t is None else t.data_ptr())
     if entry == "scan":
         return mli.mli_decode_scan_paged(p(q), p(x.table), p(x.L), p(qkt), p(out), c.B, c.S, c.D, lc.ELEM[elem], phases, p(ws), need, st)
-    if entry == "alibi":
-        return mli.mli_decode_scan_paged_alibi(p(q), p(x.table), p(x.L), p(out), c.B, c.S, c.D, *extra[:4], p(extra[4]), lc.ELEM[elem],
-                                               p(ws), need, st)
+    if entry in ("alibi", "sink_logits"):       # extra = (H, Hkv, W, K, the slopes / the logits on the device)
+        fn = mli.mli_decode_scan_paged_alibi if entry == "alibi" else mli.mli_decode_scan_paged_sink_logits
+        return fn(p(q), p(x.table), p(x.L), p(out), c.B, c.S, c.D, *extra[:4], p(extra[4]), lc.ELEM[elem], p(ws), need, st)
     name = {"heads": "mli_decode_scan_paged_heads", "window": "mli_decode_scan_paged_window", "sinks": "mli_decode_scan_paged_sinks",
             "gqa": "mli_decode_scan_paged_gqa", "softcap": "mli_decode_scan_paged_softcap"}[entry]
     return getattr(mli, name)(p(q), p(x.table), p(x.L), p(out), c.B, c.S, c.D, *extra, lc.ELEM[elem], p(ws), need, st)
 
 
-def _biased(entry, case, H, Hkv, W, K, dev):
+def _mask(S, W, K):
+    """the (window, n_sink) the kernels mask by: lean_scan_kind's hand-offs give the plain mask"""
+    if W <= 0 or W >= S:
+        return 0, 0
+    return (0, 0) if K + W >= S else (W, K)
+
+
+def _learned(x, rows, H, Hkv, W, K, what):
+    """(logits float32 [H], log-sum-exp of the judged pairs): limit_cases.learned_sparse from what the pages hold, with the
+    condition under which the comparison bites (limit_cases.biting) asserted on the device's rounded values"""
+    import sink_logits_model as sl
+    lse = lc.judged_lse(x.case, x.values_of, rows, H, Hkv, *_mask(x.case.S, W, K))
+    z = lc.learned_sparse(lse)
+    f = lc.biting(lse, z, what)
+    print(f"SINK_LOGITS {what}: logits {[round(float(t), 2) for t in z]}; the sink's share lies in {sl.SHARE_BAND} on {f:.2f} of the judged pairs")
+    return z, lse
+
+
+def _biased(entry, case, H, Hkv, W, K, dev, x=None, rows=None):
     """(arguments behind emb_dim, q on the device or None, the judge's keywords, the launch counter) of an ALiBi call with the
-    slopes of mli_alibi_slopes or a soft-capped call at cap 5 with q scaled so that the largest score is 25 (scale_q's rule)"""
+    slopes of mli_alibi_slopes, a soft-capped call at cap 5 with q scaled so that the largest score is 25 (scale_q's rule), or
+    a call with sink logits learned from the judged `rows` of the pages `x` (_learned)"""
     from min_llm_inference_amd import ops
+    if entry == "sink_logits":
+        z, _ = _learned(x, rows, H, Hkv, W, K, f"sink_logits H {H}/{Hkv} W {W} K {K} {x.elem}")
+        return (H, Hkv, W, K, _t(z, dev)), None, dict(sink=z), "scan_heads_sink_logits"
     if entry == "alibi":
         slopes = ops.alibi_slopes(H)
         return (H, Hkv, W, K, _t(slopes, dev)), None, dict(slopes=slopes), "scan_heads_alibi"
@@ -179,13 +206,19 @@ def _lean_twice(mli, dev, x, elem, what, want_counts, entry="scan", extra=(), H=
 
 
 def _judge(oracle, x, got, rows, path, elem, H=1, Hkv=None, window=0, sinks=0, **biased):
+    """asserts; returns {family: tolerance}"""
     res = lc.judge_rows(oracle, x.case, x.values_of, got, rows, H, Hkv, window, sinks, **biased)
     failures = []
+    tols = {}
     for family, (err, e_or) in sorted(res.items()):
         ck = Checker(family, elem)
         ck.check(path, "attention", np.asarray(err), np.asarray(e_or))
         failures += ck.failures
+        tols[family] = fm.tolerance(np.asarray(e_or))
+        if biased.get("sink") is not None:
+            SINK_RATIOS.append(float(np.max(err)) / tols[family])
     assert not failures, "\n".join(failures)
+    return tols
 
 
 # ---- single-head chunked scan: rows ------------------------------------------------------------------------------------------
@@ -290,8 +323,8 @@ def test_chunked_scan_beyond_the_arrival_counters(oracle, mli, dev, elem):
 
 # ---- single-head chunked scan: width -----------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=1)
-def _wide_case(D):
-    return lc.SparseCase(4200 + D, [0, 1, 16, 17, 63, 64, 127, 100], 128, D, families={6: "late_peak", 7: "offset-", 4: "early_peak"})
+def _wide_case(D, flat=False):
+    return lc.wide_case(D, flat)
 
 
 WIDE_SHAPES = [("f32", 2048), ("bf16", 4096), ("fp8", 2048)]
@@ -499,14 +532,7 @@ def test_equal_shares_lds_frontier(oracle, mli, dev, D, elem, side):
 # ---- multi-head family -------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=2)
 def _heads_case(D):
-    rng = np.random.default_rng(4600)
-    B = 16384
-    L = rng.integers(0, 41, size=B).astype(np.int32)
-    L[rng.random(B) < 0.4] = 0
-    named = {0: 63, 8191: 63, 16383: 63, 1: 0, 2: 1, 3: 16, 4: 17, 5: 18, 6: 21, 7: 33, 16382: 20, 16381: 0}
-    for b, n in named.items():
-        L[b] = n
-    return lc.SparseCase(4601, L, 64, D), sorted(named)
+    return lc.heads_case(D)
 
 
 # (entry point, arguments behind emb_dim, emb_dim, H, Hkv, W, K)
@@ -517,7 +543,10 @@ HEAD_FORMS = {"heads": ("heads", (2,), 128, 2, 2, 0, 0), "window": ("window", (2
               "alibi": ("alibi", None, 128, 2, 2, 0, 0), "alibi_gqa": ("alibi", None, 128, 2, 1, 0, 0),
               "alibi_sinks": ("alibi", None, 128, 2, 2, 16, 4),
               "softcap": ("softcap", None, 128, 2, 2, 0, 0), "softcap_gqa": ("softcap", None, 128, 2, 1, 0, 0),
-              "softcap_window": ("softcap", None, 128, 2, 2, 17, 0)}
+              "softcap_window": ("softcap", None, 128, 2, 2, 17, 0),
+              # the scan with sink logits: its plain, grouped, windowed and sinks kernels (three differently templated ones)
+              "sink_logits": ("sink_logits", None, 128, 2, 2, 0, 0), "sink_logits_gqa": ("sink_logits", None, 128, 2, 1, 0, 0),
+              "sink_logits_window": ("sink_logits", None, 128, 2, 2, 17, 0), "sink_logits_sinks": ("sink_logits", None, 128, 2, 2, 16, 4)}
 
 
 @pytest.mark.parametrize("elem", ["f32", "bf16"])
@@ -530,10 +559,11 @@ def test_heads_family_on_the_last_row(oracle, mli, dev, form, elem):
     case, named = _heads_case(D)
     x = _pages(case, elem, dev)
     counter, q, kw = "scan_heads_window", None, {}
+    rows = lc.sample_rows(case.B, named)
     if extra is None:
-        extra, q, kw, counter = _biased(entry, case, H, Hkv, W, K, dev)
+        extra, q, kw, counter = _biased(entry, case, H, Hkv, W, K, dev, x=x, rows=rows)
     got = _lean_twice(mli, dev, x, elem, f"{form} {elem}", {counter: 1}, entry=entry, extra=extra, H=H, q=q)
-    _judge(oracle, x, got, lc.sample_rows(case.B, named), f"limits: B 16384, {form}", elem, H=H, Hkv=Hkv, window=W, sinks=K, **kw)
+    _judge(oracle, x, got, rows, f"limits: B 16384, {form}", elem, H=H, Hkv=Hkv, window=W, sinks=K, **kw)
 
 
 @pytest.mark.parametrize("elem", ["f32", "bf16"])
@@ -560,25 +590,97 @@ def test_heads_on_the_last_arrival_counter(oracle, mli, dev, elem):
 
 @functools.lru_cache(maxsize=1)
 def _merge_case():
-    fams = tuple("early_peak" if h % 2 else "late_peak" for h in range(32))
-    return lc.SparseCase(4700, [16383, 129], 16384, 1024, families={0: fams, 1: fams}, H=32)
+    return lc.merge_case()
 
 
-MERGE_FORMS = ["heads", "window", "alibi", "softcap"]
+MERGE_FORMS = ["heads", "window", "alibi", "softcap", "sink_logits", "sink_logits_window"]
 
 
 @pytest.mark.parametrize("form", MERGE_FORMS)
 def test_merge_statistics_fill_their_lds(oracle, mli, dev, form):
     """bf16 (2, 16384, 1024) with 32 heads: the plan raises the item size to 128 and the last arriver stages 128 x 32 = 4096
     pairs, all the LDS the merge has; plain and under W 8192.  early_peak on odd heads, late_peak on even ones.  Both rows
-    judged, head by head."""
+    judged, head by head.
+    With sink logits the last arriver loops over 128 published pairs per head and adds the sink exactly once; the 32 logits
+    come from the two judged rows, head by head.  A second launch takes the logits of heads 8 .. 31 rotated by one (head h is
+    given the logit of head h + 1, head 31 that of head 8) and those of heads 0 .. 7 untouched: heads 0 .. 7 keep their bits and
+    every one of heads 8 .. 31 moves by more than the tolerance on both rows -- a kernel that read the logit of a neighbouring
+    head, or of head h mod 8, could not pass both launches."""
     x = _pages(_merge_case(), "bf16", dev)
-    entry, extra, W = {"heads": ("heads", (32,), 0), "window": ("window", (32, 8192), 8192)}.get(form, (form, None, 0))
+    entry, extra, W = {"heads": ("heads", (32,), 0), "window": ("window", (32, 8192), 8192),
+                       "sink_logits_window": ("sink_logits", None, 8192)}.get(form, (form, None, 0))
     counter, q, kw = "scan_heads_window", None, {}
     if extra is None:
-        extra, q, kw, counter = _biased(entry, x.case, 32, 32, 0, 0, dev)
+        extra, q, kw, counter = _biased(entry, x.case, 32, 32, W, 0, dev, x=x, rows=[0, 1])
     got = _lean_twice(mli, dev, x, "bf16", f"32 heads {form}", {counter: 1}, entry=entry, extra=extra, H=32, q=q)
-    _judge(oracle, x, got, [0, 1], f"limits: 32 heads, {form}", "bf16", H=32, window=W, **kw)
+    tols = _judge(oracle, x, got, [0, 1], f"limits: 32 heads, {form}", "bf16", H=32, window=W, **kw)
+    if entry != "sink_logits":
+        return
+    z = kw["sink"]
+    turned = z.copy()
+    turned[8:] = np.roll(z[8:], -1)
+    assert (turned[:8] == z[:8]).all() and (turned[8:] != z[8:]).all() and turned[31] == z[8] and turned[8] == z[9]
+    other = _lean_twice(mli, dev, x, "bf16", f"32 heads {form}, logits of heads 8 .. 31 rotated", {counter: 1}, entry=entry,
+                        extra=extra[:4] + (_t(turned, dev),), H=32)
+    hd = x.case.D // 32
+    assert_equal(other[:, :8 * hd], got[:, :8 * hd], what="heads 0 .. 7 under the rotated logits")
+    for b in (0, 1):
+        K, V = x.values_of(b)
+        for h, (cols, model, _) in enumerate(lc.row_truth(oracle, x.case.q[b], K, V, 32, 32, W, 0, sink=z)):
+            if h >= 8:
+                moved = float(np.abs(other[b, cols].astype(np.float64) - got[b, cols]).max() / model.o_scale[0])
+                assert moved > tols[x.case.family(b, h)], f"row {b} head {h}: the rotated logits move the result by {moved:.3e} only"
+
+
+@functools.lru_cache(maxsize=1)
+def _family_case(pair):
+    return lc.sink_family_case(pair)
+
+
+SINK_PAIRS = list(lc.SINK_FAMILY_PAIRS)
+
+
+@pytest.mark.parametrize("elem", ["bf16", "f32"])
+@pytest.mark.parametrize("pair", SINK_PAIRS, ids=["-".join(p) for p in SINK_PAIRS])
+def test_score_families_against_the_sink(oracle, mli, dev, pair, elem):
+    """(24, 1024, 256) with 8 heads on 2 K/V heads at chunk_tokens 64 -- 16 items per row, the sink added once by the last
+    arriver -- on rows of 1, 63, 64, 65, 1008, 1023, 0 and random lengths whose K/V heads carry the score families two by two
+    (flat and peaked, offset+ and offset-, late_peak and early_peak; a group's query heads score 1, 1.125, 1.25 and 1.375 times
+    the first): rows whose own scores sit at +-200 or carry a peak 30 high in their first or last page, where the items' maxima
+    and the sink's logit lie far apart.  Two launches, all rows judged:
+      1. the logits learned per head from what the pages hold (the condition on them asserted): the model;
+      2. z = 0 on every head, the "off-by-one" softmax: the offset+ heads give the bits of mli_decode_scan_paged_gqa (expf of
+         -200 and less is 0), the offset- heads are finite and at most exp(-150) max|V| in magnitude, the others the model."""
+    case = _family_case(pair)
+    x = _pages(case, elem, dev)
+    rows = list(range(case.B))
+    H, Hkv, hd = 8, 2, 32
+    what = f"families {'/'.join(pair)} {elem}"
+    try:
+        _tune(mli, chunk_tokens=64)
+        plain = _lean_twice(mli, dev, x, elem, what + " gqa", {"scan_heads_window": 1}, entry="gqa", extra=(H, Hkv, 0, 0), H=H)
+        extra, _, kw, counter = _biased("sink_logits", case, H, Hkv, 0, 0, dev, x=x, rows=rows)
+        got = _lean_twice(mli, dev, x, elem, what + " learned", {counter: 1}, entry="sink_logits", extra=extra, H=H)
+        _judge(oracle, x, got, rows, f"limits: score families against the sink, {'/'.join(pair)}", elem, H=H, Hkv=Hkv, **kw)
+        live = case.lengths > 0
+        assert np.abs(got - plain)[live].max() > 1e-3, f"{what}: the logits change nothing"
+        zero = np.zeros(H, np.float32)
+        got0 = _lean_twice(mli, dev, x, elem, what + " z = 0", {counter: 1}, entry="sink_logits", extra=(H, Hkv, 0, 0, _t(zero, dev)), H=H)
+        fams = [case.family(rows[0], h) for h in range(H)]
+        top_v = max(float(np.abs(x.values_of(b)[1]).max()) for b in rows if case.lengths[b])
+        for h, family in enumerate(fams):
+            cols = slice(h * hd, (h + 1) * hd)
+            if family == "offset+":
+                assert_equal(got0[:, cols], plain[:, cols], what=f"{what}: z = 0 on offset+ head {h} against the _gqa call")
+            elif family == "offset-":
+                assert np.isfinite(got0[:, cols]).all() and np.abs(got0[:, cols]).max() <= np.exp(-150.0) * top_v, \
+                    f"{what}: z = 0 on offset- head {h}: {np.abs(got0[:, cols]).max():.3e}"
+        rest = [h for h, family in enumerate(fams) if not family.startswith("offset")]
+        if rest:
+            _judge(oracle, x, got0, rows, f"limits: score families against the sink, {'/'.join(pair)}, z = 0", elem, H=H, Hkv=Hkv,
+                   sink=zero, heads=rest)
+    finally:
+        _tune(mli, **DEFAULTS)
 
 
 # ---- contiguous scan ---------------------------------------------------------------------------------------------------------
@@ -816,8 +918,8 @@ def test_offsets_beyond_2_31_contiguous(oracle, mli, dev):
 
 # ---- window extremes ---------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=1)
-def _window_case():
-    return lc.SparseCase(4980, [0, 1, 2, 15, 16, 17, 31, 32, 33, 48, 62, 63], 64, 64, families={11: "late_peak", 10: "offset-"})
+def _window_case(D=64, flat=False):
+    return lc.window_case(D, flat)
 
 
 # (entry point, W, K, windowed kernel?) on (12, 64, 64): the last windows the windowed kernels take, and the first hand-offs
@@ -845,20 +947,42 @@ def test_window_extremes(oracle, mli, dev, elem, H, entry, W, K, windowed):
                 assert np.array_equal(got[b], x.values_of(b)[1][-1]), f"W 1: row {b} is not V's newest row"
 
 
-BIASED_WINDOW_CALLS = [(e, W, K, w) for e in ("alibi", "softcap") for W, K, w in ((63, 0, True), (64, 0, False), (59, 4, True), (60, 4, False))]
+BIASED_WINDOW_CALLS = [(e, W, K, w) for e in ("alibi", "softcap", "sink_logits")
+                       for W, K, w in ((63, 0, True), (64, 0, False), (59, 4, True), (60, 4, False))] + [("sink_logits", 1, 0, True)]
 
 
 @pytest.mark.parametrize("entry,W,K,windowed", BIASED_WINDOW_CALLS)
 @pytest.mark.parametrize("elem", ["f32", "bf16"])
 def test_window_extremes_biased(oracle, mli, dev, elem, entry, W, K, windowed):
     """test_window_extremes for the biased and the capped scan at two heads: W 63 and K 4 + W 59 are the last windows they take,
-    W 64 and K 4 + W 60 the plain mask (the same kernel family counts either way: the result is the evidence).  All rows judged."""
-    case = _window_case()
+    W 64 and K 4 + W 60 the plain mask (the same kernel family counts either way: the result is the evidence).  All rows judged.
+    With sink logits, on (12, 64, 128) without score families (one logit per head serves every row): both sides of the hand-off
+    count as "scan_heads_sink_logits" -- the plain kind has its own sunk kernel --, the hand-offs give the bits of W 0 under the
+    same logits, and W 1 is V's newest row times 1 / (1 + exp(z - x_newest)), computed here in float64 and held at the judge's
+    tolerance."""
+    sunk = entry == "sink_logits"
+    case = _window_case(128, True) if sunk else _window_case()
     x = _pages(case, elem, dev)
-    extra, q, kw, counter = _biased(entry, case, 2, 2, W, K, dev)
+    rows = list(range(case.B))
+    extra, q, kw, counter = _biased(entry, case, 2, 2, W, K, dev, x=x, rows=rows)
     got = _lean_twice(mli, dev, x, elem, f"{entry} W {W} K {K} {elem}", {counter: 1}, entry=entry, extra=extra, H=2, q=q)
-    _judge(oracle, x, got, list(range(case.B)), f"limits: window extremes, {entry} W {W} K {K}", elem, H=2,
-           window=W if windowed else 0, sinks=K if windowed else 0, **kw)
+    tols = _judge(oracle, x, got, rows, f"limits: window extremes, {entry} W {W} K {K}", elem, H=2,
+                  window=W if windowed else 0, sinks=K if windowed else 0, **kw)
+    if sunk and not windowed:
+        plain = _lean_twice(mli, dev, x, elem, f"{entry} W 0 K 0 {elem}", {counter: 1}, entry=entry, extra=(2, 2, 0, 0, extra[4]), H=2)
+        assert_equal(got, plain, what=f"{entry} W {W} K {K}: the bits of W 0")
+    if sunk and W == 1:
+        z = kw["sink"].astype(np.float64)
+        for b in rows:
+            if case.lengths[b]:
+                Kb, Vb = x.values_of(b)
+                for h in range(2):
+                    cols = slice(64 * h, 64 * h + 64)
+                    newest = float(Kb[-1, cols].astype(np.float64) @ case.q[b, cols].astype(np.float64)) / 8.0
+                    want = Vb[-1, cols].astype(np.float64) / (1.0 + np.exp(z[h] - newest))
+                    # the condition scale of this head is |V[newest]| times the same factor
+                    err = float(np.abs(got[b, cols] - want).max() / np.abs(want).max())
+                    assert err <= tols["flat"], f"W 1: row {b} head {h} is {err:.3e} from the closed form"
 
 
 # ---- the merge statistics against the launch's LDS -----------------------------------------------------------------------------
@@ -900,15 +1024,31 @@ def test_heads_widest_rows(oracle, mli, dev, elem, D, H):
     _judge(oracle, x, got, list(range(8)), "limits: several heads, widest rows", elem, H=H)
 
 
-@pytest.mark.parametrize("entry", ["alibi", "softcap"])
+@pytest.mark.parametrize("entry", ["alibi", "softcap", "sink_logits"])
 @pytest.mark.parametrize("elem,D,H", HEADS_WIDE)
 def test_heads_widest_rows_biased(oracle, mli, dev, elem, D, H, entry):
-    """test_heads_widest_rows with the ALiBi bias and with the cap: the widest rows of their own kernel families
-    ("scan_heads_alibi" / "scan_heads_softcap" counts the launch).  All rows judged."""
-    x = _pages(_wide_case(D), elem, dev)
-    extra, q, kw, counter = _biased(entry, x.case, H, H, 0, 0, dev)
+    """test_heads_widest_rows with the ALiBi bias, with the cap and with sink logits: the widest rows of their own kernel
+    families ("scan_heads_alibi" / "scan_heads_softcap" / "scan_heads_sink_logits" counts the launch).  All rows judged.
+    Sink logits: head size 128 at both lanes-per-head settings (fp32 32 lanes, bf16 16), two lane loads; the rows carry no
+    score families (one logit per head serves every row).  A second launch puts +1e30 on the last head, which lies in the
+    second lane load: exact zeros there on every non-empty row, the other heads' bits unchanged."""
+    sunk = entry == "sink_logits"
+    x = _pages(_wide_case(D, sunk), elem, dev)
+    rows = list(range(8))
+    extra, q, kw, counter = _biased(entry, x.case, H, H, 0, 0, dev, x=x, rows=rows)
     got = _lean_twice(mli, dev, x, elem, f"{entry} D {D} {elem}", {counter: 1}, entry=entry, extra=extra, H=H, q=q)
-    _judge(oracle, x, got, list(range(8)), f"limits: several heads, widest rows, {entry}", elem, H=H, **kw)
+    _judge(oracle, x, got, rows, f"limits: several heads, widest rows, {entry}", elem, H=H, **kw)
+    if sunk:
+        import sink_logits_model as sl
+        assert sl.second_lane_load(H - 1, H, D, lc.EPL[elem]) and not sl.second_lane_load(0, H, D, lc.EPL[elem])
+        far = kw["sink"].copy()
+        far[H - 1] = 1e30
+        zeros = _lean_twice(mli, dev, x, elem, f"{entry} D {D} {elem}, +1e30 on head {H - 1}", {counter: 1}, entry=entry,
+                            extra=extra[:4] + (_t(far, dev),), H=H)
+        hd = D // H
+        assert not zeros[:, (H - 1) * hd:].any(), "the +1e30 head is not exactly zero"
+        assert_equal(zeros[:, :(H - 1) * hd], got[:, :(H - 1) * hd], what="the other heads under +1e30 on the last")
+        _judge(oracle, x, zeros, rows, f"limits: several heads, widest rows, {entry}, +1e30", elem, H=H, sink=far)
 
 
 # ---- standalone launchers ------------------------------------------------------------------------------------------------------
@@ -989,31 +1129,49 @@ def test_softmax_v_vector_and_scalar_form(oracle, mli, dev, B, S, D):
 
 
 # ---- the causal prompt scan ----------------------------------------------------------------------------------------------------
-def _prompt_twice(dev, x, segs, qv, elem, H, Hkv, W, K, cap, what):
-    """mli_prompt_scan_paged[_softcap] twice: the same bits, one launch of the family each, nothing else; [n_q, D] on the host"""
+def _prompt_twice(dev, x, segs, qv, elem, H, Hkv, W, K, cap, what, sink=None):
+    """mli_prompt_scan_paged[_softcap / _sink_logits] twice: the same bits, one launch of the family each, nothing else;
+    [n_q, D] on the host"""
     from min_llm_inference_amd import ops
     c = x.case
     q_dev = _t(qv, dev)
+    z_dev = None if sink is None else _t(np.asarray(sink, np.float32), dev)
     ops.reset_launch_counts()
     res = []
     for _ in range(2):
         out = torch.full(qv.shape, lc.SENTINEL, device=dev)
-        ops.prompt_scan_paged(q_dev, x.table, segs, out, c.B, c.S, lc.ELEM[elem], n_heads=H, n_kv_heads=Hkv, window=W, sinks=K, softcap=cap)
+        ops.prompt_scan_paged(q_dev, x.table, segs, out, c.B, c.S, lc.ELEM[elem], n_heads=H, n_kv_heads=Hkv, window=W, sinks=K, softcap=cap,
+                              sink_logits=z_dev)
         res.append(host(out).copy())
     assert_equal(res[1], res[0], what=f"{what}: second launch")
     want = {f: 0 for f in SCAN_FAMILIES}
-    want["scan_prompt" if cap is None else "scan_prompt_softcap"] = 2
+    want["scan_prompt_sink_logits" if sink is not None else "scan_prompt" if cap is None else "scan_prompt_softcap"] = 2
     assert _counts() == want, f"{what}: launch counters {_counts()}"
     assert np.isfinite(res[0]).all() and (res[0] != lc.SENTINEL).any(axis=1).all(), what
     return res[0]
 
 
-def _prompt_judged(oracle, dev, x, segs, elem, H, Hkv, W, K, what, cap=None, q_rows=None):
+def _prompt_judged(oracle, dev, x, segs, elem, H, Hkv, W, K, what, cap=None, q_rows=None, sunk=False):
+    """sunk: with sink logits learned per head from the queries themselves (limit_cases.learned_sparse over what the pages hold,
+    the condition on them asserted); all -inf then gives the bits of the plain launch"""
     rows, pos = pm.queries(segs)
     qv = pm.query_vectors(x.case.q if q_rows is None else q_rows, rows, pos)
-    got = _prompt_twice(dev, x, segs, qv, elem, H, Hkv, W, K, cap, what)
-    truth = pm.long_truth(oracle, x.case, x.values_of, qv, rows, pos, H, Hkv, W, K, cap=cap)
-    pm.hm.assert_within(pm.long_compare(got, truth, what=what), what)
+    z = None
+    if sunk:
+        import sink_logits_model as sl
+        lse = lc.judged_lse(x.case, x.values_of, rows, H, Hkv, *_mask(x.case.S, W, K), q=qv, lengths=pos + 1)
+        z = lc.learned_sparse(lse)
+        print(f"SINK_LOGITS {what}: logits {[round(float(t), 2) for t in z]}; share in the band on {lc.biting(lse, z, what):.2f} of the judged pairs")
+    got = _prompt_twice(dev, x, segs, qv, elem, H, Hkv, W, K, cap, what, sink=z)
+    truth = pm.long_truth(oracle, x.case, x.values_of, qv, rows, pos, H, Hkv, W, K, cap=cap, sink=z)
+    res = pm.long_compare(got, truth, what=what)
+    pm.hm.assert_within(res, what)
+    if sunk:
+        SINK_RATIOS.extend(worst / tol for _, worst, tol in res)
+        plain = _prompt_twice(dev, x, segs, qv, elem, H, Hkv, W, K, None, what + " plain")
+        assert np.abs(got - plain).max() > 1e-3, f"{what}: the logits change nothing"
+        assert_equal(_prompt_twice(dev, x, segs, qv, elem, H, Hkv, W, K, None, what + " all -inf", sink=sl.none(H)), plain,
+                     what=f"{what}: all -inf against the plain launch")
     return got
 
 
@@ -1032,9 +1190,17 @@ def test_prompt_scan_widest_rows(oracle, mli, dev, elem, D):
     segs = [(1, 90, 10), (0, 128 - (tq + 1), tq + 1), (3, 15, 2), (2, 0, 2 * tq + 1)]
     for W, K in ((0, 0), (40, 4)):
         _prompt_judged(oracle, dev, x, segs, elem, 1, 1, W, K, f"limits: prompt scan, widest rows, D {D} {elem} W {W} K {K}")
+    # the same width with several heads and sink logits (the single-head kernels have none): fp32 D 512 H 4, bf16 D 1024 H 8 on
+    # 2, head size 128; rows without score families, one logit per head serving every query; "scan_prompt_sink_logits" counts
+    H, Hkv = (4, 4) if elem == "f32" else (8, 2)
+    flat = lc.SparseCase(5300 + D, [128, 100, 64, 17], 128, D, full_rows=True)
+    x = _pages(flat, elem, dev)
+    for W, K in ((0, 0), (40, 4)):
+        _prompt_judged(oracle, dev, x, segs, elem, H, Hkv, W, K, f"limits: prompt scan, widest rows, sink logits, D {D} H {H}/{Hkv} {elem} W {W} K {K}",
+                       sunk=True)
 
 
-PROMPT_ROWS = [(1, None), (2, None), (2, CAP)]
+PROMPT_ROWS = [(1, None), (2, None), (2, CAP), (2, "sink_logits")]
 
 
 @pytest.mark.parametrize("elem", ["f32", "bf16"])
@@ -1049,6 +1215,9 @@ def test_prompt_scan_on_the_last_row(oracle, mli, dev, H, cap, elem):
     x = _pages(case, elem, dev)
     tq = ops.prompt_scan_tq(D, H, lc.ELEM[elem])
     segs = [(16383, 62 - tq, tq + 1), (7, 30, 3), (0, 0, 2 * tq + 1), (8191, 40, tq)]
+    if cap == "sink_logits":        # two heads with sink logits: "scan_prompt_sink_logits" counts the launch
+        _prompt_judged(oracle, dev, x, segs, elem, H, H, 0, 0, f"limits: prompt scan, B 16384, H {H} sink logits {elem}", sunk=True)
+        return
     _prompt_judged(oracle, dev, x, segs, elem, H, H, 0, 0, f"limits: prompt scan, B 16384, H {H} cap {cap} {elem}", cap=cap,
                    q_rows=None if cap is None else _scaled_q(case, H, H))
 
