@@ -629,10 +629,10 @@ int launch_stream_decode(const float* q, const void* const* page_table, const in
     } else if (nj == 1) {
         if (nt) MLI_ST_LAUNCH(1, true, 8, 4);
         else MLI_ST_LAUNCH(1, false, 8, 4);
-    } else if (kRowF <= 512) {
+    } else if constexpr (2 * kWave * E::EPL <= 512) {   // kRowF at two lane loads, a constant of the element type: fp32 ...
         if (nt) MLI_ST_LAUNCH(2, true, 4, 4);
         else MLI_ST_LAUNCH(2, false, 4, 4);
-    } else {
+    } else {                                            // ... and bf16 (the other pair is instantiated for neither)
         if (nt) MLI_ST_LAUNCH(2, true, 4, 2);
         else MLI_ST_LAUNCH(2, false, 4, 2);
     }

@@ -130,11 +130,13 @@ static int launch_gemm(const GemmArgs& g, int rows, int z, bool vec4, hipStream_
     // 128-row tiles when they still fill the chip (>= 2 workgroups per CU) -- decode projection / logits of a large
     // batch; the prefill fill keeps 64-row tiles (a new row's prompt rarely fills 128 rows)
     constexpr bool kTallOk = MODE == kPagedLatest || MODE == kNaiveLatest || MODE == kPlain;
-    if (kTallOk && vec4 && gemm_use_tall_tiles((int64_t)tiles_x * ceil_div_i(rows, 128) * z)) {
-        dim3 grid(tiles_x, ceil_div_i(rows, 128), z);
-        count_launch(kLfGemmF32Rows128);
-        hipLaunchKernelGGL((gemm_f32_mfma_kernel<MODE, BT, true, false, 2>), grid, dim3(kGemmThreads), 0, st, g);
-        return launch_status();
+    if constexpr (kTallOk) {   // (if constexpr: the fills instantiate no 128-row kernel that nothing can launch)
+        if (vec4 && gemm_use_tall_tiles((int64_t)tiles_x * ceil_div_i(rows, 128) * z)) {
+            dim3 grid(tiles_x, ceil_div_i(rows, 128), z);
+            count_launch(kLfGemmF32Rows128);
+            hipLaunchKernelGGL((gemm_f32_mfma_kernel<MODE, BT, true, false, 2>), grid, dim3(kGemmThreads), 0, st, g);
+            return launch_status();
+        }
     }
     dim3 grid(tiles_x, ceil_div_i(rows, BM), z);
     if (g.compact && (MODE == kNaiveFill || MODE == kPagedFill || MODE == kPagedFillLive))

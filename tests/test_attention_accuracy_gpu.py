@@ -290,6 +290,73 @@ def test_paged_stages(oracle, mli, dev, seed, B, S, D, chunks, family):
         ck.done()
 
 
+# ---- the non-temporal instantiations (tests/kernel_coverage.json) ------------------------------------------------------------
+# By itself nt_loads_rule (scan_plan.hpp) picks non-temporal K / V loads beyond 768 MiB of K / V only; the cases below force them
+# with mli_tune "nt_loads" = 1 at the smallest shapes that reach each kernel, under the judges above.
+@pytest.mark.parametrize("seed,B,S,D,chunks", [s for s in SCAN_SHAPES if s[0] in (131, 134, 135)])
+def test_stages_and_contiguous_scan_with_non_temporal_loads(oracle, mli, dev, seed, B, S, D, chunks):
+    """test_contiguous_stages_and_scan and test_paged_stages under nt_loads 1.  There for
+    D 64:   softmax_v_partial_kernel<4, 1, false, true> (contiguous) and <4, 1, true, true> (paged);
+    D 512:  softmax_v_partial_kernel<4, 2, false, true>, naive_decode_scan_kernel<2, true>;
+    D 2048: softmax_v_partial_bf16_kernel<2, true>."""
+    try:
+        assert mli.mli_tune(b"nt_loads", 1) == 0
+        test_contiguous_stages_and_scan(oracle, mli, dev, seed, B, S, D, chunks, "flat")
+        test_paged_stages(oracle, mli, dev, seed, B, S, D, chunks, "flat")
+    finally:
+        mli.mli_tune(b"nt_loads", 2)
+
+
+@pytest.mark.parametrize("elem,D", [("f32", 512), ("f32", 1024), ("bf16", 1024), ("bf16", 2048), ("bf16", 4096)])
+def test_paged_scan_materialising_with_non_temporal_loads(oracle, mli, dev, elem, D):
+    """mli_decode_scan_paged, materialising and lean (chunked grid), under nt_loads 1: B 14, S 128 (two items per row).  There for
+    fused_decode_scan_kernel<E, NJ, NT = true, TBR, DS, SCORES, 1> with SCORES = true, which test_paged_scan runs under the default
+    policy only -- f32 D 512: <ElemF32, 2, true, 4, false, true, 1>; f32 D 1024 (the waves split the row): <ElemF32, 1, true, 8, true,
+    true, 1>; bf16 D 1024: <ElemBF16, 2, true, 4, false, true, 1>; bf16 D 2048: <ElemBF16, 1, true, 8, true, true, 1>; bf16 D 4096:
+    <ElemBF16, 2, true, 4, true, true, 1> and the lean <ElemBF16, 2, true, 4, true, false, 1>."""
+    from min_llm_inference_amd import ops
+    B, S = 14, 128
+    x = _paged_inputs(oracle, dev, _base(171, B, S, D, (64,)), "flat", elem)
+    assert x.lengths.min() == 0 and x.lengths.max() == S - 1
+    ck = Checker("flat", elem)
+    e_o, e_p = fm.attention_error(x.oracle[2], x.model), fm.probability_error(x.oracle[1], x.model)
+    try:
+        assert mli.mli_tune(b"scan_stream", 0) == 0
+        got = {}
+        for nt in (0, 1):
+            assert mli.mli_tune(b"nt_loads", nt) == 0
+            qkt = torch.full((B, S), SENTINEL, device=dev)
+            out = torch.full((B, D), SENTINEL, device=dev)
+            ops.decode_scan_paged(x.q, x.page_table, x.L, qkt, out, ELEM[elem], phases=3)
+            ck.check(f"paged scan, materialising, nt_loads {nt}", "attention", fm.attention_error(host(out), x.model), e_o)
+            ck.check(f"paged scan, materialising, nt_loads {nt}", "probabilities", fm.probability_error(host(qkt), x.model), e_p)
+            lean = _lean_twice(ops, x, elem, f"lean, nt_loads {nt}")
+            ck.check(f"paged scan, lean, nt_loads {nt}", "attention", fm.attention_error(lean, x.model), e_o)
+            got[nt] = (host(out).copy(), host(qkt).copy(), lean)
+        for a, b, what in zip(got[1], got[0], ("attention_result", "probabilities", "lean attention_result")):
+            assert_equal(a, b, what=f"{elem} D {D} {what}: nt_loads 1 against nt_loads 0")
+    finally:
+        mli.mli_tune(b"scan_stream", 1)
+        mli.mli_tune(b"nt_loads", 2)
+    ck.done()
+
+
+@pytest.mark.parametrize("D", [128, 1536])
+def test_equal_page_shares_scan_under_both_cache_policies(oracle, mli, dev, D):
+    """test_equal_page_shares_scan (9 rows of n_sequence 1024, the lengths of STREAM_CASES' emb_dim-1024 case) under nt_loads 0 and 1.
+    There for the fp8 kernels no other judged case launches (tests/kernel_coverage.json):
+      D 128:  fused_decode_stream_kernel<ElemFP8, 1, true, 2, 4, 4> (four token slots per load instruction, non-temporal);
+      D 1536: fused_decode_stream_kernel<ElemFP8, 2, NT, 4, 2, 1> (two lane loads: emb_dim 1040 .. 2047 on fp8 pages; more than
+              64 KiB of dynamic LDS).  fp32 and bf16 pages of that width take the chunked scan."""
+    lengths = [0, 1023, 0, 0, 16, 17, 512, 1, 1008]
+    try:
+        for nt in (0, 1):
+            assert mli.mli_tune(b"nt_loads", nt) == 0
+            test_equal_page_shares_scan(oracle, mli, dev, 197, len(lengths), 1024, D, lengths, "flat")
+    finally:
+        mli.mli_tune(b"nt_loads", 2)
+
+
 # ---- the fp32 compositions, from the inputs -------------------------------------------------------------------------------
 # (seed, B, S, D): one chunk, several chunks, the long rows
 COMPOSITION_SHAPES = [(151, 24, 64, 512), (153, 20, 1024, 256), (154, 18, 4096, 512), (155, 20, 256, 1024)]

@@ -627,3 +627,21 @@ def test_full_batch_logits_wave_split_is_bit_identical(mli, dev, B, V, D):
     assert int(res[0]["toks"][5]) == V // 7, "ties go to the lowest index"
     want = (host(attn).astype(np.float64) @ host(emb).astype(np.float64).T)
     assert_close(res[0]["score"], want.astype(np.float32), thr=1e-3, what="logits vs float64")
+
+
+def test_stream_copy_copies_every_bit(mli, dev):
+    """mli_stream_copy (stream_copy_kernel, the copy the bandwidth probes time): the destination gets the source's bits -- random
+    bit patterns, NaNs included; more float4s than the grid has threads, so the stride loop runs -- and nothing behind them is
+    written.  The kernel has no floating-point result for a model to judge: tests/test_kernel_coverage_cpu.py exempts it on
+    this test."""
+    from min_llm_inference_amd import ops
+    n = 4 * (256 * 16 * 256 + 12345)                    # float4s: one full grid and a ragged tail
+    g = torch.Generator(device="cpu").manual_seed(77)
+    bits = torch.randint(-2 ** 31, 2 ** 31 - 1, (n + 64,), dtype=torch.int32, generator=g).to(dev)
+    src = bits.view(torch.float32)
+    dst = torch.full((n + 64,), 12345.0, device=dev)
+    ops.stream_copy(src[:n], dst[:n])
+    torch.cuda.synchronize()
+    assert torch.equal(dst[:n].view(torch.int32), bits[:n])
+    assert (dst[n:] == 12345.0).all()
+    assert mli.mli_stream_copy(None, None, 6, None) != 0, "a count that is no multiple of 4 is refused"

@@ -209,3 +209,15 @@ def test_self_attention_lean_refuses_what_it_does_not_cover(mli, dev):
     with pytest.raises(ops.MliError):
         ops.self_attention_lean(d["inp"], d["lengths"], d["wk"], d["wq"], d["wv"], d["new_batch_idx"], d["kt_cache"],
                                 d["v_cache"], d["q_output"], d["attention_result"], c["n_new"])
+
+
+@pytest.mark.parametrize("seed,B,S,Din,Dout", [(11, 7, 412, 101, 257), (17, 5, 128, 64, 50)])
+def test_softmax_v_with_non_temporal_loads(oracle, mli, dev, seed, B, S, Din, Dout):
+    """test_softmax_v under mli_tune "nt_loads" = 1 at widths that are no multiple of 4 (tests/kernel_coverage.json): there for
+    softmax_v_partial_kernel<1, 2, false, true> (257 columns) and <1, 1, false, true> (50 columns), which by itself only a batch
+    beyond 768 MiB of V selects."""
+    try:
+        assert mli.mli_tune(b"nt_loads", 1) == 0
+        test_softmax_v(oracle, mli, dev, seed, B, S, Din, Dout)
+    finally:
+        mli.mli_tune(b"nt_loads", 2)

@@ -240,6 +240,30 @@ def test_live_fill_under_a_window(oracle, mli, dev, fmt, fc, pf):
            (gemm, "fill_flat" if fc else "fill_per_row", fused), W=W, K=K)
 
 
+LIVE_FILL_FORMS = [
+    # The other kernels of the live fill (tests/kernel_coverage.json): gemm_f32_mfma_rope_kernel<kPagedFillLive, ...> and, from the
+    # un-rotated call of (b), gemm_f32_mfma_kernel<kPagedFillLive, ...> with the same arguments.
+    # id, fmt, D, H, knobs, families, shifted weights
+    ("f32-live-fill-split-D256-H4", "f32", 256, 4, {"fc": 1, "pf": 0, "split": 1},           # <5, false, true, false, 1, true>
+     ("gemm_f32_rows64_split", "fill_flat", "prefill_two_launch"), False),
+    ("f32-live-fill-scalar-loads-D68-H1", "f32", 68, 1, {"fc": 1, "pf": 0, "split": 0},      # <5, false, false, false, 1, false>
+     ("gemm_f32_rows64", "fill_flat", "prefill_two_launch"), True),
+    ("bf16-live-fill-widened-D128-H4", "bf16", 128, 4, {"fc": 1, "pf": 0, "native": 0},      # <5, false, true, true, 1, false>
+     ("gemm_bf16_widened", "fill_flat", "prefill_two_launch"), False),
+]
+
+
+@pytest.mark.parametrize("fmt,D,H,knobs,families,shift", [pytest.param(*c[1:], id=c[0]) for c in LIVE_FILL_FORMS])
+def test_live_fill_under_a_window_other_forms(oracle, mli, dev, request, fmt, D, H, knobs, families, shift):
+    """test_live_fill_under_a_window's rows and window at the widths and knobs that take the live fill to its split, scalar-load
+    and fp32-widened kernels"""
+    W, K = 32, 4
+    rng = np.random.default_rng(3100 + D)
+    L = np.array([100, 20, 0, 100, 50, 7, 128, 100], np.int32)
+    c = gm.Case(3100 + D, "paged", fmt, "signed", 8, 128, D, D, L, rng.permutation(8).astype(np.int32), 8, vocab=40)
+    _check(oracle, mli, dev, request.node.callspec.id, c, "prefill", H, knobs, families, W=W, K=K, shift=shift)
+
+
 # ---- positions past slot 127 and the smallest head sizes ----------------------------------------------------------------------------
 @pytest.mark.parametrize("fmt", ["f32", "bf16", "fp8"])
 def test_long_prefill_then_latest(oracle, mli, dev, fmt):

@@ -219,3 +219,31 @@ def test_lean_sinks_composition(oracle, mli, dev, elem, H):
     hm.assert_within(res, f"mli_paged_attention_lean_sinks {elem} H{H}")
     assert not np.array_equal(host(kept.out), host(plain.out)), "a window of 40 with 4 sinks gives what no window gives"
     assert not np.array_equal(host(kept.out), host(cut.out)), "4 sinks give what the window alone gives"
+
+
+@pytest.mark.parametrize("elem,D", [("f32", 1024), ("bf16", 4096)])
+def test_rows_split_across_the_waves_at_the_other_lane_counts(oracle, mli, dev, elem, D):
+    """One head on rows of more than two lane loads (the four waves split the row, DS): SINK_SHAPES has emb_dim 2048, which is two
+    lane loads per wave on fp32 pages and one on bf16 pages.  Here the other two, with sinks (K 4) and without (K 0: the windowed
+    kernel), under both nt_loads settings (tests/kernel_coverage.json):
+      f32 D 1024:  window_decode_scan_kernel<ElemF32, 1, NT, 8, true, 1, SINK>
+      bf16 D 4096: window_decode_scan_kernel<ElemBF16, 2, NT, 4, true, 1, SINK>"""
+    from min_llm_inference_amd import ops
+    seed, B, S, W = 507, 8, 128, 40
+    results = []
+    try:
+        for K in (4, 0):
+            for part in range(len(sm.sink_lengths(seed, B, S, W, 4))):
+                x = _inputs(oracle, dev, _base(seed, B, S, D, W, 4, part), 1, W, K, "flat", elem)
+                got = {}
+                for nt in (0, 1):
+                    assert mli.mli_tune(b"nt_loads", nt) == 0
+                    what = f"B{B} S{S} D{D} H1 W{W} K{K} {elem} part {part} nt_loads {nt}"
+                    got[nt] = _scan(ops, x, elem)
+                    assert (got[nt][x.lengths == 0] == 0).all(), f"{what}: rows of length 0"
+                    results += hm.compare(got[nt], x.oracle, x.model, "flat", what=what)
+                assert_equal(got[1], got[0], what=f"{what}: nt_loads 1 against nt_loads 0")
+                assert_equal(_scan(ops, x, elem), got[1], what=f"{what}: second launch")
+    finally:
+        mli.mli_tune(b"nt_loads", 2)
+    hm.assert_within(results, f"B{B} S{S} D{D} H1 W{W} {elem}")
