@@ -255,6 +255,22 @@ int mli_engine_set_softcap(mli_engine* engine, float cap);
  * combination).  Without the call nothing changes anywhere. */
 int mli_engine_set_sink_logits(mli_engine* engine, const float* logits_host, int n);
 
+/* EXTENSION: the grouped-query scan on matrix instructions (mli_kernels.h: mli_paged_attention_lean_gqa_mfma).  Every decode
+ * scan of the engine runs n_heads query heads on n_kv_heads K/V heads (a divisor of n_heads; equal: plain multi-head attention)
+ * through that kernel, which takes the rows the lane-group scan of mli_engine_set_heads refuses: head_dim = emb_dim / n_heads 64
+ * or 128, n_heads / n_kv_heads 1 .. 8, emb_dim to 8192 (mli_gqa_mfma_shape_supported).  The call sets both head counts and the
+ * switch together, so it stands in place of mli_engine_set_heads / _set_kv_heads, which afterwards accept only the counts the
+ * engine has; calling it again changes them.  Pages, pool, prefill, projection and the decoder head are untouched: the model is
+ * that of mli_engine_set_kv_heads, only the first n_kv_heads * head_dim columns of K / V are read.  Before the first step or
+ * run; MLI_ENGINE_PAGED_BF16 with lean layers.  Composes with mli_engine_set_window, _set_page_release, _set_rope[_table] (after
+ * this call: the table is sized by the heads), _set_logprobs, sampling, both loops, n_forward_rounds and preemption.  -1 with a
+ * message naming the reason for a null or started engine, every other kind, lean_layers = 0 (mli_engine_configure(e, 0, ...)
+ * afterwards is refused likewise), counts that do not divide, a shape the kernel does not take, a stored rotary table of another
+ * head count, and -- the kernel has none of them -- an engine with sink tokens (mli_engine_set_sinks), ALiBi, a soft cap, sink
+ * logits or prompt log-probabilities; each of those five setters refuses likewise when it comes second.  Without the call
+ * nothing changes anywhere. */
+int mli_engine_set_heads_mfma(mli_engine* engine, int n_heads, int n_kv_heads);
+
 /* EXTENSION: sliding-window attention (mli_kernels.h: mli_paged_attention_lean_window).  Every row attends its newest
  * `window` tokens only.  The window changes which slots the scan reads and nothing else: admission, page growth,
  * preemption, re-prefill, n_forward_rounds (the window follows the device-side length), step graphs, sampling and the

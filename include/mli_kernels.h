@@ -463,6 +463,39 @@ int mli_paged_attention_lean_sink_logits(void* const* page_table, const int* len
                                          int window, int n_sink, const float* sink_logits, const float* rope_table, int elem,
                                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- EXTENSION: the grouped-query decode scan on matrix instructions -------------------------------------------
+ * Grouped-query attention as mli_decode_scan_paged_gqa defines it (query head h attends K/V head h / g, g = n_heads /
+ * n_kv_heads; window <= 0 or >= n_sequence: none, else the row attends slots [max(0, L - window), L)), computed by another
+ * kernel: one workgroup per (row, K/V head, item), the g query heads of the group as columns of one MFMA tile, so every K and V
+ * byte is loaded once per K/V head and the row's width is no limit.  Opt-in: no other entry point ever dispatches it, at the
+ * shapes both kernels take included.  Results agree with the _gqa call within the project's fp32 tolerance, not in bits.
+ * mli_gqa_mfma_shape_supported: 1 for bf16 pages (elem MLI_ELEM_BF16), head_dim = emb_dim / n_heads 64 or 128, g any integer
+ * 1 .. MLI_GQA_MFMA_MAX_GROUP (g = 1: multi-head attention), emb_dim <= 8192, n_sequence a multiple of 16 (g = 1: at most
+ * 262144, the items whose statistics the merge can stage), and n_batch * n_kv_heads <= 16384 (the rows the arrival counters
+ * count); else 0.
+ * mli_gqa_mfma_workspace_bytes: the workspace the calls below need at most (arrival counters | (m, l) per (row, K/V head, 64
+ * tokens, head of the group) | partial rows), 0 for a shape that is not supported.  The layout is the other lean scans': one
+ * zero-initialised buffer serves them all.
+ * One launch ("scan_gqa_mfma").  MLI_ERR_BAD_ARG, before anything is launched: a shape mli_gqa_mfma_shape_supported refuses,
+ * a null data pointer.  MLI_ERR_WORKSPACE: the row has several items and the workspace is missing or too small.  There are no
+ * sink tokens, no ALiBi, no soft-cap and no sink logits in this kernel. */
+#define MLI_GQA_MFMA_MAX_GROUP 8
+int mli_gqa_mfma_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads, int elem);
+size_t mli_gqa_mfma_workspace_bytes(int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads);
+int mli_decode_scan_paged_gqa_mfma(const float* q_output, const void* const* page_table, const int* lengths,
+                                   float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                   int n_kv_heads, int window, void* workspace, size_t workspace_bytes, void* stream);
+
+/* fill (n_new_items rows) -> latest -> the scan above.  rope_table: null, or the table of mli_paged_attention_lean_rope (then
+ * fill and latest are that call's: K and q rotated).  n_sink and elem exist to be refused: MLI_ERR_BAD_ARG for n_sink != 0 and
+ * for any elem but MLI_ELEM_BF16, for a null weight pointer and, with a table, as
+ * mli_paged_attention_lean_rope. */
+int mli_paged_attention_lean_gqa_mfma(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                      const int* new_batch_idx, float* q_output, float* attention_result, int n_batch,
+                                      int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
+                                      int n_sink, const float* rope_table, int elem, void* workspace, size_t workspace_bytes,
+                                      void* stream);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */
@@ -899,6 +932,7 @@ int mli_tune(const char* key, int value);
  *   "scan_prompt_softcap"    the prompt scan with logit soft-capping (mli_prompt_scan_paged_softcap)
  *   "scan_heads_sink_logits" the multi-head scans with a learned sink logit per query head (mli_decode_scan_paged_sink_logits)
  *   "scan_prompt_sink_logits" the prompt scan with a learned sink logit per query head (mli_prompt_scan_paged_sink_logits)
+ *   "scan_gqa_mfma"          the grouped-query scan on matrix instructions (mli_decode_scan_paged_gqa_mfma)
  * Forms, counted beside the launch's kernel family:
  *   "latest_compact"         a decode projection over the compacted list of non-empty rows ("latest_compact"; the panel and
  *                            the LDS-DMA kernel have no such list)
@@ -911,6 +945,9 @@ int mli_tune(const char* key, int value);
  *                            first / in grid order ("scan_row_order") */
 int mli_launch_count(const char* family, unsigned long long* count);
 int mli_launch_counts_reset(void);
+/* The name of family or form `index` (0, 1, ... in no particular order), null from the first index past the last: how a caller
+ * lists every name mli_launch_count knows, for "nothing else ran" checks that stay complete when a family is added. */
+const char* mli_launch_family_name(int index);
 
 /* The resident slice of "scan_resident_mib", restated for tests and tools.  mli_scan_resident_threshold: the threshold
  * (0 .. 65536) of a launch whose rows hold total_pages pages in all (elem: MLI_ELEM_*; MLI_ERR_BAD_ARG for another tag, a

@@ -80,6 +80,10 @@ SIGNATURES = {
     "mli_paged_attention_lean_softcap": [_P] * 8 + [_I] * 8 + [ctypes.c_float, _P, _I, _P, _Z, _P],
     "mli_decode_scan_paged_sink_logits": [_P] * 4 + [_I] * 7 + [_P, _I, _P, _Z, _P],
     "mli_paged_attention_lean_sink_logits": [_P] * 8 + [_I] * 8 + [_P, _P, _I, _P, _Z, _P],
+    "mli_gqa_mfma_shape_supported": [_I] * 6,
+    "mli_gqa_mfma_workspace_bytes": [_I] * 5,
+    "mli_decode_scan_paged_gqa_mfma": [_P] * 4 + [_I] * 6 + [_P, _Z, _P],
+    "mli_paged_attention_lean_gqa_mfma": [_P] * 8 + [_I] * 8 + [_P, _I, _P, _Z, _P],
     "mli_rope_table": [_I, _I, ctypes.c_double, _P],
     "mli_get_latest_k_q_v_paged_rope": [_P] * 6 + [_I] * 4 + [_P, _I, _P],
     "mli_fill_new_k_v_cache_paged_rope": [_P] * 5 + [_I] * 5 + [_P, _I, _P],
@@ -127,6 +131,7 @@ SIGNATURES = {
     "mli_tune": [ctypes.c_char_p, _I],
     "mli_launch_count": [ctypes.c_char_p, ctypes.POINTER(ctypes.c_ulonglong)],
     "mli_launch_counts_reset": [],
+    "mli_launch_family_name": [_I],
     "mli_scan_resident_threshold": [ctypes.c_longlong, _I, _I, _I],
     "mli_scan_resident_keeps": [_P, _I],
     "mli_stream_copy": [_P, _P, _Z, _P],
@@ -174,6 +179,7 @@ ENGINE_SIGNATURES = {
     "mli_engine_set_window": [_P, _I],
     "mli_engine_set_sinks": [_P, _I],
     "mli_engine_set_kv_heads": [_P, _I],
+    "mli_engine_set_heads_mfma": [_P, _I, _I],
     "mli_engine_set_alibi": [_P, _P, _I],
     "mli_engine_set_softcap": [_P, ctypes.c_float],
     "mli_engine_set_sink_logits": [_P, _P, _I],
@@ -206,6 +212,7 @@ class ShardStats(ctypes.Structure):
 
 _RESTYPES = {"mli_shard_last_error": ctypes.c_char_p, "mli_shard_group_destroy": None, "mli_shard_group_engine": _P,
              "mli_attention_workspace_bytes": _Z, "mli_attention_heads_workspace_bytes": _Z,
+             "mli_gqa_mfma_workspace_bytes": _Z, "mli_launch_family_name": ctypes.c_char_p,
              "mli_decoder_scratch_bytes": _Z, "mli_prompt_logprobs_scratch_bytes": _Z,
              "mli_sample_scratch_bytes": _Z, "mli_decoder_sampled_scratch_bytes": _Z, "mli_engine_last_error": ctypes.c_char_p,
              "mli_engine_destroy": None, "mli_engine_set_lean_layers": None,

@@ -738,6 +738,10 @@ int mli_launch_count(const char* family, unsigned long long* count) {
     return 0;
 }
 
+const char* mli_launch_family_name(int index) {
+    return index >= 0 && index < mli::kLaunchFamilies ? mli::kLaunchFamilyNames[index] : nullptr;
+}
+
 int mli_launch_counts_reset(void) {
     for (int f = 0; f < mli::kLaunchFamilies; ++f) mli::g_launch_counts[f] = 0;
     return 0;

@@ -84,6 +84,9 @@ int launch_heads_softcap_scan(const float*, const void* const*, const int*, floa
 template <class E>
 int launch_heads_sink_logits_scan(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, ScanKind,
                                   int, int, const float*, void*, size_t, hipStream_t);
+// ... and the grouped-query scan on matrix instructions (attention_gqa_mfma_bf16.hip: B, S, D, n_heads, n_kv_heads, window)
+int launch_gqa_mfma_decode(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, void*, size_t,
+                           hipStream_t);
 
 // EXTENSION, rotary position embeddings (proj_gemm.hip): the projection and the fills with K and q rotated in the epilogue
 int rope_half(int D, int n_heads, const float* table);
@@ -701,6 +704,59 @@ int mli_paged_attention_lean_sink_logits(void* const* page_table, const int* len
     return mli::launch_sink_logits_scan(kind, q_output, reinterpret_cast<const void* const*>(page_table), lengths,
                                         attention_result, n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink,
                                         sink_logits, elem, workspace, workspace_bytes, st);
+}
+
+// ---- EXTENSION: the grouped-query scan on matrix instructions (attention_gqa_mfma.hpp) -----------------------------------------
+int mli_gqa_mfma_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads, int elem) {
+    return mli::gqa_mfma_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, elem) ? 1 : 0;
+}
+
+size_t mli_gqa_mfma_workspace_bytes(int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads) {
+    if (!mli::gqa_mfma_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, MLI_ELEM_BF16)) return 0;
+    // items of 64 tokens at the least: (m, l) per (virtual row, item, head of the group) and one partial row per (row, item)
+    const size_t nchunk = (size_t)mli::ceil_div_i(n_sequence, 64);
+    return mli::kArrivalRegionBytes + mli::scan_stats_bytes(n_batch * n_kv_heads, n_sequence, n_heads / n_kv_heads) +
+           (nchunk <= 1 ? 0 : (size_t)n_batch * nchunk * (size_t)emb_dim * sizeof(float));
+}
+
+int mli_decode_scan_paged_gqa_mfma(const float* q_output, const void* const* page_table, const int* lengths,
+                                   float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                   int n_kv_heads, int window, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!mli::gqa_mfma_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, MLI_ELEM_BF16)) return MLI_ERR_BAD_ARG;
+    if (q_output == nullptr || page_table == nullptr || lengths == nullptr || attention_result == nullptr) return MLI_ERR_BAD_ARG;
+    const mli::WsBody body = mli::ws_body(workspace, workspace_bytes);
+    const int w = mli::lean_scan_kind(n_sequence, window, 0) == mli::kScanWindow ? window : 0;
+    return mli::launch_gqa_mfma_decode(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
+                                       n_kv_heads, w, body.ptr, body.bytes, mli::as_stream(stream));
+}
+
+// fill -> latest (both rotated where a table is given) -> the scan above
+int mli_paged_attention_lean_gqa_mfma(void* const* page_table, const int* lengths, const void* wk, const void* wq, const void* wv,
+                                      const int* new_batch_idx, float* q_output, float* attention_result, int n_batch,
+                                      int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
+                                      int n_sink, const float* rope_table, int elem, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    if (n_sink != 0 || !mli::gqa_mfma_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, elem)) return MLI_ERR_BAD_ARG;
+    if (page_table == nullptr || lengths == nullptr || q_output == nullptr || attention_result == nullptr || wk == nullptr ||
+        wq == nullptr || wv == nullptr)
+        return MLI_ERR_BAD_ARG;
+    if (rope_table != nullptr && mli::rope_half(emb_dim, n_heads, rope_table) < 0) return MLI_ERR_BAD_ARG;
+    hipStream_t st = mli::as_stream(stream);
+    int rc;
+    if (rope_table != nullptr) {
+        rc = mli::launch_fill_paged_rope(elem, nullptr, nullptr, nullptr, page_table, new_batch_idx, lengths, wk, wv, n_batch,
+                                         n_sequence, emb_dim, n_new_items, false, 0, 0, n_heads, rope_table, st);
+        if (!rc)
+            rc = mli::launch_latest_paged_rope(elem, page_table, lengths, wk, wq, wv, q_output, n_batch, n_sequence, emb_dim,
+                                               n_heads, rope_table, st);
+    } else {
+        rc = mli::launch_fill_and_latest(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, n_batch, n_sequence,
+                                         emb_dim, n_new_items, st);
+    }
+    if (rc) return rc;
+    return mli_decode_scan_paged_gqa_mfma(q_output, reinterpret_cast<const void* const*>(page_table), lengths, attention_result,
+                                          n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, workspace, workspace_bytes,
+                                          stream);
 }
 
 int mli_get_latest_k_q_v_paged_lean(void* const* page_table, const int* lengths, const void* wk, const void* wq,

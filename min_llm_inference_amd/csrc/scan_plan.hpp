@@ -241,6 +241,24 @@ inline int gqa_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_h
 // constexpr, so that the kernel and a host program (tests/cpp/gqa_map_test.cpp) compile this text.
 constexpr int gqa_kv_unit(int u, int lg, int g) { return (((u >> lg) / g) << lg) + (u & ((1 << lg) - 1)); }
 
+// ---- the grouped-query scan on matrix instructions (attention_gqa_mfma.hpp) --------------------------------------------------
+// One workgroup per (row, K/V head, item): bf16 pages, head_dim 64 or 128, g = n_heads / n_kv_heads any integer 1 ..
+// MLI_GQA_MFMA_MAX_GROUP (the M rows of one MFMA tile hold the group), emb_dim to 8192 (the row's width shapes nothing in the
+// kernel; 8192 = 64 heads of 128), and B * n_kv_heads virtual rows within the arrival counters.  The last rule is
+// heads_lanes_log2's, over the g heads of a virtual row (g = 1: n_sequence to 262144).
+inline bool gqa_mfma_shape_ok(int B, int S, int D, int H, int Hkv, int elem) {
+    if (elem != MLI_ELEM_BF16) return false;
+    if (B <= 0 || S <= 0 || S % kPlanPage != 0 || D <= 0 || D > 8192 || H < 1 || D % H != 0) return false;
+    if (Hkv < 1 || Hkv > H || H % Hkv != 0 || H / Hkv > MLI_GQA_MFMA_MAX_GROUP) return false;
+    const int hd = D / H;
+    if (hd != 64 && hd != 128) return false;
+    if ((long long)B * Hkv > kPlanMaxRows) return false;
+    // the statistics of a row's items must fit the LDS the last arriver stages them in: scan_item_tokens raises the item size
+    // to kMaxItemTokens for that where a virtual row has several heads, and leaves items of 64 tokens where it has one
+    const int g = H / Hkv;
+    return (long long)plan_ceil_div(S, g > 1 ? kMaxItemTokens : 64) * g <= kMaxMergeStats;
+}
+
 // ---- the causal multi-query prompt scan (attention_prompt.hpp) --------------------------------------------------------------
 // What it takes: fp32 and bf16 pages with rows of at most two lane loads -- one head: fp32 to emb_dim 512, bf16 to 1024;
 // several heads, with or without grouped K/V heads: what heads_lanes_log2 / gqa_shape_supported accept.  n_kv_heads ==

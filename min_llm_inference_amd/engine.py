@@ -40,7 +40,7 @@ class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
                  n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None,
                  release_pages=False, n_kv_heads=None, logprobs=None, prompt_logprobs=False, alibi=None,
-                 rope=None, softcap=None, sink_logits=None):
+                 rope=None, softcap=None, sink_logits=None, heads_mfma=False):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -48,10 +48,13 @@ class Engine:
         assert keep[0][0].shape == (n_vocab, emb_dim) and keep[1][0].shape == (n_sequence, emb_dim)
         self._h = ctypes.c_void_p()
         self._check(self._lib.mli_engine_create(ctypes.byref(self.cfg), *[k[1] for k in keep], ctypes.byref(self._h)))
-        if n_heads != 1:
-            self.set_heads(n_heads)
-        if n_kv_heads is not None:
-            self.set_kv_heads(n_kv_heads)
+        if heads_mfma:      # both head counts and the switch in one call: shapes set_heads / set_kv_heads refuse
+            self.set_heads_mfma(n_heads, n_heads if n_kv_heads is None else n_kv_heads)
+        else:
+            if n_heads != 1:
+                self.set_heads(n_heads)
+            if n_kv_heads is not None:
+                self.set_kv_heads(n_kv_heads)
         if window is not None:
             self.set_window(window)
         if sinks is not None:
@@ -84,6 +87,14 @@ class Engine:
         serve the query heads; only the first n_kv_heads * emb_dim / n_heads output columns of wk / wv matter.  Before the
         first step or run, fp32 / bf16 paged kinds; n_kv_heads == n_heads changes nothing."""
         self._check(self._lib.mli_engine_set_kv_heads(self._h, int(n_kv_heads)))
+
+    def set_heads_mfma(self, n_heads, n_kv_heads):
+        """The grouped-query scan on matrix instructions (mli_engine_set_heads_mfma): `n_heads` query heads on `n_kv_heads` K/V
+        heads (a divisor; equal: plain multi-head attention) at head_dim 64 or 128, groups of 1 .. 8 and emb_dim up to 8192 --
+        the wide rows set_heads refuses.  Stands in place of set_heads / set_kv_heads.  Before the first step or run, the bf16
+        paged kind with lean layers; with a window, page release, RoPE, logprobs and sampling, not with sink tokens, ALiBi, a
+        soft cap, sink logits or prompt log-probabilities."""
+        self._check(self._lib.mli_engine_set_heads_mfma(self._h, int(n_heads), int(n_kv_heads)))
 
     def set_alibi(self, slopes=None):
         """ALiBi (mli_engine_set_alibi): every decode scan adds slopes[h] * (s - (L - 1)) to query head h's scaled scores.

@@ -25,6 +25,7 @@ private:  // the fp8 scan has one head: of the option setters the layer has set_
     using PagedAttentionOptionSetters::set_alibi_slopes;
     using PagedAttentionOptionSetters::set_softcap;
     using PagedAttentionOptionSetters::set_sink_logits;
+    using PagedAttentionOptionSetters::set_heads_mfma;
 };
 
 class PagedAttentionFp8InferenceModel : public PagedInferenceModel {
@@ -40,6 +41,7 @@ private:
     using PagedAttentionOptionSetters::set_alibi_slopes;
     using PagedAttentionOptionSetters::set_softcap;
     using PagedAttentionOptionSetters::set_sink_logits;
+    using PagedAttentionOptionSetters::set_heads_mfma;
     DecoderHead& decoder_head() override { return decoder_head_; }
     PagedAttentionFp8Layer attention_layer_;
     // lean only: the scratch of mli_decoder_scratch_bytes, and the logits buffer once sampling is set

@@ -67,11 +67,15 @@ struct PagedAttentionOptions {
     // one more logit of the head's softmax without a value row, in the decode scan and in the prompt scan --
     // mli_paged_attention_lean_sink_logits, mli_paged_prompt_logprobs_sink_logits
     std::shared_ptr<TensorFloat> sink_logits;
+    // The grouped-query scan on matrix instructions (bf16 pages; head_dim 64 or 128, groups of 1 .. 8 query heads, rows up to
+    // 8192 wide) in place of the lane-group scan -- mli_paged_attention_lean_gqa_mfma.  Plain and windowed, with or without a
+    // rotary table; it has no sink tokens, slopes, cap or sink logits.
+    bool heads_mfma = false;
 };
 
 // The setters of the option set, defined once for every class that has them: a layer owns the struct, a model hands out
 // its layer's.  A class whose scan has one head only (fp8 pages) takes set_n_heads / set_n_kv_heads / set_alibi_slopes /
-// set_softcap / set_sink_logits out of its interface.
+// set_softcap / set_sink_logits / set_heads_mfma out of its interface.
 class PagedAttentionOptionSetters {
 public:
     // EXTENSION: ALiBi -- slopes[h] * (s - (L - 1)) added to query head h's scaled scores; n_heads finite values, uploaded
@@ -97,6 +101,12 @@ public:
     // n_heads (>= 2), the lean layers and neither slopes nor a cap beside it at every forward, whichever setter came last
     // (PagedAttentionLayerCore::check_sink_logits).
     void set_sink_logits(const float* host, int n);
+    // EXTENSION: the MFMA grouped-query scan -- n_heads query heads on n_kv_heads K/V heads (a divisor of n_heads; equal: plain
+    // multi-head attention) decoded by mli_paged_attention_lean_gqa_mfma, which takes the wide rows the lane-group scan refuses.
+    // Sets the two head counts and the switch together; set_heads_mfma(0, 0) takes the switch away and leaves the counts.  Counts
+    // that do not divide throw here; bf16 pages, the kernel's shape, the lean layers and none of sink tokens, slopes, cap or sink
+    // logits beside it are held at every forward, whichever setter came last (PagedAttentionLayerCore::check_heads_mfma).
+    void set_heads_mfma(int n_heads, int n_kv_heads);
     void set_n_heads(int n_heads) { options().n_heads = n_heads; }
     void set_n_kv_heads(int n_kv_heads) { options().n_kv_heads = n_kv_heads; }
     void set_window(int window) { options().window = window; }
@@ -144,6 +154,10 @@ protected:
     // materialising composition has no sink logit and must never drop it silently), or ALiBi slopes or a cap stand beside them
     // (no model defines that): first thing in every forward
     void check_sink_logits() const;
+    // throws where the MFMA scan is switched on and the pages are not bf16, the kernel does not take the shape, the lean layers
+    // are off, or sink tokens, slopes, a cap or sink logits stand beside it (the kernel has none, and must never drop one
+    // silently): first thing in every forward
+    void check_heads_mfma() const;
 
     int elem_;
     Weights wk_, wq_, wv_;

@@ -73,6 +73,7 @@ PagedAttentionBf16Layer::PagedAttentionBf16Layer(TensorBf16&& wk, TensorBf16&& w
 void PagedAttentionBf16Layer::forward(TensorFloatPoint& page_table, const TensorInt& lengths,
                                       const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                       int n_new_items) {
+    check_heads_mfma();
     check_sink_logits();
     check_softcap();
     check_alibi();
@@ -80,7 +81,8 @@ void PagedAttentionBf16Layer::forward(TensorFloatPoint& page_table, const Tensor
     if (mli::runtime::lean_paged_wanted(options_.n_heads, options_.window, (int)n_sequence_)) {
         const int rc = lean_scan(page_table, lengths, new_batch_idx, attention_result, n_new_items, options_.n_heads,
                                  options_.n_kv_heads);
-        if (rc != MLI_ERR_BAD_ARG || wk_.shape()[0] <= 4096) {  // rows wider than the single-pass kernel covers: fall through
+        // rows wider than the single-pass kernel covers: fall through (never beside the MFMA scan, which throws on every failure)
+        if (rc != MLI_ERR_BAD_ARG || wk_.shape()[0] <= 4096 || options_.heads_mfma) {
             HIP_CHECK(rc);
             return;
         }

@@ -570,6 +570,8 @@ int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
     MLI_GUARD({
         if (e->started) throw std::runtime_error("mli_engine_configure after the engine has started");
         PagedAttentionOptions& o = e->options();
+        if (o.heads_mfma && lean_layers == 0)   // (named first: what else the engine has set rides on it)
+            throw std::runtime_error("the MFMA grouped-query scan (mli_engine_set_heads_mfma) has the lean compositions only");
         if (o.sink_logits && lean_layers == 0)   // (named first: an engine with sink logits has two heads at least)
             throw std::runtime_error("attention-sink logits (mli_engine_set_sink_logits) have the lean compositions only");
         if (o.softcap != 0.f && lean_layers == 0)   // (named first: an engine with a cap has two heads at least)
@@ -599,6 +601,9 @@ int mli_engine_set_heads(mli_engine* e, int n_heads) {
         if (n_heads < 1) throw std::runtime_error("mli_engine_set_heads: n_heads must be >= 1");
         if (n_heads != o.n_heads) {
             if (e->started) throw std::runtime_error("mli_engine_set_heads after the engine has started");
+            if (o.heads_mfma)
+                throw std::runtime_error("mli_engine_set_heads: the heads of an engine with the MFMA scan are those of "
+                                         "mli_engine_set_heads_mfma (call it again to change them)");
             if (!e->heads_kind())
                 throw std::runtime_error("mli_engine_set_heads: multi-head attention serves the fp32 and bf16 paged engines");
             if (n_heads > 1 && !e->lean_layers)
@@ -641,6 +646,9 @@ int mli_engine_set_kv_heads(mli_engine* e, int n_kv_heads) {
         const int then = n_kv_heads == o.n_heads ? 0 : n_kv_heads;
         if (then != o.n_kv_heads) {
             if (e->started) throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads cannot change after the engine has started");
+            if (o.heads_mfma)
+                throw std::runtime_error("mli_engine_set_kv_heads: the K/V heads of an engine with the MFMA scan are those of "
+                                         "mli_engine_set_heads_mfma (call it again to change them)");
             if (then != 0) {
                 // (n_heads > 1 here, so set_heads has accepted the kind, the lean layers and the shape; checked again all the same)
                 if (!e->heads_kind())
@@ -656,6 +664,45 @@ int mli_engine_set_kv_heads(mli_engine* e, int n_kv_heads) {
     })
 }
 
+// The switch and the two head counts are stored with the option set together: the shape is the MFMA scan's own
+// (gqa_mfma_shape_ok), so it is not held to what set_heads / set_kv_heads accept.  What the kernel does not have is refused
+// here and, for a later call, in that call's own setter.
+int mli_engine_set_heads_mfma(mli_engine* e, int n_heads, int n_kv_heads) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("null argument");
+        if (e->started) throw std::runtime_error("mli_engine_set_heads_mfma after the engine has started");
+        if (e->cfg.kind != MLI_ENGINE_PAGED_BF16)
+            throw std::runtime_error("mli_engine_set_heads_mfma: the MFMA grouped-query scan serves the bf16 paged engine");
+        if (!e->lean_layers)
+            throw std::runtime_error("mli_engine_set_heads_mfma: the MFMA grouped-query scan has the lean compositions only");
+        if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0)
+            throw std::runtime_error("mli_engine_set_heads_mfma: n_kv_heads must be >= 1 and divide n_heads");
+        if (!mli::gqa_mfma_shape_ok(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, n_kv_heads, e->elem()))
+            throw std::runtime_error("mli_engine_set_heads_mfma: unsupported (n_batch, emb_dim, n_heads, n_kv_heads): head_dim must "
+                                     "be 64 or 128, n_heads / n_kv_heads at most 8, emb_dim at most 8192 and n_batch * n_kv_heads "
+                                     "at most 16384");
+        PagedAttentionOptions& o = e->options();
+        if (o.n_sink != 0)
+            throw std::runtime_error("mli_engine_set_heads_mfma: not with sink tokens (mli_engine_set_sinks: the kernel has none)");
+        if (o.alibi_slopes)
+            throw std::runtime_error("mli_engine_set_heads_mfma: not with ALiBi (mli_engine_set_alibi: the kernel has no position "
+                                     "bias)");
+        if (o.softcap != 0.f)
+            throw std::runtime_error("mli_engine_set_heads_mfma: not with logit soft-capping (mli_engine_set_softcap: the kernel "
+                                     "has no cap)");
+        if (o.sink_logits)
+            throw std::runtime_error("mli_engine_set_heads_mfma: not with attention-sink logits (mli_engine_set_sink_logits: the "
+                                     "kernel has no sink logit)");
+        if (e->prompt_logprobs_wanted)
+            throw std::runtime_error("mli_engine_set_heads_mfma: not with prompt log-probabilities "
+                                     "(mli_engine_set_prompt_logprobs: there is no prompt scan for its shapes)");
+        if (o.rope_table && n_heads != o.n_heads)
+            throw std::runtime_error("mli_engine_set_heads_mfma: the stored rotary table (mli_engine_set_rope) is that of " +
+                                     std::to_string(o.n_heads) + " heads");
+        e->paged->set_heads_mfma(n_heads, n_kv_heads);
+    })
+}
+
 // The slopes are stored with the option set (the layer owns the device copy).  The shapes are the multi-head scan's, which
 // set_heads / set_kv_heads / set_window have validated; they are checked again here.
 int mli_engine_set_alibi(mli_engine* e, const float* slopes_host, int n) {
@@ -665,6 +712,9 @@ int mli_engine_set_alibi(mli_engine* e, const float* slopes_host, int n) {
         if (!e->heads_kind())
             throw std::runtime_error("mli_engine_set_alibi: ALiBi serves the fp32 and bf16 paged engines");
         PagedAttentionOptions& o = e->options();
+        if (o.heads_mfma)
+            throw std::runtime_error("mli_engine_set_alibi: not with the MFMA grouped-query scan (mli_engine_set_heads_mfma: the "
+                                     "kernel has no position bias)");
         if (o.n_heads < 2)
             throw std::runtime_error("mli_engine_set_alibi: n_heads must be >= 2 (mli_engine_set_heads comes first; the "
                                      "single-head scans have no bias)");
@@ -706,6 +756,9 @@ int mli_engine_set_softcap(mli_engine* e, float cap) {
             throw std::runtime_error("mli_engine_set_softcap: the cap must be finite and >= 0 (0: none)");
         PagedAttentionOptions& o = e->options();
         if (cap != 0.f) {
+            if (o.heads_mfma)
+                throw std::runtime_error("mli_engine_set_softcap: not with the MFMA grouped-query scan (mli_engine_set_heads_mfma: "
+                                         "the kernel has no cap)");
             if (o.n_heads < 2)
                 throw std::runtime_error("mli_engine_set_softcap: n_heads must be >= 2 (mli_engine_set_heads comes first; the "
                                          "single-head scans have no cap)");
@@ -736,6 +789,9 @@ int mli_engine_set_sink_logits(mli_engine* e, const float* logits_host, int n) {
             throw std::runtime_error("mli_engine_set_sink_logits: attention-sink logits serve the fp32 and bf16 paged engines");
         PagedAttentionOptions& o = e->options();
         if (logits_host != nullptr) {
+            if (o.heads_mfma)
+                throw std::runtime_error("mli_engine_set_sink_logits: not with the MFMA grouped-query scan "
+                                         "(mli_engine_set_heads_mfma: the kernel has no sink logit)");
             if (o.n_heads < 2)
                 throw std::runtime_error("mli_engine_set_sink_logits: n_heads must be >= 2 (mli_engine_set_heads comes first; the "
                                          "single-head scans have no sink logit)");
@@ -820,7 +876,8 @@ int mli_engine_set_window(mli_engine* e, int window) {
             if (then < S) {
                 if (!e->lean_layers)
                     throw std::runtime_error("mli_engine_set_window: sliding-window attention has the lean compositions only");
-                if (!mli::window_shape_supported(e->cfg.n_batch, S, e->cfg.emb_dim, o.n_heads, e->elem()))
+                // (the MFMA scan takes a window at every shape mli_engine_set_heads_mfma has accepted)
+                if (!o.heads_mfma && !mli::window_shape_supported(e->cfg.n_batch, S, e->cfg.emb_dim, o.n_heads, e->elem()))
                     throw std::runtime_error("mli_engine_set_window: the windowed scan does not take this (n_batch, n_sequence, "
                                              "emb_dim, n_heads)");
             }
@@ -840,6 +897,9 @@ int mli_engine_set_sinks(mli_engine* e, int n_sink) {
             throw std::runtime_error("mli_engine_set_sinks: attention sinks serve the paged engines");
         if (n_sink != o.n_sink) {
             if (e->started) throw std::runtime_error("mli_engine_set_sinks after the engine has started");
+            if (o.heads_mfma && n_sink != 0)
+                throw std::runtime_error("mli_engine_set_sinks: not with the MFMA grouped-query scan (mli_engine_set_heads_mfma: "
+                                         "the kernel has no sink tokens)");
             if (!e->lean_layers)
                 throw std::runtime_error("mli_engine_set_sinks: attention sinks have the lean compositions only");
             o.n_sink = n_sink;
@@ -995,6 +1055,9 @@ int mli_engine_set_prompt_logprobs(mli_engine* e, int enabled) {
         if (enabled && e->options().rope_table)
             throw std::runtime_error("mli_engine_set_prompt_logprobs: not with RoPE (mli_engine_set_rope: the prompt scan's q is "
                                      "not rotated, so the prompt would be scored under another model than the one that decodes)");
+        if (enabled && e->options().heads_mfma)
+            throw std::runtime_error("mli_engine_set_prompt_logprobs: not with the MFMA grouped-query scan "
+                                     "(mli_engine_set_heads_mfma: there is no prompt scan for its shapes)");
         if (!e->prompt_shape_ok())
             throw std::runtime_error("mli_engine_set_prompt_logprobs: the prompt scan does not take this (n_batch, n_sequence, "
                                      "emb_dim, n_heads, n_kv_heads): rows of at most two 16-byte lane loads");

@@ -32,10 +32,10 @@ void mli::runtime::release_attention_scratch(void* stream) noexcept {
     for (auto it = g_scratch.begin(); it != g_scratch.end();) it = it->first.second == stream ? g_scratch.erase(it) : std::next(it);
 }
 
-mli::runtime::Scratch mli::runtime::attention_scratch(int n_batch, int n_sequence, int dim, int n_heads) {
+// the calling thread's buffer of (device, compute stream), grown to `need` bytes
+static mli::runtime::Scratch scratch_of(size_t need) {
     std::mutex& mu = g_scratch_mu;
     auto& per_device = g_scratch;
-    const size_t need = mli_attention_heads_workspace_bytes(n_batch, n_sequence, dim, n_heads);  // n_heads 1: the plain size
     if (need == 0) return {nullptr, 0};
     std::lock_guard<std::mutex> lock(mu);
     auto& slot = per_device[{mli::runtime::current_device(), mli::runtime::compute_stream()}];
@@ -46,6 +46,10 @@ mli::runtime::Scratch mli::runtime::attention_scratch(int n_batch, int n_sequenc
         HIP_CHECK(mli_attention_workspace_init(slot->data(), need, mli::runtime::compute_stream()));
     }
     return {slot->data(), need};
+}
+
+mli::runtime::Scratch mli::runtime::attention_scratch(int n_batch, int n_sequence, int dim, int n_heads) {
+    return scratch_of(mli_attention_heads_workspace_bytes(n_batch, n_sequence, dim, n_heads));  // n_heads 1: the plain size
 }
 
 // Per THREAD, like the device and the compute stream (an engine is driven by one thread at a time, and the engine C ABI
@@ -305,7 +309,19 @@ int mli::runtime::lean_paged_attention(int elem, int n_heads, int window, int n_
                                        const int* lengths, const void* wk, const void* wq, const void* wv,
                                        const int* new_batch_idx, float* q_output, float* attention_result, int B, int S, int D,
                                        int n_new_items, int n_kv_heads, const float* alibi_slopes, const float* rope_table,
-                                       float softcap, const float* sink_logits) {
+                                       float softcap, const float* sink_logits, bool heads_mfma) {
+    if (heads_mfma) {   // with or without a window or a rotary table; the kernel has no other form, and none is dropped
+        if (alibi_slopes != nullptr) throw std::runtime_error("the MFMA grouped-query scan and ALiBi are not combined");
+        if (softcap != 0.f) throw std::runtime_error("the MFMA grouped-query scan and logit soft-capping are not combined");
+        if (sink_logits != nullptr) throw std::runtime_error("the MFMA grouped-query scan and attention-sink logits are not combined");
+        if (n_sink != 0) throw std::runtime_error("the MFMA grouped-query scan and sink tokens are not combined");
+        const int Hkv = n_kv_heads != 0 ? n_kv_heads : n_heads;
+        const Scratch ws = scratch_of(mli_gqa_mfma_workspace_bytes(B, S, D, n_heads, Hkv));   // its own size: rows past 1024
+        HIP_CHECK(mli_paged_attention_lean_gqa_mfma(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B,
+                                                    S, D, n_new_items, n_heads, Hkv, window, 0, rope_table, elem, ws.ptr, ws.bytes,
+                                                    stream()));
+        return 0;
+    }
     const Scratch ws = attention_scratch(B, S, D, n_heads > 1 ? n_heads : 1);
     if (sink_logits != nullptr) {   // with or without a rotary table; never with slopes or a cap (the entry point takes none)
         if (alibi_slopes != nullptr) throw std::runtime_error("attention-sink logits and ALiBi are not combined");

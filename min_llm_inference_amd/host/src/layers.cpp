@@ -80,6 +80,18 @@ void PagedAttentionOptionSetters::set_sink_logits(const float* values, int n) {
     options().sink_logits = std::move(device);
 }
 
+void PagedAttentionOptionSetters::set_heads_mfma(int n_heads, int n_kv_heads) {
+    if (n_heads == 0 && n_kv_heads == 0) {
+        options().heads_mfma = false;
+        return;
+    }
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0)
+        throw std::invalid_argument("set_heads_mfma: n_kv_heads must be >= 1 and divide n_heads");
+    options().n_heads = n_heads;
+    options().n_kv_heads = n_kv_heads == n_heads ? 0 : n_kv_heads;
+    options().heads_mfma = true;
+}
+
 void PagedAttentionOptionSetters::set_rope_table(const std::vector<float>& table) {
     if (table.empty()) {
         options().rope_table.reset();
@@ -188,10 +200,29 @@ void PagedAttentionLayerCore<Weights>::check_sink_logits() const {
         throw std::runtime_error("attention-sink logits (set_sink_logits) and logit soft-capping (set_softcap) are not combined");
 }
 
+// As check_alibi: the switch is held to what the kernel takes where it is used, whichever setter came last.
+template <class Weights>
+void PagedAttentionLayerCore<Weights>::check_heads_mfma() const {
+    if (!options_.heads_mfma) return;
+    const int Hkv = options_.n_kv_heads != 0 ? options_.n_kv_heads : options_.n_heads;
+    if (!mli_gqa_mfma_shape_supported((int)q_output_.shape()[0], (int)n_sequence_, (int)wk_.shape()[0], options_.n_heads, Hkv, elem_))
+        throw std::runtime_error("the MFMA grouped-query scan (set_heads_mfma) takes bf16 pages, head_dim 64 or 128, groups of 1 .. "
+                                 "8 query heads and emb_dim <= 8192: not " + std::to_string(options_.n_heads) + " heads on " +
+                                 std::to_string(Hkv) + " K/V heads at emb_dim " + std::to_string(wk_.shape()[0]));
+    if (!mli::runtime::lean_layers()) throw std::runtime_error("the MFMA grouped-query scan exists in the lean composition only");
+    if (options_.n_sink != 0) throw std::runtime_error("the MFMA grouped-query scan (set_heads_mfma) has no sink tokens (set_sinks)");
+    if (options_.alibi_slopes) throw std::runtime_error("the MFMA grouped-query scan (set_heads_mfma) has no ALiBi (set_alibi_slopes)");
+    if (options_.softcap != 0.f) throw std::runtime_error("the MFMA grouped-query scan (set_heads_mfma) has no soft cap (set_softcap)");
+    if (options_.sink_logits) throw std::runtime_error("the MFMA grouped-query scan (set_heads_mfma) has no sink logits (set_sink_logits)");
+    if (options_.prompt_logprobs != nullptr)
+        throw std::runtime_error("the MFMA grouped-query scan (set_heads_mfma) has no prompt scan (set_prompt_logprobs)");
+}
+
 template <class Weights>
 int PagedAttentionLayerCore<Weights>::lean_scan(TensorFloatPoint& page_table, const TensorInt& lengths,
                                                 const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                                 int n_new_items, int n_heads, int n_kv_heads) {
+    check_heads_mfma();
     check_sink_logits();
     check_softcap();
     check_alibi();
@@ -203,7 +234,7 @@ int PagedAttentionLayerCore<Weights>::lean_scan(TensorFloatPoint& page_table, co
                                               (int)wk_.shape()[0], n_new_items, n_kv_heads,
                                               options_.alibi_slopes ? options_.alibi_slopes->data() : nullptr,
                                               options_.rope_table ? options_.rope_table->data() : nullptr, options_.softcap,
-                                              options_.sink_logits ? options_.sink_logits->data() : nullptr);
+                                              options_.sink_logits ? options_.sink_logits->data() : nullptr, options_.heads_mfma);
 }
 
 template class PagedAttentionLayerCore<TensorFloat>;
@@ -217,6 +248,7 @@ PagedAttentionFloatLayer::PagedAttentionFloatLayer(TensorFloat&& wk, TensorFloat
 bool PagedAttentionFloatLayer::forward_lean(TensorFloatPoint& page_table, const TensorInt& lengths,
                                             const TensorInt& new_batch_idx, TensorFloat& attention_result,
                                             int n_new_items) {
+    check_heads_mfma();
     check_sink_logits();
     check_softcap();
     check_alibi();

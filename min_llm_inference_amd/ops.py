@@ -55,16 +55,27 @@ def launch_count(family):
     return int(n.value)
 
 
+def launch_families():
+    """Every name launch_count knows (mli_launch_family_name), kernel families and forms alike."""
+    lib, names = load_library(), []
+    while (name := lib.mli_launch_family_name(len(names))) is not None:
+        names.append(name.decode())
+    return names
+
+
 def reset_launch_counts():
     """Zero the calling thread's launch counters (mli_launch_counts_reset)."""
     _check(load_library().mli_launch_counts_reset(), "mli_launch_counts_reset")
 
 
-def workspace_for(n_batch, n_sequence, dim, device, n_heads=1):
+def workspace_for(n_batch, n_sequence, dim, device, n_heads=1, mfma_kv_heads=None):
     """Caller-owned scratch for the split-sequence kernels (grown on demand, never inside a timed region).  n_heads > 1:
-    sized for the multi-head scan (mli_attention_heads_workspace_bytes), which covers the single-head calls too."""
+    sized for the multi-head scan (mli_attention_heads_workspace_bytes), which covers the single-head calls too.
+    mfma_kv_heads given: sized for decode_scan_paged_gqa_mfma with that many K/V heads (mli_gqa_mfma_workspace_bytes)."""
     lib = load_library()
-    if n_heads == 1:
+    if mfma_kv_heads is not None:
+        need = int(lib.mli_gqa_mfma_workspace_bytes(n_batch, n_sequence, dim, int(n_heads), int(mfma_kv_heads)))
+    elif n_heads == 1:
         need = int(lib.mli_attention_workspace_bytes(n_batch, n_sequence, dim))
     else:
         need = int(lib.mli_attention_heads_workspace_bytes(n_batch, n_sequence, dim, int(n_heads)))
@@ -334,6 +345,19 @@ def decode_scan_paged_gqa(q_output, page_table, lengths, attention_result, n_hea
                (n_heads, n_kv_heads, window or 0, sinks or 0), n_heads, elem, q_output.device)
 
 
+def decode_scan_paged_gqa_mfma(q_output, page_table, lengths, attention_result, n_heads, n_kv_heads, window, n_sequence):
+    """decode_scan_paged_gqa computed by the matrix-instruction kernel (mli_decode_scan_paged_gqa_mfma): one workgroup per (row,
+    K/V head, item), the group's query heads share every K / V load.  bf16 pages, head size 64 or 128, n_heads / n_kv_heads
+    1 .. 8, D up to 8192; n_kv_heads None or n_heads: no grouping; window <= 0 (or None): no window.  Opt-in: no other call
+    dispatches this kernel."""
+    B, D = q_output.shape
+    Hkv = int(n_kv_heads or n_heads)
+    ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads, mfma_kv_heads=Hkv)
+    _check(load_library().mli_decode_scan_paged_gqa_mfma(_p(q_output), _p(page_table), _p(lengths), _p(attention_result), B,
+                                                         int(n_sequence), D, int(n_heads), Hkv, int(window or 0), _p(ws), need,
+                                                         _stream()), "mli_decode_scan_paged_gqa_mfma")
+
+
 def alibi_slopes(n_heads):
     """The standard ALiBi slopes of n_heads heads (mli_alibi_slopes): a float32 numpy array; 2^(-8 (i + 1) / n) over the
     largest power of two n <= n_heads, then every other slope of the 2 n series."""
@@ -400,7 +424,7 @@ def decode_scan_paged_sink_logits(q_output, page_table, lengths, attention_resul
 
 def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, n_new_items,
                          n_sequence, elem=None, n_heads=1, window=None, sinks=None, n_kv_heads=None, alibi_slopes=None,
-                         rope=None, softcap=None, sink_logits=None):
+                         rope=None, softcap=None, sink_logits=None, heads_mfma=False):
     """What the attention layers run: the paged composition without materialising scores / probabilities
     (mli_paged_attention_lean); page element type = elem (ELEM_*), default from the weights' dtype.  n_heads != 1: the
     multi-head form (mli_paged_attention_lean_heads); window given: the sliding-window form
@@ -415,7 +439,22 @@ def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_outpu
     (mli_paged_attention_lean_softcap), with any of window, sinks, n_kv_heads and rope, never with alibi_slopes;
     sink_logits given (n_heads float32 values on the device): the scan counts a learned sink logit per query head as
     decode_scan_paged_sink_logits does (mli_paged_attention_lean_sink_logits), with any of window, sinks, n_kv_heads and rope,
-    never with alibi_slopes or softcap."""
+    never with alibi_slopes or softcap;
+    heads_mfma=True: the scan is decode_scan_paged_gqa_mfma (mli_paged_attention_lean_gqa_mfma), with any of window, n_kv_heads
+    and rope, never with sinks, alibi_slopes, softcap or sink_logits."""
+    if heads_mfma:
+        for name, given in (("sink tokens", sinks), ("ALiBi", alibi_slopes), ("logit soft-capping", softcap),
+                            ("attention-sink logits", sink_logits)):
+            if given is not None:
+                raise ValueError(f"the matrix-instruction scan and {name} are not combined")
+        B, D = page_table.shape[0], wk.shape[0]
+        Hkv = int(n_kv_heads or n_heads)
+        ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads, mfma_kv_heads=Hkv)
+        _check(load_library().mli_paged_attention_lean_gqa_mfma(
+            _p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(new_batch_idx), _p(q_output), _p(attention_result), B,
+            int(n_sequence), D, int(n_new_items), int(n_heads), Hkv, int(window or 0), 0, _p(rope), _elem_of(wk, elem), _p(ws),
+            need, _stream()), "mli_paged_attention_lean_gqa_mfma")
+        return
     if sink_logits is not None:
         _sink_logits_alone(alibi_slopes, softcap)
         if sinks is not None and window is None:
