@@ -271,6 +271,16 @@ int mli_engine_set_sink_logits(mli_engine* engine, const float* logits_host, int
  * nothing changes anywhere. */
 int mli_engine_set_heads_mfma(mli_engine* engine, int n_heads, int n_kv_heads);
 
+/* EXTENSION: the prompt scan on matrix instructions (mli_kernels.h: mli_paged_prompt_logprobs_mfma).  An engine with prompt
+ * log-probabilities scores its prompts through that kernel in place of the lane-group prompt scan; decoding is untouched, so
+ * tokens and generated-token figures keep their bits, and the prompt figures agree to fp32 accuracy.  After
+ * mli_engine_set_prompt_logprobs, before the first step or run; MLI_ENGINE_PAGED_BF16.  enabled 0 turns the switch off again.
+ * -1 with a message naming mli_engine_set_prompt_mfma for a null or started engine, an engine without prompt log-probabilities,
+ * every other kind, a shape mli_prompt_scan_mfma_shape_supported refuses, and -- the kernel has none of them -- an engine with
+ * sink tokens (mli_engine_set_sinks), a soft cap or sink logits; each of those three setters refuses likewise when it comes
+ * second.  Without the call nothing changes anywhere. */
+int mli_engine_set_prompt_mfma(mli_engine* engine, int enabled);
+
 /* EXTENSION: sliding-window attention (mli_kernels.h: mli_paged_attention_lean_window).  Every row attends its newest
  * `window` tokens only.  The window changes which slots the scan reads and nothing else: admission, page growth,
  * preemption, re-prefill, n_forward_rounds (the window follows the device-side length), step graphs, sampling and the

@@ -755,6 +755,35 @@ int mli_paged_prompt_logprobs_sink_logits(const void* const* page_table, const i
                                           int n_kv_heads, int window, int n_sink, const float* sink_logits, int elem, int n_top,
                                           void* scratch, size_t scratch_bytes, void* stream);
 
+/* EXTENSION: the causal multi-query scan on matrix instructions (bf16 pages).  mli_prompt_scan_paged_mfma computes what
+ * mli_prompt_scan_paged computes -- the same segments, mask and window, the same skipped segments and never-written rows -- to
+ * fp32 accuracy, not to the same bits: one workgroup per (segment, K/V head, block of mli_prompt_scan_mfma_tq queries), scores
+ * and softmax . V on bf16 matrix instructions with q and the probabilities split into three exact bf16 parts.  One launch
+ * ("scan_prompt_mfma"), no workspace.  Opt-in: no other entry point dispatches to it.
+ * mli_prompt_scan_mfma_shape_supported: 1 for bf16 pages (elem MLI_ELEM_BF16), head_dim = emb_dim / n_heads 64 or 128,
+ *   n_heads / n_kv_heads 1, 2, 4 or 8, emb_dim <= 8192 (rows wider than mli_prompt_scan_paged's 1024 among them),
+ *   n_sequence % 16 == 0 and n_batch <= 16384; 0 otherwise.
+ * mli_prompt_scan_mfma_tq: the queries per workgroup at (emb_dim, n_heads, n_kv_heads): 16, 8 or 4 (tests place segment
+ *   boundaries by it), MLI_ERR_BAD_ARG for heads the rule refuses.
+ * mli_prompt_scan_paged_mfma takes mli_prompt_scan_paged's arguments; n_sink and elem are kept so that they can be refused.
+ * MLI_ERR_BAD_ARG before any launch and before any pointer is looked at: a refused shape (fp32 and fp8 pages among them),
+ * n_sink != 0, window < 0, n_seg < 0, max_count outside 1 .. n_sequence, n_q < 1, a grid of 2^24 workgroups or more
+ * (n_seg * ceil(max_count / tq) * n_kv_heads); then null pointers.  n_seg == 0 returns 0 and launches nothing.
+ * mli_paged_prompt_logprobs_mfma is mli_paged_prompt_logprobs with this scan as launch 2 (the gather, projection, logits and
+ * scoring launches are the same); scratch: mli_prompt_logprobs_scratch_bytes. */
+int mli_prompt_scan_mfma_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads, int elem);
+int mli_prompt_scan_mfma_tq(int emb_dim, int n_heads, int n_kv_heads);
+int mli_prompt_scan_paged_mfma(const float* q, const void* const* page_table, const int* seg_row, const int* seg_first,
+                               const int* seg_count, const int* seg_offset, float* out, int n_seg, int max_count, int n_q,
+                               int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads, int window, int n_sink,
+                               int elem, void* stream);
+int mli_paged_prompt_logprobs_mfma(const void* const* page_table, const int* inp, const void* wq, const float* emb_table,
+                                   const int* seg_row, const int* seg_first, const int* seg_count, const int* seg_offset,
+                                   float* token_logprob, int* top_ids, float* top_logprobs, int n_seg, int max_count,
+                                   int n_positions, int n_batch, int n_sequence, int emb_dim, int n_vocab, int n_heads,
+                                   int n_kv_heads, int window, int n_sink, int elem, int n_top, void* scratch, size_t scratch_bytes,
+                                   void* stream);
+
 /* PREFILL of the newly inserted rows in ONE launch: the encoder as the fill GEMM's prologue.  The A
  * tile rows are computed on the fly as emb_table[inp[b, s]] + wpe[s] -- nothing is read back from the input-embedding
  * segment -- multiplied by [Wk | Wv], and the workgroups of the first column tile also write those rows to segment 0
@@ -933,6 +962,7 @@ int mli_tune(const char* key, int value);
  *   "scan_heads_sink_logits" the multi-head scans with a learned sink logit per query head (mli_decode_scan_paged_sink_logits)
  *   "scan_prompt_sink_logits" the prompt scan with a learned sink logit per query head (mli_prompt_scan_paged_sink_logits)
  *   "scan_gqa_mfma"          the grouped-query scan on matrix instructions (mli_decode_scan_paged_gqa_mfma)
+ *   "scan_prompt_mfma"       the prompt scan on matrix instructions (mli_prompt_scan_paged_mfma)
  * Forms, counted beside the launch's kernel family:
  *   "latest_compact"         a decode projection over the compacted list of non-empty rows ("latest_compact"; the panel and
  *                            the LDS-DMA kernel have no such list)

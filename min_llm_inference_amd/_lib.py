@@ -113,6 +113,10 @@ SIGNATURES = {
     "mli_paged_prompt_logprobs_softcap": [_P] * 11 + [_I] * 11 + [ctypes.c_float, _I, _I, _P, _Z, _P],
     "mli_prompt_scan_paged_sink_logits": [_P] * 7 + [_I] * 10 + [_P, _I, _P],
     "mli_paged_prompt_logprobs_sink_logits": [_P] * 11 + [_I] * 11 + [_P, _I, _I, _P, _Z, _P],
+    "mli_prompt_scan_mfma_shape_supported": [_I] * 6,
+    "mli_prompt_scan_mfma_tq": [_I, _I, _I],
+    "mli_prompt_scan_paged_mfma": [_P] * 7 + [_I] * 11 + [_P],
+    "mli_paged_prompt_logprobs_mfma": [_P] * 11 + [_I] * 13 + [_P, _Z, _P],
     "mli_paged_prefill": [_P] * 8 + [_I] * 5 + [_P],
     "mli_paged_prefill_window": [_P] * 8 + [_I] * 7 + [_P],
     "mli_prefill": [_P] * 10 + [_I] * 5 + [_P],
@@ -180,6 +184,7 @@ ENGINE_SIGNATURES = {
     "mli_engine_set_sinks": [_P, _I],
     "mli_engine_set_kv_heads": [_P, _I],
     "mli_engine_set_heads_mfma": [_P, _I, _I],
+    "mli_engine_set_prompt_mfma": [_P, _I],
     "mli_engine_set_alibi": [_P, _P, _I],
     "mli_engine_set_softcap": [_P, ctypes.c_float],
     "mli_engine_set_sink_logits": [_P, _P, _I],

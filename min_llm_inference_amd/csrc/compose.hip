@@ -259,6 +259,8 @@ int launch_prompt_scan_elem(const float*, const void* const*, const int*, const 
                             int, int, int, int, int, int, int, int, int, hipStream_t);   // attention_prompt.hip
 int launch_prompt_softcap_scan_elem(const float*, const void* const*, const int*, const int*, const int*, const int*, float*, int,
                                     int, int, int, int, int, int, int, int, int, float, int, hipStream_t);   // attention_prompt.hip
+int launch_prompt_mfma_scan_elem(const float*, const void* const*, const int*, const int*, const int*, const int*, float*, int, int,
+                                 int, int, int, int, int, int, int, int, int, hipStream_t);   // attention_prompt_mfma_bf16.hip
 int launch_gemm_nt(const float*, const float*, float*, int, int, int, hipStream_t);
 int launch_score_tokens_skipping(const float*, const int*, float*, int*, float*, int, int, int, int, void*);   // decoder_sample.hip
 
@@ -321,22 +323,27 @@ static int prompt_logprobs(const void* const* page_table, const int* inp, const 
                               float* token_logprob, int* top_ids, float* top_logprobs, int n_seg, int max_count,
                               int n_positions, int n_batch, int n_sequence, int emb_dim, int n_vocab, int n_heads,
                               int n_kv_heads, int window, int n_sink, int elem, int n_top, void* scratch, size_t scratch_bytes,
-                              void* stream, bool capped, float cap, bool sunk = false, const float* sink_logits = nullptr) {
+                              void* stream, bool capped, float cap, bool sunk = false, const float* sink_logits = nullptr,
+                              bool mfma = false) {
     if (capped && (n_heads < 2 || !(cap > 0.f) || !std::isfinite(cap))) return MLI_ERR_BAD_ARG;
     if (sunk && (n_heads < 2 || sink_logits == nullptr)) return MLI_ERR_BAD_ARG;
     if (n_top < 0 || n_top > MLI_MAX_TOP_LOGPROBS || token_logprob == nullptr ||
         (n_top > 0 && (top_ids == nullptr || top_logprobs == nullptr)))
         return MLI_ERR_BAD_ARG;
+    // mfma: the scan on matrix instructions (attention_prompt_mfma.hpp) with its own shape rule, and no sink tokens
     if (n_seg < 0 || window < 0 || n_sink < 0 || n_vocab <= 0 ||
-        !mli::prompt_scan_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, elem))
+        !(mfma ? n_sink == 0 && mli::prompt_mfma_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, elem)
+               : mli::prompt_scan_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, elem)))
         return MLI_ERR_BAD_ARG;
     if (n_seg == 0) return 0;
     // the list's own limits, the projection's (a segment per y of the gather's grid) and the scan's grid among them: with the
     // shapes, before any pointer is looked at and before the projection is launched
     if (max_count < 1 || max_count > n_sequence || n_positions < 1 || n_seg > 65535) return MLI_ERR_BAD_ARG;
     const int epl = elem == MLI_ELEM_BF16 ? 8 : 4;
-    if (!mli::prompt_scan_grid_ok(n_seg, max_count,
-                                  mli::prompt_scan_tq(epl, mli::plan_ceil_div(emb_dim / epl, mli::kPlanWave), n_heads > 1)))
+    if (mfma ? !mli::prompt_mfma_grid_ok(n_seg, n_kv_heads, max_count,
+                                         mli::prompt_mfma_tq(emb_dim / n_heads, n_heads / n_kv_heads))
+             : !mli::prompt_scan_grid_ok(n_seg, max_count,
+                                         mli::prompt_scan_tq(epl, mli::plan_ceil_div(emb_dim / epl, mli::kPlanWave), n_heads > 1)))
         return MLI_ERR_BAD_ARG;
     if (inp == nullptr || wq == nullptr || emb_table == nullptr) return MLI_ERR_BAD_ARG;
     const mli::PromptScratch p = mli::prompt_scratch(n_positions, emb_dim, n_vocab);
@@ -350,7 +357,11 @@ static int prompt_logprobs(const void* const* page_table, const int* inp, const 
     int rc = mli::launch_prompt_project_q(elem, page_table, seg_row, seg_first, seg_count, seg_offset, wq, base + p.gathered, q,
                                           n_seg, max_count, n_positions, n_batch, n_sequence, emb_dim, st);
     if (rc) return rc;
-    if (sunk)
+    if (mfma)
+        rc = mli::launch_prompt_mfma_scan_elem(q, page_table, seg_row, seg_first, seg_count, seg_offset, attn, n_seg, max_count,
+                                               n_positions, n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window, n_sink,
+                                               elem, st);
+    else if (sunk)
         rc = mli::launch_prompt_sink_logits_scan_elem(q, page_table, seg_row, seg_first, seg_count, seg_offset, attn, n_seg,
                                                       max_count, n_positions, n_batch, n_sequence, emb_dim, n_heads, n_kv_heads,
                                                       window, n_sink, sink_logits, elem, st);
@@ -407,6 +418,18 @@ int mli_paged_prompt_logprobs_sink_logits(const void* const* page_table, const i
     return prompt_logprobs(page_table, inp, wq, emb_table, seg_row, seg_first, seg_count, seg_offset, token_logprob, top_ids,
                            top_logprobs, n_seg, max_count, n_positions, n_batch, n_sequence, emb_dim, n_vocab, n_heads, n_kv_heads,
                            window, n_sink, elem, n_top, scratch, scratch_bytes, stream, false, 0.f, true, sink_logits);
+}
+
+// EXTENSION: the same composition with the prompt scan on matrix instructions as launch 2 (attention_prompt_mfma.hpp)
+int mli_paged_prompt_logprobs_mfma(const void* const* page_table, const int* inp, const void* wq, const float* emb_table,
+                                   const int* seg_row, const int* seg_first, const int* seg_count, const int* seg_offset,
+                                   float* token_logprob, int* top_ids, float* top_logprobs, int n_seg, int max_count,
+                                   int n_positions, int n_batch, int n_sequence, int emb_dim, int n_vocab, int n_heads,
+                                   int n_kv_heads, int window, int n_sink, int elem, int n_top, void* scratch, size_t scratch_bytes,
+                                   void* stream) {
+    return prompt_logprobs(page_table, inp, wq, emb_table, seg_row, seg_first, seg_count, seg_offset, token_logprob, top_ids,
+                           top_logprobs, n_seg, max_count, n_positions, n_batch, n_sequence, emb_dim, n_vocab, n_heads, n_kv_heads,
+                           window, n_sink, elem, n_top, scratch, scratch_bytes, stream, false, 0.f, false, nullptr, true);
 }
 
 int mli_abi_version(void) { return 4; }

@@ -288,4 +288,26 @@ inline bool prompt_scan_grid_ok(int n_seg, int max_count, int tq) {
     return (long long)n_seg * plan_ceil_div(max_count, tq) * (kPlanWaves * kPlanWave) < (1LL << 32);
 }
 
+// ---- the prompt scan on matrix instructions (attention_prompt_mfma.hpp) --------------------------------------------------------
+// One workgroup per (segment, K/V head, block of queries): bf16 pages, head_dim 64 or 128, g = n_heads / n_kv_heads a power of
+// two up to 8 (the 16 columns of a tile hold whole groups), emb_dim to 8192 (the row's width shapes nothing in the kernel: rows
+// wider than the lane-group prompt scan's 1024 are inside), n_batch as the decode scans bound it.  No sink tokens.
+inline bool prompt_mfma_shape_ok(int B, int S, int D, int H, int Hkv, int elem) {
+    if (elem != MLI_ELEM_BF16) return false;
+    if (B <= 0 || B > kPlanMaxRows || S <= 0 || S % kPlanPage != 0 || D <= 0 || D > 8192 || H < 1 || D % H != 0) return false;
+    if (Hkv < 1 || Hkv > H || H % Hkv != 0) return false;
+    const int hd = D / H, g = H / Hkv;
+    return (hd == 64 || hd == 128) && (g == 1 || g == 2 || g == 4 || g == 8);
+}
+// Column tiles a workgroup holds at most: the largest of 4 / 2 / 1 per head size that compiles without scratch (DESIGN 3.6e has
+// the register table).  TQ, the queries of a workgroup, is at most 16 and fills whole tiles: TQ * g = 16, 32 or 64.
+constexpr int prompt_mfma_max_tiles(int hd) { return hd == 128 ? 2 : 4; }
+constexpr int prompt_mfma_tq(int hd, int g) {
+    return 16 * prompt_mfma_max_tiles(hd) / g < 16 ? 16 * prompt_mfma_max_tiles(hd) / g : 16;
+}
+// prompt_scan_grid_ok for the grid n_seg * ceil(max_count / TQ) * n_kv_heads
+inline bool prompt_mfma_grid_ok(int n_seg, int Hkv, int max_count, int tq) {
+    return (long long)n_seg * plan_ceil_div(max_count, tq) * Hkv * (kPlanWaves * kPlanWave) < (1LL << 32);
+}
+
 }  // namespace mli

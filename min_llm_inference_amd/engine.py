@@ -40,7 +40,7 @@ class Engine:
     def __init__(self, kind, n_batch, n_sequence, emb_dim, n_vocab, emb_table, pos_table, wk, wq, wv, n_blocks=0,
                  n_forward_rounds=1, device=0, reference_length_reset_quirk=False, n_heads=1, window=None, sinks=None,
                  release_pages=False, n_kv_heads=None, logprobs=None, prompt_logprobs=False, alibi=None,
-                 rope=None, softcap=None, sink_logits=None, heads_mfma=False):
+                 rope=None, softcap=None, sink_logits=None, heads_mfma=False, prompt_mfma=False):
         self._lib = load_library()
         self.cfg = EngineConfig(kind, n_batch, n_sequence, emb_dim, n_vocab, n_blocks, n_forward_rounds, device,
                                 int(reference_length_reset_quirk))
@@ -65,6 +65,8 @@ class Engine:
             self.set_logprobs(logprobs)
         if prompt_logprobs:
             self.set_prompt_logprobs(True)
+        if prompt_mfma:
+            self.set_prompt_mfma(True)
         if alibi is not None and alibi is not False:
             self.set_alibi(None if alibi is True else alibi)
         if rope is not None and rope is not False:
@@ -182,6 +184,12 @@ class Engine:
         token but the first, its log-probability after the tokens before it and the alternatives there.  After
         set_logprobs (which supplies n_top), before the first step or run; fp32 / bf16 paged kinds, not with page release."""
         self._check(self._lib.mli_engine_set_prompt_logprobs(self._h, int(bool(enabled))))
+
+    def set_prompt_mfma(self, enabled=True):
+        """The prompt scan on matrix instructions (mli_engine_set_prompt_mfma): the engine's prompts are scored by
+        mli_paged_prompt_logprobs_mfma; decoding is untouched.  After set_prompt_logprobs, before the first step or run; the
+        bf16 paged kind at head_dim 64 / 128 and groups of 1, 2, 4 or 8; not with sink tokens, a soft cap or sink logits."""
+        self._check(self._lib.mli_engine_set_prompt_mfma(self._h, int(bool(enabled))))
 
     def finished_prompt_logprobs(self):
         """{id: (logprobs [n], top_ids [n, n_top], top_logprobs [n, n_top])} of the finished items: entry i belongs to prompt

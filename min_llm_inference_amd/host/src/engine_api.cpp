@@ -189,6 +189,7 @@ struct mli_engine {
             std::vector<int> top_ids;
         };
         int n_top, width, limit;
+        bool mfma = false;                                          // mli_engine_set_prompt_mfma: the scan on matrix instructions
         TensorInt seg_device, seg_host, ids_device, ids_host;       // segments: [4][limit]
         TensorFloat token_device, token_host, top_device, top_host, scratch;
         size_t scratch_bytes;
@@ -234,7 +235,13 @@ struct mli_engine {
                 seg_device.copy_from(seg_host);
                 const int* d = seg_device.data();
                 // (an engine with a cap scores its prompts under the model it decodes with: the capped prompt scan)
-                const int rc = o.sink_logits
+                const int rc = mfma
+                    ? mli_paged_prompt_logprobs_mfma(          // (the setters keep sinks, cap and sink logits away from it)
+                          page_table, inp, wq, emb_table, d, d + limit, d + 2 * limit, d + 3 * limit, token_device.data(),
+                          n_top > 0 ? ids_device.data() : nullptr, n_top > 0 ? top_device.data() : nullptr, n_seg, pass.max_count,
+                          pass.n_positions, n_batch, n_sequence, emb_dim, n_vocab, o.n_heads, n_kv_heads, o.window, o.n_sink,
+                          elem, n_top, scratch.data(), scratch_bytes, mli::runtime::compute_stream())
+                    : o.sink_logits
                     ? mli_paged_prompt_logprobs_sink_logits(   // (likewise with learned sink logits)
                           page_table, inp, wq, emb_table, d, d + limit, d + 2 * limit, d + 3 * limit, token_device.data(),
                           n_top > 0 ? ids_device.data() : nullptr, n_top > 0 ? top_device.data() : nullptr, n_seg, pass.max_count,
@@ -272,6 +279,7 @@ struct mli_engine {
         }
     };
     bool prompt_logprobs_wanted = false;             // mli_engine_set_prompt_logprobs
+    bool prompt_mfma = false;                        // mli_engine_set_prompt_mfma
     std::unique_ptr<PromptLogprobs> prompt_logprobs; // from the first step or run of an engine with the switch set
 
     // the rows admitted for the next forward (both loops): their prompts are scored in that forward
@@ -285,6 +293,12 @@ struct mli_engine {
     bool prompt_shape_ok() {
         const PagedAttentionOptions& o = options();
         return mli::prompt_scan_shape_ok(cfg.n_batch, cfg.n_sequence, cfg.emb_dim, o.n_heads,
+                                         o.n_kv_heads != 0 ? o.n_kv_heads : o.n_heads, elem());
+    }
+
+    bool prompt_mfma_shape_ok() {
+        const PagedAttentionOptions& o = options();
+        return mli::prompt_mfma_shape_ok(cfg.n_batch, cfg.n_sequence, cfg.emb_dim, o.n_heads,
                                          o.n_kv_heads != 0 ? o.n_kv_heads : o.n_heads, elem());
     }
 
@@ -323,7 +337,12 @@ struct mli_engine {
         if (!paged || release_pages || !prompt_shape_ok())
             throw std::runtime_error("prompt log-probabilities (mli_engine_set_prompt_logprobs): not with page release, and "
                                      "the prompt scan does not take this (n_batch, n_sequence, emb_dim, n_heads, n_kv_heads)");
+        // (likewise for mli_engine_set_prompt_mfma: the head counts may have changed behind it)
+        if (prompt_mfma && !prompt_mfma_shape_ok())
+            throw std::runtime_error("the prompt scan on matrix instructions (mli_engine_set_prompt_mfma) does not take this "
+                                     "(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads)");
         prompt_logprobs = std::make_unique<PromptLogprobs>(logprobs_n_top, cfg.n_batch, cfg.emb_dim, cfg.n_vocab);
+        prompt_logprobs->mfma = prompt_mfma;
         paged->set_prompt_logprobs(prompt_logprobs.get());
     }
 
@@ -759,6 +778,9 @@ int mli_engine_set_softcap(mli_engine* e, float cap) {
             if (o.heads_mfma)
                 throw std::runtime_error("mli_engine_set_softcap: not with the MFMA grouped-query scan (mli_engine_set_heads_mfma: "
                                          "the kernel has no cap)");
+            if (e->prompt_mfma)
+                throw std::runtime_error("mli_engine_set_softcap: not with the prompt scan on matrix instructions "
+                                         "(mli_engine_set_prompt_mfma: the kernel has no cap)");
             if (o.n_heads < 2)
                 throw std::runtime_error("mli_engine_set_softcap: n_heads must be >= 2 (mli_engine_set_heads comes first; the "
                                          "single-head scans have no cap)");
@@ -792,6 +814,9 @@ int mli_engine_set_sink_logits(mli_engine* e, const float* logits_host, int n) {
             if (o.heads_mfma)
                 throw std::runtime_error("mli_engine_set_sink_logits: not with the MFMA grouped-query scan "
                                          "(mli_engine_set_heads_mfma: the kernel has no sink logit)");
+            if (e->prompt_mfma)
+                throw std::runtime_error("mli_engine_set_sink_logits: not with the prompt scan on matrix instructions "
+                                         "(mli_engine_set_prompt_mfma: the kernel has no sink logit)");
             if (o.n_heads < 2)
                 throw std::runtime_error("mli_engine_set_sink_logits: n_heads must be >= 2 (mli_engine_set_heads comes first; the "
                                          "single-head scans have no sink logit)");
@@ -900,6 +925,9 @@ int mli_engine_set_sinks(mli_engine* e, int n_sink) {
             if (o.heads_mfma && n_sink != 0)
                 throw std::runtime_error("mli_engine_set_sinks: not with the MFMA grouped-query scan (mli_engine_set_heads_mfma: "
                                          "the kernel has no sink tokens)");
+            if (e->prompt_mfma && n_sink != 0)
+                throw std::runtime_error("mli_engine_set_sinks: not with the prompt scan on matrix instructions "
+                                         "(mli_engine_set_prompt_mfma: the kernel has no sink tokens)");
             if (!e->lean_layers)
                 throw std::runtime_error("mli_engine_set_sinks: attention sinks have the lean compositions only");
             o.n_sink = n_sink;
@@ -1062,6 +1090,37 @@ int mli_engine_set_prompt_logprobs(mli_engine* e, int enabled) {
             throw std::runtime_error("mli_engine_set_prompt_logprobs: the prompt scan does not take this (n_batch, n_sequence, "
                                      "emb_dim, n_heads, n_kv_heads): rows of at most two 16-byte lane loads");
         e->prompt_logprobs_wanted = enabled != 0;
+    })
+}
+
+// The switch is read where the engine's prompt scoring is built (choose_head); what the kernel does not have is refused here
+// and, for a later call, in that call's own setter.
+int mli_engine_set_prompt_mfma(mli_engine* e, int enabled) {
+    MLI_GUARD({
+        if (!e) throw std::runtime_error("mli_engine_set_prompt_mfma: null argument");
+        if (e->started) throw std::runtime_error("mli_engine_set_prompt_mfma after the engine has started");
+        if (e->cfg.kind != MLI_ENGINE_PAGED_BF16)
+            throw std::runtime_error("mli_engine_set_prompt_mfma: the prompt scan on matrix instructions serves the bf16 paged "
+                                     "engine");
+        if (!e->prompt_logprobs_wanted)
+            throw std::runtime_error("mli_engine_set_prompt_mfma: an engine without prompt log-probabilities "
+                                     "(mli_engine_set_prompt_logprobs comes first)");
+        if (enabled) {
+            const PagedAttentionOptions& o = e->options();
+            if (!e->prompt_mfma_shape_ok())
+                throw std::runtime_error("mli_engine_set_prompt_mfma: unsupported (n_batch, emb_dim, n_heads, n_kv_heads): head_dim "
+                                         "must be 64 or 128, n_heads / n_kv_heads 1, 2, 4 or 8 and emb_dim at most 8192");
+            if (o.n_sink != 0)
+                throw std::runtime_error("mli_engine_set_prompt_mfma: not with sink tokens (mli_engine_set_sinks: the kernel has "
+                                         "none)");
+            if (o.softcap != 0.f)
+                throw std::runtime_error("mli_engine_set_prompt_mfma: not with logit soft-capping (mli_engine_set_softcap: the "
+                                         "kernel has no cap)");
+            if (o.sink_logits)
+                throw std::runtime_error("mli_engine_set_prompt_mfma: not with attention-sink logits (mli_engine_set_sink_logits: "
+                                         "the kernel has no sink logit)");
+        }
+        e->prompt_mfma = enabled != 0;
     })
 }
 

@@ -650,15 +650,31 @@ def prompt_scan_tq(emb_dim, n_heads, elem):
     return tq
 
 
+def _mfma_alone(who, sinks, softcap, sink_logits):
+    if sinks or softcap is not None or sink_logits is not None:
+        raise ValueError(f"{who}: mfma is not combined with sinks, softcap or sink_logits (the kernel has none of them)")
+
+
+def prompt_scan_mfma_tq(emb_dim, n_heads, n_kv_heads=None):
+    """The consecutive query positions a workgroup of prompt_scan_paged(mfma=True) holds (mli_prompt_scan_mfma_tq)."""
+    tq = int(load_library().mli_prompt_scan_mfma_tq(int(emb_dim), int(n_heads), int(n_kv_heads or n_heads)))
+    if tq < 0:
+        raise MliError(f"Hip Failure: mli_prompt_scan_mfma_tq returned {tq}")
+    return tq
+
+
 def prompt_scan_paged(q, page_table, segments, out, n_batch, n_sequence, elem, n_heads=1, n_kv_heads=None, window=None,
-                      sinks=None, seg_arrays=None, softcap=None, sink_logits=None):
+                      sinks=None, seg_arrays=None, softcap=None, sink_logits=None, mfma=False):
     """EXTENSION: the causal multi-query paged scan (mli_prompt_scan_paged).  segments = [(row, first position,
     count)]: query j of a segment is position first + j of its row and attends the slots s <= its position (inside the window or
     among the sinks); q and out [n_q, D] hold the queries in list order.  seg_arrays = (rows, first, count, offset, max_count)
     device arrays replace the list.  softcap given (a finite float > 0, n_heads >= 2): every scaled score x becomes
     softcap * tanh(x / softcap) (mli_prompt_scan_paged_softcap).  sink_logits given (n_heads float32 values on the device,
     n_heads >= 2; never with softcap): query t gets what decode_scan_paged_sink_logits gives a row of length t + 1
-    (mli_prompt_scan_paged_sink_logits)."""
+    (mli_prompt_scan_paged_sink_logits).  mfma=True: the same scan on matrix instructions (mli_prompt_scan_paged_mfma; DESIGN
+    3.6e: bf16 pages, head_dim 64 / 128, rows to 8192 wide), never with sinks, softcap or sink_logits."""
+    if mfma:
+        _mfma_alone("prompt_scan_paged", sinks, softcap, sink_logits)
     if sink_logits is not None:
         _sink_logits_alone(None, softcap)
     n_q, D = q.shape
@@ -666,6 +682,12 @@ def prompt_scan_paged(q, page_table, segments, out, n_batch, n_sequence, elem, n
         arrays, max_count, _ = _segments(segments, q.device)
     else:
         arrays, max_count = list(seg_arrays[:4]), int(seg_arrays[4])
+    if mfma:
+        _check(load_library().mli_prompt_scan_paged_mfma(_p(q), _p(page_table), *map(_p, arrays), _p(out), int(arrays[0].numel()),
+                                                         max_count, n_q, int(n_batch), int(n_sequence), D, int(n_heads),
+                                                         int(n_kv_heads or n_heads), int(window or 0), 0, int(elem), _stream()),
+               "mli_prompt_scan_paged_mfma")
+        return out
     if sink_logits is not None:
         _check(load_library().mli_prompt_scan_paged_sink_logits(_p(q), _p(page_table), *map(_p, arrays), _p(out),
                                                                 int(arrays[0].numel()), max_count, n_q, int(n_batch),
@@ -720,12 +742,15 @@ def score_tokens_logprobs(logits, targets, n_top=0):
 
 
 def paged_prompt_logprobs(page_table, inp, wq, emb_table, segments, n_batch, n_sequence, elem, n_top=0, n_heads=1,
-                          n_kv_heads=None, window=None, sinks=None, softcap=None, sink_logits=None):
+                          n_kv_heads=None, window=None, sinks=None, softcap=None, sink_logits=None, mfma=False):
     """EXTENSION: prompt log-probabilities for the positions of the segments from the pages a prefill has written
     (mli_paged_prompt_logprobs): projection, causal scan, logits, scoring of inp[row, position + 1].  Returns (token_logprob
     [n], top_ids [n, n_top], top_logprobs [n, n_top]) in list order.  softcap given: the scan with logit soft-capping
     (mli_paged_prompt_logprobs_softcap).  sink_logits given (never with softcap): the scan with a learned sink logit per query
-    head (mli_paged_prompt_logprobs_sink_logits)."""
+    head (mli_paged_prompt_logprobs_sink_logits).  mfma=True: the scan on matrix instructions as launch 2
+    (mli_paged_prompt_logprobs_mfma), never with sinks, softcap or sink_logits."""
+    if mfma:
+        _mfma_alone("paged_prompt_logprobs", sinks, softcap, sink_logits)
     if sink_logits is not None:
         _sink_logits_alone(None, softcap)
     lib = load_library()
@@ -735,6 +760,14 @@ def paged_prompt_logprobs(page_table, inp, wq, emb_table, segments, n_batch, n_s
     token_logprob, top_ids, top_logprobs = _score_outputs(n, n_top, wq.device)
     need = int(lib.mli_prompt_logprobs_scratch_bytes(n, D, V))
     sc = torch.empty(max(need, 16), dtype=torch.uint8, device=wq.device)
+    if mfma:
+        _check(lib.mli_paged_prompt_logprobs_mfma(_p(page_table), _p(inp), _p(wq), _p(emb_table), *map(_p, arrays),
+                                                  _p(token_logprob), _p(top_ids) if n_top > 0 else None,
+                                                  _p(top_logprobs) if n_top > 0 else None, len(segments), max_count, n,
+                                                  int(n_batch), int(n_sequence), D, V, int(n_heads), int(n_kv_heads or n_heads),
+                                                  int(window or 0), 0, int(elem), n_top, _p(sc), need, _stream()),
+               "mli_paged_prompt_logprobs_mfma")
+        return token_logprob, top_ids, top_logprobs
     if sink_logits is not None:
         _check(lib.mli_paged_prompt_logprobs_sink_logits(
             _p(page_table), _p(inp), _p(wq), _p(emb_table), *map(_p, arrays), _p(token_logprob),

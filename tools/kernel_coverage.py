@@ -50,7 +50,8 @@ UNPROFILED_SECONDS = {
     "test_logprobs_engine_gpu.py": 6, "test_logprobs_gpu.py": 3, "test_naive_kernels_gpu.py": 13,
     "test_page_release_engine_gpu.py": 25, "test_paged_bf16_gpu.py": 45, "test_paged_fp8_gpu.py": 77,
     "test_paged_kernels_gpu.py": 94, "test_prefill_window_gpu.py": 4, "test_prompt_logprobs_engine_gpu.py": 5,
-    "test_prompt_long_gpu.py": 44, "test_prompt_scan_gpu.py": 10, "test_prompt_score_gpu.py": 3,
+    "test_prompt_long_gpu.py": 44, "test_prompt_mfma_engine_gpu.py": 10, "test_prompt_mfma_scan_gpu.py": 20,
+    "test_prompt_scan_gpu.py": 10, "test_prompt_score_gpu.py": 3,
     "test_rope_engine_gpu.py": 6, "test_rope_gemm_gpu.py": 7, "test_rope_scan_gpu.py": 3, "test_sampling_gpu.py": 6,
     "test_scan_resident_gpu.py": 8, "test_scratch_contract_gpu.py": 8, "test_shape_limits_gpu.py": 27,
     "test_shard_group_gpu.py": 7, "test_sink_logits_engine_gpu.py": 5, "test_sink_logits_prompt_gpu.py": 4,
