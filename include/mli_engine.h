@@ -271,6 +271,13 @@ int mli_engine_set_sink_logits(mli_engine* engine, const float* logits_host, int
  * nothing changes anywhere. */
 int mli_engine_set_heads_mfma(mli_engine* engine, int n_heads, int n_kv_heads);
 
+/* EXTENSION: ... on the fp8 paged engine (mli_kernels.h: mli_paged_attention_lean_gqa_mfma_fp8).  mli_engine_set_heads_mfma's
+ * contract on MLI_ENGINE_PAGED_FP8, which has no other multi-head or grouped-query scan: the shapes are those of
+ * mli_gqa_mfma_fp8_shape_supported (emb_dim to 2048), every other kind is refused, and every refusal above -- this call's and,
+ * when they come second, the five setters' -- names mli_engine_set_heads_mfma_fp8.  (ALiBi, soft cap, sink logits and prompt
+ * log-probabilities are refused on the fp8 kind in any case.) */
+int mli_engine_set_heads_mfma_fp8(mli_engine* engine, int n_heads, int n_kv_heads);
+
 /* EXTENSION: the prompt scan on matrix instructions (mli_kernels.h: mli_paged_prompt_logprobs_mfma).  An engine with prompt
  * log-probabilities scores its prompts through that kernel in place of the lane-group prompt scan; decoding is untouched, so
  * tokens and generated-token figures keep their bits, and the prompt figures agree to fp32 accuracy.  After

@@ -496,6 +496,32 @@ int mli_paged_attention_lean_gqa_mfma(void* const* page_table, const int* length
                                       int n_sink, const float* rope_table, int elem, void* workspace, size_t workspace_bytes,
                                       void* stream);
 
+/* ---- EXTENSION: ... over fp8 (OCP e4m3) pages ----------------------------------------------------------------
+ * The scan above on pages of MLI_ELEM_FP8 (a slot row is x | K | V, 3 * emb_dim bytes): multi-head and grouped-query attention
+ * on the page type that holds twice the tokens.  The e4m3 bytes decode to bf16 exactly, so the result is, bit for bit, that of
+ * mli_decode_scan_paged_gqa_mfma on bf16 pages holding the decoded values.  Opt-in like it: no other entry point dispatches it,
+ * and every other multi-head or grouped entry point keeps refusing fp8 pages.
+ * mli_gqa_mfma_fp8_shape_supported: mli_gqa_mfma_shape_supported's rules without its element rule, AND emb_dim <= 2048.  The
+ * scan takes wider rows; the limit is that of what fills the pages -- the fp8 fill, latest and prefill GEMMs ask for emb_dim %
+ * 16 == 0 only, but are tested to emb_dim 2048 and no further (the widest row of the single-head fp8 scans), and
+ * mli_engine_create stops the fp8 engine there.
+ * Workspace: mli_gqa_mfma_workspace_bytes, as it is -- its size does not depend on the page type, and every shape accepted here
+ * is one the bf16 predicate accepts.
+ * One launch ("scan_gqa_mfma_fp8").  MLI_ERR_BAD_ARG / MLI_ERR_WORKSPACE as above. */
+int mli_gqa_mfma_fp8_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads);
+int mli_decode_scan_paged_gqa_mfma_fp8(const float* q_output, const void* const* page_table, const int* lengths,
+                                       float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                       int n_kv_heads, int window, void* workspace, size_t workspace_bytes, void* stream);
+
+/* fill (n_new_items rows) -> latest -> the fp8 scan above, on fp8 pages with bf16 weights (MLI_ELEM_FP8 of
+ * mli_paged_attention_lean).  rope_table: null, or the table of mli_paged_attention_lean_rope.  MLI_ERR_BAD_ARG for n_sink != 0,
+ * for a null weight pointer and, with a table, as mli_paged_attention_lean_rope. */
+int mli_paged_attention_lean_gqa_mfma_fp8(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                          const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                          int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads,
+                                          int window, int n_sink, const float* rope_table, void* workspace,
+                                          size_t workspace_bytes, void* stream);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */
@@ -963,6 +989,7 @@ int mli_tune(const char* key, int value);
  *   "scan_prompt_sink_logits" the prompt scan with a learned sink logit per query head (mli_prompt_scan_paged_sink_logits)
  *   "scan_gqa_mfma"          the grouped-query scan on matrix instructions (mli_decode_scan_paged_gqa_mfma)
  *   "scan_prompt_mfma"       the prompt scan on matrix instructions (mli_prompt_scan_paged_mfma)
+ *   "scan_gqa_mfma_fp8"      the grouped-query scan on matrix instructions over fp8 pages (mli_decode_scan_paged_gqa_mfma_fp8)
  * Forms, counted beside the launch's kernel family:
  *   "latest_compact"         a decode projection over the compacted list of non-empty rows ("latest_compact"; the panel and
  *                            the LDS-DMA kernel have no such list)

@@ -70,18 +70,39 @@ constexpr size_t gqa_mfma_work_bytes(int hd, int g) {
     return kPlanWaves * (gqa_mfma_vtile_bytes(hd) + (size_t)g * hd * sizeof(float) + kMfmaMaxGroup * 8);
 }
 
+// four e4m3 bytes of a page word -> four bf16 in two words, exactly (every e4m3 value is a bf16 value: 3 significand bits, and
+// the exponent range lies inside bf16's); element order kept.  ElemFP8's decode (scan_common.hpp) and the high-half pack.
+__device__ __forceinline__ mf_u32x2 mfma_fp8x4_to_bf16x4(uint32_t w) {
+    typedef float f32x2_t __attribute__((ext_vector_type(2)));
+    const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false);
+    const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+    return mf_u32x2{mfma_pack(__float_as_uint(lo.x), __float_as_uint(lo.y) & 0xffff0000u),
+                    mfma_pack(__float_as_uint(hi.x), __float_as_uint(hi.y) & 0xffff0000u)};
+}
+// 16 e4m3 bytes (one 16-byte load) -> 16 bf16: elements 0 .. 7 and 8 .. 15
+__device__ __forceinline__ void mfma_fp8x16_to_bf16(const fu_u32x4& r, fu_u32x4& first, fu_u32x4& second) {
+    const mf_u32x2 a = mfma_fp8x4_to_bf16x4(r.x), b = mfma_fp8x4_to_bf16x4(r.y);
+    const mf_u32x2 c = mfma_fp8x4_to_bf16x4(r.z), d = mfma_fp8x4_to_bf16x4(r.w);
+    first = fu_u32x4{a.x, a.y, b.x, b.y};
+    second = fu_u32x4{c.x, c.y, d.x, d.y};
+}
+
 // vb = b * Hkv + j; g = query heads per K/V head; window = 0: none, else 1 <= window < S (mli_decode_scan_paged_gqa's
 // semantics: the row attends slots [max(0, L - window), L), is taken from its first live page on, and that page's slots below
 // the window are masked).  ml: [B * Hkv][nchunk_max][g]; partial: [B * Hkv][nchunk_max][g * HD].
-template <int HD, bool NT>
+// FP8: the pages hold e4m3 bytes (attention_gqa_mfma_fp8.hip has the account of that data path); everything from the score
+// instructions on is the same text.
+template <int HD, bool NT, bool FP8 = false>
 __device__ __forceinline__ void gqa_mfma_item(
     const float* __restrict__ q, const void* const* __restrict__ page_table, const int* __restrict__ lengths,
     float* __restrict__ out, float2* ml, float* partial, int S, int D, int Hkv, int g, int ct, int nchunk_max, int direct,
     unsigned* arrivals, int vb, int c, bool first_grid_row, unsigned char* smem_raw, int window) {
     static_assert(HD == 64 || HD == 128, "head_dim 64 or 128");
     constexpr int NM = HD / 32;             // score instructions per part = 16-byte K loads = 16-byte V loads of a lane
+    constexpr int EB = FP8 ? 1 : 2;         // bytes of a page element
+    constexpr int NL = NM * EB / 2;         // ... of which fp8 pages need half: a 16-byte K load feeds two score instructions
     constexpr int NDT = HD / 16;            // 16-column tiles of the output
-    constexpr int UPT = HD / 8;             // 16-byte units of a token's V head row
+    constexpr int UPT = HD * EB / 16;       // 16-byte units of a token's V head row
     constexpr int TPI = kWave / UPT;        // tokens one V load instruction covers
     constexpr int VSTRIDE = HD * 2 + 16;    // bytes of a token row of the V tile
     constexpr int hd_shift = HD == 128 ? 7 : 6;
@@ -150,23 +171,23 @@ __device__ __forceinline__ void gqa_mfma_item(
 
     const float scale = sqrtf((float)HD);
     const float inv_scale = 1.f / scale;
-    const int row_bytes = 3 * D * 2;                 // one token slot: x | K | V, bf16
+    const int row_bytes = 3 * D * EB;                // one token slot: x | K | V
     const int block_bytes = kPage * row_bytes;
     // K: token n16, run kg of K/V head j, one 16-byte unit per instruction.  V: TPI tokens per instruction, a head row coalesced
-    const unsigned koff = (unsigned)(n16 * row_bytes + (D + j * HD + kg * (HD / 4)) * 2);
+    const unsigned koff = (unsigned)(n16 * row_bytes + (D + j * HD + kg * (HD / 4)) * EB);
     const int vtok = lane / UPT, vunit = lane % UPT;
-    const unsigned voff = (unsigned)(vtok * row_bytes + (2 * D + j * HD) * 2 + vunit * 16);
+    const unsigned voff = (unsigned)(vtok * row_bytes + (2 * D + j * HD) * EB + vunit * 16);
     unsigned char* vt = vt_all + wave * gqa_mfma_vtile_bytes(HD);
 
-    auto load_page = [&](int pi, fu_u32x4 (&kr)[NM], fu_u32x4 (&vr)[NM]) {
+    auto load_page = [&](int pi, fu_u32x4 (&kr)[NL], fu_u32x4 (&vr)[NL]) {
         const char* pg = reinterpret_cast<const char*>(wave_uniform(reinterpret_cast<const float*>(ptr_sh[pi])));
         // a null page gets an empty range: its loads return zeros; every offset below lies inside the page block
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pg), 0, pg != nullptr ? block_bytes : 0, 0x00020000);
 #pragma unroll
-        for (int i = 0; i < NM; ++i) kr[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, koff, i * 16, NT ? 2 : 0);
+        for (int i = 0; i < NL; ++i) kr[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, koff, i * 16, NT ? 2 : 0);
 #pragma unroll
-        for (int i = 0; i < NM; ++i) vr[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, i * TPI * row_bytes, NT ? 2 : 0);
+        for (int i = 0; i < NL; ++i) vr[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, i * TPI * row_bytes, NT ? 2 : 0);
     };
 
     float run_m = -INFINITY, run_l = 0.f;   // of head n16, the same bits in the head's four lanes
@@ -174,7 +195,7 @@ __device__ __forceinline__ void gqa_mfma_item(
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) acc[dt] = mf_f32x4{0.f, 0.f, 0.f, 0.f};
 
-    fu_u32x4 kc[NM], vc[NM], kn[NM], vn[NM];   // the page being consumed and the wave's next one, in flight meanwhile
+    fu_u32x4 kc[NL], vc[NL], kn[NL], vn[NL];   // the page being consumed and the wave's next one, in flight meanwhile
     if (wave < npages) load_page(wave, kc, vc);
     for (int pi = wave; pi < npages; pi += kFuWaves) {
         const bool has_next = pi + kFuWaves < npages;   // wave-uniform
@@ -183,22 +204,37 @@ __device__ __forceinline__ void gqa_mfma_item(
         const int nlo = (window > 0 && pi == 0 && s0 == 0) ? lo - p0 * kPage : 0;     // slots below the window
         auto live = [&](int t) { return t < nt && t >= nlo; };
 
-        // ---- V tile -> LDS as loaded, dead slots as zeros ----
+        // ---- V tile -> LDS as loaded (fp8: decoded to the same bf16 tile, 32 bytes a unit), dead slots as zeros ----
 #pragma unroll
-        for (int i = 0; i < NM; ++i) {
+        for (int i = 0; i < NL; ++i) {
             const int t = i * TPI + vtok;
             const fu_u32x4 v = live(t) ? vc[i] : fu_u32x4{0u, 0u, 0u, 0u};
-            *reinterpret_cast<fu_u32x4*>(vt + t * VSTRIDE + vunit * 16) = v;
+            if constexpr (FP8) {
+                fu_u32x4 v0, v1;
+                mfma_fp8x16_to_bf16(v, v0, v1);
+                *reinterpret_cast<fu_u32x4*>(vt + t * VSTRIDE + vunit * 32) = v0;
+                *reinterpret_cast<fu_u32x4*>(vt + t * VSTRIDE + vunit * 32 + 16) = v1;
+            } else {
+                *reinterpret_cast<fu_u32x4*>(vt + t * VSTRIDE + vunit * 16) = v;
+            }
         }
         __builtin_amdgcn_wave_barrier();   // other lanes of the wave read the tile back below: no LDS access moves across
 
         // ---- scores^T: lo, mid, hi parts of q into one accumulator ----
+        // (fp8: load i of the run decodes into the A fragments of instructions 2 i and 2 i + 1 -- elements 8 i' .. 8 i' + 7 of
+        // the run for instruction i', the bf16 order, so q's B fragments above serve both)
+        fu_u32x4 kf[NM];
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            if constexpr (FP8) mfma_fp8x16_to_bf16(kc[i], kf[2 * i], kf[2 * i + 1]);
+            else kf[i] = kc[i];
+        }
         mf_f32x4 sc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int p = 0; p < kMfmaParts; ++p)
 #pragma unroll
             for (int i = 0; i < NM; ++i)
-                sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mf_bf16x8, kc[i]),
+                sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mf_bf16x8, kf[i]),
                                                              __builtin_bit_cast(mf_bf16x8, qp[p][i]), sc, 0, 0, 0);
 
         // ---- online softmax of head n16 over the page: 4 tokens here, the rest in the other three 16-lane rows ----
@@ -250,7 +286,7 @@ __device__ __forceinline__ void gqa_mfma_item(
         __builtin_amdgcn_wave_barrier();   // ... and the next page's tile is written only behind these reads
         if (has_next) {
 #pragma unroll
-            for (int i = 0; i < NM; ++i) {
+            for (int i = 0; i < NL; ++i) {
                 kc[i] = kn[i];
                 vc[i] = vn[i];
             }
@@ -369,27 +405,36 @@ __global__ __launch_bounds__(kFuThreads, 2) void gqa_mfma_scan_kernel(
 
 // The plan is the chunked scans' (scan_plan.hpp) over B * Hkv virtual rows of g heads, g * hd wide, hd columns read; rows are
 // taken in grid order.  window: 0 = none (the caller has handed a window that covers n_sequence on as none).
-inline ScanPlan gqa_mfma_plan(const ScanTune& tune, int B, int S, int D, int H, int Hkv, int window) {
+inline ScanPlan gqa_mfma_plan(const ScanTune& tune, int B, int S, int D, int H, int Hkv, int window, int elem_bytes = 2) {
     ScanTune t = tune;
     t.row_order = 0;
     const int hd = D / H, g = H / Hkv;
-    return plan_chunked_scan(t, B * Hkv, S, window > 0 ? window_span(S, window) : S, g * hd, hd, g, 2);
+    return plan_chunked_scan(t, B * Hkv, S, window > 0 ? window_span(S, window) : S, g * hd, hd, g, elem_bytes);
 }
 
-// After gqa_mfma_shape_ok; ws = the workspace body.
+// The page element type of a launch: its bytes (the plan's item sizing and NT rule), its launch family, its four kernels.
+struct GqaMfmaBf16 {
+    static constexpr int kBytes = 2;
+    static constexpr LaunchFamily kFamily = kLfScanGqaMfma;
+    template <int HD, bool NT>
+    static constexpr auto kernel() { return &gqa_mfma_scan_kernel<HD, NT>; }
+};
+
+// After gqa_mfma_shape_ok (P = GqaMfmaFp8: gqa_mfma_fp8_shape_ok); ws = the workspace body.
+template <class P = GqaMfmaBf16>
 inline int launch_gqa_mfma_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S,
                                 int D, int H, int Hkv, int window, void* ws, size_t ws_bytes, hipStream_t st) {
     const int hd = D / H, g = H / Hkv;
-    const ScanPlan p = gqa_mfma_plan(scan_tune(), B, S, D, H, Hkv, window);
+    const ScanPlan p = gqa_mfma_plan(scan_tune(), B, S, D, H, Hkv, window, P::kBytes);
     ScanWs w;
     if (!carve_scan_ws(p, ws, ws_bytes, &w)) return MLI_ERR_WORKSPACE;
     const size_t work = gqa_mfma_work_bytes(hd, g), merge = heads_merge_stat_bytes(p.nchunk, g);
     const size_t smem = gqa_mfma_ptr_bytes(p.ct) + (work > merge ? work : merge);
     if (!scan_lds_fits(smem)) return MLI_ERR_BAD_ARG;   // (gqa_mfma_shape_ok keeps every accepted shape inside)
-    count_launch(kLfScanGqaMfma);
+    count_launch(P::kFamily);
     const dim3 grid(B * Hkv, p.grid_y), block(kFuThreads);
     const auto go = [&](auto hdc, auto nt) {
-        hipLaunchKernelGGL((gqa_mfma_scan_kernel<decltype(hdc)::value, decltype(nt)::value>), grid, block, smem, st, q, page_table,
+        hipLaunchKernelGGL((P::template kernel<decltype(hdc)::value, decltype(nt)::value>()), grid, block, smem, st, q, page_table,
                            lengths, out, w.ml, w.partial, S, D, Hkv, g, p.ct, p.nchunk, p.direct, w.arrivals, window);
     };
     using std::integral_constant;

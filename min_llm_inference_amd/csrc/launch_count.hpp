@@ -40,6 +40,7 @@ enum LaunchFamily {
     kLfScanPromptSinkLogits,  // attention_prompt.hpp: the prompt scan with a learned sink logit per query head
     kLfScanGqaMfma,       // attention_gqa_mfma.hpp: the grouped-query scan on matrix instructions
     kLfScanPromptMfma,    // attention_prompt_mfma.hpp: the causal prompt scan on matrix instructions
+    kLfScanGqaMfmaFp8,    // attention_gqa_mfma_fp8.hip: the grouped-query scan on matrix instructions over fp8 pages
     kLaunchFamilies
 };
 
@@ -50,7 +51,7 @@ constexpr const char* kLaunchFamilyNames[kLaunchFamilies] = {
     "scan_equal_shares", "scan_chunked",    "scan_rows_ordered",     "scan_rows_grid_order", "scan_heads_window",
     "scan_prompt",     "scan_heads_alibi",  "gemm_f32_rope",         "gemm_bf16_rope",    "scan_heads_softcap",
     "scan_prompt_softcap", "scan_heads_sink_logits", "scan_prompt_sink_logits", "scan_gqa_mfma",
-    "scan_prompt_mfma",
+    "scan_prompt_mfma", "scan_gqa_mfma_fp8",
 };
 
 inline thread_local uint64_t g_launch_counts[kLaunchFamilies] = {};

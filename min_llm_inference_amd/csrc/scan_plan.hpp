@@ -246,8 +246,7 @@ constexpr int gqa_kv_unit(int u, int lg, int g) { return (((u >> lg) / g) << lg)
 // MLI_GQA_MFMA_MAX_GROUP (the M rows of one MFMA tile hold the group), emb_dim to 8192 (the row's width shapes nothing in the
 // kernel; 8192 = 64 heads of 128), and B * n_kv_heads virtual rows within the arrival counters.  The last rule is
 // heads_lanes_log2's, over the g heads of a virtual row (g = 1: n_sequence to 262144).
-inline bool gqa_mfma_shape_ok(int B, int S, int D, int H, int Hkv, int elem) {
-    if (elem != MLI_ELEM_BF16) return false;
+inline bool gqa_mfma_heads_ok(int B, int S, int D, int H, int Hkv) {   // every rule but the page element type's
     if (B <= 0 || S <= 0 || S % kPlanPage != 0 || D <= 0 || D > 8192 || H < 1 || D % H != 0) return false;
     if (Hkv < 1 || Hkv > H || H % Hkv != 0 || H / Hkv > MLI_GQA_MFMA_MAX_GROUP) return false;
     const int hd = D / H;
@@ -257,6 +256,18 @@ inline bool gqa_mfma_shape_ok(int B, int S, int D, int H, int Hkv, int elem) {
     // to kMaxItemTokens for that where a virtual row has several heads, and leaves items of 64 tokens where it has one
     const int g = H / Hkv;
     return (long long)plan_ceil_div(S, g > 1 ? kMaxItemTokens : 64) * g <= kMaxMergeStats;
+}
+inline bool gqa_mfma_shape_ok(int B, int S, int D, int H, int Hkv, int elem) {
+    return elem == MLI_ELEM_BF16 && gqa_mfma_heads_ok(B, S, D, H, Hkv);
+}
+// ... over fp8 (OCP e4m3) pages (attention_gqa_mfma_fp8.hip): the same rules, and emb_dim to kGqaMfmaFp8MaxDim.  The scan
+// itself takes the bf16 kernel's widths.  The limit is that of what fills the pages: the fp8 fill, latest and prefill GEMMs
+// (proj_gemm_bf16.hip, plain and rotary) ask for emb_dim % 16 == 0 only, but they are held to the float64 model up to emb_dim
+// 2048 and no further -- the widest row the single-head fp8 scans take -- and mli_engine_create stops the fp8 engine there.
+// A predicate that accepted more would promise rows nothing has written under a judged test.
+constexpr int kGqaMfmaFp8MaxDim = 2048;
+inline bool gqa_mfma_fp8_shape_ok(int B, int S, int D, int H, int Hkv) {
+    return D <= kGqaMfmaFp8MaxDim && gqa_mfma_heads_ok(B, S, D, H, Hkv);
 }
 
 // ---- the causal multi-query prompt scan (attention_prompt.hpp) --------------------------------------------------------------

@@ -49,7 +49,8 @@ class Engine:
         self._h = ctypes.c_void_p()
         self._check(self._lib.mli_engine_create(ctypes.byref(self.cfg), *[k[1] for k in keep], ctypes.byref(self._h)))
         if heads_mfma:      # both head counts and the switch in one call: shapes set_heads / set_kv_heads refuse
-            self.set_heads_mfma(n_heads, n_heads if n_kv_heads is None else n_kv_heads)
+            setter = self.set_heads_mfma_fp8 if kind == PAGED_FP8 else self.set_heads_mfma
+            setter(n_heads, n_heads if n_kv_heads is None else n_kv_heads)
         else:
             if n_heads != 1:
                 self.set_heads(n_heads)
@@ -97,6 +98,11 @@ class Engine:
         paged kind with lean layers; with a window, page release, RoPE, logprobs and sampling, not with sink tokens, ALiBi, a
         soft cap, sink logits or prompt log-probabilities."""
         self._check(self._lib.mli_engine_set_heads_mfma(self._h, int(n_heads), int(n_kv_heads)))
+
+    def set_heads_mfma_fp8(self, n_heads, n_kv_heads):
+        """set_heads_mfma on the fp8 paged kind (mli_engine_set_heads_mfma_fp8): the only heads, grouped or not, that kind has;
+        emb_dim up to 2048.  The same contract otherwise; every other kind is refused."""
+        self._check(self._lib.mli_engine_set_heads_mfma_fp8(self._h, int(n_heads), int(n_kv_heads)))
 
     def set_alibi(self, slopes=None):
         """ALiBi (mli_engine_set_alibi): every decode scan adds slopes[h] * (s - (L - 1)) to query head h's scaled scores.

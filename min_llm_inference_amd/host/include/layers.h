@@ -69,13 +69,14 @@ struct PagedAttentionOptions {
     std::shared_ptr<TensorFloat> sink_logits;
     // The grouped-query scan on matrix instructions (bf16 pages; head_dim 64 or 128, groups of 1 .. 8 query heads, rows up to
     // 8192 wide) in place of the lane-group scan -- mli_paged_attention_lean_gqa_mfma.  Plain and windowed, with or without a
-    // rotary table; it has no sink tokens, slopes, cap or sink logits.
+    // rotary table; it has no sink tokens, slopes, cap or sink logits.  On fp8 pages (rows up to 2048 wide) it is
+    // mli_paged_attention_lean_gqa_mfma_fp8, the only scan with heads that page type has.
     bool heads_mfma = false;
 };
 
 // The setters of the option set, defined once for every class that has them: a layer owns the struct, a model hands out
 // its layer's.  A class whose scan has one head only (fp8 pages) takes set_n_heads / set_n_kv_heads / set_alibi_slopes /
-// set_softcap / set_sink_logits / set_heads_mfma out of its interface.
+// set_softcap / set_sink_logits out of its interface; set_heads_mfma stays in it (the MFMA scan is that page type's heads).
 class PagedAttentionOptionSetters {
 public:
     // EXTENSION: ALiBi -- slopes[h] * (s - (L - 1)) added to query head h's scaled scores; n_heads finite values, uploaded
@@ -104,8 +105,9 @@ public:
     // EXTENSION: the MFMA grouped-query scan -- n_heads query heads on n_kv_heads K/V heads (a divisor of n_heads; equal: plain
     // multi-head attention) decoded by mli_paged_attention_lean_gqa_mfma, which takes the wide rows the lane-group scan refuses.
     // Sets the two head counts and the switch together; set_heads_mfma(0, 0) takes the switch away and leaves the counts.  Counts
-    // that do not divide throw here; bf16 pages, the kernel's shape, the lean layers and none of sink tokens, slopes, cap or sink
-    // logits beside it are held at every forward, whichever setter came last (PagedAttentionLayerCore::check_heads_mfma).
+    // that do not divide throw here; bf16 or fp8 pages (the fp8 layer: mli_paged_attention_lean_gqa_mfma_fp8 under the fp8
+    // predicate), the kernel's shape, the lean layers and none of sink tokens, slopes, cap or sink logits beside it are held at
+    // every forward, whichever setter came last (PagedAttentionLayerCore::check_heads_mfma).
     void set_heads_mfma(int n_heads, int n_kv_heads);
     void set_n_heads(int n_heads) { options().n_heads = n_heads; }
     void set_n_kv_heads(int n_kv_heads) { options().n_kv_heads = n_kv_heads; }

@@ -83,6 +83,14 @@ struct mli_engine {
 
     bool paged_kind() const { return cfg.kind != MLI_ENGINE_CONTIGUOUS; }   // mli_engine_create admits the five kinds only
     bool heads_kind() const { return paged_kind() && cfg.kind != MLI_ENGINE_PAGED_FP8; }  // the fp8 scan has one head
+    // the setter that gave this engine its MFMA grouped-query scan, as the refusals of what the kernel lacks name it
+    const char* mfma_setter() const {
+        return cfg.kind == MLI_ENGINE_PAGED_FP8 ? "mli_engine_set_heads_mfma_fp8" : "mli_engine_set_heads_mfma";
+    }
+    void refuse_beside_mfma(const char* setter, const char* why) {
+        if (options().heads_mfma)
+            throw std::runtime_error(std::string(setter) + ": not with the MFMA grouped-query scan (" + mfma_setter() + ": " + why + ")");
+    }
     int elem() const {   // MLI_ELEM_* of the kind's pages
         return cfg.kind == MLI_ENGINE_PAGED_FP8 ? MLI_ELEM_FP8 : cfg.kind == MLI_ENGINE_PAGED_BF16 ? MLI_ELEM_BF16 : MLI_ELEM_F32;
     }
@@ -590,7 +598,7 @@ int mli_engine_configure(mli_engine* e, int lean_layers, int step_graphs) {
         if (e->started) throw std::runtime_error("mli_engine_configure after the engine has started");
         PagedAttentionOptions& o = e->options();
         if (o.heads_mfma && lean_layers == 0)   // (named first: what else the engine has set rides on it)
-            throw std::runtime_error("the MFMA grouped-query scan (mli_engine_set_heads_mfma) has the lean compositions only");
+            throw std::runtime_error(std::string("the MFMA grouped-query scan (") + e->mfma_setter() + ") has the lean compositions only");
         if (o.sink_logits && lean_layers == 0)   // (named first: an engine with sink logits has two heads at least)
             throw std::runtime_error("attention-sink logits (mli_engine_set_sink_logits) have the lean compositions only");
         if (o.softcap != 0.f && lean_layers == 0)   // (named first: an engine with a cap has two heads at least)
@@ -621,8 +629,8 @@ int mli_engine_set_heads(mli_engine* e, int n_heads) {
         if (n_heads != o.n_heads) {
             if (e->started) throw std::runtime_error("mli_engine_set_heads after the engine has started");
             if (o.heads_mfma)
-                throw std::runtime_error("mli_engine_set_heads: the heads of an engine with the MFMA scan are those of "
-                                         "mli_engine_set_heads_mfma (call it again to change them)");
+                throw std::runtime_error(std::string("mli_engine_set_heads: the heads of an engine with the MFMA scan are those of ") +
+                                         e->mfma_setter() + " (call it again to change them)");
             if (!e->heads_kind())
                 throw std::runtime_error("mli_engine_set_heads: multi-head attention serves the fp32 and bf16 paged engines");
             if (n_heads > 1 && !e->lean_layers)
@@ -666,8 +674,8 @@ int mli_engine_set_kv_heads(mli_engine* e, int n_kv_heads) {
         if (then != o.n_kv_heads) {
             if (e->started) throw std::runtime_error("mli_engine_set_kv_heads: n_kv_heads cannot change after the engine has started");
             if (o.heads_mfma)
-                throw std::runtime_error("mli_engine_set_kv_heads: the K/V heads of an engine with the MFMA scan are those of "
-                                         "mli_engine_set_heads_mfma (call it again to change them)");
+                throw std::runtime_error(std::string("mli_engine_set_kv_heads: the K/V heads of an engine with the MFMA scan are those of ") +
+                                         e->mfma_setter() + " (call it again to change them)");
             if (then != 0) {
                 // (n_heads > 1 here, so set_heads has accepted the kind, the lean layers and the shape; checked again all the same)
                 if (!e->heads_kind())
@@ -686,40 +694,44 @@ int mli_engine_set_kv_heads(mli_engine* e, int n_kv_heads) {
 // The switch and the two head counts are stored with the option set together: the shape is the MFMA scan's own
 // (gqa_mfma_shape_ok), so it is not held to what set_heads / set_kv_heads accept.  What the kernel does not have is refused
 // here and, for a later call, in that call's own setter.
+static void engine_set_heads_mfma(mli_engine* e, const std::string& name, bool fp8, int n_heads, int n_kv_heads) {
+    if (!e) throw std::runtime_error("null argument");
+    if (e->started) throw std::runtime_error(name + " after the engine has started");
+    if (e->cfg.kind != (fp8 ? MLI_ENGINE_PAGED_FP8 : MLI_ENGINE_PAGED_BF16))
+        throw std::runtime_error(name + (fp8 ? ": the MFMA grouped-query scan over fp8 pages serves the fp8 paged engine"
+                                             : ": the MFMA grouped-query scan serves the bf16 paged engine"));
+    if (!e->lean_layers) throw std::runtime_error(name + ": the MFMA grouped-query scan has the lean compositions only");
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0)
+        throw std::runtime_error(name + ": n_kv_heads must be >= 1 and divide n_heads");
+    const bool ok = fp8 ? mli::gqa_mfma_fp8_shape_ok(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, n_kv_heads)
+                        : mli::gqa_mfma_shape_ok(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, n_kv_heads, e->elem());
+    if (!ok)
+        throw std::runtime_error(name + ": unsupported (n_batch, emb_dim, n_heads, n_kv_heads): head_dim must be 64 or 128, "
+                                 "n_heads / n_kv_heads at most 8, emb_dim at most " + (fp8 ? "2048" : "8192") +
+                                 " and n_batch * n_kv_heads at most 16384");
+    PagedAttentionOptions& o = e->options();
+    if (o.n_sink != 0) throw std::runtime_error(name + ": not with sink tokens (mli_engine_set_sinks: the kernel has none)");
+    if (o.alibi_slopes) throw std::runtime_error(name + ": not with ALiBi (mli_engine_set_alibi: the kernel has no position bias)");
+    if (o.softcap != 0.f)
+        throw std::runtime_error(name + ": not with logit soft-capping (mli_engine_set_softcap: the kernel has no cap)");
+    if (o.sink_logits)
+        throw std::runtime_error(name + ": not with attention-sink logits (mli_engine_set_sink_logits: the kernel has no sink logit)");
+    if (e->prompt_logprobs_wanted)
+        throw std::runtime_error(name + ": not with prompt log-probabilities (mli_engine_set_prompt_logprobs: there is no prompt "
+                                 "scan for its shapes)");
+    if (o.rope_table && n_heads != o.n_heads)
+        throw std::runtime_error(name + ": the stored rotary table (mli_engine_set_rope) is that of " + std::to_string(o.n_heads) +
+                                 " heads");
+    e->paged->set_heads_mfma(n_heads, n_kv_heads);
+}
+
 int mli_engine_set_heads_mfma(mli_engine* e, int n_heads, int n_kv_heads) {
-    MLI_GUARD({
-        if (!e) throw std::runtime_error("null argument");
-        if (e->started) throw std::runtime_error("mli_engine_set_heads_mfma after the engine has started");
-        if (e->cfg.kind != MLI_ENGINE_PAGED_BF16)
-            throw std::runtime_error("mli_engine_set_heads_mfma: the MFMA grouped-query scan serves the bf16 paged engine");
-        if (!e->lean_layers)
-            throw std::runtime_error("mli_engine_set_heads_mfma: the MFMA grouped-query scan has the lean compositions only");
-        if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0)
-            throw std::runtime_error("mli_engine_set_heads_mfma: n_kv_heads must be >= 1 and divide n_heads");
-        if (!mli::gqa_mfma_shape_ok(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, n_kv_heads, e->elem()))
-            throw std::runtime_error("mli_engine_set_heads_mfma: unsupported (n_batch, emb_dim, n_heads, n_kv_heads): head_dim must "
-                                     "be 64 or 128, n_heads / n_kv_heads at most 8, emb_dim at most 8192 and n_batch * n_kv_heads "
-                                     "at most 16384");
-        PagedAttentionOptions& o = e->options();
-        if (o.n_sink != 0)
-            throw std::runtime_error("mli_engine_set_heads_mfma: not with sink tokens (mli_engine_set_sinks: the kernel has none)");
-        if (o.alibi_slopes)
-            throw std::runtime_error("mli_engine_set_heads_mfma: not with ALiBi (mli_engine_set_alibi: the kernel has no position "
-                                     "bias)");
-        if (o.softcap != 0.f)
-            throw std::runtime_error("mli_engine_set_heads_mfma: not with logit soft-capping (mli_engine_set_softcap: the kernel "
-                                     "has no cap)");
-        if (o.sink_logits)
-            throw std::runtime_error("mli_engine_set_heads_mfma: not with attention-sink logits (mli_engine_set_sink_logits: the "
-                                     "kernel has no sink logit)");
-        if (e->prompt_logprobs_wanted)
-            throw std::runtime_error("mli_engine_set_heads_mfma: not with prompt log-probabilities "
-                                     "(mli_engine_set_prompt_logprobs: there is no prompt scan for its shapes)");
-        if (o.rope_table && n_heads != o.n_heads)
-            throw std::runtime_error("mli_engine_set_heads_mfma: the stored rotary table (mli_engine_set_rope) is that of " +
-                                     std::to_string(o.n_heads) + " heads");
-        e->paged->set_heads_mfma(n_heads, n_kv_heads);
-    })
+    MLI_GUARD({ engine_set_heads_mfma(e, "mli_engine_set_heads_mfma", false, n_heads, n_kv_heads); })
+}
+
+// ... on the fp8 paged engine (mli_paged_attention_lean_gqa_mfma_fp8): the same contract, the fp8 predicate
+int mli_engine_set_heads_mfma_fp8(mli_engine* e, int n_heads, int n_kv_heads) {
+    MLI_GUARD({ engine_set_heads_mfma(e, "mli_engine_set_heads_mfma_fp8", true, n_heads, n_kv_heads); })
 }
 
 // The slopes are stored with the option set (the layer owns the device copy).  The shapes are the multi-head scan's, which
@@ -728,12 +740,10 @@ int mli_engine_set_alibi(mli_engine* e, const float* slopes_host, int n) {
     MLI_GUARD({
         if (!e) throw std::runtime_error("null argument");
         if (e->started) throw std::runtime_error("mli_engine_set_alibi after the engine has started");
+        e->refuse_beside_mfma("mli_engine_set_alibi", "the kernel has no position bias");   // (first: names the fp8 engine's setter)
         if (!e->heads_kind())
             throw std::runtime_error("mli_engine_set_alibi: ALiBi serves the fp32 and bf16 paged engines");
         PagedAttentionOptions& o = e->options();
-        if (o.heads_mfma)
-            throw std::runtime_error("mli_engine_set_alibi: not with the MFMA grouped-query scan (mli_engine_set_heads_mfma: the "
-                                     "kernel has no position bias)");
         if (o.n_heads < 2)
             throw std::runtime_error("mli_engine_set_alibi: n_heads must be >= 2 (mli_engine_set_heads comes first; the "
                                      "single-head scans have no bias)");
@@ -769,15 +779,14 @@ int mli_engine_set_softcap(mli_engine* e, float cap) {
     MLI_GUARD({
         if (!e) throw std::runtime_error("null argument");
         if (e->started) throw std::runtime_error("mli_engine_set_softcap after the engine has started");
+        if (e->cfg.kind == MLI_ENGINE_PAGED_FP8 && cap != 0.f) e->refuse_beside_mfma("mli_engine_set_softcap", "the kernel has no cap");
         if (!e->heads_kind())
             throw std::runtime_error("mli_engine_set_softcap: logit soft-capping serves the fp32 and bf16 paged engines");
         if (!std::isfinite(cap) || cap < 0.f)
             throw std::runtime_error("mli_engine_set_softcap: the cap must be finite and >= 0 (0: none)");
         PagedAttentionOptions& o = e->options();
         if (cap != 0.f) {
-            if (o.heads_mfma)
-                throw std::runtime_error("mli_engine_set_softcap: not with the MFMA grouped-query scan (mli_engine_set_heads_mfma: "
-                                         "the kernel has no cap)");
+            e->refuse_beside_mfma("mli_engine_set_softcap", "the kernel has no cap");
             if (e->prompt_mfma)
                 throw std::runtime_error("mli_engine_set_softcap: not with the prompt scan on matrix instructions "
                                          "(mli_engine_set_prompt_mfma: the kernel has no cap)");
@@ -807,13 +816,13 @@ int mli_engine_set_sink_logits(mli_engine* e, const float* logits_host, int n) {
     MLI_GUARD({
         if (!e) throw std::runtime_error("null argument");
         if (e->started) throw std::runtime_error("mli_engine_set_sink_logits after the engine has started");
+        if (e->cfg.kind == MLI_ENGINE_PAGED_FP8 && logits_host != nullptr)
+            e->refuse_beside_mfma("mli_engine_set_sink_logits", "the kernel has no sink logit");
         if (!e->heads_kind())
             throw std::runtime_error("mli_engine_set_sink_logits: attention-sink logits serve the fp32 and bf16 paged engines");
         PagedAttentionOptions& o = e->options();
         if (logits_host != nullptr) {
-            if (o.heads_mfma)
-                throw std::runtime_error("mli_engine_set_sink_logits: not with the MFMA grouped-query scan "
-                                         "(mli_engine_set_heads_mfma: the kernel has no sink logit)");
+            e->refuse_beside_mfma("mli_engine_set_sink_logits", "the kernel has no sink logit");
             if (e->prompt_mfma)
                 throw std::runtime_error("mli_engine_set_sink_logits: not with the prompt scan on matrix instructions "
                                          "(mli_engine_set_prompt_mfma: the kernel has no sink logit)");
@@ -922,9 +931,7 @@ int mli_engine_set_sinks(mli_engine* e, int n_sink) {
             throw std::runtime_error("mli_engine_set_sinks: attention sinks serve the paged engines");
         if (n_sink != o.n_sink) {
             if (e->started) throw std::runtime_error("mli_engine_set_sinks after the engine has started");
-            if (o.heads_mfma && n_sink != 0)
-                throw std::runtime_error("mli_engine_set_sinks: not with the MFMA grouped-query scan (mli_engine_set_heads_mfma: "
-                                         "the kernel has no sink tokens)");
+            if (n_sink != 0) e->refuse_beside_mfma("mli_engine_set_sinks", "the kernel has no sink tokens");
             if (e->prompt_mfma && n_sink != 0)
                 throw std::runtime_error("mli_engine_set_sinks: not with the prompt scan on matrix instructions "
                                          "(mli_engine_set_prompt_mfma: the kernel has no sink tokens)");
@@ -1071,6 +1078,8 @@ int mli_engine_set_prompt_logprobs(mli_engine* e, int enabled) {
         if (e->logprobs_n_top < 0)
             throw std::runtime_error("mli_engine_set_prompt_logprobs: an engine without logprobs (mli_engine_set_logprobs comes "
                                      "first: it supplies n_top)");
+        if (e->cfg.kind == MLI_ENGINE_PAGED_FP8 && enabled)
+            e->refuse_beside_mfma("mli_engine_set_prompt_logprobs", "there is no prompt scan for its shapes");
         if (e->cfg.kind == MLI_ENGINE_CONTIGUOUS || e->cfg.kind == MLI_ENGINE_PAGED_FP8)
             throw std::runtime_error("mli_engine_set_prompt_logprobs: prompt log-probabilities serve the fp32 and bf16 paged "
                                      "engines");
@@ -1083,9 +1092,7 @@ int mli_engine_set_prompt_logprobs(mli_engine* e, int enabled) {
         if (enabled && e->options().rope_table)
             throw std::runtime_error("mli_engine_set_prompt_logprobs: not with RoPE (mli_engine_set_rope: the prompt scan's q is "
                                      "not rotated, so the prompt would be scored under another model than the one that decodes)");
-        if (enabled && e->options().heads_mfma)
-            throw std::runtime_error("mli_engine_set_prompt_logprobs: not with the MFMA grouped-query scan "
-                                     "(mli_engine_set_heads_mfma: there is no prompt scan for its shapes)");
+        if (enabled) e->refuse_beside_mfma("mli_engine_set_prompt_logprobs", "there is no prompt scan for its shapes");
         if (!e->prompt_shape_ok())
             throw std::runtime_error("mli_engine_set_prompt_logprobs: the prompt scan does not take this (n_batch, n_sequence, "
                                      "emb_dim, n_heads, n_kv_heads): rows of at most two 16-byte lane loads");

@@ -13,8 +13,11 @@ PagedAttentionFp8Layer::PagedAttentionFp8Layer(TensorBf16&& wk, TensorBf16&& wq,
 
 void PagedAttentionFp8Layer::forward(TensorFloatPoint& page_table, const TensorInt& lengths,
                                      const TensorInt& new_batch_idx, TensorFloat& attention_result, int n_new_items) {
-    // fp8 pages have the lean composition only: one head, with or without a window and sinks, and nothing to fall back to
-    HIP_CHECK(lean_scan(page_table, lengths, new_batch_idx, attention_result, n_new_items, /*n_heads=*/1, /*n_kv_heads=*/0));
+    // fp8 pages have the lean composition only: one head, with or without a window and sinks, and nothing to fall back to --
+    // or, under set_heads_mfma, the heads of the MFMA grouped-query scan (the only scan with heads over fp8 pages)
+    const bool mfma = options_.heads_mfma;
+    HIP_CHECK(lean_scan(page_table, lengths, new_batch_idx, attention_result, n_new_items, mfma ? options_.n_heads : 1,
+                        mfma ? options_.n_kv_heads : 0));
 }
 
 PagedAttentionFp8InferenceModel::PagedAttentionFp8InferenceModel(PagedAttentionFp8Layer&& attention_layer, size_t n_batch,

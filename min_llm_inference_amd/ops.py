@@ -358,6 +358,18 @@ def decode_scan_paged_gqa_mfma(q_output, page_table, lengths, attention_result, 
                                                          _stream()), "mli_decode_scan_paged_gqa_mfma")
 
 
+def decode_scan_paged_gqa_mfma_fp8(q_output, page_table, lengths, attention_result, n_heads, n_kv_heads, window, n_sequence):
+    """decode_scan_paged_gqa_mfma over fp8 (OCP e4m3) pages (mli_decode_scan_paged_gqa_mfma_fp8): the only scan with heads,
+    grouped or not, on that page type.  Head size 64 or 128, n_heads / n_kv_heads 1 .. 8, D up to 2048; the result is, bit
+    for bit, decode_scan_paged_gqa_mfma's on bf16 pages holding the decoded values."""
+    B, D = q_output.shape
+    Hkv = int(n_kv_heads or n_heads)
+    ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads, mfma_kv_heads=Hkv)
+    _check(load_library().mli_decode_scan_paged_gqa_mfma_fp8(_p(q_output), _p(page_table), _p(lengths), _p(attention_result), B,
+                                                             int(n_sequence), D, int(n_heads), Hkv, int(window or 0), _p(ws),
+                                                             need, _stream()), "mli_decode_scan_paged_gqa_mfma_fp8")
+
+
 def alibi_slopes(n_heads):
     """The standard ALiBi slopes of n_heads heads (mli_alibi_slopes): a float32 numpy array; 2^(-8 (i + 1) / n) over the
     largest power of two n <= n_heads, then every other slope of the 2 n series."""
@@ -441,7 +453,8 @@ def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_outpu
     decode_scan_paged_sink_logits does (mli_paged_attention_lean_sink_logits), with any of window, sinks, n_kv_heads and rope,
     never with alibi_slopes or softcap;
     heads_mfma=True: the scan is decode_scan_paged_gqa_mfma (mli_paged_attention_lean_gqa_mfma), with any of window, n_kv_heads
-    and rope, never with sinks, alibi_slopes, softcap or sink_logits."""
+    and rope, never with sinks, alibi_slopes, softcap or sink_logits; with elem=ELEM_FP8 it is decode_scan_paged_gqa_mfma_fp8
+    (mli_paged_attention_lean_gqa_mfma_fp8)."""
     if heads_mfma:
         for name, given in (("sink tokens", sinks), ("ALiBi", alibi_slopes), ("logit soft-capping", softcap),
                             ("attention-sink logits", sink_logits)):
@@ -450,6 +463,12 @@ def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_outpu
         B, D = page_table.shape[0], wk.shape[0]
         Hkv = int(n_kv_heads or n_heads)
         ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads, mfma_kv_heads=Hkv)
+        if _elem_of(wk, elem) == ELEM_FP8:
+            _check(load_library().mli_paged_attention_lean_gqa_mfma_fp8(
+                _p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(new_batch_idx), _p(q_output), _p(attention_result), B,
+                int(n_sequence), D, int(n_new_items), int(n_heads), Hkv, int(window or 0), 0, _p(rope), _p(ws), need, _stream()),
+                "mli_paged_attention_lean_gqa_mfma_fp8")
+            return
         _check(load_library().mli_paged_attention_lean_gqa_mfma(
             _p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(new_batch_idx), _p(q_output), _p(attention_result), B,
             int(n_sequence), D, int(n_new_items), int(n_heads), Hkv, int(window or 0), 0, _p(rope), _elem_of(wk, elem), _p(ws),

@@ -1,0 +1,87 @@
+"""mli_decode_scan_paged_gqa_mfma_fp8 held to fp32 rounding error against the float64 model on the expanded operands,
+evaluated on the decoded fp8 pool: tests/test_gqa_mfma_scan_gpu.py's lengths, forced item sizes, cache policies, NaN poison and
+tolerance (f64_model.tolerance, unchanged).  SHAPES: one K and one V load per page (hd 64) | the largest group at the widest fp8
+row, two loads per page | plain multi-head attention there | odd g, padded tile columns | many items, the last arriver's merge.
+On the first shape the bf16 kernel runs on a bf16 pool of the decoded values: exact decode, same contraction order, same bits."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import f64_model as fm
+import gqa_model as gm
+import sinks_model as sm
+from accuracy_cases import base_case, fill_pages
+from gpu_util import host
+from helpers import assert_equal
+from test_gqa_mfma_scan_gpu import _length_vectors
+from test_gqa_scan_gpu import _device_tables, _unread_offsets
+from test_window_scan_gpu import SENTINEL, _nan_page, _poisoned_pool, _t
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(801, 6, 128, 256, 4, 2, (0, 40)), (802, 5, 256, 2048, 16, 2, (0,)), (803, 5, 256, 2048, 16, 16, (0,)),
+          (804, 5, 128, 448, 7, 1, (0, 17)), (805, 4, 1024, 1024, 8, 2, (0, 513))]
+CASES = [(seed, B, S, D, H, Hkv, W, part, assignment) for seed, B, S, D, H, Hkv, windows in SHAPES for W in windows
+         for part in range(len(_length_vectors(seed, B, S, W))) for assignment in ("mixed", "offsets")]
+
+
+@functools.lru_cache(maxsize=2)
+def _base(seed, B, S, D, W, part):
+    return base_case(seed, B, S, D, _length_vectors(seed, B, S, W)[part])
+
+
+@pytest.mark.parametrize("seed,B,S,D,H,Hkv,W,part,assignment", CASES)
+def test_gqa_mfma_fp8_scan(oracle, mli, dev, seed, B, S, D, H, Hkv, W, part, assignment):
+    from min_llm_inference_amd import ops
+    assert mli.mli_gqa_mfma_fp8_shape_supported(B, S, D, H, Hkv) == 1
+    assert {0, 1, 16, 17, 63, 64, 65, S - 1, S} | ({W} if W else set()) <= set(_length_vectors(seed, B, S, W).reshape(-1).tolist())
+    c = _base(seed, B, S, D, W, part)
+    L, hd = c["lengths"], D // H
+    q, kt = gm.apply_gqa_families(c, H, Hkv, assignment)
+    pool32, off = fill_pages(oracle, c, q, kt, c["v_cache"])
+    pages = c["table"][c["table"] >= 0].astype(np.int64)
+    x_seg = (pages[:, None, None] + (np.arange(16) * 3 * D)[None, :, None] + np.arange(D)[None, None, :]).reshape(-1)
+    gap = sm.gap_offsets(c["table"], L, S, D, W, 0) if W else np.zeros(0, np.int64)
+    dead = np.concatenate([off, gap, x_seg, _unread_offsets(c, D, Hkv * hd)])
+    pool, values = _poisoned_pool(pool32, dead, "fp8", dev)
+    s_live = max(-(-int(L.max()) // 16) * 16, 16)
+    ktm = fm.gather_pages(values, c["table"], L, s_live, D, 1).transpose(0, 2, 1)
+    v_rows = fm.gather_pages(values, c["table"], L, s_live, D, 2)
+    model, want = gm.model_gqa(q, ktm, v_rows, L, H, Hkv, W), gm.oracle_gqa(oracle, q, ktm, v_rows, L, H, Hkv, W)
+    _, table, _ = _device_tables(c, pool, "fp8", W, 0, _nan_page(D, "fp8", dev), dev)
+    qd, Ld = _t(q, dev), _t(L, dev)
+
+    def run(scan=None, pages=table):
+        out = torch.full((B, D), SENTINEL, device=dev)
+        (scan or ops.decode_scan_paged_gqa_mfma_fp8)(qd, pages, Ld, out, H, Hkv, W, S)
+        return host(out).copy()
+
+    others = [f for f in ops.launch_families() if f.startswith("scan_") and f != "scan_gqa_mfma_fp8"]
+    results = []
+    try:
+        for ct in (64, 0):
+            assert mli.mli_tune(b"chunk_tokens", ct) == 0
+            what = f"B{B} S{S} D{D} H{H} Hkv{Hkv} W{W} part {part} {assignment} chunk_tokens {ct}"
+            ops.reset_launch_counts()
+            got = run()
+            assert ops.launch_count("scan_gqa_mfma_fp8") == 1 and not any(ops.launch_count(f) for f in others), what
+            results += gm.compare(got, want, model, gm.head_families(assignment, H, Hkv), what=what)
+            assert (got[L == 0] == 0).all() and (got != SENTINEL).all(), f"{what}: rows of length 0 are exact zeros"
+            for b in np.nonzero(L == 1)[0]:
+                assert_equal(got[b], gm.expand_kv(v_rows[b, 0], H, Hkv), what=f"{what}: a row of one token returns V's row")
+            for nt in (0, 1, 2):                          # both cache policies, then the rule's: the same bits every time
+                assert mli.mli_tune(b"nt_loads", nt) == 0
+                assert_equal(run(), got, what=f"{what}: second launch, nt_loads {nt}")
+            ws, need = ops.workspace_for(B, S, D, dev, H, mfma_kv_heads=Hkv)
+            assert need > 65536 and not host(ws[:65536]).any(), f"{what}: the arrival counters are zero between calls"
+            if (B, S, D) == (6, 128, 256):
+                pool16, values16 = _poisoned_pool(values, dead, "bf16", dev)
+                assert np.array_equal(values16, values), "every e4m3 value is a bf16 value"
+                _, table16, _ = _device_tables(c, pool16, "bf16", W, 0, _nan_page(D, "bf16", dev), dev)
+                assert_equal(run(ops.decode_scan_paged_gqa_mfma, table16), got, what=f"{what}: the bf16 kernel on the decoded pool")
+    finally:
+        mli.mli_tune(b"chunk_tokens", 0)
+        mli.mli_tune(b"nt_loads", 2)
+    gm.assert_within(results, f"B{B} S{S} D{D} H{H} Hkv{Hkv} W{W} part {part} {assignment}")
