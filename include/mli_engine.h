@@ -278,6 +278,12 @@ int mli_engine_set_heads_mfma(mli_engine* engine, int n_heads, int n_kv_heads);
  * log-probabilities are refused on the fp8 kind in any case.) */
 int mli_engine_set_heads_mfma_fp8(mli_engine* engine, int n_heads, int n_kv_heads);
 
+/* EXTENSION: ... on the fp32 paged engines (mli_kernels.h: mli_paged_attention_lean_gqa_mfma_f32).  mli_engine_set_heads_mfma's
+ * contract on MLI_ENGINE_PAGED and MLI_ENGINE_PAGED_GEMM: the shapes are those of mli_gqa_mfma_f32_shape_supported (emb_dim to
+ * 2048, which mli_engine_set_heads refuses on these kinds beyond 512), every other kind is refused, and every refusal above --
+ * this call's and, when they come second, the five setters' -- names mli_engine_set_heads_mfma_f32. */
+int mli_engine_set_heads_mfma_f32(mli_engine* engine, int n_heads, int n_kv_heads);
+
 /* EXTENSION: the prompt scan on matrix instructions (mli_kernels.h: mli_paged_prompt_logprobs_mfma).  An engine with prompt
  * log-probabilities scores its prompts through that kernel in place of the lane-group prompt scan; decoding is untouched, so
  * tokens and generated-token figures keep their bits, and the prompt figures agree to fp32 accuracy.  After

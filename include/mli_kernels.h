@@ -522,6 +522,30 @@ int mli_paged_attention_lean_gqa_mfma_fp8(void* const* page_table, const int* le
                                           int window, int n_sink, const float* rope_table, void* workspace,
                                           size_t workspace_bytes, void* stream);
 
+/* ---- EXTENSION: ... over fp32 pages ---------------------------------------------------------------------------
+ * The same attention on pages of MLI_ELEM_F32 (a slot row is x | K | V, 3 * emb_dim floats), by a kernel of its own data path:
+ * fp32 K, q, probabilities and V go into v_mfma_f32_16x16x4_f32 as they are, no bf16 split.  It takes the fp32 rows the
+ * lane-group scans refuse (emb_dim > 512 with heads: the 2048-wide engine shape) and loads every K and V byte once per K/V
+ * head.  Opt-in like the two above: no other entry point dispatches it, mli_gqa_mfma_shape_supported(..., MLI_ELEM_F32) stays
+ * 0 and mli_paged_attention_lean_gqa_mfma keeps refusing fp32 pages.
+ * mli_gqa_mfma_f32_shape_supported: mli_gqa_mfma_shape_supported's rules without its element rule, AND emb_dim <= 2048 -- the
+ * widest fp32 row the fill and projection GEMMs are held to under a judged test, not a limit of the scan.
+ * Workspace: mli_gqa_mfma_workspace_bytes, as it is.  One launch ("scan_gqa_mfma_f32").  q_output and attention_result are
+ * 16-byte aligned.  MLI_ERR_BAD_ARG / MLI_ERR_WORKSPACE as above. */
+int mli_gqa_mfma_f32_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads);
+int mli_decode_scan_paged_gqa_mfma_f32(const float* q_output, const void* const* page_table, const int* lengths,
+                                       float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                       int n_kv_heads, int window, void* workspace, size_t workspace_bytes, void* stream);
+
+/* fill (n_new_items rows) -> latest -> the fp32 scan above, on fp32 pages with fp32 weights.  rope_table: null, or the table of
+ * mli_paged_attention_lean_rope.  MLI_ERR_BAD_ARG for n_sink != 0, for a null weight pointer and, with a table, as
+ * mli_paged_attention_lean_rope. */
+int mli_paged_attention_lean_gqa_mfma_f32(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                          const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                          int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads,
+                                          int window, int n_sink, const float* rope_table, void* workspace,
+                                          size_t workspace_bytes, void* stream);
+
 /* The decode projection of mli_paged_attention_lean on its own (q, k, v of every non-empty row's last token; k, v appended to
  * the page, q to q_output) for any page element type: elem = MLI_ELEM_*.  For fp32 / bf16 pages it is
  * mli_get_latest_k_q_v_paged[_bf16]; fp8 pages have no other entry point for it.  (bench.py times it apart from the scan.) */
@@ -990,6 +1014,7 @@ int mli_tune(const char* key, int value);
  *   "scan_gqa_mfma"          the grouped-query scan on matrix instructions (mli_decode_scan_paged_gqa_mfma)
  *   "scan_prompt_mfma"       the prompt scan on matrix instructions (mli_prompt_scan_paged_mfma)
  *   "scan_gqa_mfma_fp8"      the grouped-query scan on matrix instructions over fp8 pages (mli_decode_scan_paged_gqa_mfma_fp8)
+ *   "scan_gqa_mfma_f32"      the grouped-query scan on matrix instructions over fp32 pages (mli_decode_scan_paged_gqa_mfma_f32)
  * Forms, counted beside the launch's kernel family:
  *   "latest_compact"         a decode projection over the compacted list of non-empty rows ("latest_compact"; the panel and
  *                            the LDS-DMA kernel have no such list)

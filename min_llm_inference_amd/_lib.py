@@ -87,6 +87,9 @@ SIGNATURES = {
     "mli_gqa_mfma_fp8_shape_supported": [_I] * 5,
     "mli_decode_scan_paged_gqa_mfma_fp8": [_P] * 4 + [_I] * 6 + [_P, _Z, _P],
     "mli_paged_attention_lean_gqa_mfma_fp8": [_P] * 8 + [_I] * 8 + [_P, _P, _Z, _P],
+    "mli_gqa_mfma_f32_shape_supported": [_I] * 5,
+    "mli_decode_scan_paged_gqa_mfma_f32": [_P] * 4 + [_I] * 6 + [_P, _Z, _P],
+    "mli_paged_attention_lean_gqa_mfma_f32": [_P] * 8 + [_I] * 8 + [_P, _P, _Z, _P],
     "mli_rope_table": [_I, _I, ctypes.c_double, _P],
     "mli_get_latest_k_q_v_paged_rope": [_P] * 6 + [_I] * 4 + [_P, _I, _P],
     "mli_fill_new_k_v_cache_paged_rope": [_P] * 5 + [_I] * 5 + [_P, _I, _P],
@@ -188,6 +191,7 @@ ENGINE_SIGNATURES = {
     "mli_engine_set_kv_heads": [_P, _I],
     "mli_engine_set_heads_mfma": [_P, _I, _I],
     "mli_engine_set_heads_mfma_fp8": [_P, _I, _I],
+    "mli_engine_set_heads_mfma_f32": [_P, _I, _I],
     "mli_engine_set_prompt_mfma": [_P, _I],
     "mli_engine_set_alibi": [_P, _P, _I],
     "mli_engine_set_softcap": [_P, ctypes.c_float],

@@ -63,11 +63,12 @@ __device__ __forceinline__ void mfma_split3(float x, uint32_t (&part)[kMfmaParts
 __device__ __forceinline__ uint32_t mfma_pack(uint32_t first, uint32_t second) { return (first >> 16) | second; }
 
 // LDS of a workgroup: page pointers of the item (rounded to 16 bytes) | max(the waves' V tiles + parked rows + (m, l), the
-// row's (item, head) statistics during the merge).  Host and device compile this text.
-constexpr size_t gqa_mfma_vtile_bytes(int hd) { return (size_t)16 * (hd * 2 + 16); }
+// row's (item, head) statistics during the merge).  Host and device compile this text.  tile_elem_bytes: 2, the bf16 V tile
+// (bf16 and fp8 pages), or 4, the fp32 one.
+constexpr size_t gqa_mfma_vtile_bytes(int hd, int tile_elem_bytes = 2) { return (size_t)16 * (hd * tile_elem_bytes + 16); }
 constexpr size_t gqa_mfma_ptr_bytes(int ct) { return (((size_t)(ct / kPlanPage) * 8) + 15) & ~(size_t)15; }
-constexpr size_t gqa_mfma_work_bytes(int hd, int g) {
-    return kPlanWaves * (gqa_mfma_vtile_bytes(hd) + (size_t)g * hd * sizeof(float) + kMfmaMaxGroup * 8);
+constexpr size_t gqa_mfma_work_bytes(int hd, int g, int tile_elem_bytes = 2) {
+    return kPlanWaves * (gqa_mfma_vtile_bytes(hd, tile_elem_bytes) + (size_t)g * hd * sizeof(float) + kMfmaMaxGroup * 8);
 }
 
 // four e4m3 bytes of a page word -> four bf16 in two words, exactly (every e4m3 value is a bf16 value: 3 significand bits, and
@@ -415,12 +416,13 @@ inline ScanPlan gqa_mfma_plan(const ScanTune& tune, int B, int S, int D, int H, 
 // The page element type of a launch: its bytes (the plan's item sizing and NT rule), its launch family, its four kernels.
 struct GqaMfmaBf16 {
     static constexpr int kBytes = 2;
+    static constexpr int kTileBytes = 2;   // of a V tile element in LDS
     static constexpr LaunchFamily kFamily = kLfScanGqaMfma;
     template <int HD, bool NT>
     static constexpr auto kernel() { return &gqa_mfma_scan_kernel<HD, NT>; }
 };
 
-// After gqa_mfma_shape_ok (P = GqaMfmaFp8: gqa_mfma_fp8_shape_ok); ws = the workspace body.
+// After gqa_mfma_shape_ok (P = GqaMfmaFp8: gqa_mfma_fp8_shape_ok, GqaMfmaF32: gqa_mfma_f32_shape_ok); ws = the workspace body.
 template <class P = GqaMfmaBf16>
 inline int launch_gqa_mfma_scan(const float* q, const void* const* page_table, const int* lengths, float* out, int B, int S,
                                 int D, int H, int Hkv, int window, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -428,7 +430,7 @@ inline int launch_gqa_mfma_scan(const float* q, const void* const* page_table, c
     const ScanPlan p = gqa_mfma_plan(scan_tune(), B, S, D, H, Hkv, window, P::kBytes);
     ScanWs w;
     if (!carve_scan_ws(p, ws, ws_bytes, &w)) return MLI_ERR_WORKSPACE;
-    const size_t work = gqa_mfma_work_bytes(hd, g), merge = heads_merge_stat_bytes(p.nchunk, g);
+    const size_t work = gqa_mfma_work_bytes(hd, g, P::kTileBytes), merge = heads_merge_stat_bytes(p.nchunk, g);
     const size_t smem = gqa_mfma_ptr_bytes(p.ct) + (work > merge ? work : merge);
     if (!scan_lds_fits(smem)) return MLI_ERR_BAD_ARG;   // (gqa_mfma_shape_ok keeps every accepted shape inside)
     count_launch(P::kFamily);

@@ -47,6 +47,7 @@ __global__ __launch_bounds__(kFuThreads, 2) void gqa_mfma_fp8_scan_kernel(
 
 struct GqaMfmaFp8 {
     static constexpr int kBytes = 1;
+    static constexpr int kTileBytes = 2;
     static constexpr LaunchFamily kFamily = kLfScanGqaMfmaFp8;
     template <int HD, bool NT>
     static constexpr auto kernel() { return &gqa_mfma_fp8_scan_kernel<HD, NT>; }

@@ -87,8 +87,10 @@ int launch_heads_sink_logits_scan(const float*, const void* const*, const int*, 
 // ... and the grouped-query scan on matrix instructions (attention_gqa_mfma_bf16.hip: B, S, D, n_heads, n_kv_heads, window)
 int launch_gqa_mfma_decode(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, void*, size_t,
                            hipStream_t);
-// ... and the same over fp8 pages (attention_gqa_mfma_fp8.hip)
+// ... and the same over fp8 pages (attention_gqa_mfma_fp8.hip) and over fp32 pages (attention_gqa_mfma_f32.hip)
 int launch_gqa_mfma_fp8_decode(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, void*, size_t,
+                               hipStream_t);
+int launch_gqa_mfma_f32_decode(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, void*, size_t,
                                hipStream_t);
 
 // EXTENSION, rotary position embeddings (proj_gemm.hip): the projection and the fills with K and q rotated in the epilogue
@@ -773,13 +775,14 @@ int mli_decode_scan_paged_gqa_mfma_fp8(const float* q_output, const void* const*
                                            n_kv_heads, w, body.ptr, body.bytes, mli::as_stream(stream));
 }
 
-// fill -> latest (both rotated where a table is given) -> the fp8 scan above; bf16 weights
-int mli_paged_attention_lean_gqa_mfma_fp8(void* const* page_table, const int* lengths, const void* wk, const void* wq,
-                                          const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
-                                          int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads,
-                                          int window, int n_sink, const float* rope_table, void* workspace,
-                                          size_t workspace_bytes, void* stream) {
-    if (n_sink != 0 || !mli::gqa_mfma_fp8_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads)) return MLI_ERR_BAD_ARG;
+// fill -> latest (both rotated where a table is given) -> `scan`, one of the two typed scans (fp8 pages with bf16 weights, fp32
+// pages with fp32 weights), after the caller's shape predicate
+using TypedGqaMfmaScan = int (*)(const float*, const void* const*, const int*, float*, int, int, int, int, int, int, void*, size_t,
+                                 void*);
+static int lean_gqa_mfma_typed(int elem, TypedGqaMfmaScan scan, void* const* page_table, const int* lengths, const void* wk,
+                               const void* wq, const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                               int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads, int window,
+                               const float* rope_table, void* workspace, size_t workspace_bytes, void* stream) {
     if (page_table == nullptr || lengths == nullptr || q_output == nullptr || attention_result == nullptr || wk == nullptr ||
         wq == nullptr || wv == nullptr)
         return MLI_ERR_BAD_ARG;
@@ -787,19 +790,56 @@ int mli_paged_attention_lean_gqa_mfma_fp8(void* const* page_table, const int* le
     hipStream_t st = mli::as_stream(stream);
     int rc;
     if (rope_table != nullptr) {
-        rc = mli::launch_fill_paged_rope(MLI_ELEM_FP8, nullptr, nullptr, nullptr, page_table, new_batch_idx, lengths, wk, wv,
-                                         n_batch, n_sequence, emb_dim, n_new_items, false, 0, 0, n_heads, rope_table, st);
+        rc = mli::launch_fill_paged_rope(elem, nullptr, nullptr, nullptr, page_table, new_batch_idx, lengths, wk, wv, n_batch,
+                                         n_sequence, emb_dim, n_new_items, false, 0, 0, n_heads, rope_table, st);
         if (!rc)
-            rc = mli::launch_latest_paged_rope(MLI_ELEM_FP8, page_table, lengths, wk, wq, wv, q_output, n_batch, n_sequence,
-                                               emb_dim, n_heads, rope_table, st);
+            rc = mli::launch_latest_paged_rope(elem, page_table, lengths, wk, wq, wv, q_output, n_batch, n_sequence, emb_dim,
+                                               n_heads, rope_table, st);
     } else {
-        rc = mli::launch_fill_and_latest(MLI_ELEM_FP8, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, n_batch,
-                                         n_sequence, emb_dim, n_new_items, st);
+        rc = mli::launch_fill_and_latest(elem, page_table, lengths, wk, wq, wv, new_batch_idx, q_output, n_batch, n_sequence,
+                                         emb_dim, n_new_items, st);
     }
     if (rc) return rc;
-    return mli_decode_scan_paged_gqa_mfma_fp8(q_output, reinterpret_cast<const void* const*>(page_table), lengths,
-                                              attention_result, n_batch, n_sequence, emb_dim, n_heads, n_kv_heads, window,
-                                              workspace, workspace_bytes, stream);
+    return scan(q_output, reinterpret_cast<const void* const*>(page_table), lengths, attention_result, n_batch, n_sequence, emb_dim,
+                n_heads, n_kv_heads, window, workspace, workspace_bytes, stream);
+}
+
+int mli_paged_attention_lean_gqa_mfma_fp8(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                          const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                          int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads,
+                                          int window, int n_sink, const float* rope_table, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    if (n_sink != 0 || !mli::gqa_mfma_fp8_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads)) return MLI_ERR_BAD_ARG;
+    return lean_gqa_mfma_typed(MLI_ELEM_FP8, mli_decode_scan_paged_gqa_mfma_fp8, page_table, lengths, wk, wq, wv, new_batch_idx,
+                               q_output, attention_result, n_batch, n_sequence, emb_dim, n_new_items, n_heads, n_kv_heads, window,
+                               rope_table, workspace, workspace_bytes, stream);
+}
+
+// ... over fp32 pages (attention_gqa_mfma_f32.hip): the same workspace, for the same reason
+int mli_gqa_mfma_f32_shape_supported(int n_batch, int n_sequence, int emb_dim, int n_heads, int n_kv_heads) {
+    return mli::gqa_mfma_f32_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads) ? 1 : 0;
+}
+
+int mli_decode_scan_paged_gqa_mfma_f32(const float* q_output, const void* const* page_table, const int* lengths,
+                                       float* attention_result, int n_batch, int n_sequence, int emb_dim, int n_heads,
+                                       int n_kv_heads, int window, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!mli::gqa_mfma_f32_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads)) return MLI_ERR_BAD_ARG;
+    if (q_output == nullptr || page_table == nullptr || lengths == nullptr || attention_result == nullptr) return MLI_ERR_BAD_ARG;
+    const mli::WsBody body = mli::ws_body(workspace, workspace_bytes);
+    const int w = mli::lean_scan_kind(n_sequence, window, 0) == mli::kScanWindow ? window : 0;
+    return mli::launch_gqa_mfma_f32_decode(q_output, page_table, lengths, attention_result, n_batch, n_sequence, emb_dim, n_heads,
+                                           n_kv_heads, w, body.ptr, body.bytes, mli::as_stream(stream));
+}
+
+int mli_paged_attention_lean_gqa_mfma_f32(void* const* page_table, const int* lengths, const void* wk, const void* wq,
+                                          const void* wv, const int* new_batch_idx, float* q_output, float* attention_result,
+                                          int n_batch, int n_sequence, int emb_dim, int n_new_items, int n_heads, int n_kv_heads,
+                                          int window, int n_sink, const float* rope_table, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    if (n_sink != 0 || !mli::gqa_mfma_f32_shape_ok(n_batch, n_sequence, emb_dim, n_heads, n_kv_heads)) return MLI_ERR_BAD_ARG;
+    return lean_gqa_mfma_typed(MLI_ELEM_F32, mli_decode_scan_paged_gqa_mfma_f32, page_table, lengths, wk, wq, wv, new_batch_idx,
+                               q_output, attention_result, n_batch, n_sequence, emb_dim, n_new_items, n_heads, n_kv_heads, window,
+                               rope_table, workspace, workspace_bytes, stream);
 }
 
 // fill -> latest (both rotated where a table is given) -> mli_decode_scan_paged_gqa_mfma

@@ -41,6 +41,7 @@ enum LaunchFamily {
     kLfScanGqaMfma,       // attention_gqa_mfma.hpp: the grouped-query scan on matrix instructions
     kLfScanPromptMfma,    // attention_prompt_mfma.hpp: the causal prompt scan on matrix instructions
     kLfScanGqaMfmaFp8,    // attention_gqa_mfma_fp8.hip: the grouped-query scan on matrix instructions over fp8 pages
+    kLfScanGqaMfmaF32,    // attention_gqa_mfma_f32.hip: the grouped-query scan on matrix instructions over fp32 pages
     kLaunchFamilies
 };
 
@@ -51,7 +52,7 @@ constexpr const char* kLaunchFamilyNames[kLaunchFamilies] = {
     "scan_equal_shares", "scan_chunked",    "scan_rows_ordered",     "scan_rows_grid_order", "scan_heads_window",
     "scan_prompt",     "scan_heads_alibi",  "gemm_f32_rope",         "gemm_bf16_rope",    "scan_heads_softcap",
     "scan_prompt_softcap", "scan_heads_sink_logits", "scan_prompt_sink_logits", "scan_gqa_mfma",
-    "scan_prompt_mfma", "scan_gqa_mfma_fp8",
+    "scan_prompt_mfma", "scan_gqa_mfma_fp8", "scan_gqa_mfma_f32",
 };
 
 inline thread_local uint64_t g_launch_counts[kLaunchFamilies] = {};

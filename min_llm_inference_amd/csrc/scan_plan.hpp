@@ -270,6 +270,14 @@ inline bool gqa_mfma_fp8_shape_ok(int B, int S, int D, int H, int Hkv) {
     return D <= kGqaMfmaFp8MaxDim && gqa_mfma_heads_ok(B, S, D, H, Hkv);
 }
 
+// ... over fp32 pages (attention_gqa_mfma_f32.hip): the same rules, and emb_dim to kGqaMfmaF32MaxDim.  The scan itself takes
+// the bf16 kernel's widths.  The limit is again that of what fills the pages under a judged test: fp32 rows are held to the
+// float64 model up to emb_dim 2048 (tests/test_shape_limits_gpu.py::test_widest_rows, the benchmark's engine shape), not beyond.
+constexpr int kGqaMfmaF32MaxDim = 2048;
+inline bool gqa_mfma_f32_shape_ok(int B, int S, int D, int H, int Hkv) {
+    return D <= kGqaMfmaF32MaxDim && gqa_mfma_heads_ok(B, S, D, H, Hkv);
+}
+
 // ---- the causal multi-query prompt scan (attention_prompt.hpp) --------------------------------------------------------------
 // What it takes: fp32 and bf16 pages with rows of at most two lane loads -- one head: fp32 to emb_dim 512, bf16 to 1024;
 // several heads, with or without grouped K/V heads: what heads_lanes_log2 / gqa_shape_supported accept.  n_kv_heads ==

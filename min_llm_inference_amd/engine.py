@@ -49,7 +49,8 @@ class Engine:
         self._h = ctypes.c_void_p()
         self._check(self._lib.mli_engine_create(ctypes.byref(self.cfg), *[k[1] for k in keep], ctypes.byref(self._h)))
         if heads_mfma:      # both head counts and the switch in one call: shapes set_heads / set_kv_heads refuse
-            setter = self.set_heads_mfma_fp8 if kind == PAGED_FP8 else self.set_heads_mfma
+            setter = {PAGED_FP8: self.set_heads_mfma_fp8, PAGED: self.set_heads_mfma_f32,
+                      PAGED_GEMM: self.set_heads_mfma_f32}.get(kind, self.set_heads_mfma)
             setter(n_heads, n_heads if n_kv_heads is None else n_kv_heads)
         else:
             if n_heads != 1:
@@ -103,6 +104,11 @@ class Engine:
         """set_heads_mfma on the fp8 paged kind (mli_engine_set_heads_mfma_fp8): the only heads, grouped or not, that kind has;
         emb_dim up to 2048.  The same contract otherwise; every other kind is refused."""
         self._check(self._lib.mli_engine_set_heads_mfma_fp8(self._h, int(n_heads), int(n_kv_heads)))
+
+    def set_heads_mfma_f32(self, n_heads, n_kv_heads):
+        """set_heads_mfma on the fp32 paged kinds, PAGED and PAGED_GEMM (mli_engine_set_heads_mfma_f32): emb_dim up to 2048,
+        where set_heads stops at 512.  The same contract otherwise; every other kind is refused."""
+        self._check(self._lib.mli_engine_set_heads_mfma_f32(self._h, int(n_heads), int(n_kv_heads)))
 
     def set_alibi(self, slopes=None):
         """ALiBi (mli_engine_set_alibi): every decode scan adds slopes[h] * (s - (L - 1)) to query head h's scaled scores.

@@ -71,6 +71,8 @@ struct PagedAttentionOptions {
     // 8192 wide) in place of the lane-group scan -- mli_paged_attention_lean_gqa_mfma.  Plain and windowed, with or without a
     // rotary table; it has no sink tokens, slopes, cap or sink logits.  On fp8 pages (rows up to 2048 wide) it is
     // mli_paged_attention_lean_gqa_mfma_fp8, the only scan with heads that page type has.
+    // On fp32 pages (rows up to 2048 wide, where the lane-group scans with heads stop at 512) it is
+    // mli_paged_attention_lean_gqa_mfma_f32.
     bool heads_mfma = false;
 };
 

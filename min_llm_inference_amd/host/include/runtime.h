@@ -52,7 +52,7 @@ bool lean_layers();
 // other options are, slopes included; every failure throws.  softcap (EXTENSION, logit soft-capping; 0: none):
 // mli_paged_attention_lean_softcap, with or without a rotary table; slopes beside it throw.  sink_logits (EXTENSION, n_heads
 // floats in device memory; null: none): mli_paged_attention_lean_sink_logits, with or without a rotary table; slopes or a cap
-// beside them throw.  heads_mfma (EXTENSION, bf16 pages; fp8 pages: ..._gqa_mfma_fp8): mli_paged_attention_lean_gqa_mfma with a scratch of its own size, with
+// beside them throw.  heads_mfma (EXTENSION, bf16 pages; fp8 pages: ..._gqa_mfma_fp8; fp32 pages: ..._gqa_mfma_f32): mli_paged_attention_lean_gqa_mfma with a scratch of its own size, with
 // or without a window or a rotary table; slopes, a cap, sink logits or sink tokens beside it throw, and so does every failure.
 bool lean_paged_wanted(int n_heads, int window, int n_sequence);
 int lean_paged_attention(int elem, int n_heads, int window, int n_sink, void* const* page_table, const int* lengths,

@@ -85,7 +85,9 @@ struct mli_engine {
     bool heads_kind() const { return paged_kind() && cfg.kind != MLI_ENGINE_PAGED_FP8; }  // the fp8 scan has one head
     // the setter that gave this engine its MFMA grouped-query scan, as the refusals of what the kernel lacks name it
     const char* mfma_setter() const {
-        return cfg.kind == MLI_ENGINE_PAGED_FP8 ? "mli_engine_set_heads_mfma_fp8" : "mli_engine_set_heads_mfma";
+        return cfg.kind == MLI_ENGINE_PAGED_FP8    ? "mli_engine_set_heads_mfma_fp8"
+               : cfg.kind == MLI_ENGINE_PAGED_BF16 ? "mli_engine_set_heads_mfma"
+                                                   : "mli_engine_set_heads_mfma_f32";
     }
     void refuse_beside_mfma(const char* setter, const char* why) {
         if (options().heads_mfma)
@@ -694,20 +696,24 @@ int mli_engine_set_kv_heads(mli_engine* e, int n_kv_heads) {
 // The switch and the two head counts are stored with the option set together: the shape is the MFMA scan's own
 // (gqa_mfma_shape_ok), so it is not held to what set_heads / set_kv_heads accept.  What the kernel does not have is refused
 // here and, for a later call, in that call's own setter.
-static void engine_set_heads_mfma(mli_engine* e, const std::string& name, bool fp8, int n_heads, int n_kv_heads) {
+static void engine_set_heads_mfma(mli_engine* e, const std::string& name, int elem, int n_heads, int n_kv_heads) {
     if (!e) throw std::runtime_error("null argument");
     if (e->started) throw std::runtime_error(name + " after the engine has started");
-    if (e->cfg.kind != (fp8 ? MLI_ENGINE_PAGED_FP8 : MLI_ENGINE_PAGED_BF16))
-        throw std::runtime_error(name + (fp8 ? ": the MFMA grouped-query scan over fp8 pages serves the fp8 paged engine"
-                                             : ": the MFMA grouped-query scan serves the bf16 paged engine"));
+    const bool fp8 = elem == MLI_ELEM_FP8, f32 = elem == MLI_ELEM_F32;
+    if (!e->paged_kind() || e->elem() != elem)
+        throw std::runtime_error(name + (fp8   ? ": the MFMA grouped-query scan over fp8 pages serves the fp8 paged engine"
+                                         : f32 ? ": the MFMA grouped-query scan over fp32 pages serves the fp32 paged engines"
+                                               : ": the MFMA grouped-query scan serves the bf16 paged engine"));
     if (!e->lean_layers) throw std::runtime_error(name + ": the MFMA grouped-query scan has the lean compositions only");
     if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads != 0)
         throw std::runtime_error(name + ": n_kv_heads must be >= 1 and divide n_heads");
-    const bool ok = fp8 ? mli::gqa_mfma_fp8_shape_ok(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, n_kv_heads)
-                        : mli::gqa_mfma_shape_ok(e->cfg.n_batch, e->cfg.n_sequence, e->cfg.emb_dim, n_heads, n_kv_heads, e->elem());
+    const int B = e->cfg.n_batch, S = e->cfg.n_sequence, D = e->cfg.emb_dim;
+    const bool ok = fp8   ? mli::gqa_mfma_fp8_shape_ok(B, S, D, n_heads, n_kv_heads)
+                    : f32 ? mli::gqa_mfma_f32_shape_ok(B, S, D, n_heads, n_kv_heads)
+                          : mli::gqa_mfma_shape_ok(B, S, D, n_heads, n_kv_heads, elem);
     if (!ok)
         throw std::runtime_error(name + ": unsupported (n_batch, emb_dim, n_heads, n_kv_heads): head_dim must be 64 or 128, "
-                                 "n_heads / n_kv_heads at most 8, emb_dim at most " + (fp8 ? "2048" : "8192") +
+                                 "n_heads / n_kv_heads at most 8, emb_dim at most " + (fp8 || f32 ? "2048" : "8192") +
                                  " and n_batch * n_kv_heads at most 16384");
     PagedAttentionOptions& o = e->options();
     if (o.n_sink != 0) throw std::runtime_error(name + ": not with sink tokens (mli_engine_set_sinks: the kernel has none)");
@@ -726,12 +732,17 @@ static void engine_set_heads_mfma(mli_engine* e, const std::string& name, bool f
 }
 
 int mli_engine_set_heads_mfma(mli_engine* e, int n_heads, int n_kv_heads) {
-    MLI_GUARD({ engine_set_heads_mfma(e, "mli_engine_set_heads_mfma", false, n_heads, n_kv_heads); })
+    MLI_GUARD({ engine_set_heads_mfma(e, "mli_engine_set_heads_mfma", MLI_ELEM_BF16, n_heads, n_kv_heads); })
 }
 
 // ... on the fp8 paged engine (mli_paged_attention_lean_gqa_mfma_fp8): the same contract, the fp8 predicate
 int mli_engine_set_heads_mfma_fp8(mli_engine* e, int n_heads, int n_kv_heads) {
-    MLI_GUARD({ engine_set_heads_mfma(e, "mli_engine_set_heads_mfma_fp8", true, n_heads, n_kv_heads); })
+    MLI_GUARD({ engine_set_heads_mfma(e, "mli_engine_set_heads_mfma_fp8", MLI_ELEM_FP8, n_heads, n_kv_heads); })
+}
+
+// ... on the fp32 paged engines, PAGED and PAGED_GEMM (mli_paged_attention_lean_gqa_mfma_f32): the same contract, the fp32 predicate
+int mli_engine_set_heads_mfma_f32(mli_engine* e, int n_heads, int n_kv_heads) {
+    MLI_GUARD({ engine_set_heads_mfma(e, "mli_engine_set_heads_mfma_f32", MLI_ELEM_F32, n_heads, n_kv_heads); })
 }
 
 // The slopes are stored with the option set (the layer owns the device copy).  The shapes are the multi-head scan's, which

@@ -317,10 +317,10 @@ int mli::runtime::lean_paged_attention(int elem, int n_heads, int window, int n_
         if (n_sink != 0) throw std::runtime_error("the MFMA grouped-query scan and sink tokens are not combined");
         const int Hkv = n_kv_heads != 0 ? n_kv_heads : n_heads;
         const Scratch ws = scratch_of(mli_gqa_mfma_workspace_bytes(B, S, D, n_heads, Hkv));   // its own size: rows past 1024
-        if (elem == MLI_ELEM_FP8)
-            HIP_CHECK(mli_paged_attention_lean_gqa_mfma_fp8(page_table, lengths, wk, wq, wv, new_batch_idx, q_output,
-                                                            attention_result, B, S, D, n_new_items, n_heads, Hkv, window, 0,
-                                                            rope_table, ws.ptr, ws.bytes, stream()));
+        if (elem == MLI_ELEM_FP8 || elem == MLI_ELEM_F32)
+            HIP_CHECK((elem == MLI_ELEM_FP8 ? mli_paged_attention_lean_gqa_mfma_fp8 : mli_paged_attention_lean_gqa_mfma_f32)(
+                page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result, B, S, D, n_new_items, n_heads, Hkv,
+                window, 0, rope_table, ws.ptr, ws.bytes, stream()));
         else
             HIP_CHECK(mli_paged_attention_lean_gqa_mfma(page_table, lengths, wk, wq, wv, new_batch_idx, q_output, attention_result,
                                                         B, S, D, n_new_items, n_heads, Hkv, window, 0, rope_table, elem, ws.ptr,

@@ -206,9 +206,10 @@ void PagedAttentionLayerCore<Weights>::check_heads_mfma() const {
     if (!options_.heads_mfma) return;
     const int Hkv = options_.n_kv_heads != 0 ? options_.n_kv_heads : options_.n_heads;
     const int B = (int)q_output_.shape()[0], S = (int)n_sequence_, D = (int)wk_.shape()[0];
-    if (elem_ == MLI_ELEM_FP8 ? !mli_gqa_mfma_fp8_shape_supported(B, S, D, options_.n_heads, Hkv)
-                              : !mli_gqa_mfma_shape_supported(B, S, D, options_.n_heads, Hkv, elem_))
-        throw std::runtime_error("the MFMA grouped-query scan (set_heads_mfma) takes bf16 pages (emb_dim <= 8192) or fp8 pages (<= 2048), "
+    if (elem_ == MLI_ELEM_FP8   ? !mli_gqa_mfma_fp8_shape_supported(B, S, D, options_.n_heads, Hkv)
+        : elem_ == MLI_ELEM_F32 ? !mli_gqa_mfma_f32_shape_supported(B, S, D, options_.n_heads, Hkv)
+                                : !mli_gqa_mfma_shape_supported(B, S, D, options_.n_heads, Hkv, elem_))
+        throw std::runtime_error("the MFMA grouped-query scan (set_heads_mfma) takes bf16 pages (emb_dim <= 8192) or fp8 or fp32 pages (<= 2048), "
                                  "head_dim 64 or 128 and groups of 1 .. 8 query heads: not " + std::to_string(options_.n_heads) + " heads on " +
                                  std::to_string(Hkv) + " K/V heads at emb_dim " + std::to_string(wk_.shape()[0]));
     if (!mli::runtime::lean_layers()) throw std::runtime_error("the MFMA grouped-query scan exists in the lean composition only");

@@ -370,6 +370,18 @@ def decode_scan_paged_gqa_mfma_fp8(q_output, page_table, lengths, attention_resu
                                                              need, _stream()), "mli_decode_scan_paged_gqa_mfma_fp8")
 
 
+def decode_scan_paged_gqa_mfma_f32(q_output, page_table, lengths, attention_result, n_heads, n_kv_heads, window, n_sequence):
+    """decode_scan_paged_gqa_mfma over fp32 pages (mli_decode_scan_paged_gqa_mfma_f32), on fp32 matrix instructions without a
+    bf16 split: the fp32 rows with heads that the lane-group scans refuse.  Head size 64 or 128, n_heads / n_kv_heads 1 .. 8,
+    D up to 2048."""
+    B, D = q_output.shape
+    Hkv = int(n_kv_heads or n_heads)
+    ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads, mfma_kv_heads=Hkv)
+    _check(load_library().mli_decode_scan_paged_gqa_mfma_f32(_p(q_output), _p(page_table), _p(lengths), _p(attention_result), B,
+                                                             int(n_sequence), D, int(n_heads), Hkv, int(window or 0), _p(ws),
+                                                             need, _stream()), "mli_decode_scan_paged_gqa_mfma_f32")
+
+
 def alibi_slopes(n_heads):
     """The standard ALiBi slopes of n_heads heads (mli_alibi_slopes): a float32 numpy array; 2^(-8 (i + 1) / n) over the
     largest power of two n <= n_heads, then every other slope of the 2 n series."""
@@ -454,7 +466,7 @@ def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_outpu
     never with alibi_slopes or softcap;
     heads_mfma=True: the scan is decode_scan_paged_gqa_mfma (mli_paged_attention_lean_gqa_mfma), with any of window, n_kv_heads
     and rope, never with sinks, alibi_slopes, softcap or sink_logits; with elem=ELEM_FP8 it is decode_scan_paged_gqa_mfma_fp8
-    (mli_paged_attention_lean_gqa_mfma_fp8)."""
+    (mli_paged_attention_lean_gqa_mfma_fp8), with fp32 weights decode_scan_paged_gqa_mfma_f32 (mli_paged_attention_lean_gqa_mfma_f32)."""
     if heads_mfma:
         for name, given in (("sink tokens", sinks), ("ALiBi", alibi_slopes), ("logit soft-capping", softcap),
                             ("attention-sink logits", sink_logits)):
@@ -463,11 +475,12 @@ def paged_attention_lean(page_table, lengths, wk, wq, wv, new_batch_idx, q_outpu
         B, D = page_table.shape[0], wk.shape[0]
         Hkv = int(n_kv_heads or n_heads)
         ws, need = workspace_for(B, n_sequence, D, q_output.device, n_heads, mfma_kv_heads=Hkv)
-        if _elem_of(wk, elem) == ELEM_FP8:
-            _check(load_library().mli_paged_attention_lean_gqa_mfma_fp8(
+        if _elem_of(wk, elem) != ELEM_BF16:     # the typed compositions: fp8 pages (bf16 weights), fp32 pages
+            name = "mli_paged_attention_lean_gqa_mfma_" + ("fp8" if _elem_of(wk, elem) == ELEM_FP8 else "f32")
+            _check(getattr(load_library(), name)(
                 _p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(new_batch_idx), _p(q_output), _p(attention_result), B,
                 int(n_sequence), D, int(n_new_items), int(n_heads), Hkv, int(window or 0), 0, _p(rope), _p(ws), need, _stream()),
-                "mli_paged_attention_lean_gqa_mfma_fp8")
+                name)
             return
         _check(load_library().mli_paged_attention_lean_gqa_mfma(
             _p(page_table), _p(lengths), _p(wk), _p(wq), _p(wv), _p(new_batch_idx), _p(q_output), _p(attention_result), B,

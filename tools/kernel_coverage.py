@@ -45,6 +45,7 @@ UNPROFILED_SECONDS = {
     "test_encoder_decoder_gpu.py": 3, "test_engine_dispatch_gpu.py": 23, "test_engine_gpu.py": 25,
     "test_engine_replay_gpu.py": 21, "test_full_size_properties_gpu.py": 12, "test_gemm_edges_gpu.py": 24,
     "test_golden_gpu.py": 3, "test_gqa_engine_gpu.py": 4, "test_gqa_mfma_engine_gpu.py": 20,
+    "test_gqa_mfma_f32_engine_gpu.py": 9, "test_gqa_mfma_f32_scan_gpu.py": 6,
     "test_gqa_mfma_fp8_engine_gpu.py": 7, "test_gqa_mfma_fp8_scan_gpu.py": 6, "test_gqa_mfma_scan_gpu.py": 7, "test_gqa_scan_gpu.py": 12,
     "test_heads_engine_gpu.py": 4,
     "test_heads_instantiations_gpu.py": 4, "test_heads_scan_gpu.py": 7, "test_lean_path_gpu.py": 65,
